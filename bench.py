@@ -19,8 +19,17 @@ fp32: exact fp32 MFMA everywhere.
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline     dominant kernel (the 512->512 3x3 conv @16x129 as implicit GEMM)
                timed live with HIP events inside the timed region (d2t_profile_*)
+A plain run does only that: set up, warm up, time the K steps, print the line.
+
+--full adds everything else the line can carry, each measured outside the headline's timed region:
+  parity       the timed configuration's first rows against the CPU oracle
   cpu_baseline the CPU oracle in reference-faithful mode (no KV cache, unfused BN),
                timed on this box's host cores on a bounded sample (rank 0, N=1 only)
+  secondary    transfer-inclusive rate, the other arithmetics, C0 / C1 / C3 / C4
+  stem_hbm     HBM traffic of the network's front from the committed PMC pass
+
+--dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/tokens.npy (float64) and
+DIR/logits.npy (float32); inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -106,6 +115,31 @@ def stem_hbm():
 
 def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor} as dirname/<name>.npy: integer arrays as float64 (exact), the rest as float32.  If the arrays
+    exceed DUMP_LIMIT_BYTES together, the same fixed, seeded sample of leading-axis rows is taken from each of them (its
+    row indices go to rows.npy)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        out[k] = a.astype(np.float64 if np.issubdtype(a.dtype, np.integer) else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = min(a.shape[0] for a in out.values())
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // total))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        out = {k: a[rows] for k, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+    log(f"outputs written to {dirname}: " + ", ".join(f"{k} {list(a.shape)} {a.dtype}" for k, a in out.items()))
 
 
 def cpu_baseline(cfg_name, H, W, max_len, sample_b, passes=3):
@@ -259,6 +293,8 @@ def train_bench(args, rank, world, dev, dist, emit=True):
             del model, opt
             torch.cuda.empty_cache()
             return line
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loss": loss})
         print(json.dumps(line), flush=True)
     if dist and emit:
         dist.destroy_process_group()
@@ -767,8 +803,15 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=8,
                     help="crops in the CPU-baseline sample (1 warm-up + 3 timed passes in each of the two oracle modes: ~30 s)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements (transfer-inclusive rate, exact-fp32 mode)")
+                    help="with --full: skip the secondary measurements (transfer-inclusive rate, exact-fp32 mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the oracle parity check, the CPU baseline, the secondary "
+                         "measurements and the other configurations (off: only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline, args.no_secondary = True, True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start one fresh rank process per GPU ourselves (before anything here
@@ -832,9 +875,12 @@ def main():
     result, out = serving_bench(args, name, rank, world, dev, dist, secondary_runs=not args.no_secondary)
     if rank == 0:
         H, W, L, B = result.pop("_shape")
-        stem = stem_hbm()
-        if stem:
-            result["stem_hbm"] = stem
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"tokens": out[0], "logits": out[1]})
+        if args.full:
+            stem = stem_hbm()
+            if stem:
+                result["stem_hbm"] = stem
         parity_ok = True
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"], result["cpu_baseline_cached"], answers = cpu_baseline(name, H, W, L, args.cpu_sample)

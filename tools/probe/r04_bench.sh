@@ -4,7 +4,7 @@ out=$R/gpurun_out/r04_bench
 mkdir -p $out
 cd $R
 t0=$(date +%s)
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"
+timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"
 tail -5 $out/bench.err
 python3 - <<'PY'
 import json,sys,os
