@@ -171,7 +171,7 @@ struct d2t_ctx {
   float* skv_alt = nullptr; size_t skv_alt_cap = 0;  // beam: reorder target (ping-pong with skv_cur)
   float* skv_cur = nullptr;                          // cache decode_step reads / appends
   float* beam_ws = nullptr; size_t beam_ws_cap = 0;  // beam logits / scores / tokens / top-k
-  char* h_beam = nullptr; size_t h_beam_cap = 0;     // pinned host mirror of the device-side beam search's result block
+  char* h_beam = nullptr; size_t h_beam_cap = 0;     // pinned host staging of the beam searches (ensure_host_beam)
   bool cross_fp32 = false;  // probe builds: the greedy decode's cross-attention on the fp32 MFMA instead of split-bf16
   // beam search: 1 = one cross-attention block per SAMPLE serving all its hypotheses from one staged memory tile
   // (d2t_set_beam_shared_tile; measured slower than one block per hypothesis row at 128 samples x 5: DESIGN.md 5.4), 0 = per row

@@ -3,6 +3,7 @@
 // conv_mfma.hip / ops.hip on the caller's HIP stream; there is no CPU compute
 // path and no fallback.
 #include "ctx.h"
+#include <functional>
 #include <mutex>
 
 namespace {
@@ -1122,10 +1123,9 @@ hipError_t cross_kv(d2t_ctx* c, hipStream_t s, const float* memory, int B, int T
 //   [LN3 prev] qkv GEMM | fused row kernel (self-attn, out-proj+res, LN1, q-proj, cross-attn, out-proj+res)
 //   | [LN2] ff1+ReLU GEMM | ff2+res GEMM
 // All position-dependent values come from the device step counter (graph-replayable).
-// shared_mem: cross K/V of sample 0 shared by every row (beam search over one sample).
 // beam > 0 (beam search with at most 6 hypotheses per sample, absorbed form): the row work runs as pre / per-SAMPLE cross /
-// post (launch_decoder_row_beam) with the samples' row segments in `seg` (nullptr: one sample, rows [0, M)).
-hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int T, int kvB, bool shared_mem,
+// post (launch_decoder_row_beam) with the samples' row segments in `seg`.
+hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int T, int kvB,
                        float* logits, long long logit_row_stride, long long logit_step_stride, int ckvB = -1,
                        const int* row_map = nullptr, const int* stop = nullptr, int beam = 0, const int* seg = nullptr,
                        const int* anc = nullptr, const int* rows_ptr = nullptr) {
@@ -1136,7 +1136,7 @@ hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int 
 #define TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
   const size_t skv_layer = (size_t)kvB * heads * Lmax * hd;
   // batched beam search: ckvB samples' cross K/V, row b attends over sample row_map[b]
-  const size_t ckv_slab = (size_t)(shared_mem ? 1 : (ckvB > 0 ? ckvB : kvB)) * heads * T * hd;
+  const size_t ckv_slab = (size_t)(ckvB > 0 ? ckvB : kvB) * heads * T * hd;
   for (int l = 0; l < g.dec_layers; ++l) {
     const DecLayer& L = c->dec[l];
     if (l == 0) {
@@ -1149,7 +1149,7 @@ hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int 
     r.sk = c->skv_cur + (size_t)(2 * l) * skv_layer; r.sv = c->skv_cur + (size_t)(2 * l + 1) * skv_layer;
     r.s_batch_stride = (long long)heads * Lmax * hd; r.s_Lmax = Lmax;
     r.ck = c->ckv + (size_t)(2 * l) * ckv_slab; r.cv = c->ckv + (size_t)(2 * l + 1) * ckv_slab;
-    r.c_batch_stride = shared_mem ? 0 : (long long)heads * T * hd;  // beam: every hypothesis reads sample 0
+    r.c_batch_stride = (long long)heads * T * hd;
     r.c_row_map = row_map;
     r.T = T;
     r.wo_t = L.sa_out_t; r.bo = L.sa_out.b; r.ln1_g = L.n1.g; r.ln1_b = L.n1.b; r.eps = 1e-5f;
@@ -1159,15 +1159,15 @@ hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int 
     r.stop_at = stop;
     r.anc = anc; r.anc_stride = Lmax; r.one_row = beam > 0;
     r.rows_ptr = rows_ptr;
-    if (c->dec_absorbed && c->beam_shared_tile && beam > 0 && beam <= 6 && c->beam_qp && (shared_mem || row_map))
-      TRY(launch_decoder_row_beam(r, c->ckv, shared_mem ? 0 : (long long)T * d, L.ca_wk, L.ca_v_t, L.ca_bv, c->beam_qp,
-                                  c->beam_qp + (size_t)kvB * 8 * d, seg, shared_mem ? 1 : ckvB, s));
+    if (c->dec_absorbed && c->beam_shared_tile && beam > 0 && beam <= 6 && c->beam_qp && row_map)
+      TRY(launch_decoder_row_beam(r, c->ckv, (long long)T * d, L.ca_wk, L.ca_v_t, L.ca_bv, c->beam_qp,
+                                  c->beam_qp + (size_t)kvB * 8 * d, seg, ckvB, s));
     else if (c->dec_absorbed) {
       // the split-bf16 cross-attention reads the planes behind the slot's fp32 rows (cross_kv): greedy rows (two per block) and beam
       // rows (one per block, ancestry) alike
-      const size_t memn = (size_t)(shared_mem ? 1 : (ckvB > 0 ? ckvB : kvB)) * T * d;
+      const size_t memn = (size_t)(ckvB > 0 ? ckvB : kvB) * T * d;
       const uint16_t* mhi = c->cross_fp32 ? nullptr : reinterpret_cast<const uint16_t*>(c->ckv + memn);
-      TRY(launch_decoder_row_absorbed(r, c->ckv, shared_mem ? 0 : (long long)T * d, L.ca_wk, L.ca_v_t, L.ca_bv, s, mhi, mhi ? mhi + memn : nullptr));
+      TRY(launch_decoder_row_absorbed(r, c->ckv, (long long)T * d, L.ca_wk, L.ca_v_t, L.ca_bv, s, mhi, mhi ? mhi + memn : nullptr));
     }
     else TRY(launch_decoder_row(r, s));
     TRY(skinny(s, Lin{bf.y2, d, &L.l1, nullptr, bf.f, g.dec_ff, ACT_RELU}, M, &L.n2, bf.x2, nullptr, 0, trace_slot(c), stop, step));
@@ -1181,6 +1181,51 @@ hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int 
 }  // namespace
 
 namespace {
+// The context's graph of `k` (a small cache, most recently used last); on a miss `enqueue` is captured on s, instantiated and
+// cached, evicting the least recently used of 40.  `what` names the loop in an error message.
+int cached_graph(d2t_ctx* c, hipStream_t s, const d2t_ctx::GraphKey& k, const char* what,
+                 const std::function<hipError_t(hipStream_t)>& enqueue, hipGraphExec_t* out) {
+  for (size_t i = 0; i < c->graphs.size(); ++i)
+    if (memcmp(&k, &c->graphs[i].key, sizeof k) == 0) {
+      *out = c->graphs[i].exec;
+      if (i + 1 != c->graphs.size()) std::swap(c->graphs[i], c->graphs.back());
+      return D2T_OK;
+    }
+  c->dtrace_next = 0;  // debug timeline (D2T_DECODE_TRACE): the kernel nodes of THIS captured loop get slots 0 .. n-1
+  hipGraph_t gr = nullptr;
+  HIPCHK(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  hipError_t e = enqueue(s);
+  hipError_t e2 = hipStreamEndCapture(s, &gr);
+  if (e != hipSuccess || e2 != hipSuccess) {
+    if (gr) hipGraphDestroy(gr);
+    return fail(c, D2T_EHIP, "%s graph capture: %s", what, hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  hipGraphExec_t exec = nullptr;
+  e = hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0);
+  hipGraphDestroy(gr);
+  if (e != hipSuccess) return fail(c, D2T_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+  if (c->graphs.size() >= 40) {  // evict the least recently used; it may still be queued on a decode stream
+    HIPCHK(c, sync_chains(c));
+    hipGraphExecDestroy(c->graphs.front().exec);
+    c->graphs.erase(c->graphs.begin());
+  }
+  c->graphs.push_back({k, exec});
+  *out = exec;
+  return D2T_OK;
+}
+
+// The pinned host staging buffer of the beam searches (c->h_beam), grown on demand.  Every search synchronises its stream
+// before it returns, so the buffer is idle between calls.
+int ensure_host_beam(d2t_ctx* c, size_t bytes) {
+  if (c->h_beam_cap >= bytes) return D2T_OK;
+  if (c->h_beam) hipHostFree(c->h_beam);
+  c->h_beam = nullptr; c->h_beam_cap = 0;
+  if (hipHostMalloc(reinterpret_cast<void**>(&c->h_beam), bytes, hipHostMallocDefault) != hipSuccess)
+    return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
+  c->h_beam_cap = bytes;
+  return D2T_OK;
+}
+
 // Greedy decode.  The cross-attention K/V projection runs on the caller's stream into one of two slots;
 // the step loop runs on the internal stream, ordered after it.  async != 0: return right after
 // enqueueing (always max_seq_len+1 steps); the caller orders later work with d2t_decode_wait.
@@ -1239,7 +1284,7 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
   am.batch_end_count = grp; am.batch_steps_done = grp + GRP_MAXB; am.batches_done = grp + 2 * GRP_MAXB;
   am.stop_at = dev_exit ? grp + 2 * GRP_MAXB + 1 : nullptr;
   auto one_step = [&](hipStream_t st) -> hipError_t {
-    hipError_t e = decode_step(c, st, bf, B, T, B, false, logits, (long long)S * V, V, -1, nullptr, stop);
+    hipError_t e = decode_step(c, st, bf, B, T, B, logits, (long long)S * V, V, -1, nullptr, stop);
     if (e != hipSuccess) return e;
     am.trace = trace_slot(c);
     return launch_argmax_embed(am, st);
@@ -1256,36 +1301,14 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
     k.B = B; k.T = T; k.steps = steps_per_graph; k.tok = tokens; k.logits = logits; k.ckv = c->ckv; k.dws = c->dws;
     k.skv = c->skv; k.dstate = c->dstate;
     k.variant = (dev_exit ? 1 : 0) | ((long long)rows_per_batch << 1);
-    for (size_t i = 0; i < c->graphs.size(); ++i)
-      if (memcmp(&k, &c->graphs[i].key, sizeof k) == 0) {
-        exec = c->graphs[i].exec;
-        if (i + 1 != c->graphs.size()) std::swap(c->graphs[i], c->graphs.back());
-        break;
-      }
-    if (!exec) {
-      if (D2T_PROBE_ENV_STR("D2T_DECODE_TRACE")) {  // debug timeline: the kernel nodes of THIS captured loop get slots 0 .. n-1
-        if (!c->dtrace) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->dtrace), (size_t)d2t_ctx::DTRACE_SLOTS * 16));
-        c->dtrace_next = 0;
-      }
-      hipGraph_t gr = nullptr;
-      HIPCHK(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    if (D2T_PROBE_ENV_STR("D2T_DECODE_TRACE") && !c->dtrace)  // debug timeline of the kernel nodes of a captured loop
+      HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->dtrace), (size_t)d2t_ctx::DTRACE_SLOTS * 16));
+    rc = cached_graph(c, s, k, "decode", [&](hipStream_t st) {
       hipError_t e = hipSuccess;
-      for (int t = 0; t < steps_per_graph && e == hipSuccess; ++t) e = one_step(s);
-      hipError_t e2 = hipStreamEndCapture(s, &gr);
-      if (e != hipSuccess || e2 != hipSuccess) {
-        if (gr) hipGraphDestroy(gr);
-        return fail(c, D2T_EHIP, "decode graph capture: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-      }
-      e = hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0);
-      hipGraphDestroy(gr);
-      if (e != hipSuccess) return fail(c, D2T_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-      if (c->graphs.size() >= 40) {  // evict the least recently used; it may still be queued on a decode stream
-        HIPCHK(c, sync_chains(c));
-        hipGraphExecDestroy(c->graphs.front().exec);
-        c->graphs.erase(c->graphs.begin());
-      }
-      c->graphs.push_back({k, exec});
-    }
+      for (int t = 0; t < steps_per_graph && e == hipSuccess; ++t) e = one_step(st);
+      return e;
+    }, &exec);
+    if (rc) return rc;
   }
   int steps = S;
   // device-side early exit: the loop stops writing at the group's stop step, so define everything past it (PAD ids, zero
@@ -1347,6 +1370,24 @@ int d2t_decode_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, con
   return greedy_impl(c, memory, B, T, start_tokens, is_test, tokens, logits, steps_out, (hipStream_t)stream, false);
 }
 
+namespace {
+// The fields of the LSTM-attention decoder launch that every caller sets alike: memory [*][T][H], its key projection kp,
+// the weights.  The caller adds its outputs, row count, step count and (beam search) the step-mode fields.
+AttnDecP attn_dec_params(const d2t_ctx* c, const float* memory, int T, const float* kp) {
+  const d2t_config& g = c->cfg;
+  AttnDecP p{};
+  p.mem = memory; p.T = T; p.D = g.attn_hidden; p.key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  p.init_mode = !g.attn_enc_init ? 0 : (g.attn_keys == D2T_ATTN_KEYS_ALL_INIT_MEAN ? 1 : 2);
+  p.kp = kp; p.wq_t = c->attn.wq_t; p.bq = c->attn.bq; p.wloc = c->attn.wloc; p.bloc = c->attn.bloc;
+  p.taps = c->attn.taps; p.wscore = c->attn.wscore; p.bscore = c->attn.bscore;
+  p.wx_t = c->attn.wx_t; p.bx = c->attn.bx; p.wg_t = c->attn.wg_t; p.bg = c->attn.bg;
+  p.wih_t = c->attn.wih_t; p.bih = c->attn.bih; p.wic_t = c->attn.wic_t; p.bic = c->attn.bic;
+  p.emb = c->attn.emb; p.tokgate = c->attn.tokgate;
+  p.V = g.vocab; p.H = g.attn_hidden; p.E = g.attn_hidden; p.coverage = g.attn_coverage; p.end_token = 1;  // attn_converter.py:8
+  return p;
+}
+}  // namespace
+
 int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
                            float* probs, int32_t* steps_out, d2t_stream stream) {
   DevGuard dg_(c);
@@ -1365,15 +1406,9 @@ int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T
   int* end_step = reinterpret_cast<int*>(c->dws + (size_t)B * T * Hh);
   HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, B * T, ACT_NONE));
   HIPCHK(c, hipMemsetAsync(end_step, 0xFF, (size_t)B * 4, s));  // -1 = never emitted [s]
-  AttnDecP p{};
-  p.mem = memory; p.T = T; p.D = Hh; p.key_off = key_off;
-  p.init_mode = !g.attn_enc_init ? 0 : (g.attn_keys == D2T_ATTN_KEYS_ALL_INIT_MEAN ? 1 : 2);
-  p.kp = kp; p.wq_t = c->attn.wq_t; p.bq = c->attn.bq; p.wloc = c->attn.wloc; p.bloc = c->attn.bloc;
-  p.taps = c->attn.taps; p.wscore = c->attn.wscore; p.bscore = c->attn.bscore;
-  p.wx_t = c->attn.wx_t; p.bx = c->attn.bx; p.wg_t = c->attn.wg_t; p.bg = c->attn.bg;
-  p.wih_t = c->attn.wih_t; p.bih = c->attn.bih; p.wic_t = c->attn.wic_t; p.bic = c->attn.bic;
-  p.emb = c->attn.emb; p.tokgate = c->attn.tokgate; p.probs = probs; p.tokens = tokens; p.end_step = end_step;
-  p.B = B; p.S = S; p.V = V; p.H = Hh; p.E = Hh; p.coverage = g.attn_coverage; p.end_token = 1;  // attn_converter.py:8
+  AttnDecP p = attn_dec_params(c, memory, T, kp);
+  p.probs = probs; p.tokens = tokens; p.end_step = end_step;
+  p.B = B; p.S = S;
   HIPCHK(c, launch_attn_decode(p, s));
   int steps = S;
   if (is_test) {
@@ -1398,159 +1433,20 @@ int d2t_decode_attn_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t bea
                          float* score_out, d2t_stream stream) {
   DevGuard dg_(c);
   // Attention.forward_beam (prediction_head/seq2seq.py:83-222) / AttentionV2.forward_beam (seq2seq_v2.py:12-174) for
-  // one sample: the attention cell + LSTMCell + generator of every live hypothesis run as ONE launch per step (the
-  // greedy kernel in step mode, one block per hypothesis, keys shared), log_softmax + flat top-k on the device, the
-  // reference's bookkeeping on the host -- including its quirks: step 0 ranks row 0 only; the LSTM state follows
-  // prev_word_inds[incomplete] but the coverage memory only `incomplete`; if the last executed step completed nothing
-  // the first live sequence is returned; otherwise the best score/len sequence with the MAXIMUM raw score.
-  if (!c || !memory || !seq_out || !len_out || !score_out || T < 1) return fail(c, D2T_EINVAL, "bad argument");
-  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
-  const d2t_config& g = c->cfg;
-  if (g.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "context was not created with the Attn decoder");
-  if (!g.attn_coverage && g.attn_cell != D2T_ATTN_CELL_BAHDANAU)
-    return fail(c, D2T_ESTATE, "LSTM beam search is implemented for the coverage and Bahdanau cells (the reference's 'loc_aware' beam "
-                "hands the previous beam's un-reordered alignment to the next step, seq2seq.py:207)");
-  if (beam_size < 1 || beam_size > 16) return fail(c, D2T_EINVAL, "beam_size must be in [1,16]");
-  const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab, cap = beam_size;
-  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
-  const int Tk = T - key_off;
-  if (Tk < 1 || Tk > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if ((rc = ensure(c, &c->dws, &c->dws_cap, ((size_t)T * Hh + 16) * 4))) return rc;
-  float* kp = c->dws;
-  // workspace (floats): logits [cap][V] | scores | topv | h_in c_in h_out c_out [cap][H] | mem_in mem_out [cap][Tk]
-  //                     | tok i64 [cap] | dummy tokens i64 [cap] | topi | idx_h | idx_m | end_step  (ints [cap])
-  const size_t nf = (size_t)cap * V + 2 * cap + 4 * (size_t)cap * Hh + 2 * (size_t)cap * Tk;
-  const size_t tok_off = (nf + 1) & ~(size_t)1;
-  const size_t ws_bytes = tok_off * 4 + 2 * (size_t)cap * 8 + 4 * (size_t)cap * 4 + 64;
-  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, ws_bytes))) return rc;
-  float* d_logits = c->beam_ws;
-  float* d_scores = d_logits + (size_t)cap * V;
-  float* d_topv = d_scores + cap;
-  float* st[6];
-  st[0] = d_topv + cap;                          // h_in
-  st[1] = st[0] + (size_t)cap * Hh;              // c_in
-  st[2] = st[1] + (size_t)cap * Hh;              // h_out
-  st[3] = st[2] + (size_t)cap * Hh;              // c_out
-  st[4] = st[3] + (size_t)cap * Hh;              // mem_in
-  st[5] = st[4] + (size_t)cap * Tk;              // mem_out
-  int64_t* d_tok = reinterpret_cast<int64_t*>(d_logits + tok_off);
-  int64_t* d_dummy = d_tok + cap;
-  int* d_topi = reinterpret_cast<int*>(d_dummy + cap);
-  int* d_idxh = d_topi + cap;
-  int* d_idxm = d_idxh + cap;
-  int* d_end = d_idxm + cap;
-  char* hp = nullptr;
-  const size_t hbytes = (size_t)cap * (8 + 4 * 5) + 64;
-  if (hipHostMalloc(reinterpret_cast<void**>(&hp), hbytes, hipHostMallocDefault) != hipSuccess)
-    return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
-  int64_t* h_tok = reinterpret_cast<int64_t*>(hp);
-  float* h_scores = reinterpret_cast<float*>(hp + (size_t)cap * 8);
-  float* h_topv = h_scores + cap;
-  int* h_topi = reinterpret_cast<int*>(h_topv + cap);
-  int* h_idxh = h_topi + cap;
-  int* h_idxm = h_idxh + cap;
-  auto done = [&](int code) { hipHostFree(hp); return code; };
-#define BCHK(expr)                                                                              \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return done(fail(c, D2T_EHIP, "%s: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
-  BCHK(linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, T, ACT_NONE));
-  AttnDecP p{};
-  p.mem = memory; p.T = T; p.D = Hh; p.key_off = key_off;
-  p.init_mode = !g.attn_enc_init ? 0 : (g.attn_keys == D2T_ATTN_KEYS_ALL_INIT_MEAN ? 1 : 2);
-  p.kp = kp; p.wq_t = c->attn.wq_t; p.bq = c->attn.bq; p.wloc = c->attn.wloc; p.bloc = c->attn.bloc;
-  p.taps = c->attn.taps; p.wscore = c->attn.wscore; p.bscore = c->attn.bscore;
-  p.wx_t = c->attn.wx_t; p.bx = c->attn.bx; p.wg_t = c->attn.wg_t; p.bg = c->attn.bg;
-  p.wih_t = c->attn.wih_t; p.bih = c->attn.bih; p.wic_t = c->attn.wic_t; p.bic = c->attn.bic;
-  p.emb = c->attn.emb; p.tokgate = c->attn.tokgate; p.probs = d_logits; p.tokens = d_dummy; p.end_step = d_end;
-  p.S = 1; p.V = V; p.H = Hh; p.E = Hh; p.coverage = 1; p.end_token = 1;
-  p.step_mode = 1;
-  p.st_h_in = st[0]; p.st_c_in = st[1]; p.st_mem_in = st[4];
-  p.st_h_out = st[2]; p.st_c_out = st[3]; p.st_mem_out = st[5];
-  p.tok_in = d_tok;
-
-  std::vector<std::vector<int64_t>> seqs((size_t)beam_size, std::vector<int64_t>{0});  // each starts with [GO] = 0
-  std::vector<float> live_scores((size_t)beam_size, 0.f);
-  std::vector<std::vector<int64_t>> complete;
-  std::vector<float> complete_scores;
-  int k = beam_size;
-  bool last_completed_any = false;
-  for (int step = 0; step < S; ++step) {
-    const int M = (int)seqs.size();
-    for (int i = 0; i < M; ++i) h_scores[i] = live_scores[i];
-    BCHK(hipMemcpyAsync(d_scores, h_scores, (size_t)M * 4, hipMemcpyHostToDevice, s));
-    p.B = M; p.first = step == 0;
-    BCHK(launch_attn_decode(p, s));
-    // step 0: the rows are identical and the reference ranks row 0 only (seq2seq.py:145-146)
-    BCHK(launch_beam_topk(d_logits, d_scores, step == 0 ? 1 : M, V, k, d_topv, d_topi, s));
-    BCHK(hipMemcpyAsync(h_topv, d_topv, (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    BCHK(hipMemcpyAsync(h_topi, d_topi, (size_t)k * 4, hipMemcpyDeviceToHost, s));
-    BCHK(hipStreamSynchronize(s));
-    std::vector<std::vector<int64_t>> nseqs;
-    std::vector<float> nscores;
-    int ninc = 0;
-    last_completed_any = false;
-    for (int r = 0; r < k; ++r) {
-      const int prev = h_topi[r] / V, word = h_topi[r] % V;
-      std::vector<int64_t> sq = seqs[prev];
-      sq.push_back(word);
-      if (word == 1) {  // [s] (attn_converter.py:8)
-        complete.push_back(std::move(sq));
-        complete_scores.push_back(h_topv[r]);
-        last_completed_any = true;
-      } else {
-        h_idxh[ninc] = prev;  // LSTM state: hidden[prev_word_inds[incomplete]]
-        h_idxm[ninc] = r;     // coverage memory: (alpha_cum + alpha)[incomplete]
-        h_tok[ninc] = word;
-        nseqs.push_back(std::move(sq));
-        nscores.push_back(h_topv[r]);
-        ++ninc;
-      }
-    }
-    seqs.swap(nseqs);
-    live_scores.swap(nscores);
-    k = ninc;
-    if (k == 0) break;
-    if (step + 1 < S) {
-      BCHK(hipMemcpyAsync(d_idxh, h_idxh, (size_t)k * 4, hipMemcpyHostToDevice, s));
-      BCHK(hipMemcpyAsync(d_idxm, h_idxm, (size_t)k * 4, hipMemcpyHostToDevice, s));
-      BCHK(hipMemcpyAsync(d_tok, h_tok, (size_t)k * 8, hipMemcpyHostToDevice, s));
-      BCHK(launch_gather_rows(st[2], st[0], d_idxh, k, Hh, s));
-      BCHK(launch_gather_rows(st[3], st[1], d_idxh, k, Hh, s));
-      BCHK(launch_gather_rows(st[5], st[4], d_idxm, k, Tk, s));
-    }
-  }
-  BCHK(hipStreamSynchronize(s));
-#undef BCHK
-  std::vector<int64_t> out;
-  float score;
-  if (!last_completed_any) {  // seq2seq.py:209-216
-    out.assign(seqs[0].begin() + 1, seqs[0].end());
-    score = live_scores[0];
-  } else {
-    size_t best = 0;
-    for (size_t i = 1; i < complete.size(); ++i)
-      if ((double)complete_scores[i] / (double)complete[i].size() > (double)complete_scores[best] / (double)complete[best].size())
-        best = i;
-    out.assign(complete[best].begin() + 1, complete[best].end());
-    score = *std::max_element(complete_scores.begin(), complete_scores.end());
-  }
-  const int n = (int)std::min<size_t>(out.size(), (size_t)S);
-  for (int i = 0; i < n; ++i) seq_out[i] = out[i];
-  *len_out = n;
-  *score_out = score;
-  return done(D2T_OK);
+  // one sample: the batched search with N = 1.
+  return d2t_decode_attn_beam_batch(c, memory, 1, T, beam_size, seq_out, len_out, score_out, stream);
 }
 
 int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
                                int32_t* len_out, float* score_out, d2t_stream stream) {
   DevGuard dg_(c);
   // Attention / AttentionV2.forward_beam for N samples in one step loop: rows = live hypotheses of all samples, each
-  // attending over its own sample's keys (row map); log_softmax + top-k per sample segment; per-sample bookkeeping
-  // exactly as in d2t_decode_attn_beam (whose results this reproduces sample by sample).
+  // attending over its own sample's keys (row map).  The attention cell + LSTMCell + generator of every live hypothesis run
+  // as ONE launch per step (the greedy kernel in step mode, one block per hypothesis), log_softmax + top-k per sample
+  // segment on the device, the reference's bookkeeping per sample on the host -- including its quirks: step 0 ranks row 0
+  // only; the LSTM state follows prev_word_inds[incomplete] but the coverage memory only `incomplete`; if the last executed
+  // step completed nothing the first live sequence is returned; otherwise the best score/len sequence with the MAXIMUM raw
+  // score.
   if (!c || !memory || !seq_out || !len_out || !score_out || N < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
   if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
   const d2t_config& g = c->cfg;
@@ -1567,56 +1463,47 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
   int rc;
   if ((rc = ensure(c, &c->dws, &c->dws_cap, ((size_t)N * T * Hh + 16) * 4))) return rc;
   float* kp = c->dws;
-  const size_t nf = (size_t)cap * V + 2 * (size_t)cap + 4 * (size_t)cap * Hh + 2 * (size_t)cap * Tk;
-  const size_t tok_off = (nf + 1) & ~(size_t)1;
-  const size_t ws_bytes = tok_off * 4 + 2 * (size_t)cap * 8 + (5 * (size_t)cap + 3 * (size_t)N) * 4 + 64;
-  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, ws_bytes))) return rc;
+  // workspace: logits [cap][V] | topv [cap] | topi [cap] (one device -> host copy per step) | h_in c_in h_out c_out [cap][H]
+  //            | mem_in mem_out [cap][Tk] | end_step [cap] | dummy tokens i64 [cap] | step pack (one host -> device copy per
+  //            step): tok i64 [cap] | scores [cap] | map [cap] | idx_h [cap] | idx_m [cap] | seg [N][3]
+  const size_t nf = (size_t)cap * V + 2 * (size_t)cap + 4 * (size_t)cap * Hh + 2 * (size_t)cap * Tk + cap;
+  const size_t pack_off = ((nf * 4 + 15) & ~(size_t)15) + (size_t)cap * 8;
+  const size_t pack_bytes = ((size_t)cap * (8 + 4 * 4) + (size_t)N * 12 + 15) & ~(size_t)15;
+  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, pack_off + pack_bytes + 64))) return rc;
   float* d_logits = c->beam_ws;
-  float* d_scores = d_logits + (size_t)cap * V;
-  float* d_topv = d_scores + cap;
+  float* d_topv = d_logits + (size_t)cap * V;
+  int* d_topi = reinterpret_cast<int*>(d_topv + cap);
   float* st[6];
-  st[0] = d_topv + cap;
-  st[1] = st[0] + (size_t)cap * Hh;
-  st[2] = st[1] + (size_t)cap * Hh;
-  st[3] = st[2] + (size_t)cap * Hh;
-  st[4] = st[3] + (size_t)cap * Hh;
-  st[5] = st[4] + (size_t)cap * Tk;
-  int64_t* d_tok = reinterpret_cast<int64_t*>(d_logits + tok_off);
-  int64_t* d_dummy = d_tok + cap;
-  int* d_topi = reinterpret_cast<int*>(d_dummy + cap);
-  int* d_idxh = d_topi + cap;
+  st[0] = reinterpret_cast<float*>(d_topi + cap);  // h_in
+  st[1] = st[0] + (size_t)cap * Hh;               // c_in
+  st[2] = st[1] + (size_t)cap * Hh;               // h_out
+  st[3] = st[2] + (size_t)cap * Hh;               // c_out
+  st[4] = st[3] + (size_t)cap * Hh;               // mem_in
+  st[5] = st[4] + (size_t)cap * Tk;               // mem_out
+  int* d_end = reinterpret_cast<int*>(st[5] + (size_t)cap * Tk);
+  char* d_pack = reinterpret_cast<char*>(c->beam_ws) + pack_off;
+  int64_t* d_dummy = reinterpret_cast<int64_t*>(d_pack) - cap;
+  int64_t* d_tok = reinterpret_cast<int64_t*>(d_pack);
+  float* d_scores = reinterpret_cast<float*>(d_tok + cap);
+  int* d_map = reinterpret_cast<int*>(d_scores + cap);
+  int* d_idxh = d_map + cap;
   int* d_idxm = d_idxh + cap;
-  int* d_end = d_idxm + cap;
-  int* d_map = d_end + cap;
-  int* d_seg = d_map + cap;
-  char* hp = nullptr;
-  const size_t hbytes = (size_t)cap * (8 + 4 * 6) + (size_t)N * 12 + 64;
-  if (hipHostMalloc(reinterpret_cast<void**>(&hp), hbytes, hipHostMallocDefault) != hipSuccess)
-    return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
+  int* d_seg = d_idxm + cap;
+  // pinned host mirror: the step pack | topv [cap] | topi [cap]
+  if ((rc = ensure_host_beam(c, pack_bytes + 2 * (size_t)cap * 4))) return rc;
+  char* hp = c->h_beam;
   int64_t* h_tok = reinterpret_cast<int64_t*>(hp);
-  float* h_scores = reinterpret_cast<float*>(hp + (size_t)cap * 8);
-  float* h_topv = h_scores + cap;
-  int* h_topi = reinterpret_cast<int*>(h_topv + cap);
-  int* h_idxh = h_topi + cap;
+  float* h_scores = reinterpret_cast<float*>(h_tok + cap);
+  int* h_map = reinterpret_cast<int*>(h_scores + cap);
+  int* h_idxh = h_map + cap;
   int* h_idxm = h_idxh + cap;
-  int* h_map = h_idxm + cap;
-  int* h_seg = h_map + cap;
-  auto done = [&](int code) { hipHostFree(hp); return code; };
-#define BCHK(expr)                                                                              \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return done(fail(c, D2T_EHIP, "%s: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
-  BCHK(linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, N * T, ACT_NONE));
-  AttnDecP p{};
-  p.mem = memory; p.T = T; p.D = Hh; p.key_off = key_off;
-  p.init_mode = !g.attn_enc_init ? 0 : (g.attn_keys == D2T_ATTN_KEYS_ALL_INIT_MEAN ? 1 : 2);
-  p.kp = kp; p.wq_t = c->attn.wq_t; p.bq = c->attn.bq; p.wloc = c->attn.wloc; p.bloc = c->attn.bloc;
-  p.taps = c->attn.taps; p.wscore = c->attn.wscore; p.bscore = c->attn.bscore;
-  p.wx_t = c->attn.wx_t; p.bx = c->attn.bx; p.wg_t = c->attn.wg_t; p.bg = c->attn.bg;
-  p.wih_t = c->attn.wih_t; p.bih = c->attn.bih; p.wic_t = c->attn.wic_t; p.bic = c->attn.bic;
-  p.emb = c->attn.emb; p.tokgate = c->attn.tokgate; p.probs = d_logits; p.tokens = d_dummy; p.end_step = d_end;
-  p.S = 1; p.V = V; p.H = Hh; p.E = Hh; p.coverage = 1; p.end_token = 1;
+  int* h_seg = h_idxm + cap;
+  float* h_topv = reinterpret_cast<float*>(hp + pack_bytes);
+  int* h_topi = reinterpret_cast<int*>(h_topv + cap);
+  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, N * T, ACT_NONE));
+  AttnDecP p = attn_dec_params(c, memory, T, kp);
+  p.probs = d_logits; p.tokens = d_dummy; p.end_step = d_end;
+  p.S = 1; p.coverage = 1;
   p.step_mode = 1;
   p.st_h_in = st[0]; p.st_c_in = st[1]; p.st_mem_in = st[4];
   p.st_h_out = st[2]; p.st_c_out = st[3]; p.st_mem_out = st[5];
@@ -1630,30 +1517,31 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
   };
   std::vector<Smp> sm((size_t)N);
   for (auto& x : sm) {
-    x.seqs.assign((size_t)beam_size, std::vector<int64_t>{0});
+    x.seqs.assign((size_t)beam_size, std::vector<int64_t>{0});  // each starts with [GO] = 0
     x.live.assign((size_t)beam_size, 0.f);
     x.k = beam_size;
   }
-  for (int step = 0; step < S; ++step) {
+  // the rows of a step in sample order: segments, scores and row map into the pack; returns the row count
+  auto stage = [&](int step) {
     int rows = 0;
     for (int i = 0; i < N; ++i) {
       Smp& x = sm[i];
       const int M = x.finished ? 0 : (int)x.seqs.size();
-      // step 0: all rows of a sample are identical and the reference ranks its row 0 only
+      // step 0: all rows of a sample are identical and the reference ranks its row 0 only (seq2seq.py:145-146)
       h_seg[3 * i] = rows; h_seg[3 * i + 1] = M ? (step == 0 ? 1 : M) : 0; h_seg[3 * i + 2] = x.finished ? 0 : x.k;
       for (int j = 0; j < M; ++j) { h_scores[rows + j] = x.live[j]; h_map[rows + j] = i; }
       rows += M;
     }
-    if (!rows) break;
-    BCHK(hipMemcpyAsync(d_scores, h_scores, (size_t)rows * 4, hipMemcpyHostToDevice, s));
-    BCHK(hipMemcpyAsync(d_map, h_map, (size_t)rows * 4, hipMemcpyHostToDevice, s));
-    BCHK(hipMemcpyAsync(d_seg, h_seg, (size_t)N * 12, hipMemcpyHostToDevice, s));
+    return rows;
+  };
+  int rows = stage(0);
+  HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
+  for (int step = 0; step < S; ++step) {
     p.B = rows; p.first = step == 0;
-    BCHK(launch_attn_decode(p, s));
-    BCHK(launch_beam_topk_batch(d_logits, d_scores, d_seg, N, V, beam_size, d_topv, d_topi, s));
-    BCHK(hipMemcpyAsync(h_topv, d_topv, (size_t)cap * 4, hipMemcpyDeviceToHost, s));
-    BCHK(hipMemcpyAsync(h_topi, d_topi, (size_t)cap * 4, hipMemcpyDeviceToHost, s));
-    BCHK(hipStreamSynchronize(s));
+    HIPCHK(c, launch_attn_decode(p, s));
+    HIPCHK(c, launch_beam_topk_batch(d_logits, d_scores, d_seg, N, V, beam_size, d_topv, d_topi, s));
+    HIPCHK(c, hipMemcpyAsync(h_topv, d_topv, 2 * (size_t)cap * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
     int nrows = 0;
     for (int i = 0; i < N; ++i) {
       Smp& x = sm[i];
@@ -1661,21 +1549,20 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
       const int off = h_seg[3 * i];
       std::vector<std::vector<int64_t>> nseqs;
       std::vector<float> nscores;
-      std::vector<int> ih, im;
-      std::vector<int64_t> nt;
       x.last_completed = false;
       for (int r = 0; r < x.k; ++r) {
         const int idx = h_topi[(size_t)i * beam_size + r], prev = idx / V, word = idx % V;
         std::vector<int64_t> sq = x.seqs[prev];
         sq.push_back(word);
-        if (word == 1) {
+        if (word == 1) {  // [s] (attn_converter.py:8)
           x.complete.push_back(std::move(sq));
           x.cscores.push_back(h_topv[(size_t)i * beam_size + r]);
           x.last_completed = true;
         } else {
-          ih.push_back(off + prev);  // LSTM state: hidden[prev_word_inds[incomplete]]
-          im.push_back(off + r);     // coverage memory: (alpha_cum + alpha)[incomplete]
-          nt.push_back(word);
+          h_idxh[nrows] = off + prev;  // LSTM state: hidden[prev_word_inds[incomplete]]
+          h_idxm[nrows] = off + r;     // coverage memory: (alpha_cum + alpha)[incomplete]
+          h_tok[nrows] = word;
+          ++nrows;
           nseqs.push_back(std::move(sq));
           nscores.push_back(h_topv[(size_t)i * beam_size + r]);
         }
@@ -1683,20 +1570,16 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
       x.seqs.swap(nseqs);
       x.live.swap(nscores);
       x.k = (int)x.seqs.size();
-      if (x.k == 0) { x.finished = true; continue; }
-      for (size_t j = 0; j < ih.size(); ++j) { h_idxh[nrows] = ih[j]; h_idxm[nrows] = im[j]; h_tok[nrows] = nt[j]; ++nrows; }
+      if (x.k == 0) x.finished = true;
     }
-    if (nrows && step + 1 < S) {
-      BCHK(hipMemcpyAsync(d_idxh, h_idxh, (size_t)nrows * 4, hipMemcpyHostToDevice, s));
-      BCHK(hipMemcpyAsync(d_idxm, h_idxm, (size_t)nrows * 4, hipMemcpyHostToDevice, s));
-      BCHK(hipMemcpyAsync(d_tok, h_tok, (size_t)nrows * 8, hipMemcpyHostToDevice, s));
-      BCHK(launch_gather_rows(st[2], st[0], d_idxh, nrows, Hh, s));
-      BCHK(launch_gather_rows(st[3], st[1], d_idxh, nrows, Hh, s));
-      BCHK(launch_gather_rows(st[5], st[4], d_idxm, nrows, Tk, s));
-    }
+    if (!nrows || step + 1 == S) break;
+    rows = stage(step + 1);  // == nrows: the survivors, in the order of their gather indices
+    HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, launch_gather_rows(st[2], st[0], d_idxh, rows, Hh, s));
+    HIPCHK(c, launch_gather_rows(st[3], st[1], d_idxh, rows, Hh, s));
+    HIPCHK(c, launch_gather_rows(st[5], st[4], d_idxm, rows, Tk, s));
   }
-  BCHK(hipStreamSynchronize(s));
-#undef BCHK
+  HIPCHK(c, hipStreamSynchronize(s));
   for (int i = 0; i < N; ++i) {
     Smp& x = sm[i];
     std::vector<int64_t> out;
@@ -1716,7 +1599,7 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
     len_out[i] = n;
     score_out[i] = score;
   }
-  return done(D2T_OK);
+  return D2T_OK;
 }
 
 int d2t_decode_greedy_async(d2t_ctx* c, const float* memory, int32_t B, int32_t T, const int64_t* start_tokens,
@@ -1877,13 +1760,7 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
   int* d_anc[2] = {reinterpret_cast<int*>(base + o_anc), reinterpret_cast<int*>(base + o_anc) + (size_t)cap * Lmax};
   const int* rows_ptr = b.ctrl + 1;
   const int* stop = b.ctrl + 2;
-  if (c->h_beam_cap < res_words * 4) {
-    if (c->h_beam) hipHostFree(c->h_beam);
-    c->h_beam = nullptr; c->h_beam_cap = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_beam), res_words * 4, hipHostMallocDefault) != hipSuccess)
-      return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
-    c->h_beam_cap = res_words * 4;
-  }
+  if ((rc = ensure_host_beam(c, res_words * 4))) return rc;
   HIPCHK(c, hipEventRecord(c->ev_in, user));
   HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
   c->ckv = c->ckv2[0];  // the internal stream is in order, so earlier decodes are done with the slot
@@ -1897,7 +1774,7 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
     for (int step = 0; step < S; ++step) {
       LTRY(launch_beam_ancestry(d_anc[(step + 1) & 1], d_anc[step & 1], b.prev, cap, Lmax, b.ctrl, c->dstate, st, rows_ptr, stop));
       LTRY(launch_embed_tokens(c->word_embed, c->word_pe, b.tok, c->dstate, bf.x, cap, d, st, rows_ptr, stop));
-      LTRY(decode_step(c, st, bf, cap, T, cap, false, d_logits, V, 0, N, b.map, stop, beam_size, b.seg, d_anc[step & 1], rows_ptr));
+      LTRY(decode_step(c, st, bf, cap, T, cap, d_logits, V, 0, N, b.map, stop, beam_size, b.seg, d_anc[step & 1], rows_ptr));
       LTRY(launch_beam_topk_batch(d_logits, b.scores, b.seg, N, V, beam_size, base + o_topv, reinterpret_cast<int*>(base + o_topi), st,
                                   c->dstate, stop));
       LTRY(launch_beam_dev_advance(b, st));
@@ -1912,31 +1789,7 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
     k.B = cap; k.T = T; k.steps = S; k.tok = nullptr; k.logits = base; k.ckv = c->ckv; k.dws = c->dws; k.skv = c->skv; k.dstate = c->dstate;
     k.variant = 3 | ((long long)N << 8) | ((long long)beam_size << 40);  // (bits 0-1 = 3: the device-side beam loop)
     hipGraphExec_t exec = nullptr;
-    for (size_t i = 0; i < c->graphs.size(); ++i)
-      if (memcmp(&k, &c->graphs[i].key, sizeof k) == 0) {
-        exec = c->graphs[i].exec;
-        if (i + 1 != c->graphs.size()) std::swap(c->graphs[i], c->graphs.back());
-        break;
-      }
-    if (!exec) {
-      hipGraph_t gr = nullptr;
-      HIPCHK(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      hipError_t e = enqueue_loop(s);
-      hipError_t e2 = hipStreamEndCapture(s, &gr);
-      if (e != hipSuccess || e2 != hipSuccess) {
-        if (gr) hipGraphDestroy(gr);
-        return fail(c, D2T_EHIP, "beam graph capture: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-      }
-      e = hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0);
-      hipGraphDestroy(gr);
-      if (e != hipSuccess) return fail(c, D2T_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-      if (c->graphs.size() >= 40) {
-        HIPCHK(c, sync_chains(c));
-        hipGraphExecDestroy(c->graphs.front().exec);
-        c->graphs.erase(c->graphs.begin());
-      }
-      c->graphs.push_back({k, exec});
-    }
+    if ((rc = cached_graph(c, s, k, "beam", enqueue_loop, &exec))) return rc;
     HIPCHK(c, hipGraphLaunch(exec, s));
   } else {
     HIPCHK(c, enqueue_loop(s));
@@ -1989,130 +1842,9 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
 int d2t_decode_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out, int32_t* len_out,
                     float* score_out, d2t_stream stream) {
   DevGuard dg_(c);
-  // TransformerPrediction.forward_beam (tfm.py:145-186) with tools/beam.py:38-140 bookkeeping on the
-  // host; a fresh beam per call (demo reset_beam semantics).  The model runs KV-cached on
-  // the device for the live hypotheses only; log_softmax + flat top-k run on the device too, so each
-  // step moves k <= beam_size (value, index) pairs to the host instead of the [hyp, V] log-prob matrix.
-  if (!c || !memory || !seq_out || !len_out || !score_out || T < 1) return fail(c, D2T_EINVAL, "bad argument");
-  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
-  if (beam_size < 1 || beam_size > 16) return fail(c, D2T_EINVAL, "beam_size must be in [1,16]");
-  if (c->cfg.decoder != D2T_DEC_TFM) return fail(c, D2T_ESTATE, "beam search is implemented for the TFM decoder only");
-  if (T > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d > %d unsupported", T, memory_cap(c));
-  const d2t_config& g = c->cfg;
-  const int S = g.max_seq_len + 1, V = g.vocab, d = g.dec_dim, cap = beam_size;
-  const int heads = g.dec_heads, hd = d / heads, Lmax = g.max_seq_len + 2;
-  if ((long long)cap * V > 16 * 4096) return fail(c, D2T_EINVAL, "beam_size * vocab too large");
-  // the absorbed d_model-256 decoder: the device-side loop of the batched search with one sample (the same row kernels, so
-  // batched == per-sample bit for bit), one graph launch per call instead of ~4000 kernel launches and 151 host round trips
-  if (c->dec_absorbed && !c->beam_shared_tile && Lmax <= 512 && D2T_PROBE_ENV_STR("D2T_BEAM_HOST") == nullptr)
-    return beam_device_impl(c, memory, 1, T, beam_size, seq_out, len_out, score_out, (hipStream_t)stream);
-  select_chain(c, 0);
-  hipStream_t user = (hipStream_t)stream, s = c->dstream;
-  DecBufs bf;
-  int rc = dec_prepare(c, cap, T, &bf);
-  if (rc) return rc;
-  const size_t skv_bytes = (size_t)g.dec_layers * 2 * cap * Lmax * d * 4;
-  if ((rc = ensure(c, &c->skv_alt, &c->skv_alt_cap, skv_bytes))) return rc;
-  // beam workspace: logits [cap][V] | scores [cap] | topv [cap] | tok [cap] i64 | topi [cap] | prev [cap]
-  const size_t ws_bytes = ((size_t)cap * V + 2 * cap) * 4 + (size_t)cap * 8 + 2 * (size_t)cap * 4 + 64;
-  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, ws_bytes))) return rc;
-  float* d_logits = c->beam_ws;
-  float* d_scores = d_logits + (size_t)cap * V;
-  float* d_topv = d_scores + cap;
-  const size_t tok_off = ((size_t)cap * V + 2 * (size_t)cap + 1) & ~(size_t)1;  // 8-byte aligned
-  int64_t* d_tok = reinterpret_cast<int64_t*>(d_logits + tok_off);
-  int* d_topi = reinterpret_cast<int*>(d_tok + cap);
-  int* d_prev = d_topi + cap;
-  // pinned host mirror: [0]=step | tok i64[cap] | scores[cap] | topv[cap] | topi[cap] | prev[cap]
-  static_assert(sizeof(int64_t) == 8, "");
-  char* hp = nullptr;
-  const size_t hbytes = 16 + (size_t)cap * (8 + 4 * 4);
-  if (hipHostMalloc(reinterpret_cast<void**>(&hp), hbytes, hipHostMallocDefault) != hipSuccess)
-    return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
-  int* h_step = reinterpret_cast<int*>(hp);
-  int64_t* h_tok = reinterpret_cast<int64_t*>(hp + 16);
-  float* h_scores = reinterpret_cast<float*>(hp + 16 + (size_t)cap * 8);
-  float* h_topv = h_scores + cap;
-  int* h_topi = reinterpret_cast<int*>(h_topv + cap);
-  int* h_prev = h_topi + cap;
-  auto done = [&](int code) { hipHostFree(hp); return code; };
-#define BCHK(expr)                                                                              \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return done(fail(c, D2T_EHIP, "%s: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
-
-  BCHK(hipEventRecord(c->ev_in, user));
-  BCHK(hipStreamWaitEvent(s, c->ev_in, 0));
-  BCHK(hipMemsetAsync(c->dstate, 0, (size_t)(4 + cap) * 4, s));
-  c->ckv = c->ckv2[0];  // the internal stream is in order, so earlier decodes are done with the slot
-  BCHK(cross_kv(c, s, memory, 1, T));
-  c->skv_cur = c->skv;
-  float* skv_other = c->skv_alt;
-
-  struct Hyp { std::vector<int64_t> seq; float score; };  // seq without the leading [GO]
-  std::vector<Hyp> hyps(1), completed;
-  hyps[0].score = 0.f;
-  int64_t last_tok[16];
-  last_tok[0] = TOK_GO;
-  for (int step = 0; step < S; ++step) {
-    const int M = (int)hyps.size();
-    *h_step = step;
-    for (int i = 0; i < M; ++i) { h_tok[i] = last_tok[i]; h_scores[i] = hyps[i].score; }
-    BCHK(hipMemcpyAsync(c->dstate, h_step, 4, hipMemcpyHostToDevice, s));
-    BCHK(hipMemcpyAsync(d_tok, h_tok, (size_t)M * 8, hipMemcpyHostToDevice, s));
-    BCHK(hipMemcpyAsync(d_scores, h_scores, (size_t)M * 4, hipMemcpyHostToDevice, s));
-    BCHK(launch_embed_tokens(c->word_embed, c->word_pe, d_tok, c->dstate, bf.x, M, d, s));
-    BCHK(decode_step(c, s, bf, M, T, cap, true, d_logits, V, 0, -1, nullptr, nullptr, beam_size));
-    const int live = beam_size - (int)completed.size();
-    BCHK(launch_beam_topk(d_logits, d_scores, M, V, live, d_topv, d_topi, s));
-    BCHK(hipMemcpyAsync(h_topv, d_topv, (size_t)live * 4, hipMemcpyDeviceToHost, s));
-    BCHK(hipMemcpyAsync(h_topi, d_topi, (size_t)live * 4, hipMemcpyDeviceToHost, s));
-    BCHK(hipStreamSynchronize(s));
-    // Beam.advance (tools/beam.py:68-105)
-    std::vector<Hyp> next;
-    int nprev = 0;
-    for (int r = 0; r < live; ++r) {
-      const int prev = h_topi[r] / V, word = h_topi[r] % V;
-      Hyp h;
-      h.seq = hyps[prev].seq;
-      h.seq.push_back(word);
-      h.score = h_topv[r];
-      if (word == TOK_END) {
-        completed.push_back(std::move(h));
-      } else {
-        last_tok[nprev] = word;
-        h_prev[nprev++] = prev;
-        next.push_back(std::move(h));
-      }
-    }
-    if ((int)completed.size() == beam_size) { hyps.swap(next); break; }  // Beam.done, tfm.py:175-176
-    hyps.swap(next);
-    if (step + 1 < S) {  // reorder the self-attention caches to the surviving hypotheses
-      BCHK(hipMemcpyAsync(d_prev, h_prev, (size_t)nprev * 4, hipMemcpyHostToDevice, s));
-      BCHK(launch_cache_gather(c->skv_cur, skv_other, d_prev, g.dec_layers * 2, cap, nprev, heads, Lmax, hd, step + 1,
-                               s));
-      std::swap(c->skv_cur, skv_other);
-    }
-  }
-  BCHK(hipStreamSynchronize(s));
-#undef BCHK
-  if (completed.empty()) {  // Beam.set_hypothesis (beam.py:132-140): hypotheses[0, 1:] incl. trailing [PAD]s
-    Hyp h = hyps.empty() ? Hyp{} : hyps[0];
-    h.seq.resize((size_t)g.max_seq_len + 1, TOK_PAD);
-    completed.push_back(std::move(h));
-  }
-  size_t best = 0;
-  for (size_t i = 1; i < completed.size(); ++i)
-    if ((double)completed[i].score / (double)std::max<size_t>(1, completed[i].seq.size()) >
-        (double)completed[best].score / (double)std::max<size_t>(1, completed[best].seq.size()))
-      best = i;
-  const Hyp& bh = completed[best];
-  const int n = (int)std::min<size_t>(bh.seq.size(), (size_t)S);
-  for (int i = 0; i < n; ++i) seq_out[i] = bh.seq[i];
-  *len_out = n;
-  *score_out = bh.score;
-  return done(D2T_OK);
+  // TransformerPrediction.forward_beam (tfm.py:145-186) with tools/beam.py:38-140 bookkeeping, a fresh beam per call (demo
+  // reset_beam semantics): the batched search with N = 1.
+  return d2t_decode_beam_batch(c, memory, 1, T, beam_size, seq_out, len_out, score_out, stream);
 }
 
 int d2t_decode_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
@@ -2120,8 +1852,9 @@ int d2t_decode_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T,
   DevGuard dg_(c);
   // forward_beam (tfm.py:145-186) + Beam (tools/beam.py) for N samples AT ONCE: the hypotheses of all samples are rows
   // of one step loop (each row attends over its own sample's cross K/V through a row map), log_softmax + top-k run per
-  // sample segment, the bookkeeping of every sample is the single-sample one.  Results equal N calls of
-  // d2t_decode_beam; the point is throughput (one host round trip per step instead of N).
+  // sample segment, the bookkeeping of every sample is the single-sample one (d2t_decode_beam is this search with N = 1).
+  // The absorbed d_model-256 decoder runs it on the device (beam_device_impl); the others (d_model 512) and
+  // beam_shared_tile keep this host-side loop with one round trip per step.
   if (!c || !memory || !seq_out || !len_out || !score_out || N < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
   if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
   if (beam_size < 1 || beam_size > 16) return fail(c, D2T_EINVAL, "beam_size must be in [1,16]");
@@ -2162,9 +1895,8 @@ int d2t_decode_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T,
   int* d_seg = d_prev + cap;
   int* d_step = d_seg + 3 * (size_t)N;
   int* d_anc[2] = {reinterpret_cast<int*>(d_pack + pack_bytes), reinterpret_cast<int*>(d_pack + pack_bytes) + (size_t)cap * Lmax};
-  char* hp = nullptr;
-  if (hipHostMalloc(reinterpret_cast<void**>(&hp), pack_bytes + 2 * (size_t)cap * 4 + 64, hipHostMallocDefault) != hipSuccess)
-    return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
+  if ((rc = ensure_host_beam(c, pack_bytes + 2 * (size_t)cap * 4))) return rc;
+  char* hp = c->h_beam;
   int64_t* h_tok = reinterpret_cast<int64_t*>(hp);
   float* h_scores = reinterpret_cast<float*>(h_tok + cap);
   int* h_map = reinterpret_cast<int*>(h_scores + cap);
@@ -2173,17 +1905,11 @@ int d2t_decode_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T,
   int* h_step = h_seg + 3 * (size_t)N;
   float* h_topv = reinterpret_cast<float*>(hp + pack_bytes);  // [topv | topi]: one device -> host copy per step
   int* h_topi = reinterpret_cast<int*>(h_topv + cap);
-  auto done = [&](int code) { hipHostFree(hp); return code; };
-#define BCHK(expr)                                                                              \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return done(fail(c, D2T_EHIP, "%s: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
-  BCHK(hipEventRecord(c->ev_in, user));
-  BCHK(hipStreamWaitEvent(s, c->ev_in, 0));
-  BCHK(hipMemsetAsync(c->dstate, 0, (size_t)(4 + cap) * 4, s));
+  HIPCHK(c, hipEventRecord(c->ev_in, user));
+  HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
+  HIPCHK(c, hipMemsetAsync(c->dstate, 0, (size_t)(4 + cap) * 4, s));
   c->ckv = c->ckv2[0];
-  BCHK(cross_kv(c, s, memory, N, T));
+  HIPCHK(c, cross_kv(c, s, memory, N, T));
   c->skv_cur = c->skv;
   float* skv_other = c->skv_alt;
 
@@ -2207,24 +1933,24 @@ int d2t_decode_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T,
       rows += M;
     }
     if (!rows) break;
-    if (step > 0 && nprev != rows) return done(fail(c, D2T_ESTATE, "beam bookkeeping: %d survivors, %d rows", nprev, rows));
+    if (step > 0 && nprev != rows) return fail(c, D2T_ESTATE, "beam bookkeeping: %d survivors, %d rows", nprev, rows);
     *h_step = step;
-    BCHK(hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
     if (use_anc) {
-      BCHK(launch_beam_ancestry(d_anc[(step + 1) & 1], d_anc[step & 1], d_prev, rows, Lmax, d_step, c->dstate, s));
+      HIPCHK(c, launch_beam_ancestry(d_anc[(step + 1) & 1], d_anc[step & 1], d_prev, rows, Lmax, d_step, c->dstate, s));
     } else {
-      BCHK(launch_beam_ancestry(nullptr, nullptr, d_prev, 1, 0, d_step, c->dstate, s));  // publishes the step only
+      HIPCHK(c, launch_beam_ancestry(nullptr, nullptr, d_prev, 1, 0, d_step, c->dstate, s));  // publishes the step only
       if (step > 0) {  // the survivors' caches move to their new row positions
-        BCHK(launch_cache_gather(c->skv_cur, skv_other, d_prev, g.dec_layers * 2, cap, rows, heads, Lmax, hd, step, s));
+        HIPCHK(c, launch_cache_gather(c->skv_cur, skv_other, d_prev, g.dec_layers * 2, cap, rows, heads, Lmax, hd, step, s));
         std::swap(c->skv_cur, skv_other);
       }
     }
-    BCHK(launch_embed_tokens(c->word_embed, c->word_pe, d_tok, c->dstate, bf.x, rows, d, s));
-    BCHK(decode_step(c, s, bf, rows, T, cap, false, d_logits, V, 0, N, d_map, nullptr, beam_size, d_seg,
-                     use_anc ? d_anc[step & 1] : nullptr));
-    BCHK(launch_beam_topk_batch(d_logits, d_scores, d_seg, N, V, beam_size, d_topv, d_topi, s));
-    BCHK(hipMemcpyAsync(h_topv, d_topv, 2 * (size_t)cap * 4, hipMemcpyDeviceToHost, s));
-    BCHK(hipStreamSynchronize(s));
+    HIPCHK(c, launch_embed_tokens(c->word_embed, c->word_pe, d_tok, c->dstate, bf.x, rows, d, s));
+    HIPCHK(c, decode_step(c, s, bf, rows, T, cap, d_logits, V, 0, N, d_map, nullptr, beam_size, d_seg,
+                          use_anc ? d_anc[step & 1] : nullptr));
+    HIPCHK(c, launch_beam_topk_batch(d_logits, d_scores, d_seg, N, V, beam_size, d_topv, d_topi, s));
+    HIPCHK(c, hipMemcpyAsync(h_topv, d_topv, 2 * (size_t)cap * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
     nprev = 0;
     for (int i = 0; i < N; ++i) {  // Beam.advance (tools/beam.py:68-105) per sample
       if (finished[i]) continue;
@@ -2250,8 +1976,7 @@ int d2t_decode_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T,
       if ((int)completed[i].size() == beam_size) { finished[i] = 1; nprev = first_prev; }  // Beam.done: its rows drop out
     }
   }
-  BCHK(hipStreamSynchronize(s));
-#undef BCHK
+  HIPCHK(c, hipStreamSynchronize(s));
   for (int i = 0; i < N; ++i) {
     std::vector<Hyp>& comp = completed[i];
     bool padded = false;
@@ -2274,7 +1999,7 @@ int d2t_decode_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T,
     len_out[i] = n;
     score_out[i] = bh.score;
   }
-  return done(D2T_OK);
+  return D2T_OK;
 }
 
 int d2t_set_reserved_blocks(d2t_ctx* c, int32_t blocks) {

@@ -285,15 +285,12 @@ struct ArgmaxP {
 };
 hipError_t launch_argmax_embed(const ArgmaxP& p, hipStream_t s);
 
-// ---- beam search helpers (tools/beam.py semantics, one sample) ----
+// ---- beam search helpers (tools/beam.py semantics) ----
 // x[i] = emb[tok[i]]*sqrt(d) + pe[*step]
 hipError_t launch_embed_tokens(const float* emb, const float* pe, const int64_t* tok, const int* step_ptr, float* x,
                                int M, int d, hipStream_t s, const int* rows_ptr = nullptr, const int* stop = nullptr);
-// cand[i*V+v] = score[i] + log_softmax(logits[i])[v]; the k best (value desc, flat index asc on ties)
-// are written to topv[k], topi[k].  One block; M*V <= 16 * 4096.
-hipError_t launch_beam_topk(const float* logits, const float* scores, int M, int V, int k, float* topv, int* topi,
-                            hipStream_t s);
-// the same for N independent segments of rows: seg[i] = {first row, rows, k}; results at topv/topi[i * kmax ...]
+// N independent segments of rows, seg[n] = {first row, rows <= 16, k}: cand[i*V+v] = score[i] + log_softmax(logits[i])[v]
+// over the segment's rows i; its k best (value desc, flat index asc on ties) at topv/topi[n * kmax ...].  One block each.
 hipError_t launch_beam_topk_batch(const float* logits, const float* scores, const int* seg, int N, int V, int kmax,
                                   float* topv, int* topi, hipStream_t s, const int* step = nullptr, const int* stop = nullptr);
 // Device-side beam bookkeeping (round 4; tools/beam.py:68-105 without a host round trip).  State block `BeamDev`: every array lives

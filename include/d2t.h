@@ -220,11 +220,13 @@ int d2t_decode_wait_ticket(d2t_ctx* ctx, int64_t ticket, d2t_stream stream, int3
  * memory [1,T,d].  seq_out: HOST buffer of max_seq_len+1 int64; *len_out its
  * used length; *score_out the hypothesis score (tools/beam.py semantics:
  * best = argmax score/len over completed hypotheses).
- * d_model 256 (round 4): Beam.advance (tools/beam.py:68-105) runs on the device -- candidate walk, completed set, row
- * compaction and a (parent, token) history per step in one single-block kernel -- and the whole max_seq_len + 1 step loop is
- * ONE captured graph per (N, T, beam); the host copies one result block back and walks the best hypothesis through the
- * history.  d2t_decode_beam is that loop with N = 1 (the same row kernels as d2t_decode_beam_batch: bit-identical).  Other
- * decoders (d_model 512) and d2t_set_beam_shared_tile(1) keep the host-side loop with one round trip per step. */
+ * Every single-sample beam call is its batched call with N = 1 (d2t_decode_beam = d2t_decode_beam_batch,
+ * d2t_decode_attn_beam = d2t_decode_attn_beam_batch); which loop runs depends on the decoder.  d_model 256 (round 4):
+ * Beam.advance (tools/beam.py:68-105) runs on the device -- candidate walk, completed set, row compaction and a
+ * (parent, token) history per step in one single-block kernel -- and the whole max_seq_len + 1 step loop is ONE captured
+ * graph per (N, T, beam); the host copies one result block back and walks the best hypothesis through the history.  Other
+ * TFM decoders (d_model 512), d2t_set_beam_shared_tile(1) and the LSTM-attention heads run a host-side loop with one
+ * round trip per step. */
 int d2t_decode_beam(d2t_ctx* ctx, const float* memory_dev, int32_t T, int32_t beam_size, int64_t* seq_out,
                     int32_t* len_out, float* score_out, d2t_stream stream);
 
@@ -242,7 +244,8 @@ int d2t_decode_beam_batch(d2t_ctx* ctx, const float* memory, int32_t N, int32_t 
 /* LSTM-attention beam search for ONE sample (reference: Attention.forward_beam, prediction_head/seq2seq.py:83-222;
  * AttentionV2.forward_beam, seq2seq_v2.py:12-174 -- what config/test.yaml runs with beam_size 5 / 10).  Coverage
  * attention only.  memory [1][T][256]; seq_out (host, >= batch_max_length + 1 entries) receives the token ids without
- * the leading [GO]; *score_out the reference's returned score.  1 <= beam_size <= 16. */
+ * the leading [GO]; *score_out the reference's returned score.  1 <= beam_size <= 16.  d2t_decode_attn_beam_batch with
+ * N = 1. */
 int d2t_decode_attn_beam(d2t_ctx* ctx, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out,
                          int32_t* len_out, float* score_out, d2t_stream stream);
 

@@ -262,6 +262,38 @@ def test_beam_vs_oracle_other_seeds(cases, manifests):
         assert abs(score - oscore) <= _score_tol(m, seq.shape[1])
 
 
+def test_d_model_512_beam_vs_oracle_and_batched(manifests):
+    """T1 (d_model 512): the decoder whose beam search runs the host-side step loop.  The reference-shaped single-sample
+    call against the oracle, then the batched call against the single-sample one on every sample.  At these [s] biases
+    some samples complete before the length limit and others run into it."""
+    L = 12
+    kinds = set()
+    for iseed, eb, beam in [(702, 4.0, 5), (703, 2.9, 4), (704, 5.0, 3)]:
+        cfg, m = engine_model("T1", L, 1234, eb, beam_size=beam)
+        ocfg, sd = oracle_state_dict("T1", manifests["T1"], L, 1234, eb)
+        ocfg["beam_size"] = beam
+        img = synth.synth_images(1, 32, 64, seed=iseed)
+        text = torch.full((1, 1), R.GO, dtype=torch.long)
+        with torch.no_grad():
+            seq, score, _ = m(img.cuda(), text.cuda(), is_train=False, is_test=True)
+            oseq, oscore, _ = R.forward(ocfg, sd, img, text, is_test=True)
+        assert seq[0].tolist() == oseq[0].tolist(), (iseed, eb, beam)
+        assert abs(score - oscore) <= _score_tol(m, seq.shape[1])
+        kinds.add(R.END in seq[0].tolist())
+    assert kinds == {True, False}
+    cfg, m = engine_model("T1", L, 1234, 2.9, beam_size=4)
+    img = torch.cat([synth.synth_images(1, 32, 64, seed=s) for s in range(701, 707)]).cuda()
+    text = torch.full((1, 1), R.GO, dtype=torch.long, device="cuda")
+    with torch.no_grad():
+        single = [m(img[i:i + 1], text, is_train=False, is_test=True)[:2] for i in range(6)]
+        batch = m.beam_search_batch(img)
+    assert len(batch) == 6
+    for i, ((s1, v1), (s2, v2)) in enumerate(zip(single, batch)):
+        assert torch.equal(s1, s2), i
+        assert v1 == v2, i
+    assert {R.END in s[0].tolist() for s, _ in single} == {True, False}
+
+
 @pytest.mark.parametrize("name", ["ts0_beam5", "c0_beam3", "c0_beam3_end", "s0_beam10", "s0_beam10_late", "ts0_beam4_nofinish",
                                   "b0_beam3", "b0_beam3_end", "tb0_beam4", "to0_beam5", "to0_beam5_end"])
 def test_attn_beam_vs_reference_fixture(cases, name):
