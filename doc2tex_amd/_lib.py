@@ -45,6 +45,7 @@ NORM_ALB, NORM_RAW = 0, 1
 PREP_OK, PREP_UNBOUND_LOCAL, PREP_FALLBACK = 0, 1, 2
 PREP_FLAG_PASTE_MISMATCH = 1
 POST_NONE, POST_API, POST_DEMO = 0, 1, 2
+ATTN_MAP_BUDGET = 256 << 20  # include/d2t.h D2T_ATTN_MAP_BUDGET: bytes of a beam search's alignment history
 
 _P = C.c_void_p
 _I = C.c_int32
@@ -62,6 +63,7 @@ SIGNATURES = {
     "d2t_encode": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "d2t_decode_greedy": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, C.POINTER(_I), _P]),
     "d2t_decode_attn_greedy": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(_I), _P]),
+    "d2t_decode_attn_greedy_alpha": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, C.POINTER(_I), _P]),
     "d2t_decode_greedy_async": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "d2t_decode_wait": (_I, [_P, _P, _I]),
     "d2t_decode_greedy_submit": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, C.POINTER(_L)]),
@@ -72,6 +74,8 @@ SIGNATURES = {
     "d2t_decode_beam": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_decode_beam_batch": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_decode_attn_beam_batch": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
+    "d2t_decode_attn_beam_batch_alpha": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P,
+                                               _P]),
     "d2t_decode_attn_beam": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_set_conv_precision": (_I, [_P, _I]),
     "d2t_set_mixed_units": (_I, [_P, _I]),
@@ -93,6 +97,7 @@ SIGNATURES = {
     "d2t_train_decision_count": (_I, [_P]),
     "d2t_train_read_decision": (_I, [_P, _I, _P, C.c_int64, C.POINTER(_I), C.POINTER(C.c_int64), _P]),
     "d2t_train_read_mask": (_I, [_P, _I, _P, C.c_int64, _P]),
+    "d2t_train_read_attn_alpha": (_I, [_P, _P, C.c_int64, _P]),
     "d2t_train_release": (None, [_P]),
     "d2t_profile_enable": (_I, [_P, _I]),
     "d2t_profile_read": (_I, [_P, _I, C.POINTER(_I)] + [C.POINTER(_I)] * 3 + [C.POINTER(C.c_float)]),

@@ -17,6 +17,19 @@ from . import params as P
 from .engine import Engine
 
 
+def decoder_attn_outputs(stages, decoder_attn, output_shape, feat_pad):
+    """The alignment-map entries Model.forward adds to addition_outputs (reference build_model.py:66-77): none unless
+    the decoder returned a map (LSTM-attention beam search with viz_attn) AND the encoder reports a feature grid (ViT).
+    An Attn (v1) head on the ViT attends over the cls row too; that row is dropped before the map is laid on the grid.
+    The key names are the reference's: "feat_width" is output_shape[0], "feat_height" output_shape[1]."""
+    if decoder_attn is None or output_shape is None:
+        return {}
+    if stages["Pred"] == "Attn" and stages["Seq"] == "ViT":
+        decoder_attn = decoder_attn[:, 1:]
+    decoder_attn = decoder_attn.reshape(-1, output_shape[0], output_shape[1])
+    return {"decoder_attn": decoder_attn, "feat_width": output_shape[0], "feat_height": output_shape[1], "feat_pad": feat_pad}
+
+
 class FeatExtractorBuilder(nn.Module):
     """recognizers/build_feat.py:8-63 (parameter tree; ResNet or VGG; the height-mean for Seq=BiLSTM
     runs inside the engine)."""
@@ -210,15 +223,29 @@ class Model(nn.Module):
         # data-parallel training: a doc2tex_amd.dist.GradSync makes loss.backward() return all-reduced (mean) gradients
         self.grad_sync = None
 
-    def beam_search_batch(self, input, beam_size=None):
+    def beam_search_batch(self, input, beam_size=None, return_attn=False):
         """Extension (the reference's beam search takes one sample per call, tfm.py:146-148): encode the whole batch
         and advance the hypotheses of all samples in one step loop.  Returns [(LongTensor [1, len], score)] per
-        sample, each identical to `forward(input[i:i+1], ...)` with `beam_size` set."""
+        sample, each identical to `forward(input[i:i+1], ...)` with `beam_size` set.
+
+        return_attn (LSTM-attention heads): [(seq, score, decoder_attn)] per sample, decoder_attn [len, Tk] being what
+        forward_decoder returns for that sample alone with viz_attn set (decoder_attn_outputs lays it on the feature grid).
+        A batch whose alignment history would exceed _lib.ATTN_MAP_BUDGET bytes is searched in several parts."""
         beam = int(beam_size or self.opt.get("beam_size", 1))
         memory, _, _ = self.forward_encoder(input)
         if self.stages["Pred"] == "TFM":
+            if return_attn:
+                raise ValueError("the TFM head has no decoder alignment maps (build_pred.py:46-49)")
             return self.engine().decode_beam_batch(memory.contiguous(), beam)
-        return self.engine().decode_attn_beam_batch(memory.contiguous(), beam)
+        eng = self.engine()
+        if not return_attn:
+            return eng.decode_attn_beam_batch(memory.contiguous(), beam)
+        from . import _lib
+        per = max(1, _lib.ATTN_MAP_BUDGET // max(1, eng.attn_map_bytes(memory.shape[1], beam)))
+        out = []
+        for a in range(0, memory.shape[0], per):
+            out += eng.decode_attn_beam_batch(memory[a:a + per].contiguous(), beam, return_alpha=True)
+        return out
 
     def _group_decode(self, eng, memory, start, is_test=False):
         """pipelined + decode_group > 1: collect the encoder memories of consecutive calls, launch one decode per group.
@@ -376,10 +403,24 @@ class Model(nn.Module):
                     "memory): call model.eval() and pass is_train=False (engine/inferencing.py:70-76).  The teacher-forced "
                     "training pass of the LSTM-attention head runs through Model.forward() under model.train(), which keeps "
                     "the whole step on one autograd node")
-            if beam_size > 1:  # seq2seq.py:333-347 -> forward_beam (one sample, returns (seq, score, None))
-                prediction, logits = eng.decode_attn_beam(contextual_feature.contiguous(), beam_size)
+            pred = self.predicter.Prediction
+            viz = bool(getattr(pred, "viz_attn", False))  # read on every call, like the reference (seq2seq.py:124,267)
+            if beam_size > 1:  # seq2seq.py:333-347 -> forward_beam (one sample, returns (seq, score, alphas or None))
+                if not viz:
+                    prediction, logits = eng.decode_attn_beam(contextual_feature.contiguous(), beam_size)
+                    return prediction, logits, None, {}
+                if contextual_feature.shape[0] != 1:
+                    raise AssertionError("forward_beam takes one sample (seq2seq.py:90)")
+                prediction, logits, alphas = eng.decode_attn_beam_batch(contextual_feature.contiguous(), beam_size,
+                                                                        return_alpha=True)[0]
+                return prediction, logits, alphas, {}
+            if not viz:
+                prediction, logits = eng.decode_attn_greedy(contextual_feature.contiguous(), is_test)
                 return prediction, logits, None, {}
-            prediction, logits = eng.decode_attn_greedy(contextual_feature.contiguous(), is_test)
+            # greedy: the alignments go to Prediction.alpha_stores [B, S, Tk, 1] (seq2seq.py:267-272,300-301), not to the
+            # return value
+            prediction, logits, alpha = eng.decode_attn_greedy(contextual_feature.contiguous(), is_test, return_alpha=True)
+            pred.alpha_stores = alpha.unsqueeze(-1)
             return prediction, logits, None, {}
         if self.training:
             raise NotImplementedError(
@@ -430,5 +471,6 @@ class Model(nn.Module):
         contextual_feature, output_shape, feat_pad = self.forward_encoder(input)
         prediction, logits, decoder_attn, addition_outputs = self.forward_decoder(
             contextual_feature, text=text, is_train=is_train, is_test=is_test, rtl_text=rtl_text)
-        # decoder_attn is always None for the TFM head (build_pred.py:34,46-49)
+        # decoder_attn is always None for the TFM head (build_pred.py:34,46-49) and for greedy decoding
+        addition_outputs.update(decoder_attn_outputs(self.stages, decoder_attn, output_shape, feat_pad))
         return prediction, logits, addition_outputs

@@ -453,6 +453,7 @@ void d2t_destroy(d2t_ctx* c) {
   if (c->skv) hipFree(c->skv);
   if (c->skv_alt) hipFree(c->skv_alt);
   if (c->beam_ws) hipFree(c->beam_ws);
+  if (c->beam_hist) hipFree(c->beam_hist);
   if (c->h_beam) hipHostFree(c->h_beam);
   if (c->beam_qp) hipFree(c->beam_qp);
   if (c->dws) hipFree(c->dws);
@@ -1390,6 +1391,11 @@ AttnDecP attn_dec_params(const d2t_ctx* c, const float* memory, int T, const flo
 
 int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
                            float* probs, int32_t* steps_out, d2t_stream stream) {
+  return d2t_decode_attn_greedy_alpha(c, memory, B, T, is_test, tokens, probs, nullptr, steps_out, stream);
+}
+
+int d2t_decode_attn_greedy_alpha(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                                 float* probs, float* alpha, int32_t* steps_out, d2t_stream stream) {
   DevGuard dg_(c);
   if (!c || !memory || !tokens || !probs || !steps_out || B < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
   if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
@@ -1408,6 +1414,7 @@ int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T
   HIPCHK(c, hipMemsetAsync(end_step, 0xFF, (size_t)B * 4, s));  // -1 = never emitted [s]
   AttnDecP p = attn_dec_params(c, memory, T, kp);
   p.probs = probs; p.tokens = tokens; p.end_step = end_step;
+  p.sv_alpha = alpha;  // optional [B][S][Tk]: the alignment of every step (viz_attn, seq2seq.py:267-272,300-301)
   p.B = B; p.S = S;
   HIPCHK(c, launch_attn_decode(p, s));
   int steps = S;
@@ -1423,6 +1430,8 @@ int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T
       steps = last + 1;
       HIPCHK(c, hipMemset2DAsync(probs + (size_t)steps * V, (size_t)S * V * 4, 0, (size_t)(S - steps) * V * 4, B, s));
       HIPCHK(c, hipMemset2DAsync(tokens + steps, (size_t)S * 8, 0, (size_t)(S - steps) * 8, B, s));
+      const size_t Tk = (size_t)(T - key_off);
+      if (alpha) HIPCHK(c, hipMemset2DAsync(alpha + (size_t)steps * Tk, (size_t)S * Tk * 4, 0, (size_t)(S - steps) * Tk * 4, B, s));
     }
   }
   *steps_out = steps;
@@ -1439,6 +1448,11 @@ int d2t_decode_attn_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t bea
 
 int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
                                int32_t* len_out, float* score_out, d2t_stream stream) {
+  return d2t_decode_attn_beam_batch_alpha(c, memory, N, T, beam_size, seq_out, len_out, score_out, nullptr, stream);
+}
+
+int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
+                                     int32_t* len_out, float* score_out, float* alpha_out, d2t_stream stream) {
   DevGuard dg_(c);
   // Attention / AttentionV2.forward_beam for N samples in one step loop: rows = live hypotheses of all samples, each
   // attending over its own sample's keys (row map).  The attention cell + LSTMCell + generator of every live hypothesis run
@@ -1461,6 +1475,19 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
   if (Tk < 1 || Tk > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
   hipStream_t s = (hipStream_t)stream;
   int rc;
+  // alignment maps (viz_attn): every step's launch writes its rows' alignments into its own slice of a history
+  // [S][cap][Tk], kept apart from the workspace below; the chosen paths [N][S] and lengths [N] follow it
+  float* d_hist = nullptr;
+  int* d_path = nullptr;
+  if (alpha_out) {
+    const size_t hist_bytes = (size_t)S * cap * Tk * 4;
+    if (hist_bytes > D2T_ATTN_MAP_BUDGET)
+      return fail(c, D2T_EINVAL, "beam alignment history of %zu bytes (%d steps x %d samples x beam %d x %d keys x 4) exceeds the "
+                  "%llu-byte budget: decode fewer samples per call", hist_bytes, S, N, beam_size, Tk, (unsigned long long)D2T_ATTN_MAP_BUDGET);
+    if ((rc = ensure(c, &c->beam_hist, &c->beam_hist_cap, hist_bytes + ((size_t)N * (S + 1) + 16) * 4))) return rc;
+    d_hist = c->beam_hist;
+    d_path = reinterpret_cast<int*>(d_hist + (size_t)S * cap * Tk);
+  }
   if ((rc = ensure(c, &c->dws, &c->dws_cap, ((size_t)N * T * Hh + 16) * 4))) return rc;
   float* kp = c->dws;
   // workspace: logits [cap][V] | topv [cap] | topi [cap] (one device -> host copy per step) | h_in c_in h_out c_out [cap][H]
@@ -1511,6 +1538,7 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
 
   struct Smp {
     std::vector<std::vector<int64_t>> seqs, complete;
+    std::vector<std::vector<int>> paths, cpaths;  // maps only: per hypothesis, the launch row of its parent at every step
     std::vector<float> live, cscores;
     int k;
     bool last_completed = false, finished = false;
@@ -1520,6 +1548,7 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
     x.seqs.assign((size_t)beam_size, std::vector<int64_t>{0});  // each starts with [GO] = 0
     x.live.assign((size_t)beam_size, 0.f);
     x.k = beam_size;
+    if (alpha_out) x.paths.assign((size_t)beam_size, std::vector<int>{});
   }
   // the rows of a step in sample order: segments, scores and row map into the pack; returns the row count
   auto stage = [&](int step) {
@@ -1538,6 +1567,7 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
   HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
   for (int step = 0; step < S; ++step) {
     p.B = rows; p.first = step == 0;
+    if (d_hist) p.sv_alpha = d_hist + (size_t)step * cap * Tk;
     HIPCHK(c, launch_attn_decode(p, s));
     HIPCHK(c, launch_beam_topk_batch(d_logits, d_scores, d_seg, N, V, beam_size, d_topv, d_topi, s));
     HIPCHK(c, hipMemcpyAsync(h_topv, d_topv, 2 * (size_t)cap * 4, hipMemcpyDeviceToHost, s));
@@ -1548,14 +1578,21 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
       if (x.finished) continue;
       const int off = h_seg[3 * i];
       std::vector<std::vector<int64_t>> nseqs;
+      std::vector<std::vector<int>> npaths;
       std::vector<float> nscores;
       x.last_completed = false;
       for (int r = 0; r < x.k; ++r) {
         const int idx = h_topi[(size_t)i * beam_size + r], prev = idx / V, word = idx % V;
         std::vector<int64_t> sq = x.seqs[prev];
         sq.push_back(word);
+        std::vector<int> pa;
+        if (alpha_out) {  // the step's alignment row of this hypothesis = its parent's row: seqs_alpha[prev_word_inds]
+          pa = x.paths[prev];
+          pa.push_back(off + prev);
+        }
         if (word == 1) {  // [s] (attn_converter.py:8)
           x.complete.push_back(std::move(sq));
+          if (alpha_out) x.cpaths.push_back(std::move(pa));
           x.cscores.push_back(h_topv[(size_t)i * beam_size + r]);
           x.last_completed = true;
         } else {
@@ -1564,10 +1601,12 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
           h_tok[nrows] = word;
           ++nrows;
           nseqs.push_back(std::move(sq));
+          if (alpha_out) npaths.push_back(std::move(pa));
           nscores.push_back(h_topv[(size_t)i * beam_size + r]);
         }
       }
       x.seqs.swap(nseqs);
+      x.paths.swap(npaths);
       x.live.swap(nscores);
       x.k = (int)x.seqs.size();
       if (x.k == 0) x.finished = true;
@@ -1580,24 +1619,39 @@ int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32
     HIPCHK(c, launch_gather_rows(st[5], st[4], d_idxm, rows, Tk, s));
   }
   HIPCHK(c, hipStreamSynchronize(s));
+  std::vector<int> h_path;  // maps: [N][S] chosen paths | [N] lengths, uploaded in one copy
+  if (alpha_out) h_path.assign((size_t)N * (S + 1), 0);
   for (int i = 0; i < N; ++i) {
     Smp& x = sm[i];
     std::vector<int64_t> out;
+    const std::vector<int>* path = nullptr;
     float score;
     if (!x.last_completed) {  // seq2seq.py:209-216
       out.assign(x.seqs[0].begin() + 1, x.seqs[0].end());
       score = x.live[0];
+      if (alpha_out) path = &x.paths[0];
     } else {
       size_t best = 0;
       for (size_t j = 1; j < x.complete.size(); ++j)
         if ((double)x.cscores[j] / (double)x.complete[j].size() > (double)x.cscores[best] / (double)x.complete[best].size()) best = j;
       out.assign(x.complete[best].begin() + 1, x.complete[best].end());
       score = *std::max_element(x.cscores.begin(), x.cscores.end());
+      if (alpha_out) path = &x.cpaths[best];
     }
     const int n = (int)std::min<size_t>(out.size(), (size_t)S);
     for (int j = 0; j < n; ++j) seq_out[(size_t)i * S + j] = out[j];
     len_out[i] = n;
     score_out[i] = score;
+    if (alpha_out) {  // one path entry per emitted token; entries index rows of that step's launch (< cap)
+      const int m = (int)std::min<size_t>(path->size(), (size_t)n);
+      for (int j = 0; j < m; ++j) h_path[(size_t)i * S + j] = (*path)[j];
+      h_path[(size_t)N * S + i] = m;
+    }
+  }
+  if (alpha_out) {  // seqs_alpha[best][1:] of every sample: one upload, one gather over all samples
+    HIPCHK(c, hipMemcpyAsync(d_path, h_path.data(), h_path.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, launch_attn_alpha_gather(d_hist, d_path, d_path + (size_t)N * S, alpha_out, N, S, cap, Tk, s));
+    HIPCHK(c, hipStreamSynchronize(s));  // h_path is pageable and local
   }
   return D2T_OK;
 }

@@ -199,6 +199,10 @@ hipError_t launch_sum_over_rows(const float* part, float* out, int B, int C, hip
 // dst[i][0..width) = src[idx[i]][0..width)
 hipError_t launch_gather_rows(const float* src, float* dst, const int* idx, int rows, int width, hipStream_t s);
 hipError_t launch_attn_decode(const AttnDecP& p, hipStream_t s);
+// Beam-search alignment maps from the step history hist [S][cap][Tk]: out [N][S][Tk], row j of sample i =
+// hist[j][path[i*S + j]] for j < len[i], zeros beyond.  out must be 16-byte aligned.
+hipError_t launch_attn_alpha_gather(const float* hist, const int* path, const int* len, float* out, int N, int S, int cap,
+                                    int Tk, hipStream_t s);
 // dst[(row_off + c) * ld + r] = src[r * cols + c]
 hipError_t launch_transpose_into(const float* src, int rows, int cols, float* dst, int ld, int row_off, hipStream_t s);
 hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* y, int rows, int D, float eps,

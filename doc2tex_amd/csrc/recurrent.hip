@@ -3,6 +3,9 @@
 // LSTMCell attention decoder (prediction_head/seq2seq.py:224-331, seq2seq_v2.py:176-293,
 // addon_module/attention1D.py:121-161,203-242).  These paths are sequential in time and
 // row-local, so each is ONE launch that loops over all time steps inside the kernel.
+#include <algorithm>
+#include <cstdint>
+
 #include "kernels.h"
 
 namespace d2t {
@@ -702,6 +705,61 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, float* __restr
 hipError_t launch_gather_rows(const float* src, float* dst, const int* idx, int rows, int width, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, s, src, dst, idx, width);
+  return hipGetLastError();
+}
+
+// Beam-search alignment maps: out[i][j][:] = hist[j][path[i*S + j]][:] for j < len[i], zeros for len[i] <= j < S.
+// The output is walked as flat float4 chunks, so every store is 16 bytes (out comes from a 256-byte aligned allocation;
+// a ragged tail of numel % 4 elements is stored one by one).  A chunk that lies inside one alignment row whose source is
+// 16-byte aligned is read with one float4 load, any other chunk element by element.
+__global__ void attn_alpha_gather_kernel(const float* __restrict__ hist, const int* __restrict__ path,
+                                         const int* __restrict__ len, float* __restrict__ out, int N, int S, int cap, int Tk) {
+  const size_t numel = (size_t)N * S * Tk;
+  const size_t chunks = (numel + 3) / 4;
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < chunks; k += (size_t)gridDim.x * blockDim.x) {
+    const size_t e0 = k * 4;
+    const size_t r0 = e0 / Tk;
+    const int t0 = (int)(e0 - r0 * Tk);
+    float v[4];
+    if (t0 + 4 <= Tk) {  // one row
+      const int i = (int)(r0 / S), j = (int)(r0 - (size_t)i * S);
+      if (j >= len[i]) {
+        v[0] = v[1] = v[2] = v[3] = 0.f;
+      } else {
+        const size_t src = ((size_t)j * cap + path[(size_t)i * S + j]) * Tk + t0;
+        if ((src & 3) == 0) {
+          const float4 q = *reinterpret_cast<const float4*>(hist + src);
+          v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) v[u] = hist[src + u];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const size_t e = e0 + u;
+        v[u] = 0.f;
+        if (e >= numel) continue;
+        const size_t r = e / Tk;
+        const int t = (int)(e - r * Tk), i = (int)(r / S), j = (int)(r - (size_t)i * S);
+        if (j < len[i]) v[u] = hist[((size_t)j * cap + path[(size_t)i * S + j]) * Tk + t];
+      }
+    }
+    if (e0 + 4 <= numel) {
+      *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      for (int u = 0; e0 + u < numel; ++u) out[e0 + u] = v[u];
+    }
+  }
+}
+hipError_t launch_attn_alpha_gather(const float* hist, const int* path, const int* len, float* out, int N, int S, int cap,
+                                    int Tk, hipStream_t s) {
+  if (N <= 0 || S <= 0 || Tk <= 0) return hipSuccess;
+  if (reinterpret_cast<uintptr_t>(out) & 15) return hipErrorInvalidValue;  // the float4 stores need a 16-byte aligned base
+  const size_t chunks = ((size_t)N * S * Tk + 3) / 4;
+  const int blocks = (int)std::min<size_t>((chunks + 255) / 256, 2048);
+  hipLaunchKernelGGL(attn_alpha_gather_kernel, dim3(blocks), dim3(256), 0, s, hist, path, len, out, N, S, cap, Tk);
   return hipGetLastError();
 }
 

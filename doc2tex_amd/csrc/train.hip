@@ -1532,6 +1532,23 @@ int d2t_train_read_mask(d2t_ctx* c, int32_t index, uint8_t* dst, int64_t numel, 
   return D2T_OK;
 }
 
+// The alignments the last training forward saved for its backward pass (LSTM-attention heads): [B][S][Tk].
+int d2t_train_read_attn_alpha(d2t_ctx* c, float* dst, int64_t numel, d2t_stream stream) {
+  DevGuard dg_(c);
+  if (!c || !dst) return fail(c, D2T_EINVAL, "bad argument");
+  if (c->cfg.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "the TFM head has no alignment maps");
+  d2t_train_state* st = c->train;
+  if (!st || !st->have_forward) return fail(c, D2T_ESTATE, "no training forward to read the alignments of");
+  for (const Node& n : st->nodes) {
+    if (n.kind != N_LSTM) continue;
+    const int64_t want = (int64_t)n.nb * n.Lq * (n.Lk - n.koff);
+    if (numel != want) return fail(c, D2T_EINVAL, "the saved alignments have %lld elements, not %lld", (long long)want, (long long)numel);
+    HIPCHK(c, hipMemcpyAsync(dst, n.aux[5], (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return D2T_OK;
+  }
+  return fail(c, D2T_ESTATE, "the last training forward ran no LSTM-attention decoder");
+}
+
 int d2t_train_mask_count(d2t_ctx* c) { return c && c->train ? (int)c->train->masks.size() : 0; }
 
 // The discrete decisions of the last training forward, in network order: one entry per ReLU (convolution + BatchNorm

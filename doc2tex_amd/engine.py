@@ -207,6 +207,13 @@ class Engine:
                                                _lib.stream_of(image)), "train_forward")
         return logits
 
+    def read_attn_alpha(self, B, L, Tk, device):
+        """The alignments of the last training forward of an LSTM-attention head, [B, L, Tk] (a fresh tensor: no autograd
+        history)."""
+        a = torch.empty((B, L, Tk), dtype=torch.float32, device=device)
+        self._check(self.lib.d2t_train_read_attn_alpha(self.ctx, _lib.ptr(a), a.numel(), _lib.stream_of(a)), "train_read_attn_alpha")
+        return a
+
     def set_dropout(self, p, seed):
         """Dropout probability of the decoder layers in the training step and the seed of its Philox masks."""
         self._check(self.lib.d2t_train_set_dropout(self.ctx, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF), "train_set_dropout")
@@ -349,18 +356,29 @@ class Engine:
         s = steps.value
         return tokens[:, :s], logits[:, :s]
 
-    def decode_attn_greedy(self, memory, is_test):
-        """Attention/AttentionV2.forward_greedy in eval mode: full-size (preds_index [B,S], probs [B,S,V])."""
+    def attn_keys(self, T):
+        """Keys the LSTM-attention decoder attends over in a memory of T tokens (AttentionV2 + TFM drops the cls row)."""
+        return T - (1 if self.cfg.attn_keys == _lib.ATTN_KEYS_NOCLS_INIT_CLS else 0)
+
+    def decode_attn_greedy(self, memory, is_test, return_alpha=False):
+        """Attention/AttentionV2.forward_greedy in eval mode: full-size (preds_index [B,S], probs [B,S,V]); with
+        return_alpha also the alignment of every step, [B,S,Tk] (zeros after an is_test early exit)."""
         memory = memory.float().contiguous()
         B, T, _ = memory.shape
         S, V = self.cfg.batch_max_length + 1, self.cfg.vocab
         tokens = torch.zeros((B, S), dtype=torch.int64, device=memory.device)
         probs = torch.zeros((B, S, V), dtype=torch.float32, device=memory.device)
         steps = C.c_int32(0)
-        self._check(self.lib.d2t_decode_attn_greedy(self.ctx, _lib.ptr(memory), B, T, int(bool(is_test)),
-                                                    _lib.ptr(tokens), _lib.ptr(probs), C.byref(steps),
-                                                    _lib.stream_of(memory)), "decode_attn_greedy")
-        return tokens, probs
+        if not return_alpha:
+            self._check(self.lib.d2t_decode_attn_greedy(self.ctx, _lib.ptr(memory), B, T, int(bool(is_test)),
+                                                        _lib.ptr(tokens), _lib.ptr(probs), C.byref(steps),
+                                                        _lib.stream_of(memory)), "decode_attn_greedy")
+            return tokens, probs
+        alpha = torch.empty((B, S, self.attn_keys(T)), dtype=torch.float32, device=memory.device)
+        self._check(self.lib.d2t_decode_attn_greedy_alpha(self.ctx, _lib.ptr(memory), B, T, int(bool(is_test)),
+                                                          _lib.ptr(tokens), _lib.ptr(probs), _lib.ptr(alpha), C.byref(steps),
+                                                          _lib.stream_of(memory)), "decode_attn_greedy_alpha")
+        return tokens, probs, alpha
 
     def decode_greedy_async(self, memory, start_tokens, is_test=False):
         """Pipelined greedy decode (max_seq_len+1 steps; with is_test the device stops early): returns (tokens, logits, ticket).  The tensors are fresh
@@ -446,17 +464,30 @@ class Engine:
                                                   C.byref(n), C.byref(score), _lib.stream_of(memory)), "decode_attn_beam")
         return torch.LongTensor(list(seq[: n.value])).unsqueeze(0), torch.tensor(float(score.value))
 
-    def decode_attn_beam_batch(self, memory, beam_size):
-        """LSTM-attention beam search for every sample of memory [N,T,256] in one step loop."""
+    def decode_attn_beam_batch(self, memory, beam_size, return_alpha=False):
+        """LSTM-attention beam search for every sample of memory [N,T,256] in one step loop.  return_alpha: each entry
+        also carries the returned hypothesis's alignment map [len, Tk] (the reference's seqs_alpha[best][1:]), on the
+        memory's device; the call is refused when the step history exceeds _lib.ATTN_MAP_BUDGET bytes."""
         memory = memory.float().contiguous()
-        N, S = memory.shape[0], self.cfg.batch_max_length + 1
+        N, T, S = memory.shape[0], memory.shape[1], self.cfg.batch_max_length + 1
         seq = (C.c_int64 * (N * S))()
         n = (C.c_int32 * N)()
         score = (C.c_float * N)()
-        self._check(self.lib.d2t_decode_attn_beam_batch(self.ctx, _lib.ptr(memory), N, memory.shape[1], int(beam_size), seq,
-                                                        n, score, _lib.stream_of(memory)), "decode_attn_beam_batch")
-        return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i])))
+        if not return_alpha:
+            self._check(self.lib.d2t_decode_attn_beam_batch(self.ctx, _lib.ptr(memory), N, T, int(beam_size), seq,
+                                                            n, score, _lib.stream_of(memory)), "decode_attn_beam_batch")
+            return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i])))
+                    for i in range(N)]
+        alpha = torch.empty((N, S, self.attn_keys(T)), dtype=torch.float32, device=memory.device)
+        self._check(self.lib.d2t_decode_attn_beam_batch_alpha(self.ctx, _lib.ptr(memory), N, T, int(beam_size), seq, n, score,
+                                                              _lib.ptr(alpha), _lib.stream_of(memory)),
+                    "decode_attn_beam_batch_alpha")
+        return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i])), alpha[i, :n[i]])
                 for i in range(N)]
+
+    def attn_map_bytes(self, T, beam_size):
+        """Bytes of alignment history one sample adds to a beam search with maps (d2t_decode_attn_beam_batch_alpha)."""
+        return (self.cfg.batch_max_length + 1) * int(beam_size) * self.attn_keys(T) * 4
 
     def decode_beam_batch(self, memory, beam_size):
         """Beam search for every sample of memory [N,T,d] in one shared step loop: [(LongTensor [1,len], score)] * N,

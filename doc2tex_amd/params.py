@@ -393,6 +393,8 @@ class AttentionParams(_Holder):
         self.kernel_size, self.kernel_dim = kernel_size, kernel_dim
         self.attn_type, self.enc_init, self.seqmodel, self.device = attn_type, enc_init, seqmodel, device
         self.embed_target, self.teacher_forcing = embed_target, teacher_forcing
+        # viz_attn (seq2seq.py:65): read on every forward, so setting it after construction works as in the reference
+        self.viz_attn = viz_attn
         if enc_init:  # init_hidden, seq2seq.py:80-82
             self.proj_init_h = nn.Linear(input_size, hidden_size, bias=True)
             self.proj_init_c = nn.Linear(input_size, hidden_size, bias=True)

@@ -155,6 +155,8 @@ _CONFIGS["TB0"] = copy.deepcopy(_CONFIGS["TS0"])  # tiny HybridViT + Attnv2, Bah
 _CONFIGS["TB0"]["Prediction"]["params"].update({"attn_type": "bahdanau", "embed_target": False, "enc_init": False})
 _CONFIGS["TO0"] = copy.deepcopy(_CONFIGS["TS0"])  # tiny HybridViT + Attnv2, coverage cell, one-hot targets
 _CONFIGS["TO0"]["Prediction"]["params"]["embed_target"] = False
+_CONFIGS["TA0"] = copy.deepcopy(_CONFIGS["TS0"])  # tiny HybridViT + Attn (v1): attends over every token, cls row included,
+_CONFIGS["TA0"]["Prediction"]["name"] = "Attn"     # initial state from token 0 (seq2seq.py:229-238)
 _CONFIGS["TL0"] = copy.deepcopy(_CONFIGS["TS0"])  # Luong cell: constructs, every forward raises (attention_cell.reset_mem)
 _CONFIGS["TL0"]["Prediction"]["params"].update({"attn_type": "luong", "method": "general"})
 _CONFIGS["C3"] = copy.deepcopy(_CONFIGS["C2"])

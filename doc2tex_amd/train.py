@@ -29,6 +29,13 @@ class _TrainStep(torch.autograd.Function):
             flags = [1] + [0 if tf < random.random() else 1 for _ in range(text.shape[1] - 1)]
             eng.set_teacher_flags(None if all(flags) else flags)
         logits = eng.train_forward(image, text)
+        pred = model.predicter.Prediction
+        if not tfm and getattr(pred, "viz_attn", False):
+            # alpha_stores (seq2seq.py:267-272,300-301) from the alignments the step saved for its backward pass.  Unlike the
+            # reference's, this tensor is detached: no gradient flows through it
+            B, _, H, W = image.shape
+            Tk = eng.attn_keys(eng.encoder_shape(H, W)[0])
+            pred.alpha_stores = eng.read_attn_alpha(B, text.shape[1], Tk, logits.device).unsqueeze(-1)
         # BatchNorm side effects of module.train(): running statistics and the batch counter
         with torch.no_grad():
             stats = [(name, buf) for name, buf in model.named_buffers() if name.endswith(("running_mean", "running_var"))]

@@ -183,6 +183,14 @@ int d2t_decode_greedy(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t 
 int d2t_decode_attn_greedy(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T, int32_t is_test,
                            int64_t* tokens_dev, float* probs_dev, int32_t* steps_out, d2t_stream stream);
 
+/* d2t_decode_attn_greedy plus the alignment of every step (the reference's `alpha_stores` with viz_attn,
+ * seq2seq.py:267-272,300-301): alpha_dev [B][S][Tk] fp32, Tk = T - 1 for the Attnv2 + TFM key mode (the cls row is not
+ * a key) and T otherwise.  With is_test the steps after the early exit are zeroed like probs.  alpha_dev NULL =
+ * d2t_decode_attn_greedy. */
+int d2t_decode_attn_greedy_alpha(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T, int32_t is_test,
+                                 int64_t* tokens_dev, float* probs_dev, float* alpha_dev, int32_t* steps_out,
+                                 d2t_stream stream);
+
 /* Pipelined variant: always runs max_seq_len+1 steps (is_test = 0 semantics) and returns as soon as the
  * work is enqueued, so the caller can start encoding the next batch while this one decodes (the decode
  * loop is latency-bound and leaves most CUs idle).  tokens_dev / logits_dev / start_tokens_dev must stay
@@ -234,6 +242,15 @@ int d2t_decode_beam(d2t_ctx* ctx, const float* memory_dev, int32_t T, int32_t be
  * seq_out (host) [N][batch_max_length + 1]; len_out, score_out (host) [N]. */
 int d2t_decode_attn_beam_batch(d2t_ctx* ctx, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
                                int32_t* len_out, float* score_out, d2t_stream stream);
+/* ... plus each returned hypothesis's alignment map (the reference's decoder_attn with viz_attn, seq2seq.py:174-221):
+ * alpha_dev [N][S][Tk] fp32 (device, 16-byte aligned), row j < len_out[i] = the alignment of step j in the row that was the
+ * hypothesis's parent at that step, zeros beyond.  The search keeps every step's alignments in a history of
+ * S * N * beam_size * Tk floats beside its workspace; a call whose history would exceed D2T_ATTN_MAP_BUDGET bytes is
+ * refused with D2T_EINVAL (split the batch).  alpha_dev NULL = d2t_decode_attn_beam_batch. */
+#define D2T_ATTN_MAP_BUDGET (256ull << 20)
+int d2t_decode_attn_beam_batch_alpha(d2t_ctx* ctx, const float* memory, int32_t N, int32_t T, int32_t beam_size,
+                                     int64_t* seq_out, int32_t* len_out, float* score_out, float* alpha_dev,
+                                     d2t_stream stream);
 
 /* Beam search for N samples at once (not in the reference, whose forward_beam is single-sample): the same results as
  * N calls of d2t_decode_beam, with the hypotheses of all samples advanced by one shared step loop.  memory [N][T][d];
@@ -350,6 +367,9 @@ int d2t_train_decision_count(d2t_ctx* ctx);
 int d2t_train_read_decision(d2t_ctx* ctx, int32_t index, uint8_t* dst, int64_t numel, int32_t* is_pool_out,
                             int64_t* numel_out, d2t_stream stream);
 int d2t_train_read_mask(d2t_ctx* ctx, int32_t index, uint8_t* dst, int64_t numel, d2t_stream stream);
+/* The alignments of the last d2t_train_forward of an LSTM-attention head, [B][S][Tk] (S = batch_max_length + 1), copied
+ * into dst (device).  D2T_ESTATE for the TFM head and before any forward (or after its backward consumed it). */
+int d2t_train_read_attn_alpha(d2t_ctx* ctx, float* dst, int64_t numel, d2t_stream stream);
 /* free the training tape, gradient buffers and workspace */
 void d2t_train_release(d2t_ctx* ctx);
 
