@@ -61,6 +61,7 @@ SIGNATURES = {
     "d2t_finalize_weights": (_I, [_P, _P]),
     "d2t_encoder_shape": (_I, [_P, _I, _I] + [C.POINTER(_I)] * 6),
     "d2t_encode": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "d2t_encode_attn": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(_P), _I, _P]),
     "d2t_decode_greedy": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, C.POINTER(_I), _P]),
     "d2t_decode_attn_greedy": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(_I), _P]),
     "d2t_decode_attn_greedy_alpha": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, C.POINTER(_I), _P]),
@@ -110,6 +111,7 @@ SIGNATURES = {
     "d2t_op_maxpool2x2": (_I, [_P, _P] + [_I] * 8 + [_P]),
     "d2t_op_layernorm": (_I, [_P] * 4 + [_I, _I, C.c_float, _P]),
     "d2t_op_vit_attention": (_I, [_P, _P, _I, _I, _I, _P]),
+    "d2t_op_vit_attention_probs": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "d2t_op_decode_attention": (_I, [_P] * 4 + [_I] * 5 + [_P]),
     "d2t_ce_forward": (_I, [_P, _P, _P, _P, _I, _I, _L, _P]),
     "d2t_ce_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _P]),

@@ -383,9 +383,47 @@ class Model(nn.Module):
         return out
 
     # -- reference API -------------------------------------------------------
+    def _hooked_attn_drops(self):
+        """The ViT blocks whose attn_drop carries a forward hook or forward pre-hook: [(block index, module)]."""
+        if self.stages["Seq"] != "ViT":
+            return []
+        return [(i, blk.attn.attn_drop) for i, blk in enumerate(self.seqmodeler.SequenceModeling.blocks)
+                if blk.attn.attn_drop._forward_hooks or blk.attn.attn_drop._forward_pre_hooks]
+
+    def _refuse_train_attn_hooks(self):
+        if self.training and self._hooked_attn_drops():
+            raise NotImplementedError(
+                "forward hooks on attn_drop read the ViT attention maps of the inference encoder only: the training step's "
+                "attention kernels (attn_train_fwd_kernel / attn_train_bwd_kernel) do not write the probabilities.  Call "
+                "model.eval() for the maps, or remove the hooks before training")
+
     def forward_encoder(self, input, *args, **kwargs):
-        """build_model.py:36-43 -> (contextual_feature [B,T,d], output_shape, feat_pad)."""
-        memory, grid, pad = self.engine().encode(input)
+        """build_model.py:36-43 -> (contextual_feature [B,T,d], output_shape, feat_pad).
+
+        ViT encoders: when a block's attn.attn_drop has a forward hook or pre-hook (as the reference's attention rollout
+        registers, tools/interpretation/vit_visualize.py:26-93), the encoder also writes that block's attention
+        probabilities [B, heads, T, T] and then calls attn_drop on them in block order, so the hooks see what they see in
+        the reference.  Only hooked blocks are allocated; without hooks the encoder runs exactly as before."""
+        self._refuse_train_attn_hooks()
+        hooked = self._hooked_attn_drops()
+        eng = self.engine()
+        if not hooked:
+            memory, grid, pad = eng.encode(input)
+        else:
+            B, _, H, W = input.shape
+            T = eng.encoder_shape(H, W)[0]
+            maps = [None] * eng.cfg.vit_depth
+            for i, _ in hooked:
+                maps[i] = torch.empty((B, eng.cfg.vit_heads, T, T), dtype=torch.float32, device=input.device)
+            memory, grid, pad = eng.encode(input, attn_maps=maps)
+            for i, mod in hooked:
+                # eval: Dropout returns its input.  A hook (or pre-hook) handing back another tensor would change the rest
+                # of the reference's forward, but the engine has already used the unmodified probabilities
+                if mod(maps[i]) is not maps[i]:
+                    raise RuntimeError(
+                        f"a hook on seqmodeler.SequenceModeling.blocks.{i}.attn.attn_drop returned a replacement tensor: the "
+                        "HIP encoder computes attention in one kernel and has already used the unmodified probabilities, so "
+                        "hooks on attn_drop may read the maps but not replace them")
         if self.stages["Seq"] == "ViT":
             return memory, grid, pad  # build_seq.py:59-66
         return memory, None, None  # build_seq.py:69-76
@@ -460,6 +498,7 @@ class Model(nn.Module):
             # with is_train), one autograd node over the whole network so that loss.backward() (engine/training.py:137)
             # fills every .grad
             from .train import train_forward
+            self._refuse_train_attn_hooks()
             if self.stages["Pred"] == "TFM":
                 if self.stages["Seq"] not in ("ViT", "None"):
                     raise NotImplementedError("the training step is implemented for the HybridViT + TFM and ResNet + TFM stacks")

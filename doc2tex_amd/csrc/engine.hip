@@ -881,6 +881,11 @@ int d2t_encoder_shape(const d2t_ctx* c, int32_t H, int32_t W, int32_t* T, int32_
 static int memory_cap(const d2t_ctx*) { return 4096; }
 
 int d2t_encode(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_t W, float* memory, d2t_stream stream) {
+  return d2t_encode_attn(c, image, B, H, W, memory, nullptr, 0, stream);
+}
+
+int d2t_encode_attn(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_t W, float* memory, float* const* maps_dev,
+                    int32_t n_maps, d2t_stream stream) {
   DevGuard dg_(c);
   if (!c || !image || !memory || B < 1) return fail(c, D2T_EINVAL, "bad argument");
   if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
@@ -888,6 +893,14 @@ int d2t_encode(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_t W, 
   if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const d2t_config& g = c->cfg;
+  if (n_maps < 0 || (n_maps > 0 && !maps_dev)) return fail(c, D2T_EINVAL, "bad attention-map list (%d entries)", n_maps);
+  for (int i = 0; i < n_maps; ++i) {
+    if (!maps_dev[i]) continue;
+    if (g.encoder != D2T_ENC_HYBRID_VIT) return fail(c, D2T_EINVAL, "attention maps need the ViT encoder (this one has no self-attention)");
+    if (int rc = check_dev_ptr(c, maps_dev[i], "attention map")) return rc;
+  }
+  if (g.encoder == D2T_ENC_HYBRID_VIT && n_maps > 0 && n_maps != (int)c->vit.size())
+    return fail(c, D2T_EINVAL, "%d attention maps for a ViT of depth %d (pass 0 or one per block)", n_maps, (int)c->vit.size());
   int T, dim, gh, gw, pw, ph;
   if (d2t_encoder_shape(c, H, W, &T, &dim, &gh, &gw, &pw, &ph))
     return fail(c, D2T_EINVAL, "unsupported crop %dx%d (backbone output would be empty)", H, W);
@@ -1002,11 +1015,14 @@ int d2t_encode(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_t W, 
   float* Hn = pick(c, {X});
   float* Q = pick(c, {X, Hn});
   float* X2 = pick(c, {X, Hn, Q});
-  for (const VitBlock& vb : c->vit) {
+  for (size_t i = 0; i < c->vit.size(); ++i) {
+    const VitBlock& vb = c->vit[i];
     // Block.forward (vision_transformer.py:119-122), LayerNorm eps 1e-6 (:175)
     HIPCHK(c, launch_layernorm(X, vb.n1.g, vb.n1.b, Hn, M, dim, 1e-6f, s));
     HIPCHK(c, linear_any(c, s, Hn, vb.qkv, nullptr, Q, M, ACT_NONE));
-    HIPCHK(c, launch_vit_attention(Q, Hn, B, T, g.vit_heads, s));
+    float* map = i < (size_t)n_maps ? maps_dev[i] : nullptr;  // the block's attn_drop input [B][heads][T][T]
+    if (map) HIPCHK(c, launch_vit_attention_probs(Q, Hn, map, B, T, g.vit_heads, s));
+    else HIPCHK(c, launch_vit_attention(Q, Hn, B, T, g.vit_heads, s));
     HIPCHK(c, linear_any(c, s, Hn, vb.proj, X, X2, M, ACT_NONE));
     HIPCHK(c, launch_layernorm(X2, vb.n2.g, vb.n2.b, Hn, M, dim, 1e-6f, s));
     HIPCHK(c, linear_any(c, s, Hn, vb.fc1, nullptr, Q, M, ACT_GELU));
@@ -2332,6 +2348,12 @@ int d2t_op_layernorm(const float* x, const float* gamma, const float* beta, floa
 int d2t_op_vit_attention(const float* qkv, float* y, int32_t B, int32_t N, int32_t heads, d2t_stream stream) {
   if (!qkv || !y) return D2T_EINVAL;
   return launch_vit_attention(qkv, y, B, N, heads, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_vit_attention_probs(const float* qkv, float* y, float* probs, int32_t B, int32_t N, int32_t heads,
+                               d2t_stream stream) {
+  if (!qkv || !y || !probs || B < 1 || N < 1 || heads < 1) return D2T_EINVAL;
+  return launch_vit_attention_probs(qkv, y, probs, B, N, heads, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
 }
 
 int d2t_op_decode_attention(const float* q, const float* k, const float* v, float* y, int32_t B, int32_t heads,

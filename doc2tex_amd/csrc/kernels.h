@@ -208,6 +208,8 @@ hipError_t launch_transpose_into(const float* src, int rows, int cols, float* ds
 hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* y, int rows, int D, float eps,
                             hipStream_t s);
 hipError_t launch_vit_attention(const float* qkv, float* y, int B, int N, int heads, hipStream_t s);
+// ... plus the softmax probabilities, maps [B][heads][N][N] fp32 (always the matrix-core kernel); maps NULL = the above
+hipError_t launch_vit_attention_probs(const float* qkv, float* y, float* maps, int B, int N, int heads, hipStream_t s);
 
 // Single-query attention, one wave per (b, head).
 struct DecAttnP {

@@ -346,9 +346,16 @@ __global__ __launch_bounds__(512) void vit_attention_kernel(const float* __restr
 // sequences (crops beyond about 180 x 720: the shipped configurations allow up to 448 x 960 = 1695 tokens) take the same
 // loop in CHUNKS of `kct` key tiles staged one after the other -- the running maximum / sum / O carry over, the keys are
 // visited in the same order -- and the queries are split over `qchunks` blocks of up to 16 waves per (image, head).
+// MAPS also writes the normalised probabilities (the tensor the reference's attn_drop sees, vision_transformer.py:74-76) to
+// maps [B][heads][N][N]: after the loop above a second sweep recomputes every score tile with the same MFMAs and operands
+// (bitwise the same S) and writes exp(S - m) / l with the final m and l.  Up to 512 tokens K is still in LDS; chunked
+// launches stage K again chunk by chunk (V is not needed).  The V region becomes per-wave scratch (512 floats = 32 queries x
+// 16 keys) through which each half-tile is turned from accumulator layout into 64-byte runs of keys per query row.
 // ---------------------------------------------------------------------------
+template <bool MAPS>
 __global__ __launch_bounds__(1024) void vit_attention_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ y,
-                                                                  int N, int heads, int tiles, int kct, int qchunks) {
+                                                                  float* __restrict__ maps, int N, int heads, int tiles,
+                                                                  int kct, int qchunks) {
   // Round 3: the score product is taken TRANSPOSED (S^T = K Q^T: rows = keys, columns = this wave's 32 queries), so a lane
   // holds, for ONE query (its column), 16 of the tile's 32 keys in its accumulator registers -- and that is already the
   // A-operand layout of the second product when MFMA step kk is made to mean "key (kk & 3) + 8 (kk >> 2) + 4 h" (the V rows are
@@ -437,28 +444,90 @@ __global__ __launch_bounds__(1024) void vit_attention_mfma_kernel(const float* _
     const int row = q0 + qi;
     if (row < N) y[((size_t)b * N + row) * C + hh * 32 + r] = o[e] / l;
   }
+  if constexpr (MAPS) {
+    __syncthreads();  // every wave is past its last P V product: the V region is scratch from here on
+    float* ws = Vs + (size_t)wave * 512;       // [32 queries][16 keys], key column XOR (query >> 1): conflict-free both ways
+    float* pm = maps + (size_t)bh * N * N;     // this (image, head)'s [N][N]
+    const int c = lane & 15;                   // read-back: lane = key column c of query row 4 i + (lane >> 4)
+    for (int t0 = 0; t0 < tiles; t0 += kct) {
+      if (kct < tiles) {  // chunked launch: stage this chunk's K again
+        if (t0) __syncthreads();
+        for (int i = tid; i < Np * 8; i += nthreads) {
+          const int jl = i >> 3, j = t0 * 32 + jl, cc = (i & 7) * 4;
+          float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (j < N) kv = *reinterpret_cast<const float4*>(base + (size_t)j * 3 * C + C + hh * 32 + cc);
+          float* kd = Ks + jl * 33 + cc;
+          kd[0] = kv.x; kd[1] = kv.y; kd[2] = kv.z; kd[3] = kv.w;
+        }
+        __syncthreads();
+      }
+      const int tend = t0 + kct < tiles ? t0 + kct : tiles;
+      for (int t = t0; t < tend; ++t) {
+        f32x16 sacc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
+        const float* ka = Ks + (size_t)((t - t0) * 32 + r) * 33 + h;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[2 * kk], qb[kk], sacc, 0, 0, 0);
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          // registers 8 half + i hold keys t*32 + 16 half + (i & 3) + 8 (i >> 2) + 4 h of query q0 + r
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const int kl = (i & 3) + 8 * (i >> 2) + 4 * h;
+            ws[r * 16 + (kl ^ ((r >> 1) & 15))] = expf(sacc[8 * half + i] - mrun) / lrun;
+          }
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the half-tile is visible to the whole wave
+          const int key = t * 32 + 16 * half + c;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const int qr = 4 * i + (lane >> 4), row = q0 + qr;
+            const float p = ws[qr * 16 + (c ^ ((qr >> 1) & 15))];
+            if (row < N && key < N) pm[(size_t)row * N + key] = p;  // never the zero-padded keys or the clamped queries
+          }
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+    }
+  }
+}
+
+template <bool MAPS>
+static hipError_t launch_vit_attention_mfma(const float* qkv, float* y, float* maps, int B, int N, int heads, hipStream_t s,
+                                           bool* launched) {
+  const int tiles = (N + 31) / 32;
+  // up to 512 tokens: the whole head in one chunk, one block per (image, head) -- the launch of rounds 2-3, unchanged;
+  // beyond: 256-key chunks (66 KB: two blocks per CU) and the queries in blocks of sixteen waves
+  const int kct = tiles <= 16 ? tiles : 8, qchunks = (tiles + 15) / 16, waves = tiles < 16 ? tiles : 16;
+  const size_t lds2 = ((size_t)kct * 32 * 33 + (size_t)kct * 32 * 32) * sizeof(float);
+  static bool attr2 = false;
+  if (!attr2) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention_mfma_kernel<MAPS>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    attr2 = true;
+  }
+  *launched = lds2 <= 160 * 1024;
+  if (!*launched) return hipSuccess;
+  hipLaunchKernelGGL(vit_attention_mfma_kernel<MAPS>, dim3(B * heads * qchunks), dim3(waves * 64), lds2, s, qkv, y, maps, N,
+                     heads, tiles, kct, qchunks);
+  return hipGetLastError();
+}
+
+hipError_t launch_vit_attention_probs(const float* qkv, float* y, float* maps, int B, int N, int heads, hipStream_t s) {
+  if (!maps) return launch_vit_attention(qkv, y, B, N, heads, s);
+  bool launched = false;
+  const hipError_t e = launch_vit_attention_mfma<true>(qkv, y, maps, B, N, heads, s, &launched);
+  return e != hipSuccess ? e : launched ? hipSuccess : hipErrorInvalidValue;
 }
 
 hipError_t launch_vit_attention(const float* qkv, float* y, int B, int N, int heads, hipStream_t s) {
   static const bool valu = D2T_PROBE_ENV_STR("D2T_VIT_ATTN_VALU") != nullptr;
   if (!valu) {
-    const int tiles = (N + 31) / 32;
-    // up to 512 tokens: the whole head in one chunk, one block per (image, head) -- the launch of rounds 2-3, unchanged;
-    // beyond: 256-key chunks (66 KB: two blocks per CU) and the queries in blocks of sixteen waves
-    const int kct = tiles <= 16 ? tiles : 8, qchunks = (tiles + 15) / 16, waves = tiles < 16 ? tiles : 16;
-    const size_t lds2 = ((size_t)kct * 32 * 33 + (size_t)kct * 32 * 32) * sizeof(float);
-    static bool attr2 = false;
-    if (!attr2) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention_mfma_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attr2 = true;
-    }
-    if (lds2 <= 160 * 1024) {
-      hipLaunchKernelGGL(vit_attention_mfma_kernel, dim3(B * heads * qchunks), dim3(waves * 64), lds2, s, qkv, y, N, heads, tiles,
-                         kct, qchunks);
-      return hipGetLastError();
-    }
+    bool launched = false;
+    const hipError_t e = launch_vit_attention_mfma<false>(qkv, y, nullptr, B, N, heads, s, &launched);
+    if (e != hipSuccess || launched) return e;
   }
   if (N > 64 * VA_MAXKPL) return hipErrorInvalidValue;
   const size_t lds = ((((size_t)N * 33 + 3) & ~(size_t)3) + (size_t)N * 32 + 8 * (size_t)N) * sizeof(float);

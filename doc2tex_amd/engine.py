@@ -280,7 +280,11 @@ class Engine:
         T, d, gh, gw, pw, ph = [x.value for x in v]
         return T, d, gh, gw, pw, ph
 
-    def encode(self, image):
+    def encode(self, image, attn_maps=None):
+        """image [B,1,H,W] -> (memory [B,T,d], (grid_h, grid_w), (pad_w, pad_h)).  attn_maps (ViT encoders): a list of
+        vit_depth entries, each None or a caller-allocated contiguous fp32 tensor [B, heads, T, T] on the image's device
+        that receives that block's self-attention probabilities (the reference's attn_drop input); memory is bitwise the
+        same with or without them."""
         self._on_device(image, "input")
         if image.dim() != 4 or image.shape[1] != 1:
             raise ValueError(f"expected image [B,1,H,W], got {tuple(image.shape)}")
@@ -288,8 +292,22 @@ class Engine:
         B, _, H, W = image.shape
         T, d, gh, gw, pw, ph = self.encoder_shape(H, W)
         memory = torch.empty((B, T, d), dtype=torch.float32, device=image.device)
-        self._check(self.lib.d2t_encode(self.ctx, _lib.ptr(image), B, H, W, _lib.ptr(memory),
-                                        _lib.stream_of(image)), "encode")
+        if attn_maps is None:
+            self._check(self.lib.d2t_encode(self.ctx, _lib.ptr(image), B, H, W, _lib.ptr(memory),
+                                            _lib.stream_of(image)), "encode")
+            return memory, (gh, gw), (pw, ph)
+        n = len(attn_maps)
+        shape = (B, self.cfg.vit_heads, T, T)
+        for i, a in enumerate(attn_maps):
+            if a is None:
+                continue
+            self._on_device(a, f"attn_maps[{i}]")
+            if a.dtype != torch.float32 or tuple(a.shape) != shape or not a.is_contiguous():
+                raise ValueError(f"attn_maps[{i}] must be a contiguous float32 tensor of shape {shape}, got "
+                                 f"{a.dtype} {tuple(a.shape)}")
+        ptrs = (C.c_void_p * max(n, 1))(*[None if a is None else _lib.ptr(a) for a in attn_maps])
+        self._check(self.lib.d2t_encode_attn(self.ctx, _lib.ptr(image), B, H, W, _lib.ptr(memory), ptrs, n,
+                                             _lib.stream_of(image)), "encode_attn")
         return memory, (gh, gw), (pw, ph)
 
     def set_conv_precision(self, mode):

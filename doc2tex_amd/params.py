@@ -161,6 +161,9 @@ class _VitAttnParams(_Holder):
     def __init__(self, dim):
         super().__init__()
         self.qkv = nn.Linear(dim, dim * 3, bias=True)  # qkv_bias=True, vision_transformer.py:142
+        # vision_transformer.py:57: no state, but forward hooks on it see the block's attention probabilities
+        # [B, heads, T, T] (Model.forward_encoder calls it on the engine's maps when it is hooked)
+        self.attn_drop = nn.Dropout(0.0)
         self.proj = nn.Linear(dim, dim)
 
 

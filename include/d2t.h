@@ -160,6 +160,13 @@ int d2t_encoder_shape(const d2t_ctx* ctx, int32_t H, int32_t W, int32_t* T, int3
                       int32_t* grid_w, int32_t* pad_w, int32_t* pad_h);
 int d2t_encode(d2t_ctx* ctx, const float* image_dev, int32_t B, int32_t H, int32_t W, float* memory_dev,
                d2t_stream stream);
+/* d2t_encode plus the ViT self-attention probabilities of chosen blocks (what the reference's `attn_drop` modules see,
+ * vision_transformer.py:74-76): maps_dev (host array) holds n_maps = 0 or vit_depth device pointers; entry i, if not
+ * NULL, receives block i's softmax(q k^T / sqrt(32)) as contiguous fp32 [B][heads][T][T] (key innermost, caller-allocated,
+ * B*heads*T*T*4 bytes).  NULL entries cost nothing; memory is bitwise the same as without maps.  A non-NULL entry on an
+ * encoder without self-attention (ResNet, VGG / ResNet + BiLSTM) is refused with D2T_EINVAL.  n_maps 0 = d2t_encode. */
+int d2t_encode_attn(d2t_ctx* ctx, const float* image_dev, int32_t B, int32_t H, int32_t W, float* memory_dev,
+                    float* const* maps_dev, int32_t n_maps, d2t_stream stream);
 
 /* ---- greedy decode -------------------------------------------------------
  * memory [B,T,d]; start_tokens [B] int64 ([GO]).  Runs up to max_seq_len+1
@@ -419,6 +426,9 @@ int d2t_op_layernorm(const float* x, const float* gamma, const float* beta, floa
                      float eps, d2t_stream stream);
 /* ViT self-attention.  qkv [B,N,3,heads,32] -> y [B,N,heads*32]; softmax(q k^T / sqrt(32)) v. */
 int d2t_op_vit_attention(const float* qkv, float* y, int32_t B, int32_t N, int32_t heads, d2t_stream stream);
+/* ... plus the softmax probabilities, probs [B,heads,N,N] fp32 (key innermost); y is bitwise d2t_op_vit_attention's. */
+int d2t_op_vit_attention_probs(const float* qkv, float* y, float* probs, int32_t B, int32_t N, int32_t heads,
+                               d2t_stream stream);
 /* Single-query attention (decoder step).  q [B,heads*hd]; k,v [B,heads,Lmax,hd];
  * attends over the first L keys; y [B,heads*hd].  hd = 32 or 64. */
 int d2t_op_decode_attention(const float* q, const float* k, const float* v, float* y, int32_t B, int32_t heads,
