@@ -46,6 +46,7 @@ PREP_OK, PREP_UNBOUND_LOCAL, PREP_FALLBACK = 0, 1, 2
 PREP_FLAG_PASTE_MISMATCH = 1
 POST_NONE, POST_API, POST_DEMO = 0, 1, 2
 ATTN_MAP_BUDGET = 256 << 20  # include/d2t.h D2T_ATTN_MAP_BUDGET: bytes of a beam search's alignment history
+ATTN_MAX_CLASSES = 16384  # include/d2t.h D2T_ATTN_MAX_CLASSES: largest num_class of the Attn / Attnv2 heads
 
 _P = C.c_void_p
 _I = C.c_int32

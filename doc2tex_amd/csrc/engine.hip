@@ -407,7 +407,8 @@ int d2t_create(const d2t_config* cfg, d2t_ctx** out) {
   } else if (cfg->decoder == D2T_DEC_ATTN) {
     if (cfg->attn_hidden != 256) return fail(c, D2T_EINVAL, "Attn hidden_size / input_size must be 256");
     if (cfg->attn_kernel_size < 0 || cfg->attn_kernel_size > 5) return fail(c, D2T_EINVAL, "Attn kernel_size must be <= 5");
-    if (cfg->vocab > 1024) return fail(c, D2T_EINVAL, "Attn decoder supports num_class <= 1024");
+    if (cfg->vocab > D2T_ATTN_MAX_CLASSES)
+      return fail(c, D2T_EINVAL, "Attn decoder supports num_class <= %d, got %d", D2T_ATTN_MAX_CLASSES, cfg->vocab);
     if (cfg->batch_max_length < 1) return fail(c, D2T_EINVAL, "batch_max_length must be >= 1");
     if (cfg->encoder == D2T_ENC_RESNET) return fail(c, D2T_EINVAL, "Feat=ResNet+Seq=None is paired with the TFM decoder only");
     if (cfg->encoder == D2T_ENC_HYBRID_VIT && cfg->vit_dim != 256) return fail(c, D2T_EINVAL, "Attn over ViT needs hidden_size 256");

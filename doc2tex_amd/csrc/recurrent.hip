@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "../../include/d2t.h"
 #include "kernels.h"
 
 namespace d2t {
@@ -120,18 +121,22 @@ hipError_t launch_bilstm(const float* g, const float* whh_t, float* out, int B, 
 
 // ---------------------------------------------------------------------------
 // LSTM-attention greedy decoder: one block (1024 threads) per batch row runs every step.
-// D = E = H = 256, V <= 1024, Tk <= 4096 keys (two alignment rows of that length in LDS: 32 of the block's 58 KB; the
-// shipped max_dimension [800, 800] gives 2525).  The backward kernel of the training step keeps six such rows (96 of its 134 KB).
+// D = E = H = 256, V <= D2T_ATTN_MAX_CLASSES, Tk <= 4096 keys (two alignment rows of that length in LDS: 32 of the block's
+// 58 KB; the shipped max_dimension [800, 800] gives 2525).  The backward kernel of the training step keeps six such rows (96
+// of its 134 KB).  WIDE = false: V <= 1024, one class per thread, logits staged in LDS for wave 0's argmax.  WIDE = true:
+// any V, thread tid takes classes tid, tid + 1024, ... in order, keeps its first maximum, and the block reduces those.
 // ---------------------------------------------------------------------------
 constexpr int AD_MAXT = 4096, AD_MAXT_TRAIN = 4096;
 
+template <bool WIDE>
 __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   constexpr int H = 256;
   __shared__ float x_s[3 * H];  // [context | embedding | h]  = LSTMCell input
   __shared__ float c_s[H], hq_s[H];
   __shared__ float mem_s[AD_MAXT + 16], alpha_s[AD_MAXT], red_s[32];
   __shared__ float gate_s[4 * H];
-  __shared__ float logit_s[1024];
+  __shared__ float logit_s[WIDE ? 16 : 1024];  // WIDE: each wave's best value
+  __shared__ int besti_s[16];                  // WIDE: and its index
   __shared__ int tok_s;
   __shared__ __attribute__((aligned(16))) float wloc_s[11 * H];  // folded location filter, [tap][n]
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -302,6 +307,38 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
     }
     __syncthreads();
     // (6) generator logits + argmax (first maximum)
+    if constexpr (WIDE) {
+      // a class's logit is computed as in the one-class-per-thread build; the winner is the same total order's
+      // (value descending, index ascending) first element, reduced over the lanes, then over the waves
+      float best = -INFINITY;
+      int bi = 0x7fffffff;
+      for (int cls = tid; cls < p.V; cls += 1024) {
+        float v = p.bg[cls];
+#pragma unroll 8
+        for (int k = 0; k < H; ++k) v = fmaf(h_s[k], p.wg_t[(size_t)k * p.V + cls], v);
+        if (p.out_dropmask) v = p.out_dropmask[((size_t)b * p.S + step) * p.V + cls] ? v * p.out_dropscale : 0.f;
+        p.probs[((size_t)b * p.S + step) * p.V + cls] = v;
+        if (v > best || (v == best && cls < bi)) { best = v; bi = cls; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+      }
+      if (lane == 0) { logit_s[wave] = best; besti_s[wave] = bi; }
+      __syncthreads();
+      if (tid == 0) {
+        for (int w = 1; w < 16; ++w)
+          if (logit_s[w] > best || (logit_s[w] == best && besti_s[w] < bi)) { best = logit_s[w]; bi = besti_s[w]; }
+        if (bi >= p.V) bi = 0;
+        tok_s = bi;
+        p.tokens[(size_t)b * p.S + step] = bi;
+        if (bi == p.end_token && !ended) { ended = 1; p.end_step[b] = step; }
+      }
+      __syncthreads();
+      continue;
+    }
     float v = -INFINITY;
     if (tid < p.V) {
       v = p.bg[tid];
@@ -633,7 +670,9 @@ hipError_t launch_attn_train_lstm_bwd(const AttnTrainBwdP& p_in, hipStream_t s) 
   AttnTrainBwdP p = p_in;
   static const int probe = D2T_PROBE_ENV("D2T_LSTM_BWD_PROBE");
   p.probe = probe;
-  if (p.H != 256 || p.D != 256 || p.E != 256 || p.V > 1024 || p.T - p.key_off > AD_MAXT_TRAIN || p.T - p.key_off < 1 || p.taps > 11)
+  // V > 1024 needs the dlogits . generator product from the caller (p.dhl); the in-kernel product stages 1024 classes
+  if (p.H != 256 || p.D != 256 || p.E != 256 || p.V > D2T_ATTN_MAX_CLASSES || (p.V > 1024 && !p.dhl) ||
+      p.T - p.key_off > AD_MAXT_TRAIN || p.T - p.key_off < 1 || p.taps > 11)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(attn_train_lstm_bwd_kernel, dim3(p.B), dim3(1024), 0, s, p);
   return hipGetLastError();
@@ -764,10 +803,13 @@ hipError_t launch_attn_alpha_gather(const float* hist, const int* path, const in
 }
 
 hipError_t launch_attn_decode(const AttnDecP& p, hipStream_t s) {
-  if (p.H != 256 || p.D != 256 || p.E != 256 || p.V > 1024 || p.T - p.key_off > AD_MAXT || p.taps > 11 ||
-      p.T - p.key_off < 1)
+  if (p.H != 256 || p.D != 256 || p.E != 256 || p.V > D2T_ATTN_MAX_CLASSES || p.T - p.key_off > AD_MAXT ||
+      p.taps > 11 || p.T - p.key_off < 1)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(attn_decode_kernel, dim3(p.B), dim3(1024), 0, s, p);
+  if (p.V <= 1024)
+    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(p.B), dim3(1024), 0, s, p);
+  else
+    hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(p.B), dim3(1024), 0, s, p);
   return hipGetLastError();
 }
 

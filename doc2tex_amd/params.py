@@ -12,6 +12,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ._lib import ATTN_MAX_CLASSES
+
 RESNET_LAYERS = (1, 2, 5, 3)  # feature_extractor/resnet.py:262
 
 
@@ -380,8 +382,9 @@ class AttentionParams(_Holder):
             embed_dim = input_size
         if input_size != 256 or hidden_size != 256 or (embed_target and embed_dim != 256):
             raise NotImplementedError("the Attn kernel is built for input_size = hidden_size = embed_dim = 256")
-        if not embed_target and num_classes > 1024:
-            raise NotImplementedError("one-hot targets: the Attn kernel handles up to 1024 classes")
+        if not embed_target and num_classes > ATTN_MAX_CLASSES:
+            raise NotImplementedError(f"one-hot targets: the Attn kernel handles up to {ATTN_MAX_CLASSES} classes, "
+                                      f"got num_class = {num_classes}")
         if embed_target:
             self.embedding = nn.Embedding(num_classes, embed_dim, padding_idx=0)  # ATTN.START() = 0
         num_embeddings = embed_dim if embed_target else num_classes

@@ -124,6 +124,10 @@ typedef struct d2t_config {
   int32_t vit_pos;          /* D2T_VIT_POS_* */
 } d2t_config;
 
+/* Largest num_class (d2t_config.vocab) of the LSTM-attention decoders: d2t_create refuses more.  probs [B][S][vocab] fp32
+ * stays caller memory (2.1 GB at B = 64, S = 501 and this cap). */
+#define D2T_ATTN_MAX_CLASSES 16384
+
 /* ---- lifecycle ----------------------------------------------------------
  * d2t_create binds the context to the HIP device that is current for the calling thread (the reference picks its
  * device from the string opt["device"], build_pred.py:17 -- the Python layer above translates "cuda:N" into
