@@ -32,7 +32,7 @@ class D2TConfig(C.Structure):
 
 class D2TPrepConfig(C.Structure):  # include/d2t_prep.h d2t_prep_config
     _fields_ = [(n, C.c_int32) for n in ("max_h", "max_w", "min_h", "min_w", "downsample", "variant")] + \
-               [("mean", C.c_float), ("std", C.c_float), ("norm_mode", C.c_int32)]
+               [("mean", C.c_float), ("std", C.c_float), ("norm_mode", C.c_int32), ("channels", C.c_int32)]
 
 
 class D2TPrepPlan(C.Structure):  # include/d2t_prep.h d2t_prep_plan

@@ -216,8 +216,8 @@ int run_backbone(d2t_ctx* c, hipStream_t s, const float* img, int B, int H, int 
   const int nmix = (sp && !f16 && c->conv_pipelined == 3) ? c->mixed_units : 0;
   auto mixed = [&](int u) { return u >= 0 && u < nmix; };
   auto fmt_for = [&](int consumer_unit) { return mixed(consumer_unit) ? 2 : -1; };
-  if (sp) HIPCHK(c, launch_stem_split(img, c->stem.w, c->stem.bias, x.planes(), B, H, W, c->stem.Cout, ACT_RELU, s, f16));
-  else HIPCHK(c, launch_stem(img, c->stem.w, c->stem.bias, x.p, B, H, W, c->stem.Cout, ACT_RELU, s));
+  if (sp) HIPCHK(c, launch_stem_split(img, c->stem.w, c->stem.bias, x.planes(), B, c->stem.Cin, H, W, c->stem.Cout, ACT_RELU, s, f16));
+  else HIPCHK(c, launch_stem(img, c->stem.w, c->stem.bias, x.p, B, c->stem.Cin, H, W, c->stem.Cout, ACT_RELU, s));
   // the two 2x2 / stride 2 max-pools (resnet.py:94,106) run inside the epilogue of the convolution in front of them on the
   // split-record path with the 16x16x32 kernels: conv0_2 writes 268 MB instead of 1.07 GB and no pool kernel re-reads it
   const bool fuse_pool = sp && c->conv_pipelined == 3 && !c->no_pool_fusion;
@@ -385,7 +385,8 @@ int d2t_create(const d2t_config* cfg, d2t_ctx** out) {
   d2t_ctx* c = new d2t_ctx();
   c->cfg = *cfg;
   *out = c;  // returned even on error so that d2t_last_error works; caller destroys it
-  if (cfg->in_channels != 1) return fail(c, D2T_EINVAL, "in_channels must be 1 (grey crops)");
+  if (cfg->in_channels != 1 && cfg->in_channels != 3)
+    return fail(c, D2T_EINVAL, "in_channels must be 1 (grey crops) or 3 (rgb crops), got %d", cfg->in_channels);
   if (cfg->backbone_out != 512) return fail(c, D2T_EINVAL, "backbone output_channel must be 512");
   if (cfg->encoder == D2T_ENC_HYBRID_VIT) {
     if (cfg->vit_dim != 256 && cfg->vit_dim != 512) return fail(c, D2T_EINVAL, "ViT hidden_size must be 256 or 512");
@@ -530,13 +531,14 @@ int d2t_finalize_weights(d2t_ctx* c, d2t_stream stream) {
     const char* bns[7] = {"", "", "", "", "12", "15", ""};
     for (int i = 0; i < 7; ++i)
       if ((rc = pack_conv(c, bb + convs[i], bns[i][0] ? bb + bns[i] : std::string(), &c->vgg[i], s))) return rc;
-    if (c->vgg[0].Cin != 1 || c->vgg[0].KH != 3 || c->vgg[6].KH != 2 || c->vgg[6].Cout != 512)
+    if (c->vgg[0].Cin != g.in_channels || c->vgg[0].KH != 3 || c->vgg[0].KW != 3 || c->vgg[6].KH != 2 || c->vgg[6].Cout != 512)
       return fail(c, D2T_EINVAL, "unexpected VGG_FeatureExtractor shapes");
   }
   if (!is_vgg) {
   if ((rc = pack_conv(c, bb + "conv0_1", bb + "bn0_1", &c->stem, s))) return rc;
-  if (c->stem.Cin != 1 || c->stem.KH != 3 || c->stem.KW != 3)
-    return fail(c, D2T_EINVAL, "conv0_1 must be 1-channel 3x3");
+  if (c->stem.Cin != g.in_channels || c->stem.KH != 3 || c->stem.KW != 3)
+    return fail(c, D2T_EINVAL, "conv0_1 must be %d-channel 3x3 (the config's in_channels), got %d channels %dx%d", g.in_channels,
+                c->stem.Cin, c->stem.KH, c->stem.KW);
   if ((rc = pack_conv(c, bb + "conv0_2", bb + "bn0_2", &c->conv0_2, s))) return rc;
   for (int li = 0; li < 4; ++li) {
     for (int bi = 0; bi < RESNET_LAYERS[li]; ++bi) {
@@ -937,7 +939,7 @@ int d2t_encode_attn(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_
     if (g.encoder == D2T_ENC_VGG_BILSTM) {
       // VGG_FeatureExtractor.forward (feature_extractor/vgg.py:16-44)
       Act x{pick(c, {}), B, H, W, c->vgg[0].Cout};
-      HIPCHK(c, launch_stem(image, c->vgg[0].w, c->vgg[0].bias, x.p, B, H, W, x.C, ACT_RELU, s));
+      HIPCHK(c, launch_stem(image, c->vgg[0].w, c->vgg[0].bias, x.p, B, c->vgg[0].Cin, H, W, x.C, ACT_RELU, s));
       auto pool = [&](const Act& a, int kh, int kw) {
         Act y{pick(c, {a.p}), a.B, (a.H - kh) / kh + 1, (a.W - kw) / kw + 1, a.C};
         hipError_t e = launch_maxpool_k(a.p, y.p, a.B, a.H, a.W, a.C, kh, kw, kh, kw, 0, 0, s);
@@ -2183,9 +2185,9 @@ int d2t_op_conv2d(const float* x, const float* w, const float* bias, const float
                   int32_t PH, int32_t PW, int32_t act, d2t_stream stream) {
   if (!x || !w || !y || SH < 1 || SW < 1) return D2T_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (Cin == 1) {
+  if (Cin == 1 || Cin == 3) {  // the stem kernels: x is the image as the encoder takes it, NCHW planar [B][Cin][H][W]
     if (KH != 3 || KW != 3 || SH != 1 || SW != 1 || PH != 1 || PW != 1 || residual) return D2T_EINVAL;
-    return launch_stem(x, w, bias, y, B, H, W, Cout, act, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+    return launch_stem(x, w, bias, y, B, Cin, H, W, Cout, act, s) == hipSuccess ? D2T_OK : D2T_EHIP;
   }
   if (Cin % 32) return D2T_EINVAL;
   float* wp = nullptr;  // the kernel's K order (test entry point: temporary repack, synchronous)

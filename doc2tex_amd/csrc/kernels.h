@@ -111,11 +111,12 @@ struct SkinnyP {
 };
 hipError_t launch_skinny(const SkinnyP& p, hipStream_t s);
 
-// conv0_1: Cin = 1, 3x3, stride 1, pad 1, Cout % 4 == 0, fused bias + ReLU.  w [Cout][9].
-hipError_t launch_stem(const float* img, const float* w, const float* bias, float* out, int B, int H, int W, int Cout,
+// conv0_1: Cin = 1 or 3, 3x3, stride 1, pad 1, Cout % 4 == 0, fused bias + ReLU.  img NCHW planar [B][Cin][H][W],
+// w [Cout][9][Cin] (pack_conv's layout).
+hipError_t launch_stem(const float* img, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                        int act, hipStream_t s);
 // same, writing split-bf16 planes
-hipError_t launch_stem_split(const float* img, const float* w, const float* bias, uint16_t* out, int B, int H, int W,
+hipError_t launch_stem_split(const float* img, const float* w, const float* bias, uint16_t* out, int B, int Cin, int H, int W,
                              int Cout, int act, hipStream_t s, int f16 = 0);
 // fp32 [rows][C] <-> split-activation records (C % 32 == 0); used by the test entry point
 hipError_t launch_split_act(const float* x, uint16_t* planes, size_t rows, int C, hipStream_t s, int f16 = 0);
@@ -477,8 +478,10 @@ hipError_t launch_bicubic_table(const float* src, float* dst, int GH, int GW, in
 hipError_t launch_bicubic_table_bwd(const float* ddst, float* dsrc, int GH, int GW, int gh, int gw, int D, float scale_h,
                                     float scale_w, hipStream_t s);
 hipError_t launch_sum_over_batch(const float* x, float* out, int B, long long stride, long long n, hipStream_t s);
-hipError_t launch_stem_raw(const float* img, const float* w, float* z, int B, int H, int W, int Cout, hipStream_t s);
-hipError_t launch_stem_wgrad(const float* img, const float* dz, float* part, int B, int H, int W, int Cout, int chunk,
+// training stem (Cin = 1 or 3): img NCHW planar, w raw OIHW [Cout][Cin][3][3]; the weight-gradient partials are
+// [chunk][9 * Cin][Cout], tap index = (ci * 3 + kh) * 3 + kw
+hipError_t launch_stem_raw(const float* img, const float* w, float* z, int B, int Cin, int H, int W, int Cout, hipStream_t s);
+hipError_t launch_stem_wgrad(const float* img, const float* dz, float* part, int B, int Cin, int H, int W, int Cout, int chunk,
                              int nchunks, hipStream_t s);
 
 // One launch for many device-to-device copies: block b copies chunk b = {src, dst, n floats} of the table.

@@ -17,9 +17,13 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // ---------------------------------------------------------------------------
-// conv0_1 + bn0_1 + ReLU (feature_extractor/resnet.py:206-208): Cin = 1, 3x3 pad 1.
+// conv0_1 + bn0_1 + ReLU (feature_extractor/resnet.py:206-208): Cin = 1 (grey) or 3 (rgb: True), 3x3 pad 1.
 // HBM-write-bound: one thread = one pixel x 4 output channels, 16-B coalesced stores.
+// The image is NCHW planar [B][CIN][H][W]; the weights are pack_conv's [Cout][kh][kw][CIN] (for CIN = 1 that is [Cout][9]).
+// Accumulation order inside a pixel: channel-major, then kh, kw -- a = fmaf(v[c][kh][kw], w[oc][kh][kw][c], a) -- so the
+// fp32 path has one defined result; the CIN = 1 instantiation is the nine-tap chain it has always been.
 // ---------------------------------------------------------------------------
+template <int CIN>
 __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                    const float* __restrict__ bias, float* __restrict__ out, int B,
                                                    int H, int W, int Cout, int act) {
@@ -32,22 +36,28 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ img
     const int x = (int)(pix % W);
     const int y = (int)((pix / W) % H);
     const long long b = pix / ((long long)W * H);
-    const float* im = img + b * H * W;
-    float v[9];
+    const float* im = img + b * CIN * H * W;
+    float v[CIN][9];
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
+    for (int ci = 0; ci < CIN; ++ci)
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int yy = y + kh - 1, xx = x + kw - 1;
-        v[kh * 3 + kw] = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) ? im[(long long)yy * W + xx] : 0.f;
-      }
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+          const int yy = y + kh - 1, xx = x + kw - 1;
+          // (plane offset added to the row offset: the 64-bit row product is shared by the planes)
+          v[ci][kh * 3 + kw] = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
+                                   ? im[(long long)ci * H * W + ((long long)yy * W + xx)] : 0.f;
+        }
     float o[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int oc = c4 * 4 + c;
       float a = 0.f;
 #pragma unroll
-      for (int t = 0; t < 9; ++t) a = fmaf(v[t], w[oc * 9 + t], a);
+      for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+        for (int t = 0; t < 9; ++t) a = fmaf(v[ci][t], w[(oc * 9 + t) * CIN + ci], a);
       a += bias ? bias[oc] : 0.f;
       o[c] = act == ACT_RELU ? fmaxf(a, 0.f) : a;
     }
@@ -55,18 +65,23 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ img
   }
 }
 
+template <int CIN>
 __global__ __launch_bounds__(256) void stem_split_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                          const float* __restrict__ bias, uint16_t* __restrict__ out,
                                                          int B, int H, int W, int Cout, int act, int f16) {
   const int cq = Cout >> 2;  // == 8: the stride of the loop below is a multiple of 8, so a thread keeps its 4 channels
   const long long total = (long long)B * H * W * cq;
   const int c4 = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) % cq);
-  float wr[4][9], br[4];  // this thread's filter taps, loaded once (36 loads per pixel otherwise)
+  // this thread's filter taps, loaded once (36 loads per pixel otherwise; 108 with three channels).  Every index below is a
+  // compile-time constant after unrolling, so the 4 x 9 x CIN taps and the 9 x CIN pixels live in registers
+  float wr[4][CIN][9], br[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     br[c] = bias ? bias[c4 * 4 + c] : 0.f;
 #pragma unroll
-    for (int t = 0; t < 9; ++t) wr[c][t] = w[(c4 * 4 + c) * 9 + t];
+    for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) wr[c][ci][t] = w[((c4 * 4 + c) * 9 + t) * CIN + ci];
   }
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (long long)gridDim.x * blockDim.x) {
@@ -74,21 +89,27 @@ __global__ __launch_bounds__(256) void stem_split_kernel(const float* __restrict
     const int x = (int)(pix % W);
     const int y = (int)((pix / W) % H);
     const long long b = pix / ((long long)W * H);
-    const float* im = img + b * H * W;
-    float v[9];
+    const float* im = img + b * CIN * H * W;
+    float v[CIN][9];
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
+    for (int ci = 0; ci < CIN; ++ci)
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int yy = y + kh - 1, xx = x + kw - 1;
-        v[kh * 3 + kw] = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) ? im[(long long)yy * W + xx] : 0.f;
-      }
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+          const int yy = y + kh - 1, xx = x + kw - 1;
+          // (plane offset added to the row offset: the 64-bit row product is shared by the planes)
+          v[ci][kh * 3 + kw] = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
+                                   ? im[(long long)ci * H * W + ((long long)yy * W + xx)] : 0.f;
+        }
     uint16_t hi[4], lo[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       float a = 0.f;
 #pragma unroll
-      for (int t = 0; t < 9; ++t) a = fmaf(v[t], wr[c][t], a);
+      for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+        for (int t = 0; t < 9; ++t) a = fmaf(v[ci][t], wr[c][ci][t], a);
       a += br[c];
       split_rec(act == ACT_RELU ? fmaxf(a, 0.f) : a, hi[c], lo[c], f16);
     }
@@ -98,21 +119,25 @@ __global__ __launch_bounds__(256) void stem_split_kernel(const float* __restrict
   }
 }
 
-hipError_t launch_stem_split(const float* img, const float* w, const float* bias, uint16_t* out, int B, int H, int W,
+hipError_t launch_stem_split(const float* img, const float* w, const float* bias, uint16_t* out, int B, int Cin, int H, int W,
                              int Cout, int act, hipStream_t s, int f16) {
   if (Cout != 32) return hipErrorInvalidValue;  // 8 channel quads per pixel: see the kernel's hoisted weights
   const long long total = (long long)B * H * W * (Cout / 4);
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(stem_split_kernel, dim3(blocks), dim3(256), 0, s, img, w, bias, out, B, H, W, Cout, act, f16);
+  if (Cin == 1) hipLaunchKernelGGL(stem_split_kernel<1>, dim3(blocks), dim3(256), 0, s, img, w, bias, out, B, H, W, Cout, act, f16);
+  else if (Cin == 3) hipLaunchKernelGGL(stem_split_kernel<3>, dim3(blocks), dim3(256), 0, s, img, w, bias, out, B, H, W, Cout, act, f16);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-hipError_t launch_stem(const float* img, const float* w, const float* bias, float* out, int B, int H, int W, int Cout,
+hipError_t launch_stem(const float* img, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                        int act, hipStream_t s) {
   if (Cout % 4) return hipErrorInvalidValue;
   const long long total = (long long)B * H * W * (Cout / 4);
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(stem_kernel, dim3(blocks), dim3(256), 0, s, img, w, bias, out, B, H, W, Cout, act);
+  if (Cin == 1) hipLaunchKernelGGL(stem_kernel<1>, dim3(blocks), dim3(256), 0, s, img, w, bias, out, B, H, W, Cout, act);
+  else if (Cin == 3) hipLaunchKernelGGL(stem_kernel<3>, dim3(blocks), dim3(256), 0, s, img, w, bias, out, B, H, W, Cout, act);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

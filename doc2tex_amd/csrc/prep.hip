@@ -174,6 +174,11 @@ int plan_image(const d2t_prep_config* c, int src_h, int src_w, d2t_prep_plan* p)
         p->status = D2T_PREP_UNBOUND_LOCAL;
         return D2T_OK;
       }
+      if (c->channels == 3) {  // is_gray False: MODE / BACKGROUND are unassigned when Image.new needs them (data_utils.py:75-79)
+        p->min_branch = 1;
+        p->status = D2T_PREP_UNBOUND_LOCAL;
+        return D2T_OK;
+      }
       if (nh < h || nw < w || nh <= 0 || nw <= 0) {  // canvas smaller than the image: paste raises ValueError
         plan_fallback(c, p);
         return D2T_OK;
@@ -316,7 +321,7 @@ constexpr int FR = 8, FIN_ROWS = 96;  // output rows per block; LDS window (rows
 __global__ __launch_bounds__(256) void prep_finish_kernel(const PrepDesc* __restrict__ descs, const uint8_t* __restrict__ src,
                                                           const uint8_t* __restrict__ work, const int32_t* __restrict__ tabs,
                                                           const float* __restrict__ lut, float* __restrict__ out, int out_h,
-                                                          int out_w, int32_t* __restrict__ bits) {
+                                                          int out_w, int32_t* __restrict__ bits, int channels) {
   __shared__ uint8_t win[FIN_ROWS][256];
   const PrepDesc d = descs[blockIdx.z];
   const int y0 = blockIdx.y * FR, x = blockIdx.x * 256 + threadIdx.x;
@@ -356,7 +361,9 @@ __global__ __launch_bounds__(256) void prep_finish_kernel(const PrepDesc* __rest
       o = lut[v];  // the fallback normalises with the same transform (predict_utils.py:89)
       if (d.min_branch && v) mybits |= 1 | (y == 0 ? 2 : 0) | (y == d.rs_h - 1 ? 4 : 0) | (x == 0 ? 8 : 0) | (x == d.rs_w - 1 ? 16 : 0);
     }
-    if (x < out_w) out[((size_t)blockIdx.z * out_h + y) * out_w + x] = o;
+    // `rgb: True`: the "RGB" conversion of the grey image (predict_utils.py:50) -- every plane takes the same value
+    if (x < out_w)
+      for (int ch = 0; ch < channels; ++ch) out[(((size_t)blockIdx.z * channels + ch) * out_h + y) * out_w + x] = o;
   }
   if (d.min_branch) {
     for (int s = 32; s; s >>= 1) mybits |= __shfl_xor(mybits, s);
@@ -536,6 +543,8 @@ int d2t_prep_create(const d2t_prep_config* cfg, d2t_prep** out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(p, D2T_EHIP, "no HIP device visible (the pre-processing has no CPU path)");
   if (cfg->norm_mode != D2T_NORM_ALB && cfg->norm_mode != D2T_NORM_RAW) return fail(p, D2T_EINVAL, "bad norm_mode");
+  if (cfg->channels != 0 && cfg->channels != 1 && cfg->channels != 3)
+    return fail(p, D2T_EINVAL, "channels must be 1 (rgb: False) or 3 (rgb: True), got %d", cfg->channels);
   float host[256];
   for (int v = 0; v < 256; ++v) host[v] = normalise_value(*cfg, (float)v);
   PHIP(p, hipMalloc(&p->lut, sizeof host));
@@ -799,7 +808,7 @@ int d2t_prep_run(d2t_prep* p, int n, const d2t_prep_plan* plans, const uint8_t* 
   }
   if (any_min) PHIP(p, hipMemsetAsync(p->d_bits, 0, (size_t)n * 4, stream));
   hipLaunchKernelGGL(prep_finish_kernel, dim3((out_w + 255) / 256, (out_h + FR - 1) / FR, n), dim3(256), 0, stream, d_descs, src_dev,
-                     (const uint8_t*)p->d_work, d_tabs, (const float*)p->lut, out_dev, out_h, out_w, p->d_bits);
+                     (const uint8_t*)p->d_work, d_tabs, (const float*)p->lut, out_dev, out_h, out_w, p->d_bits, c.channels == 3 ? 3 : 1);
   if (flags_dev) {
     if (!any_min) PHIP(p, hipMemsetAsync(p->d_bits, 0, (size_t)n * 4, stream));
     hipLaunchKernelGGL(prep_flags_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_descs, (const int32_t*)p->d_bits,

@@ -351,16 +351,16 @@ struct Tr {  // builder / runner bound to one context and stream
     TCHK(launch_bn_finalize(st->part, chunks, C, P, 1e-5f, 0.1f, n.mean, n.rstd, rm->p, rv->p, s));
     return D2T_OK;
   }
-  int stem(const float* img, int B, int H, int W, const std::string& wkey, const std::string& bnkey, int* out) {
+  int stem(const float* img, int B, int Cin, int H, int W, const std::string& wkey, const std::string& bnkey, int* out) {
     const int Cout = 32;
     const long long P = (long long)B * H * W;
     Node n;
-    n.kind = N_CONV; n.stem = true; n.wkey = wkey; n.bnkey = bnkey; n.relu = true; n.N = Cout; n.K = 9;
+    n.kind = N_CONV; n.stem = true; n.wkey = wkey; n.bnkey = bnkey; n.relu = true; n.N = Cout; n.K = 9 * Cin;
     n.KH = n.KW = 3; n.PH = n.PW = 1;
     const float* w;
-    RC(raw(wkey + ".weight", &w, (size_t)Cout * 9));
+    RC(raw(wkey + ".weight", &w, (size_t)Cout * 9 * Cin));
     RC(alloc(&n.z, (size_t)P * Cout));
-    TCHK(launch_stem_raw(img, w, n.z, B, H, W, Cout, s));
+    TCHK(launch_stem_raw(img, w, n.z, B, Cin, H, W, Cout, s));
     RC(bn_forward(n, P, Cout, -1));
     RC(new_tensor(P, Cout, out, B, H, W));
     const float *g, *b;
@@ -384,7 +384,7 @@ struct Tr {  // builder / runner bound to one context and stream
   }
   int backbone(const float* img, int B, int H, int W, const std::string& p, int* out) {
     int x;
-    RC(stem(img, B, H, W, p + "conv0_1", p + "bn0_1", &x));
+    RC(stem(img, B, c->cfg.in_channels, H, W, p + "conv0_1", p + "bn0_1", &x));
     RC(conv_bn(x, p + "conv0_2", p + "bn0_2", 64, 3, 3, 1, 1, 1, 1, true, -1, &x));
     RC(pool(x, 2, 2, 0, 0, &x));
     const int chans[4] = {128, 256, 512, 512};
@@ -420,16 +420,18 @@ struct Tr {  // builder / runner bound to one context and stream
   // two convolutions + ReLU, (2,1) pool, two bias-free convolutions with BatchNorm + ReLU, (2,1) pool, a 2x2 convolution + ReLU
   int vgg(const float* img, int B, int H, int W, const std::string& p, int* out) {
     int x;
-    {  // first layer: one input channel, the stem kernels (weight gradient included) with a bias instead of a BatchNorm
+    {  // first layer: the image's one or three channels, the stem kernels (weight gradient included) with a bias instead
+       // of a BatchNorm
+      const int Cin = c->cfg.in_channels;
       const float *w, *b;
-      RC(raw(p + "0.weight", &w, (size_t)64 * 9));
+      RC(raw(p + "0.weight", &w, (size_t)64 * 9 * Cin));
       RC(raw(p + "0.bias", &b, 64));
       const long long P = (long long)B * H * W;
       Node n;
-      n.kind = N_CONV; n.wkey = p + "0"; n.KH = n.KW = 3; n.PH = n.PW = 1; n.N = 64; n.K = 9; n.stem = true;
+      n.kind = N_CONV; n.wkey = p + "0"; n.KH = n.KW = 3; n.PH = n.PW = 1; n.N = 64; n.K = 9 * Cin; n.stem = true;
       RC(new_tensor(P, 64, &x, B, H, W));
       n.z = st->t[x].p;
-      TCHK(launch_stem_raw(img, w, n.z, B, H, W, 64, s));
+      TCHK(launch_stem_raw(img, w, n.z, B, Cin, H, W, 64, s));
       TCHK(launch_bias_add(n.z, b, P, 64, s));
       n.out = x;
       st->nodes.push_back(n);
@@ -1141,9 +1143,9 @@ struct Tr {  // builder / runner bound to one context and stream
     }
     if (n.stem) {
       const int chunk = 1024, nch = (int)((P + chunk - 1) / chunk);
-      RC(ensure_part((size_t)nch * 9 * Cout));
-      TCHK(launch_stem_wgrad(st->image, dz, st->part, st->B, st->H, st->W, Cout, chunk, nch, s));
-      TCHK(launch_wgrad_reduce(st->part, dW, nch, 9, Cout, 1, 1, 0, s));
+      RC(ensure_part((size_t)nch * n.K * Cout));  // n.K = 9 * image channels
+      TCHK(launch_stem_wgrad(st->image, dz, st->part, st->B, n.K / 9, st->H, st->W, Cout, chunk, nch, s));
+      TCHK(launch_wgrad_reduce(st->part, dW, nch, n.K, Cout, 1, 1, 0, s));
       return D2T_OK;
     }
     const TT& x = st->t[n.in];
@@ -1667,8 +1669,8 @@ int d2t_op_train_conv(const float* x, const float* w, const float* bias, const f
                       float* dgamma, float* dbeta, float* dres, int32_t B, int32_t H, int32_t W, int32_t Cin,
                       int32_t Cout, int32_t KH, int32_t KW, int32_t SH, int32_t SW, int32_t PH, int32_t PW, int32_t relu,
                       int32_t bf16x3, d2t_stream stream) {
-  if (!x || !w || !dy || (gamma && !beta) || (!gamma && !bias && Cin != 1) || SH < 1 || SW < 1) return D2T_EINVAL;
-  if (Cin != 1 && Cin % 32) return D2T_EINVAL;
+  if (!x || !w || !dy || (gamma && !beta) || (!gamma && !bias && Cin != 1 && Cin != 3) || SH < 1 || SW < 1) return D2T_EINVAL;
+  if (Cin != 1 && Cin != 3 && Cin % 32) return D2T_EINVAL;
   OpCtx o(bf16x3, (hipStream_t)stream);
   Tr& tr = o.tr;
   o.put("w.weight", w, {Cout, Cin, KH, KW});
@@ -1684,11 +1686,11 @@ int d2t_op_train_conv(const float* x, const float* w, const float* bias, const f
   }
   int xin = -1, res = -1, out = -1;
   auto run = [&]() -> int {
-    if (Cin == 1) {  // the stem: 3x3, stride 1, pad 1, BatchNorm + ReLU (resnet.py:205-207)
+    if (Cin == 1 || Cin == 3) {  // the stem: 3x3, stride 1, pad 1, BatchNorm + ReLU (resnet.py:205-207); x is the image, NCHW planar
       if (KH != 3 || KW != 3 || SH != 1 || SW != 1 || PH != 1 || PW != 1 || !gamma || residual || !relu || Cout != 32)
         return fail(&o.c, D2T_EINVAL, "stem geometry");
       o.st.image = x; o.st.B = B; o.st.H = H; o.st.W = W;
-      RC(tr.stem(x, B, H, W, "w", "bn", &out));
+      RC(tr.stem(x, B, Cin, H, W, "w", "bn", &out));
     } else {
       RC(tr.new_tensor((long long)B * H * W, Cin, &xin, B, H, W, const_cast<float*>(x)));
       const int OH = (H + 2 * PH - KH) / SH + 1, OW = (W + 2 * PW - KW) / SW + 1;

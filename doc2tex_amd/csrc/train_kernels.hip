@@ -1649,14 +1649,17 @@ hipError_t launch_sum_rows_strided(const float* x, float* out, int B, long long 
   return hipGetLastError();
 }
 
-// Stem convolution (Cin = 1, 3x3, pad 1) in training mode: raw weights, no bias / BN (z = conv(x)); and its
-// weight gradient dW[co][kh][kw] = sum_p dz[p][co] * x[p + tap]  (block per (co-group), deterministic).
+// Stem convolution (Cin = 1 or 3, 3x3, pad 1) in training mode: raw weights, no bias / BN (z = conv(x)); and its
+// weight gradient dW[co][ci][kh][kw] = sum_p dz[p][co] * x[ci][p + tap]  (block per (co-group), deterministic).
+// The image is NCHW planar; a "tap" below is (ci * 3 + kh) * 3 + kw, the OIHW order of the raw weights.
+template <int CIN>
 __global__ __launch_bounds__(256) void stem_raw_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                        float* __restrict__ z, int B, int H, int W, int Cout) {
-  // a thread owns four consecutive output channels of one pixel: nine image loads serve all four, the filter comes
+  // a thread owns four consecutive output channels of one pixel: 9 * CIN image loads serve all four, the filter comes
   // from LDS as [tap][co] float4s, the store is 16 bytes
-  __shared__ __attribute__((aligned(16))) float ws[9][64];
-  for (int i = threadIdx.x; i < 9 * Cout; i += 256) ws[i % 9][i / 9] = w[i];  // w is [co][9]
+  constexpr int K = 9 * CIN;
+  __shared__ __attribute__((aligned(16))) float ws[K][64];
+  for (int i = threadIdx.x; i < K * Cout; i += 256) ws[i % K][i / K] = w[i];  // w is [co][K]
   __syncthreads();
   const int C4 = Cout >> 2;
   const size_t total = (size_t)B * H * W * C4;
@@ -1665,66 +1668,78 @@ __global__ __launch_bounds__(256) void stem_raw_kernel(const float* __restrict__
     const int x = (int)((i / C4) % W), y = (int)((i / ((size_t)C4 * W)) % H), b = (int)(i / ((size_t)C4 * W * H));
     float a[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
+    for (int ci = 0; ci < CIN; ++ci)
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int ih = y + kh - 1, iw = x + kw - 1;
-        if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
-          const float v = img[((size_t)b * H + ih) * W + iw];
-          const float4 w4 = *reinterpret_cast<const float4*>(&ws[kh * 3 + kw][co]);
-          a[0] = fmaf(v, w4.x, a[0]); a[1] = fmaf(v, w4.y, a[1]); a[2] = fmaf(v, w4.z, a[2]); a[3] = fmaf(v, w4.w, a[3]);
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+          const int ih = y + kh - 1, iw = x + kw - 1;
+          if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
+            const float v = img[(((size_t)b * CIN + ci) * H + ih) * W + iw];
+            const float4 w4 = *reinterpret_cast<const float4*>(&ws[(ci * 3 + kh) * 3 + kw][co]);
+            a[0] = fmaf(v, w4.x, a[0]); a[1] = fmaf(v, w4.y, a[1]); a[2] = fmaf(v, w4.z, a[2]); a[3] = fmaf(v, w4.w, a[3]);
+          }
         }
-      }
     *reinterpret_cast<float4*>(z + i * 4) = make_float4(a[0], a[1], a[2], a[3]);
   }
 }
-hipError_t launch_stem_raw(const float* img, const float* w, float* z, int B, int H, int W, int Cout, hipStream_t s) {
+hipError_t launch_stem_raw(const float* img, const float* w, float* z, int B, int Cin, int H, int W, int Cout, hipStream_t s) {
   if (Cout % 4 || Cout > 64) return hipErrorInvalidValue;
   const size_t total = (size_t)B * H * W * (Cout / 4);
-  hipLaunchKernelGGL(stem_raw_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1u << 16)), dim3(256), 0, s, img, w, z,
-                     B, H, W, Cout);
+  const dim3 grid((unsigned)std::min<size_t>((total + 255) / 256, 1u << 16));
+  if (Cin == 1) hipLaunchKernelGGL(stem_raw_kernel<1>, grid, dim3(256), 0, s, img, w, z, B, H, W, Cout);
+  else if (Cin == 3) hipLaunchKernelGGL(stem_raw_kernel<3>, grid, dim3(256), 0, s, img, w, z, B, H, W, Cout);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
-// part[chunk][tap][co]: chunked over pixels; reduced by launch_wgrad_reduce with M = Cout, N = 1 ... (taps = 9)
-template <int CO>  // output channels: 32 (ResNet conv0_1) or 64 (VGG's first convolution)
+// part[chunk][tap][co]: chunked over pixels; reduced by launch_wgrad_reduce with M = Cout, N = 1 ... (taps = 9 * CIN)
+template <int CO, int CIN>  // output channels: 32 (ResNet conv0_1) or 64 (VGG's first convolution); image channels 1 or 3
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ img, const float* __restrict__ dz,
                                                          float* __restrict__ part, int B, int H, int W, int chunk) {
   // thread -> (co = tid % CO, pixel lane = tid / CO)
-  constexpr int NPL = 256 / CO;
-  __shared__ float red[NPL][9][CO];
+  constexpr int NPL = 256 / CO, K = 9 * CIN;
+  __shared__ float red[NPL][K][CO];
   const int co = threadIdx.x % CO, pl = threadIdx.x / CO;
   const long long P = (long long)B * H * W;
   const long long r0 = (long long)blockIdx.x * chunk, r1 = r0 + chunk < P ? r0 + chunk : P;
-  float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float acc[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) acc[t] = 0.f;
   for (long long r = r0 + pl; r < r1; r += NPL) {
     const int x = (int)(r % W), y = (int)((r / W) % H);
     const long long b = r / ((long long)W * H);
     const float g = dz[(size_t)r * CO + co];
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
+    for (int ci = 0; ci < CIN; ++ci)
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int ih = y + kh - 1, iw = x + kw - 1;
-        if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W)
-          acc[kh * 3 + kw] = fmaf(g, img[((size_t)b * H + ih) * W + iw], acc[kh * 3 + kw]);
-      }
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+          const int ih = y + kh - 1, iw = x + kw - 1;
+          if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W)
+            acc[(ci * 3 + kh) * 3 + kw] = fmaf(g, img[(((size_t)b * CIN + ci) * H + ih) * W + iw], acc[(ci * 3 + kh) * 3 + kw]);
+        }
   }
 #pragma unroll
-  for (int t = 0; t < 9; ++t) red[pl][t][co] = acc[t];
+  for (int t = 0; t < K; ++t) red[pl][t][co] = acc[t];
   __syncthreads();
-  for (int i = threadIdx.x; i < 9 * CO; i += 256) {
+  for (int i = threadIdx.x; i < K * CO; i += 256) {
     const int t = i / CO, c = i % CO;
     float v = 0.f;
 #pragma unroll
     for (int k = 0; k < NPL; ++k) v += red[k][t][c];
-    part[((size_t)blockIdx.x * 9 + t) * CO + c] = v;  // [chunk][tap][co] == wgrad partial layout with M = Cout, N = 1
+    part[((size_t)blockIdx.x * K + t) * CO + c] = v;  // [chunk][tap][co] == wgrad partial layout with M = Cout, N = 1
   }
 }
-hipError_t launch_stem_wgrad(const float* img, const float* dz, float* part, int B, int H, int W, int Cout, int chunk,
+hipError_t launch_stem_wgrad(const float* img, const float* dz, float* part, int B, int Cin, int H, int W, int Cout, int chunk,
                              int nchunks, hipStream_t s) {
-  if (Cout == 32) hipLaunchKernelGGL(stem_wgrad_kernel<32>, dim3(nchunks), dim3(256), 0, s, img, dz, part, B, H, W, chunk);
-  else if (Cout == 64) hipLaunchKernelGGL(stem_wgrad_kernel<64>, dim3(nchunks), dim3(256), 0, s, img, dz, part, B, H, W, chunk);
+#define D2T_STEM_WGRAD(CO, CI) hipLaunchKernelGGL((stem_wgrad_kernel<CO, CI>), dim3(nchunks), dim3(256), 0, s, img, dz, part, B, H, W, chunk)
+  if (Cout == 32 && Cin == 1) D2T_STEM_WGRAD(32, 1);
+  else if (Cout == 64 && Cin == 1) D2T_STEM_WGRAD(64, 1);
+  else if (Cout == 32 && Cin == 3) D2T_STEM_WGRAD(32, 3);
+  else if (Cout == 64 && Cin == 3) D2T_STEM_WGRAD(64, 3);
   else return hipErrorInvalidValue;
+#undef D2T_STEM_WGRAD
   return hipGetLastError();
 }
 

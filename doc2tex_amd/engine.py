@@ -197,6 +197,8 @@ class Engine:
         """Model.forward under module.train(): logits [B,L,V] of the teacher-forced pass (BatchNorm on batch
         statistics; the engine's running statistics are updated, see read_weight)."""
         self._on_device(image, "input")
+        if image.dim() != 4 or image.shape[1] != self.cfg.in_channels:
+            raise ValueError(f"expected image [B,{self.cfg.in_channels},H,W], got {tuple(image.shape)}")
         image = image.float().contiguous()
         tgt = tgt.to(device=image.device, dtype=torch.int64).contiguous()
         B, _, H, W = image.shape
@@ -281,13 +283,13 @@ class Engine:
         return T, d, gh, gw, pw, ph
 
     def encode(self, image, attn_maps=None):
-        """image [B,1,H,W] -> (memory [B,T,d], (grid_h, grid_w), (pad_w, pad_h)).  attn_maps (ViT encoders): a list of
+        """image [B,in_channels,H,W] (1 grey plane or 3 colour planes, as the config says) -> (memory [B,T,d], (grid_h, grid_w), (pad_w, pad_h)).  attn_maps (ViT encoders): a list of
         vit_depth entries, each None or a caller-allocated contiguous fp32 tensor [B, heads, T, T] on the image's device
         that receives that block's self-attention probabilities (the reference's attn_drop input); memory is bitwise the
         same with or without them."""
         self._on_device(image, "input")
-        if image.dim() != 4 or image.shape[1] != 1:
-            raise ValueError(f"expected image [B,1,H,W], got {tuple(image.shape)}")
+        if image.dim() != 4 or image.shape[1] != self.cfg.in_channels:
+            raise ValueError(f"expected image [B,{self.cfg.in_channels},H,W], got {tuple(image.shape)}")
         image = image.float().contiguous()
         B, _, H, W = image.shape
         T, d, gh, gw, pw, ph = self.encoder_shape(H, W)

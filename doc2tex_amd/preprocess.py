@@ -3,16 +3,24 @@
 Host-side mirror of the reference's `resize()` -- `doc2tex/utils/predict_utils.py:14-115` (what `api/infer.py:62`
 calls with an image path; variant "api") and `demo/HybridViT/helper.py:134-207` (what `demo/HybridViT/recog_flow.py:81`
 calls with a PIL image; variant "demo") -- for the configuration the shipped YAMLs use: `imgH: null`, no learned
-resizer, grayscale; `pad: True` (contrast-normalise, crop to the text's bounding rectangle, extend to multiples of 32:
+resizer; `pad: True` (contrast-normalise, crop to the text's bounding rectangle, extend to multiples of 32:
 `utils/data_utils.py:10-45`) is supported too.  Same argument meaning, same return value (a float32 `[1,1,H,W]` tensor, here on the
-GPU), same exceptions.  All pixel work runs in `libd2t.so` (`d2t_prep_run`, include/d2t_prep.h): there is no CPU path.
+GPU; `[1,3,H,W]` with `rgb: True`), same exceptions.
+
+`rgb: True` is what the reference makes of it: both copies open the image with `.convert("L")` (predict_utils.py:16,
+helper.py:136), resize the grey image, convert it to "RGB" (predict_utils.py:50, helper.py:158), normalise the three
+planes with the same scalar mean / std (`to_3tuple`, math_transform.py:44) and drop planes only when `rgb` is false.  So
+the three planes are equal and each is bitwise the plane `rgb: False` returns; the normalise kernel writes them in one
+pass.  One quirk comes along: `minmax_size(..., is_gray = not opt["rgb"])` defines MODE / BACKGROUND only when `is_gray`
+(data_utils.py:75-78, helper.py:124-126), so an image below `min_dimension` raises `UnboundLocalError` instead of being
+pasted on a white canvas, and `resize()` does not catch it.  All pixel work runs in `libd2t.so` (`d2t_prep_run`, include/d2t_prep.h): there is no CPU path.
 
 The two reference copies differ in `get_divisible_size`: the "api" copy (`utils/data_utils.py:48-60`) leaves its result
 unassigned when a scaled size is already a multiple of 32 and raises `UnboundLocalError` -- for nearly every image that
 needs resizing -- while the "demo" copy (`helper.py:95-107`) is repaired.  Both behaviours are mirrored; "demo" is the
 default for arrays / PIL images, "api" for paths, as in the reference.
 
-`Preprocessor.batch()` is the serving extension: many images per call, grouped by output size into `[n,1,H,W]` batches
+`Preprocessor.batch()` is the serving extension: many images per call, grouped by output size into `[n,C,H,W]` batches
 (the bucketed batches `data/collate_fn.py:15-47` builds), each image bit-identical to its single-image `resize()`.
 """
 import ctypes as C
@@ -45,8 +53,7 @@ class Preprocessor:
         if self.fixed_height and variant == "demo":
             # helper.py:142-207 has no `else:` for a set imgH: `new_img` is never assigned
             raise UnboundLocalError("local variable 'new_img' referenced before assignment (demo/HybridViT/helper.py:206)")
-        if opt.get("rgb", False):
-            raise NotImplementedError("doc2tex_amd.preprocess: grayscale only (rgb: False in every shipped config)")
+        self.channels = 3 if opt.get("rgb", False) else 1
         self.pad = bool(opt.get("pad", False))
         if opt.get("use_resizer", False):
             raise NotImplementedError("doc2tex_amd.preprocess: the learned resizer loop is not on this path")
@@ -69,13 +76,14 @@ class Preprocessor:
             # Normalize(mean, std) on the 0..255 values
             self.pad = False
             self.cfg = _lib.D2TPrepConfig(max_h=1 << 30, max_w=1 << 30, min_h=0, min_w=0, downsample=0, variant=_lib.PREP_API,
-                                          mean=float(opt["mean"]), std=float(opt["std"]), norm_mode=_lib.NORM_RAW)
+                                          mean=float(opt["mean"]), std=float(opt["std"]), norm_mode=_lib.NORM_RAW,
+                                          channels=self.channels)
         else:
             self.cfg = _lib.D2TPrepConfig(
                 max_h=opt["max_dimension"][0], max_w=opt["max_dimension"][1],
                 min_h=opt["min_dimension"][0], min_w=opt["min_dimension"][1],
                 downsample=int(ds) if ds else 0, variant=_lib.PREP_API if variant == "api" else _lib.PREP_DEMO,
-                mean=float(opt["mean"]), std=float(opt["std"]), norm_mode=_lib.NORM_ALB)
+                mean=float(opt["mean"]), std=float(opt["std"]), norm_mode=_lib.NORM_ALB, channels=self.channels)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self.lib.d2t_prep_create(C.byref(self.cfg), C.byref(h))
@@ -136,12 +144,12 @@ class Preprocessor:
         return src, offs
 
     def _run(self, src, offs, plans, out_h, out_w):
-        """One d2t_prep_run over device-resident sources -> ([n,1,H,W] float32 on the device, flags tensor or None)."""
+        """One d2t_prep_run over device-resident sources -> ([n,C,H,W] float32 on the device, flags tensor or None)."""
         import torch
         n = len(plans)
         offs = np.ascontiguousarray(offs, dtype=np.int64)
         with torch.cuda.device(self.device):
-            out = torch.empty((n, 1, out_h, out_w), dtype=torch.float32, device=self.device)
+            out = torch.empty((n, self.channels, out_h, out_w), dtype=torch.float32, device=self.device)
             need_flags = any(p.min_branch for p in plans)
             flags = torch.empty(n, dtype=torch.int32, device=self.device) if need_flags else None
             rc = self.lib.d2t_prep_run(self.h, n, (_lib.D2TPrepPlan * n)(*plans), _lib.ptr(src),
@@ -218,8 +226,8 @@ class Preprocessor:
         return dst, doffs, [(int(dh[i]), int(dw[i])) for i in range(n)], errors
 
     def batch(self, images):
-        """images: paths / PIL images / uint8 [h,w] arrays -> (tensors, errors): tensors[i] is image i's [1,1,H,W] result
-        (a view into the [n,1,H,W] batch of its size bucket; `tensors[i]._base` is the bucket), errors[i] the exception
+        """images: paths / PIL images / uint8 [h,w] arrays -> (tensors, errors): tensors[i] is image i's [1,C,H,W] result
+        (a view into the [n,C,H,W] batch of its size bucket; `tensors[i]._base` is the bucket), errors[i] the exception
         instance the reference's resize() raises for image i (tensors[i] is None then)."""
         t_in = time.perf_counter()
         arrays = [_as_gray_array(im) for im in images]
@@ -248,7 +256,12 @@ class Preprocessor:
             buckets = {}
             for i in pending:
                 p = plans[i]
-                if p.status == _lib.PREP_UNBOUND_LOCAL:
+                if p.status == _lib.PREP_UNBOUND_LOCAL and p.min_branch:
+                    # rgb: True -> minmax_size(..., is_gray=False): MODE / BACKGROUND are assigned under `if is_gray:` only
+                    # (data_utils.py:75-78, helper.py:124-126); not a ValueError, so resize() lets it through
+                    errors[i] = UnboundLocalError("local variable 'MODE' referenced before assignment "
+                                                  "(minmax_size with is_gray=False, utils/data_utils.py:75-79)")
+                elif p.status == _lib.PREP_UNBOUND_LOCAL:
                     errors[i] = UnboundLocalError("local variable 'new_h' referenced before assignment "
                                                   "(get_divisible_size, utils/data_utils.py:48-60)")
                 elif p.status == _lib.PREP_FALLBACK and self.variant == "api":
@@ -298,7 +311,7 @@ def resize(resizer, img, opt, variant=None):
         variant = "api" if isinstance(img, (str, os.PathLike)) else "demo"
     key = (variant, opt["imgH"] is not None, bool(opt.get("pad", False)), tuple(opt["max_dimension"]),
            tuple(opt["min_dimension"]), opt.get("downsample", None),
-           float(opt["mean"]), float(opt["std"]), str(opt.get("device", "cuda")))
+           float(opt["mean"]), float(opt["std"]), str(opt.get("device", "cuda")), bool(opt.get("rgb", False)))
     pre = _cache.get(key)
     if pre is None:
         pre = _cache[key] = Preprocessor(opt, variant)

@@ -163,6 +163,28 @@ _CONFIGS["C3"] = copy.deepcopy(_CONFIGS["C2"])
 _CONFIGS["C3"]["_batch"] = 32  # per GPU; 256 global over 8 GPUs
 
 
+def _colour_twin(name):
+    """Deep copy of a configuration with every `input_channel` set to 3 (`rgb: True` models: ResNet_FeatureExtractor's and
+    HybridEmbed's own defaults).  For ViT stacks both SequenceModeling.params and its backbone carry the key and HybridEmbed's
+    dry run needs them equal."""
+    cfg = copy.deepcopy(_CONFIGS[name])
+    fp = cfg["FeatureExtraction"]["params"]
+    if "input_channel" in fp:
+        fp["input_channel"] = 3
+    sp = cfg["SequenceModeling"]["params"]
+    if "input_channel" in sp:
+        sp["input_channel"] = 3
+        sp["backbone"]["input_channel"] = 3
+    cfg["rgb"] = True
+    return cfg
+
+
+# colour twins: T2C tiny HybridViT + TFM, TS0C tiny HybridViT + Attnv2 (the shipped recipe), C0C VGG + BiLSTM + Attn,
+# T1C ResNet + PositionalEncoding2D + TFM (d_model 512), C2C the headline size
+for _n in ("T2", "TS0", "C0", "T1", "C2"):
+    _CONFIGS[_n + "C"] = _colour_twin(_n)
+
+
 def make_config(name, device="cpu", max_seq_len=None, beam_size=None):
     """Return a fresh (deep-copied) reference-schema config dict.
 
@@ -182,6 +204,14 @@ def make_config(name, device="cpu", max_seq_len=None, beam_size=None):
     if beam_size is not None:
         cfg["beam_size"] = beam_size
     return cfg
+
+
+def image_channels(cfg):
+    """Planes of the image a configuration's model reads: the `input_channel` of its (hybrid) backbone, 1 or 3."""
+    seq = cfg.get("SequenceModeling") or {}
+    if seq.get("name") == "ViT":
+        return int(seq["params"]["backbone"]["input_channel"])
+    return int(cfg["FeatureExtraction"]["params"]["input_channel"])
 
 
 def crop_shape(name):
@@ -277,11 +307,12 @@ def synth_state_dict(template, seed=1234, end_bias=0.0, learned_pos=False):
     return out
 
 
-def synth_images(batch, h, w, seed=1000):
+def synth_images(batch, h, w, seed=1000, channels=1):
     """Seeded crops, uniform in [-1, 1] after the reference normalisation
-    x/255 -> (x-0.5)/0.5 (transform/math_transform.py:35-38).  [B,1,H,W] f32."""
+    x/255 -> (x-0.5)/0.5 (transform/math_transform.py:35-38).  [B,channels,H,W] f32; the planes of a colour crop
+    (channels=3) are independent draws, so a stem that mixed them up would show."""
     g = _rng(seed, "images")
-    u8 = g.integers(0, 256, size=(batch, 1, h, w), dtype=np.int64).astype(np.float32)
+    u8 = g.integers(0, 256, size=(batch, channels, h, w), dtype=np.int64).astype(np.float32)
     x = (u8 / np.float32(255.0) - np.float32(0.5)) / np.float32(0.5)
     return torch.from_numpy(x.astype(np.float32))
 

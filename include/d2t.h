@@ -96,7 +96,7 @@ enum { D2T_VIT_POS_SINCOS_PREFIX = 0, D2T_VIT_POS_LEARNED_INTERP = 1, D2T_VIT_PO
 
 typedef struct d2t_config {
   int32_t encoder;      /* D2T_ENC_*: Feat=ResNet+Seq=None  |  Seq=ViT (hybrid) */
-  int32_t in_channels;  /* 1 (grey crops) */
+  int32_t in_channels;  /* 1 (grey crops) or 3 (rgb: True) */
   int32_t backbone_out; /* ResNet output_channel, 512 */
   int32_t vit_depth, vit_heads, vit_dim; /* ViT blocks / heads / hidden_size */
   int32_t patch_h, patch_w;              /* patch_size */
@@ -158,8 +158,9 @@ int d2t_finalize_weights(d2t_ctx* ctx, d2t_stream stream);
  * d2t_encoder_shape: host-only; token count T, feature dim d, patch grid
  * (grid_h, grid_w; the backbone feature map size for the ResNet encoder) and
  * HybridEmbed's (pad_w, pad_h) for an H x W crop.
- * d2t_encode: image [B,1,H,W] fp32 in [-1,1] [device] -> memory [B,T,d]
- * [device, caller-allocated]. */
+ * d2t_encode: image [B,in_channels,H,W] fp32 in [-1,1] [device] (NCHW planar; in_channels
+ * is the config's, 1 or 3) -> memory [B,T,d] [device, caller-allocated].  d2t_encode_attn
+ * and d2t_train_forward take the same image layout. */
 int d2t_encoder_shape(const d2t_ctx* ctx, int32_t H, int32_t W, int32_t* T, int32_t* d, int32_t* grid_h,
                       int32_t* grid_w, int32_t* pad_w, int32_t* pad_h);
 int d2t_encode(d2t_ctx* ctx, const float* image_dev, int32_t B, int32_t H, int32_t W, float* memory_dev,
@@ -397,7 +398,8 @@ int d2t_profile_read(d2t_ctx* ctx, int32_t max_records, int32_t* n, int32_t* M, 
  */
 /* y = act(conv2d(x, w) + bias + residual).  x [B,H,W,Cin] NHWC, w [Cout,KH,KW,Cin]
  * (OHWI), bias [Cout] or NULL, residual [B,OH,OW,Cout] or NULL, y [B,OH,OW,Cout].
- * Out-of-range taps read as zero.  Cin must be 1 (direct kernel, 3x3 pad 1 only)
+ * Out-of-range taps read as zero.  Cin must be 1 or 3 (direct stem kernels, 3x3 pad 1 only;
+ * x is then the image as d2t_encode takes it, NCHW planar [B,Cin,H,W], w still OHWI)
  * or a multiple of 32 (MFMA implicit GEMM). */
 int d2t_op_conv2d(const float* x, const float* w, const float* bias, const float* residual, float* y, int32_t B,
                   int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t SH, int32_t SW,
@@ -456,7 +458,8 @@ int d2t_ce_backward(const float* logits, const int64_t* target, const float* lse
  * be NULL.  bf16x3 != 0: split-bf16 arithmetic for the convolution / data-gradient / weight-gradient GEMMs.
  * Synchronous (the call returns after the stream has drained). */
 /* y = [relu]( BN_batchstats( conv(x, w) ) [+ residual] )  (gamma != NULL)   or   conv(x, w) + bias  (gamma == NULL).
- * Cin == 1 selects the stem (3x3, pad 1, BN + ReLU, 32 output channels: resnet.py:205-207). */
+ * Cin == 1 or 3 selects the stem (3x3, pad 1, BN + ReLU, 32 output channels: resnet.py:205-207); x is then the image,
+ * NCHW planar [B,Cin,H,W], and no dx is written (the image needs no gradient). */
 int d2t_op_train_conv(const float* x, const float* w, const float* bias, const float* gamma, const float* beta,
                       const float* residual, const float* dy, float* y, float* dx, float* dw, float* dbias,
                       float* dgamma, float* dbeta, float* dres, int32_t B, int32_t H, int32_t W, int32_t Cin,

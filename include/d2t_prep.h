@@ -61,10 +61,13 @@ typedef struct {
   int32_t min_h, min_w; /* opt["min_dimension"] */
   int32_t downsample;   /* opt["downsample"] (variant API only), 0 = none */
   int32_t variant;      /* D2T_PREP_DEMO / D2T_PREP_API */
-  float mean, std;      /* opt["mean"], opt["std"] (grayscale) */
+  float mean, std;      /* opt["mean"], opt["std"]: one scalar each, applied to every plane (to_3tuple, math_transform.py:44) */
   int32_t norm_mode;    /* D2T_NORM_ALB: (v - mean*255) * float32(1/(std*255))  -- albumentations, the `imgH: null` branch;
                            D2T_NORM_RAW: (v - mean) / std on the 0..255 values  -- torchvision Normalize, the `imgH` branch
                            (predict_utils.py:98-114, which neither resizes nor divides by 255)                          */
+  int32_t channels;     /* planes of the output tensor: 1 (`rgb: False`; 0 means 1 too) or 3 (`rgb: True`: resize() works on the
+                           "L" image throughout and converts it to "RGB" before normalising, predict_utils.py:16,50, so the
+                           three planes are copies of the grey one, written by the same kernel)                        */
 } d2t_prep_config;
 
 typedef struct {
@@ -72,7 +75,8 @@ typedef struct {
   int32_t ds_h, ds_w;   /* after the INTER_AREA downsample (== src when it does not apply) */
   int32_t rs_h, rs_w;   /* after the LANCZOS resize (== ds when the image already fits max_dimension) */
   int32_t out_h, out_w; /* tensor height / width: rs, or the min_dimension canvas, or max_dimension for the fallback */
-  int32_t min_branch;   /* 1: pasted on a 255 canvas (data_utils.py:70-81); the paste check applies */
+  int32_t min_branch;   /* 1: pasted on a 255 canvas (data_utils.py:70-81); the paste check applies.  With channels = 3 the
+                           canvas cannot be made (MODE is unassigned): min_branch = 1 then comes with status _UNBOUND_LOCAL */
   int32_t status;       /* D2T_PREP_OK / _UNBOUND_LOCAL / _FALLBACK */
 } d2t_prep_plan;
 
@@ -86,7 +90,7 @@ void d2t_prep_destroy(d2t_prep* p);
 const char* d2t_prep_last_error(const d2t_prep* p);
 
 /*
- * Pre-process n images into out_dev[n][1][out_h][out_w] (float32).
+ * Pre-process n images into out_dev[n][channels][out_h][out_w] (float32; channels = the config's, 1 or 3).
  *   plans        [host]   n plans from d2t_prep_plan_image / _fallback; every plan must have status OK or FALLBACK and
  *                         (out_h, out_w) equal to the call's
  *   src_dev      [device] the uint8 pixels of all images, row-major, image i at src_dev + src_offsets[i]

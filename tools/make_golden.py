@@ -214,7 +214,7 @@ def run_greedy(case):
     name, cname, B, H, W, L, wseed, iseed, end_bias, is_test = case
     t0 = time.time()
     cfg, m, sd = build_ref(cname, L, beam_size=1, wseed=wseed, end_bias=end_bias)  # greedy: beam_size 1 (C4 defaults to 5)
-    img = synth.synth_images(B, H, W, seed=iseed)
+    img = synth.synth_images(B, H, W, seed=iseed, channels=synth.image_channels(cfg))
     text = torch.full((B, 1), R.GO, dtype=torch.long)
     rep = {"case": name, "config": cname, "B": B, "H": H, "W": W, "max_seq_len": L, "wseed": wseed, "beam_size": 1,
            "iseed": iseed, "end_bias": end_bias, "is_test": is_test, "torch": torch.__version__}
@@ -276,7 +276,7 @@ def run_greedy(case):
 def run_beam(case):
     name, cname, H, W, L, wseed, iseed, end_bias, beam = case
     cfg, m, sd = build_ref(cname, L, beam_size=beam, wseed=wseed, end_bias=end_bias)
-    img = synth.synth_images(1, H, W, seed=iseed)
+    img = synth.synth_images(1, H, W, seed=iseed, channels=synth.image_channels(cfg))
     text = torch.full((1, 1), R.GO, dtype=torch.long)
     pred = m.predicter.Prediction
     # fresh Beam per sample (demo reset_beam semantics)
@@ -297,7 +297,7 @@ def run_beam(case):
 def run_attn_beam(case):
     name, cname, H, W, L, wseed, iseed, end_bias, beam = case
     cfg, m, sd = build_ref(cname, L, beam_size=beam, wseed=wseed, end_bias=end_bias)
-    img = synth.synth_images(1, H, W, seed=iseed)
+    img = synth.synth_images(1, H, W, seed=iseed, channels=synth.image_channels(cfg))
     text = torch.zeros(1, L + 1, dtype=torch.long)  # engine/inferencing.py:58-63 (ignored by the beam path)
     with torch.no_grad():
         seq, score, _ = m(img, text, is_train=False, is_test=True)
@@ -335,7 +335,7 @@ def run_train(case):
     name, cname, B, H, W, L, wseed, iseed = case
     cfg, m, sd = build_ref(cname, L, wseed=wseed)
     m.train()  # teacher forcing (tfm.py:103); BN switches to batch statistics
-    img = synth.synth_images(B, H, W, seed=iseed)
+    img = synth.synth_images(B, H, W, seed=iseed, channels=synth.image_channels(cfg))
     text = synth.synth_labels(B, max_len=L, seed=iseed)
     text[:, 8:] = 0
     text[:, 7] = R.END  # short labels so PAD masking is exercised
@@ -389,7 +389,7 @@ def run_train_step(case):
     name, cname, B, H, W, L, wseed, iseed = case
     cfg, m, sd = build_ref(cname, L, wseed=wseed)
     m.train()
-    img = synth.synth_images(B, H, W, seed=iseed)
+    img = synth.synth_images(B, H, W, seed=iseed, channels=synth.image_channels(cfg))
     text = train_labels(cfg, B, L, iseed)
     t0 = time.time()
     # GlobalContext blocks carry an nn.Dropout(0.25) that module.train() switches on (visual_attention.py:86-101): the
@@ -473,7 +473,7 @@ def run_train_dropout(case):
         for layer in m.predicter.Prediction.model.layers:
             layer.self_attn.dropout = 0.0
             layer.multihead_attn.dropout = 0.0
-    img = synth.synth_images(B, H, W, seed=iseed)
+    img = synth.synth_images(B, H, W, seed=iseed, channels=synth.image_channels(cfg))
     text = train_labels(cfg, B, L, iseed) if lstm else synth.synth_labels(B, max_len=L, seed=iseed)
     import random
     random.seed(mseed)  # scheduled sampling of the LSTM head draws random.random() once per step (seq2seq.py:312)
