@@ -117,12 +117,17 @@ class DecodeHandle:
     engine's decode stream is still writing.  `wait()` orders the current stream (optionally the host) after exactly that
     decode -- launching the group first if it is still collecting batches -- and `done()` polls without blocking.
     `result()` waits and returns (prediction, logits) as the synchronous call would: with is_test they are cut at the
-    first step at which every row of THIS batch had emitted [s] (tfm.py:138-140)."""
+    first step at which every row of THIS batch had emitted [s] (tfm.py:138-140).
 
-    def __init__(self, model, eng, ticket=None, index=0, tensors=None):
+    LSTM-attention heads (full_size): `result()` returns the FULL-SIZE tensors, zeros after the exit step, because that
+    is what their synchronous forward -- and the reference (seq2seq.py:224-331) -- returns; `steps()` is the reference's
+    step count."""
+
+    def __init__(self, model, eng, ticket=None, index=0, tensors=None, full_size=False):
         self._model, self._eng, self.ticket = model, eng, ticket
         self._index, self._tensors = index, tensors  # position of this batch inside its decode group; full-size views
         self._steps = None
+        self._full_size = full_size
 
     def steps(self):
         """Valid length of this batch's tokens / logits (blocks the host until its decode is complete).  Cached: the
@@ -137,6 +142,8 @@ class DecodeHandle:
     def result(self):
         n = self.steps()  # blocks the host until the decode is complete
         p, l = self._tensors
+        if self._full_size:
+            return p, l
         return p[:, :n], l[:, :n]
 
     def _launch(self):
@@ -187,7 +194,10 @@ class Model(nn.Module):
         self.beam_shared_tile = False
         # pipelined mode: decode loops in flight side by side (1 .. 4)
         self.decode_chains = 1
-        # pipelined mode: decode the rows of this many consecutive forward() calls in ONE step loop.  The decode step is a
+        # (LSTM-attention heads: each of the chains holds one forward's whole loop, key projection and state block)
+        # pipelined mode, TFM head: decode the rows of this many consecutive forward() calls in ONE step loop.  Ignored by the
+        # LSTM-attention heads, whose loop already is one launch with one block per row and whose early exit is decided over
+        # the forward's own batch.  The decode step is a
         # chain of small latency-bound kernels whose duration barely depends on the row count, so two batches per loop halve
         # the launches (and the interference with the next encoders) per formula.  Rows are independent and every kernel is
         # dispatched by layer shape only, so each row's tokens / logits are bit-identical to an ungrouped decode.  Results
@@ -452,6 +462,15 @@ class Model(nn.Module):
                 prediction, logits, alphas = eng.decode_attn_beam_batch(contextual_feature.contiguous(), beam_size,
                                                                         return_alpha=True)[0]
                 return prediction, logits, alphas, {}
+            if self.pipelined:
+                # the forward returns while the loop runs on one of the engine's decode streams; tensors are full size as in
+                # the synchronous call and complete (zeros after an is_test exit included) once the handle is
+                out = eng.decode_attn_greedy_async(contextual_feature.contiguous(), is_test, return_alpha=viz)
+                prediction, logits, ticket = out[0], out[1], out[-1]
+                if viz:  # set at call time, complete with the handle (seq2seq.py:267-272,300-301)
+                    pred.alpha_stores = out[2].unsqueeze(-1)
+                handle = DecodeHandle(self, eng, ticket, 0, (prediction, logits), full_size=True)
+                return prediction, logits, None, {"decode": handle}
             if not viz:
                 prediction, logits = eng.decode_attn_greedy(contextual_feature.contiguous(), is_test)
                 return prediction, logits, None, {}

@@ -181,7 +181,8 @@ struct d2t_ctx {
   int no_pool_fusion = 0;  // debug / A-B: 1 = the two 2x2 max-pools as their own kernels (d2t_set_conv_fusion)
   float* beam_qp = nullptr; size_t beam_qp_cap = 0;  // beam, absorbed cross-attention: q' / context rows + LN1 rows (decode.hip)
   float* dws = nullptr; size_t dws_cap = 0;
-  int* dstate = nullptr;   // [0]=step [1]=end_count [2]=steps_done [3..]=ended[B]
+  int* dstate = nullptr;   // TFM: [0]=step [1]=end_count [2]=steps_done [3..]=ended[B]
+                           // LSTM-attention heads: [0..1]=exit word (AttnDecP::exit_state) [2]=steps [3]=pad [4..]=end_step[B]
   size_t dstate_cap = 0;
   int* h_pinned = nullptr;
   void* zero_page = nullptr;  // 256 zero bytes: out-of-image taps of the split-bf16 convolution

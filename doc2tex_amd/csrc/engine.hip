@@ -1408,6 +1408,82 @@ AttnDecP attn_dec_params(const d2t_ctx* c, const float* memory, int T, const flo
 }
 }  // namespace
 
+namespace {
+// What every greedy call of the LSTM-attention heads refuses, before anything is enqueued.
+int attn_greedy_check(d2t_ctx* c, const float* memory, int B, int T, const int64_t* tokens, const float* probs) {
+  if (!c || !memory || !tokens || !probs || B < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
+  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
+  const d2t_config& g = c->cfg;
+  if (g.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "context was not created with the Attn decoder");
+  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  if (T - key_off < 1 || T - key_off > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
+  if (g.vocab > D2T_ATTN_MAX_CLASSES) return fail(c, D2T_EINVAL, "Attn decoder supports num_class <= %d, got %d", D2T_ATTN_MAX_CLASSES, g.vocab);
+  return D2T_OK;
+}
+
+// Greedy decode of the LSTM-attention heads.  Synchronous (async == false): everything on the caller's stream, in chain
+// 0's workspace.  Asynchronous: the chains take turns; the key projection, the one-launch step loop and the finalize
+// kernel run on the chain's stream, ordered behind the caller's stream by an event, and the call returns once they are
+// enqueued (no host synchronisation).  A chain's stream is in order, so its workspace (key projection, state block) is
+// never rewritten under a loop that still reads it.
+// is_test: the reference's early exit is taken inside the kernel (AttnDecP::exit_state) and the finalize kernel zeroes
+// what lies behind it and leaves the step count in the state block: one path for the rule, synchronous or not.
+int attn_greedy_impl(d2t_ctx* c, const float* memory, int B, int T, int is_test, int64_t* tokens, float* probs, float* alpha,
+                     int* steps_out, hipStream_t user, bool async) {
+  const d2t_config& g = c->cfg;
+  const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab;
+  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  const int chain = async ? (int)(c->decode_seq++ % (unsigned)c->n_chains) : 0;
+  select_chain(c, chain);
+  hipStream_t s = async ? c->dstream : user;
+  int rc;
+  // workspace of the chain: key_proj(memory) [B*T][H]; state: exit word | steps | pad (16 bytes) | end_step [B]
+  if ((rc = ensure(c, &c->dws, &c->dws_cap, ((size_t)B * T * Hh + 16) * 4))) return rc;
+  if ((rc = ensure(c, &c->dstate, &c->dstate_cap, ((size_t)B + 4) * 4))) return rc;
+  float* kp = c->dws;
+  unsigned long long* exit_state = reinterpret_cast<unsigned long long*>(c->dstate);
+  int* steps_dev = c->dstate + 2;
+  int* end_step = c->dstate + 4;
+  if (async) {  // the chain's stream starts behind the caller's work (the memory)
+    HIPCHK(c, hipEventRecord(c->ev_in, user));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
+  } else if (c->ev_done_valid[chain]) {  // an asynchronous decode of this chain may still read the workspace
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_done[chain], 0));
+  }
+  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, B * T, ACT_NONE));
+  HIPCHK(c, hipMemsetAsync(c->dstate, 0, 16, s));
+  HIPCHK(c, hipMemsetAsync(end_step, 0xFF, (size_t)B * 4, s));  // -1 = never emitted [s]
+  AttnDecP p = attn_dec_params(c, memory, T, kp);
+  p.probs = probs; p.tokens = tokens; p.end_step = end_step;
+  p.sv_alpha = alpha;  // optional [B][S][Tk]: the alignment of every step (viz_attn, seq2seq.py:267-272,300-301)
+  p.B = B; p.S = S;
+  p.exit_state = is_test ? exit_state : nullptr;
+  HIPCHK(c, launch_attn_decode(p, s));
+  // reference: break after the first step at which every row has emitted [s]; its pre-zeroed outputs keep zeros behind it
+  if (is_test) HIPCHK(c, launch_attn_decode_finalize(exit_state, steps_dev, B, S, V, T - key_off, tokens, probs, alpha, s));
+  int steps = S;
+  if (async) {
+    HIPCHK(c, hipEventRecord(c->ev_done[chain], s));
+    c->ev_done_valid[chain] = true;
+    const int64_t t = ++c->last_ticket;  // the ticket counter and ring of the TFM decodes
+    c->decode_in_flight = true;
+    const int slot = (int)(t % d2t_ctx::TICKET_RING);
+    if (!c->h_steps) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_steps), (size_t)d2t_ctx::TICKET_RING * GRP_MAXB * 4, hipHostMallocDefault));
+    c->ticket_batches[slot] = is_test ? 1 : -S;  // (< 0: all -ticket_batches steps)
+    if (is_test) HIPCHK(c, hipMemcpyAsync(c->h_steps + (size_t)slot * GRP_MAXB, steps_dev, 4, hipMemcpyDeviceToHost, s));
+    hipEvent_t& ev = c->ticket_ev[slot];
+    if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(ev, s));
+  } else if (is_test) {
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned, steps_dev, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    steps = c->h_pinned[0];
+  }
+  if (steps_out) *steps_out = steps;
+  return D2T_OK;
+}
+}  // namespace
+
 int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
                            float* probs, int32_t* steps_out, d2t_stream stream) {
   return d2t_decode_attn_greedy_alpha(c, memory, B, T, is_test, tokens, probs, nullptr, steps_out, stream);
@@ -1416,45 +1492,20 @@ int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T
 int d2t_decode_attn_greedy_alpha(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
                                  float* probs, float* alpha, int32_t* steps_out, d2t_stream stream) {
   DevGuard dg_(c);
-  if (!c || !memory || !tokens || !probs || !steps_out || B < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
-  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
-  const d2t_config& g = c->cfg;
-  if (g.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "context was not created with the Attn decoder");
-  const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab;
-  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
-  if (T - key_off < 1 || T - key_off > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  // workspace: key_proj(memory) [B*T][H] | end_step [B]
-  if ((rc = ensure(c, &c->dws, &c->dws_cap, ((size_t)B * T * Hh + B + 16) * 4))) return rc;
-  float* kp = c->dws;
-  int* end_step = reinterpret_cast<int*>(c->dws + (size_t)B * T * Hh);
-  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, B * T, ACT_NONE));
-  HIPCHK(c, hipMemsetAsync(end_step, 0xFF, (size_t)B * 4, s));  // -1 = never emitted [s]
-  AttnDecP p = attn_dec_params(c, memory, T, kp);
-  p.probs = probs; p.tokens = tokens; p.end_step = end_step;
-  p.sv_alpha = alpha;  // optional [B][S][Tk]: the alignment of every step (viz_attn, seq2seq.py:267-272,300-301)
-  p.B = B; p.S = S;
-  HIPCHK(c, launch_attn_decode(p, s));
-  int steps = S;
-  if (is_test) {
-    // reference: break as soon as every row has emitted [s]; the pre-zeroed probs keep zeros afterwards
-    std::vector<int> h(B);
-    HIPCHK(c, hipMemcpyAsync(h.data(), end_step, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    int last = -1;
-    bool all = true;
-    for (int b = 0; b < B; ++b) { all = all && h[b] >= 0; last = std::max(last, h[b]); }
-    if (all && last + 1 < S) {
-      steps = last + 1;
-      HIPCHK(c, hipMemset2DAsync(probs + (size_t)steps * V, (size_t)S * V * 4, 0, (size_t)(S - steps) * V * 4, B, s));
-      HIPCHK(c, hipMemset2DAsync(tokens + steps, (size_t)S * 8, 0, (size_t)(S - steps) * 8, B, s));
-      const size_t Tk = (size_t)(T - key_off);
-      if (alpha) HIPCHK(c, hipMemset2DAsync(alpha + (size_t)steps * Tk, (size_t)S * Tk * 4, 0, (size_t)(S - steps) * Tk * 4, B, s));
-    }
-  }
-  *steps_out = steps;
-  return D2T_OK;
+  if (!steps_out) return fail(c, D2T_EINVAL, "bad argument");
+  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
+  return attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, steps_out, (hipStream_t)stream, false);
+}
+
+int d2t_decode_attn_greedy_submit(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                                  float* probs, float* alpha, d2t_stream stream, int64_t* ticket_out) {
+  DevGuard dg_(c);
+  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, probs, "probs")) return rc;
+  const int rc = attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, nullptr, (hipStream_t)stream, true);
+  if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
+  return rc;
 }
 
 int d2t_decode_attn_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out, int32_t* len_out,
@@ -1507,6 +1558,10 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
     d_hist = c->beam_hist;
     d_path = reinterpret_cast<int*>(d_hist + (size_t)S * cap * Tk);
   }
+  // the key projection lives in chain 0's workspace, like the synchronous greedy call's: behind that chain's last
+  // asynchronous greedy decode (d2t_decode_attn_greedy_submit), which may still read it
+  select_chain(c, 0);
+  if (c->ev_done_valid[0]) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done[0], 0));
   if ((rc = ensure(c, &c->dws, &c->dws_cap, ((size_t)N * T * Hh + 16) * 4))) return rc;
   float* kp = c->dws;
   // workspace: logits [cap][V] | topv [cap] | topi [cap] (one device -> host copy per step) | h_in c_in h_out c_out [cap][H]
@@ -1756,9 +1811,9 @@ int d2t_decode_steps(d2t_ctx* c, int64_t ticket, int32_t* steps_out, int32_t max
   HIPCHK(c, hipEventSynchronize(c->ticket_ev[slot]));
   const int nb = c->ticket_batches[slot];
   const int S = c->cfg.max_seq_len + 1;
-  if (nb < 0) {  // not an early-exit decode: one entry, all steps
+  if (nb < 0) {  // not an early-exit decode: one entry, all steps (-nb: the step count of that decode's head)
     if (max_batches < 1) return fail(c, D2T_EINVAL, "steps_out too small");
-    steps_out[0] = S;
+    steps_out[0] = -nb;
     if (n_out) *n_out = 1;
     return D2T_OK;
   }

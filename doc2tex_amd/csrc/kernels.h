@@ -171,7 +171,17 @@ struct AttnDecP {
   float* sv_alpha;         // [B][S][T - key_off]
   float* sv_hq;            // [B][S][H]   query projection
   float* sv_x;             // [B][S][D + E]: LSTMCell input [context | embedding]
+  // Early exit across blocks (greedy is_test; null = every block runs all S steps, on a build of the kernel without it).  ONE 64-bit word, zeroed before the
+  // launch: {rows that have emitted [s] : high 32 bits, largest end step so far : low 32 bits}, updated by an agent-scope
+  // compare-and-swap when a row ends and read with agent-scope loads between steps.  A block stops once all B rows have
+  // ended and its next step lies beyond the largest end step; it never waits for another block.
+  unsigned long long* exit_state;
 };
+// After launch_attn_decode with an exit_state, on the same stream: steps = largest end step + 1 if all B rows ended, else
+// S; written to *steps_dev, and tokens [B][S], probs [B][S][V], alpha [B][S][Tk] (optional) zeroed for the steps
+// [steps, S) of every row -- whatever the buffers held and however far single blocks ran past the exit.
+hipError_t launch_attn_decode_finalize(const unsigned long long* exit_state, int* steps_dev, int B, int S, int V, int Tk,
+                                       int64_t* tokens, float* probs, float* alpha, hipStream_t s);
 // Backward of the teacher-forced loop above (one block per batch row, steps in reverse).  Gradients that are sums
 // over (row, step) of outer products are left as per-(row, step) factors for GEMMs: dgates, dhq, demb, dh0 / dc0.
 struct AttnTrainBwdP {

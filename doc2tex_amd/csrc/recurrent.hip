@@ -128,7 +128,26 @@ hipError_t launch_bilstm(const float* g, const float* whh_t, float* out, int B, 
 // ---------------------------------------------------------------------------
 constexpr int AD_MAXT = 4096, AD_MAXT_TRAIN = 4096;
 
-template <bool WIDE>
+// Early exit across blocks (AttnDecP::exit_state): a row that has just emitted [s] at `step` counts itself into the high
+// half of the word and raises the low half to its end step, in ONE agent-scope compare-and-swap -- a reader on another
+// XCD sees both halves of one update or neither, so no ordering between two words is needed.  Lock-free: a failed swap
+// means another row's update went through.
+__device__ __forceinline__ void attn_exit_publish(unsigned long long* w, int step) {
+  unsigned long long old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (;;) {
+    const unsigned cnt = (unsigned)(old >> 32) + 1u;
+    const unsigned mx = (unsigned)old > (unsigned)step ? (unsigned)old : (unsigned)step;
+    if (__hip_atomic_compare_exchange_strong(w, &old, ((unsigned long long)cnt << 32) | mx, __ATOMIC_RELAXED,
+                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      return;
+  }
+}
+// thread 0, end of `step`, with the word as it read it at the start of the step: stop before step + 1?
+__device__ __forceinline__ int attn_exit_reached(unsigned long long seen, int B, int step) {
+  return (unsigned)(seen >> 32) == (unsigned)B && (unsigned)(step + 1) > (unsigned)seen;
+}
+
+template <bool WIDE, bool EXIT>
 __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   constexpr int H = 256;
   __shared__ float x_s[3 * H];  // [context | embedding | h]  = LSTMCell input
@@ -138,6 +157,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   __shared__ float logit_s[WIDE ? 16 : 1024];  // WIDE: each wave's best value
   __shared__ int besti_s[16];                  // WIDE: and its index
   __shared__ int tok_s;
+  [[maybe_unused]] __shared__ int stop_s;  // EXIT: thread 0's decision, read by the block behind the step's last barrier
   __shared__ __attribute__((aligned(16))) float wloc_s[11 * H];  // folded location filter, [tap][n]
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int Tk = p.T - p.key_off;
@@ -178,7 +198,10 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
     c_s[tid] = cc;
   }
   if (tid == 0) tok_s = 0;  // [GO]
+  if constexpr (EXIT)
+    if (tid == 0) stop_s = 0;
   int ended = 0;
+  [[maybe_unused]] unsigned long long seen = 0;  // EXIT, thread 0: the exit word as of the start of the current step
   __syncthreads();
   if (p.step_mode && !p.first) {  // resume a hypothesis from its stored state
     if (tid < H) { h_s[tid] = p.st_h_in[(size_t)b * H + tid]; c_s[tid] = p.st_c_in[(size_t)b * H + tid]; }
@@ -188,6 +211,10 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   }
 
   for (int step = 0; step < p.S; ++step) {
+    // early exit: ONE lane looks at the word now (a load that bypasses the L1; nothing waits for it here) and the block
+    // acts on it behind the step's last barrier
+    if constexpr (EXIT)
+      if (tid == 0) seen = __hip_atomic_load(p.exit_state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (p.teacher && tid == 0) {
       if (step == 0 || !p.use_teacher || p.use_teacher[step]) tok_s = (int)p.teacher[(size_t)b * p.S + step];
       if (p.sv_tok) p.sv_tok[(size_t)b * p.S + step] = tok_s;  // otherwise: the argmax of the previous step
@@ -334,9 +361,16 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
         if (bi >= p.V) bi = 0;
         tok_s = bi;
         p.tokens[(size_t)b * p.S + step] = bi;
-        if (bi == p.end_token && !ended) { ended = 1; p.end_step[b] = step; }
+        if (bi == p.end_token && !ended) {
+          ended = 1;
+          p.end_step[b] = step;
+          if constexpr (EXIT) attn_exit_publish(p.exit_state, step);
+        }
+        if constexpr (EXIT) stop_s = attn_exit_reached(seen, p.B, step);
       }
       __syncthreads();
+      if constexpr (EXIT)
+        if (stop_s) break;
       continue;
     }
     float v = -INFINITY;
@@ -366,10 +400,17 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
       if (lane == 0) {
         tok_s = bi;
         p.tokens[(size_t)b * p.S + step] = bi;
-        if (bi == p.end_token && !ended) { ended = 1; p.end_step[b] = step; }
+        if (bi == p.end_token && !ended) {
+          ended = 1;
+          p.end_step[b] = step;
+          if constexpr (EXIT) attn_exit_publish(p.exit_state, step);
+        }
+        if constexpr (EXIT) stop_s = attn_exit_reached(seen, p.B, step);
       }
     }
     __syncthreads();
+    if constexpr (EXIT)
+      if (stop_s) break;
   }
   if (p.step_mode) {
     if (tid < H) { p.st_h_out[(size_t)b * H + tid] = h_s[tid]; p.st_c_out[(size_t)b * H + tid] = c_s[tid]; }
@@ -806,10 +847,50 @@ hipError_t launch_attn_decode(const AttnDecP& p, hipStream_t s) {
   if (p.H != 256 || p.D != 256 || p.E != 256 || p.V > D2T_ATTN_MAX_CLASSES || p.T - p.key_off > AD_MAXT ||
       p.taps > 11 || p.T - p.key_off < 1)
     return hipErrorInvalidValue;
-  if (p.V <= 1024)
-    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(p.B), dim3(1024), 0, s, p);
-  else
-    hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(p.B), dim3(1024), 0, s, p);
+  // EXIT builds (an exit_state is given: greedy is_test) carry the early exit across blocks; the others are the loop without
+  // it, instruction for instruction (beam search's step mode, the training forward, greedy without is_test)
+  if (p.exit_state && (p.step_mode || p.teacher)) return hipErrorInvalidValue;
+  auto k = p.V <= 1024 ? (p.exit_state ? attn_decode_kernel<false, true> : attn_decode_kernel<false, false>)
+                       : (p.exit_state ? attn_decode_kernel<true, true> : attn_decode_kernel<true, false>);
+  hipLaunchKernelGGL(k, dim3(p.B), dim3(1024), 0, s, p);
+  return hipGetLastError();
+}
+
+// The 4-byte words [a, e) of a buffer := 0 by thread i of n: 16-byte stores on the aligned body, single words at its ends.
+__device__ __forceinline__ void zero_words(uint32_t* a, uint32_t* e, size_t i, size_t n) {
+  if (a >= e) return;
+  uint32_t* body = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(a) + 15) & ~(uintptr_t)15);
+  if (body > e) body = e;
+  uint32_t* bend = body + ((size_t)(e - body) & ~(size_t)3);
+  for (uint32_t* q = a + i; q < body; q += n) *q = 0u;
+  for (uint4* q = reinterpret_cast<uint4*>(body) + i; q < reinterpret_cast<uint4*>(bend); q += n) *q = make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t* q = bend + i; q < e; q += n) *q = 0u;
+}
+
+// grid (x, y): blockIdx.y strides over the rows, the threads of the x blocks over a row's tail
+__global__ __launch_bounds__(256) void attn_decode_finalize_kernel(const unsigned long long* exit_state, int* steps_dev, int B, int S, int V, int Tk,
+                                                                   int64_t* tokens, float* probs, float* alpha) {
+  const unsigned long long w = __hip_atomic_load(exit_state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned mx = (unsigned)w;
+  const int steps = ((unsigned)(w >> 32) == (unsigned)B && mx + 1u < (unsigned)S) ? (int)mx + 1 : S;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *steps_dev = steps;
+  if (steps >= S) return;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, n = (size_t)gridDim.x * blockDim.x;
+  for (size_t b = blockIdx.y; b < (size_t)B; b += gridDim.y) {
+    const size_t r0 = b * S + steps, r1 = (b + 1) * S;  // (row, step) pairs to clear
+    zero_words(reinterpret_cast<uint32_t*>(tokens + r0), reinterpret_cast<uint32_t*>(tokens + r1), i, n);
+    zero_words(reinterpret_cast<uint32_t*>(probs + r0 * V), reinterpret_cast<uint32_t*>(probs + r1 * V), i, n);
+    if (alpha) zero_words(reinterpret_cast<uint32_t*>(alpha + r0 * Tk), reinterpret_cast<uint32_t*>(alpha + r1 * Tk), i, n);
+  }
+}
+
+hipError_t launch_attn_decode_finalize(const unsigned long long* exit_state, int* steps_dev, int B, int S, int V, int Tk,
+                                       int64_t* tokens, float* probs, float* alpha, hipStream_t s) {
+  if (!exit_state || !steps_dev || !tokens || !probs || B < 1 || S < 1 || V < 1 || Tk < 1) return hipErrorInvalidValue;
+  const size_t row_vec = ((size_t)S * (size_t)std::max(V, Tk) + 3) / 4;  // 16-byte stores of a whole row, at most
+  const unsigned gx = (unsigned)std::min<size_t>(64, (row_vec + 255) / 256);
+  hipLaunchKernelGGL(attn_decode_finalize_kernel, dim3(gx, (unsigned)std::min(B, 256)), dim3(256), 0, s, exit_state,
+                     steps_dev, B, S, V, Tk, tokens, probs, alpha);
   return hipGetLastError();
 }
 

@@ -400,6 +400,27 @@ class Engine:
                                                           _lib.stream_of(memory)), "decode_attn_greedy_alpha")
         return tokens, probs, alpha
 
+    def decode_attn_greedy_async(self, memory, is_test, return_alpha=False):
+        """decode_attn_greedy without the wait (d2t_decode_attn_greedy_submit): returns (tokens [B,S], probs [B,S,V]
+        [, alpha [B,S,Tk]], ticket).  The tensors are fresh allocations that one of the engine's decode streams is still
+        writing; they are complete -- zeros after an is_test early exit included -- once `ticket` is (wait_ticket /
+        decode_wait / ticket_done), and decode_steps(ticket) is then [the reference's step count].  `memory` and the
+        outputs stay referenced here until the ticket completes."""
+        self._on_device(memory, "memory")
+        memory = memory.float().contiguous()
+        B, T, _ = memory.shape
+        S, V = self.cfg.batch_max_length + 1, self.cfg.vocab
+        tokens = torch.empty((B, S), dtype=torch.int64, device=memory.device)
+        probs = torch.empty((B, S, V), dtype=torch.float32, device=memory.device)
+        alpha = torch.empty((B, S, self.attn_keys(T)), dtype=torch.float32, device=memory.device) if return_alpha else None
+        t = C.c_int64(0)
+        self._check(self.lib.d2t_decode_attn_greedy_submit(self.ctx, _lib.ptr(memory), B, T, int(bool(is_test)),
+                                                           _lib.ptr(tokens), _lib.ptr(probs),
+                                                           None if alpha is None else _lib.ptr(alpha),
+                                                           _lib.stream_of(memory), C.byref(t)), "decode_attn_greedy_submit")
+        ticket = self._hold(int(t.value), memory, (memory, tokens, probs, alpha))
+        return (tokens, probs, ticket) if alpha is None else (tokens, probs, alpha, ticket)
+
     def decode_greedy_async(self, memory, start_tokens, is_test=False):
         """Pipelined greedy decode (max_seq_len+1 steps; with is_test the device stops early): returns (tokens, logits, ticket).  The tensors are fresh
         allocations written by the engine's decode stream; they are valid once `ticket` is complete (wait_ticket /
@@ -423,12 +444,15 @@ class Engine:
         self._check(self.lib.d2t_decode_greedy_submit(self.ctx, _lib.ptr(memory), B, T, _lib.ptr(start), int(bool(is_test)),
                                                       int(rows_per_batch), _lib.ptr(tokens), _lib.ptr(logits),
                                                       _lib.stream_of(memory), C.byref(t)), "decode_greedy_submit")
+        return self._hold(int(t.value), memory, (memory, start, tokens, logits))
+
+    def _hold(self, ticket, memory, tensors):
+        """Keep the buffers of the asynchronous decode `ticket` referenced until it completes; returns the ticket."""
         self._wait_dev = memory.device
-        ticket = int(t.value)
         held = getattr(self, "_held", None)
         if held is None:
             held = self._held = []
-        held.append((ticket, (memory, start, tokens, logits)))
+        held.append((ticket, tensors))
         while held and self.ticket_done(held[0][0]):  # tickets complete in order per chain; at most a few stay pending
             self.decode_steps(held.pop(0)[0])  # keep its step counts past the C side's 64-entry ring
         if len(held) > 48:  # the C side keeps 64 ticket events: never let a live ticket fall out of its ring

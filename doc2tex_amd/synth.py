@@ -317,6 +317,17 @@ def synth_images(batch, h, w, seed=1000, channels=1):
     return torch.from_numpy(x.astype(np.float32))
 
 
+def staggered_images(seed=1300):
+    """Four 48 x 64 crops whose rows differ in more than noise (synth_images rows are i.i.d., and with the seeded weights
+    such rows all emit [s] at the same step): per-row scales, row 1's right half and row 2's bottom half blank.  The
+    LSTM-attention heads then end the rows at DIFFERENT steps (tools/make_golden_attn_serve.py), which the early exit
+    across blocks needs to be tested on."""
+    x = synth_images(4, 48, 64, seed=seed) * torch.tensor([1.0, 0.6, 0.25, -0.7]).view(4, 1, 1, 1)
+    x[1, :, :, 32:] = 1.0
+    x[2, :, 24:, :] = 1.0
+    return x
+
+
 def synth_labels(batch, max_len=MAX_LEN, seed=2000, vocab=VOCAB):
     """Teacher-forcing labels as converter.encode lays them out
     (tfm_converter.py:36-57): [GO] tokens... [s] [PAD]...; shape [B, max_len+2]."""

@@ -25,8 +25,8 @@
  *   d2t_train_forward / d2t_train_backward / d2t_train_grad (+ dropout, scheduled-sampling setters)
  *        <- Model.forward under module.train() and loss.backward(): forward_step / train_one_step
  *           engine/training.py:76-164 (tfm.py:103-118, seq2seq.py:224-331 with is_train)
- *   d2t_decode_greedy_async / d2t_decode_wait, d2t_set_reserved_blocks / d2t_set_decode_chains,
- *   d2t_decode_beam_batch / d2t_decode_attn_beam_batch
+ *   d2t_decode_greedy_async / d2t_decode_greedy_submit / d2t_decode_attn_greedy_submit / d2t_decode_wait,
+ *   d2t_set_reserved_blocks / d2t_set_decode_chains, d2t_decode_beam_batch / d2t_decode_attn_beam_batch
  *        -- serving extensions without a reference counterpart (cross-batch pipelining, batched beam search);
  *           their results equal the corresponding reference-shaped calls bit for bit
  *   d2t_op_*  -- single-kernel entry points used by the parity tests.
@@ -230,6 +230,24 @@ int d2t_decode_wait(d2t_ctx* ctx, d2t_stream stream, int32_t host_sync);
 int d2t_decode_greedy_submit(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T, const int64_t* start_tokens_dev,
                              int32_t is_test, int32_t rows_per_batch, int64_t* tokens_dev, float* logits_dev,
                              d2t_stream stream, int64_t* ticket_out);
+/* The LSTM-attention heads (Attn / Attnv2) through the same serving machinery: d2t_decode_attn_greedy[_alpha] without
+ * the wait.  The key projection, the one-launch step loop and a small finalize kernel are enqueued on the stream of one of
+ * the d2t_set_decode_chains chains (they take turns), ordered behind `stream` by an event; the call returns once that is
+ * done and never synchronises the host.  Every chain has its own key-projection workspace and state block, so up to
+ * `chains` decodes are in flight side by side.
+ *   is_test != 0   the reference's early exit (seq2seq.py:224-331, seq2seq_v2.py:176-293), decided inside the kernel: a
+ *                  block stops once ALL rows have emitted [s] and its next step lies beyond the largest end step, and the
+ *                  finalize kernel zeroes tokens / probs / alpha of the steps behind the exit -- the outputs are those of
+ *                  the synchronous call bit for bit, whatever the buffers held before;
+ *   alpha_dev      NULL, or [B][S][Tk] as for d2t_decode_attn_greedy_alpha.
+ * The decode takes the next ticket of the counter above: d2t_decode_query / d2t_decode_wait_ticket / d2t_decode_wait /
+ * d2t_decode_last_ticket work unchanged, and d2t_decode_steps reports ONE entry, the reference's step count
+ * (batch_max_length + 1 without is_test, or when some row never emitted [s]).  memory_dev, tokens_dev, probs_dev and
+ * alpha_dev belong to the engine until the ticket is complete.  Refuses what the synchronous call refuses (a TFM context:
+ * D2T_ESTATE; an unsupported memory length: D2T_EINVAL) before anything is enqueued. */
+int d2t_decode_attn_greedy_submit(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T, int32_t is_test,
+                                  int64_t* tokens_dev, float* probs_dev, float* alpha_dev, d2t_stream stream,
+                                  int64_t* ticket_out);
 /* Step counts of the batches of one asynchronous decode (blocks until it is complete). */
 int d2t_decode_steps(d2t_ctx* ctx, int64_t ticket, int32_t* steps_out, int32_t max_batches, int32_t* n_out);
 int64_t d2t_decode_last_ticket(const d2t_ctx* ctx);
