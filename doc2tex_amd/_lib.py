@@ -115,6 +115,14 @@ SIGNATURES = {
     "d2t_op_vit_attention": (_I, [_P, _P, _I, _I, _I, _P]),
     "d2t_op_vit_attention_probs": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "d2t_op_decode_attention": (_I, [_P] * 4 + [_I] * 5 + [_P]),
+    # the decode step's kernels one at a time (test infrastructure)
+    "d2t_op_skinny": (_I, [_P] * 6 + [C.c_float, _P, _P] + [_I] * 6 + [_P, _L, _P]),
+    "d2t_op_decoder_row": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 7 + [_P, _P, _I, _P, _I, _P]),
+    "d2t_op_argmax_embed": (_I, [_P, _I] + [_P] * 13 + [_I] * 6 + [_P]),
+    "d2t_op_beam_topk": (_I, [_P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
+    "d2t_op_beam_advance": (_I, [_I, _L] + [_P] * 15 + [_I] * 6 + [_P]),
+    "d2t_op_beam_ancestry": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "d2t_op_cache_gather": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "d2t_ce_forward": (_I, [_P, _P, _P, _P, _I, _I, _L, _P]),
     "d2t_ce_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _P]),
     "d2t_op_train_conv": (_I, [_P] * 14 + [_I] * 13 + [_P]),

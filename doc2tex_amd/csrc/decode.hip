@@ -229,6 +229,8 @@ static int decode_small() {
 hipError_t launch_skinny(const SkinnyP& p, hipStream_t s) {
   if (p.M <= 0 || p.N <= 0) return hipSuccess;
   if (p.K % 16 != 0 || p.ldx % 4 != 0) return hipErrorInvalidValue;
+  // ln_out[m][nn] is written by the block that owns output column nn: all K columns exist only when N >= K
+  if (p.ln_out && (!p.ln_g || p.N < p.K)) return hipErrorInvalidValue;
   // narrow outputs (N <= 512) take 16-row tiles so that the few column tiles still fill >= 64 CUs
   const int mt = p.N <= 512 ? 1 : 2;
   const dim3 grid((p.N + 15) / 16, (p.M + 16 * mt - 1) / (16 * mt));
@@ -445,6 +447,36 @@ hipError_t launch_argmax_embed(const ArgmaxP& p, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // Fused row kernel (see DecRowP).  512 threads = 8 waves = 8 heads.
 // ---------------------------------------------------------------------------
+// The online-softmax arithmetic of the d_model 512 row kernels' attention loops (head dim 64), spelled with explicit fmaf.
+// decoder_row2_kernel promises the one-row kernel's bits per row; written as a * b + c * d the compiler's contraction may fuse
+// either product, and chose differently in the two loops (tests/test_decode_ops_gpu.py: the builds differed by 1-3 ulp).
+// Head dim 32 keeps the plain expressions below: its results are pinned bit for bit by arrays dumped from earlier builds
+// (tests/golden/rgb_grey_baseline.npz), and no two builds of it promise each other's bits.
+__device__ __forceinline__ float att_dot4(const float4& q, const float4& k) {
+  return fmaf(q.x, k.x, q.y * k.y) + fmaf(q.z, k.z, q.w * k.w);
+}
+__device__ __forceinline__ void att_update(float sj, const float4& v, float& m, float& l, float4& acc) {
+  const float mn = fmaxf(m, sj);
+  const float f = expf(m - mn);  // exp(-inf) = 0 on the first key
+  const float pj = expf(sj - mn);
+  l = fmaf(l, f, pj);
+  acc.x = fmaf(pj, v.x, acc.x * f); acc.y = fmaf(pj, v.y, acc.y * f);
+  acc.z = fmaf(pj, v.z, acc.z * f); acc.w = fmaf(pj, v.w, acc.w * f);
+  m = mn;
+}
+// (m, l, acc) += lane ^ o's triple (log-sum-exp combine of two key groups)
+__device__ __forceinline__ void att_merge(int o, float& m, float& l, float4& acc) {
+  const float mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
+  const float ax = __shfl_xor(acc.x, o, 64), ay = __shfl_xor(acc.y, o, 64);
+  const float az = __shfl_xor(acc.z, o, 64), aw = __shfl_xor(acc.w, o, 64);
+  const float mn = fmaxf(m, mo);
+  const float f1 = l > 0.f ? expf(m - mn) : 0.f, f2 = lo > 0.f ? expf(mo - mn) : 0.f;
+  l = fmaf(lo, f2, l * f1);
+  acc.x = fmaf(ax, f2, acc.x * f1); acc.y = fmaf(ay, f2, acc.y * f1);
+  acc.z = fmaf(az, f2, acc.z * f1); acc.w = fmaf(aw, f2, acc.w * f1);
+  m = mn;
+}
+
 template <int HD, int U>  // U key groups fetched together: 2*U 16-B loads in flight per lane
 __device__ __forceinline__ void row_attention(const float* q, const float* Kc, const float* Vc, const float* curk,
                                               const float* curv, int t, int L, float* out, int lane,
@@ -473,32 +505,40 @@ __device__ __forceinline__ void row_attention(const float* q, const float* Kc, c
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int j = (it0 + u) * KPI + kig;
-      float d = (q4.x * k4[u].x + q4.y * k4[u].y) + (q4.z * k4[u].z + q4.w * k4[u].w);
+      float d = HD == 64 ? att_dot4(q4, k4[u]) : (q4.x * k4[u].x + q4.y * k4[u].y) + (q4.z * k4[u].z + q4.w * k4[u].w);
 #pragma unroll
       for (int o = 1; o < LPK; o <<= 1) d += __shfl_xor(d, o, 64);
       if (j < L) {
-        const float sj = d * scale;
-        const float mn = fmaxf(m, sj);
-        const float f = expf(m - mn);  // exp(-inf) = 0 on the first key
-        const float pj = expf(sj - mn);
-        l = l * f + pj;
-        acc.x = acc.x * f + pj * v4[u].x; acc.y = acc.y * f + pj * v4[u].y;
-        acc.z = acc.z * f + pj * v4[u].z; acc.w = acc.w * f + pj * v4[u].w;
-        m = mn;
+        if constexpr (HD == 64) {
+          att_update(d * scale, v4[u], m, l, acc);
+        } else {
+          const float sj = d * scale;
+          const float mn = fmaxf(m, sj);
+          const float f = expf(m - mn);  // exp(-inf) = 0 on the first key
+          const float pj = expf(sj - mn);
+          l = l * f + pj;
+          acc.x = acc.x * f + pj * v4[u].x; acc.y = acc.y * f + pj * v4[u].y;
+          acc.z = acc.z * f + pj * v4[u].z; acc.w = acc.w * f + pj * v4[u].w;
+          m = mn;
+        }
       }
     }
   }
 #pragma unroll
   for (int o = LPK; o < 64; o <<= 1) {  // merge the key groups (log-sum-exp combine)
-    const float mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
-    const float ax = __shfl_xor(acc.x, o, 64), ay = __shfl_xor(acc.y, o, 64);
-    const float az = __shfl_xor(acc.z, o, 64), aw = __shfl_xor(acc.w, o, 64);
-    const float mn = fmaxf(m, mo);
-    const float f1 = l > 0.f ? expf(m - mn) : 0.f, f2 = lo > 0.f ? expf(mo - mn) : 0.f;
-    l = l * f1 + lo * f2;
-    acc.x = acc.x * f1 + ax * f2; acc.y = acc.y * f1 + ay * f2;
-    acc.z = acc.z * f1 + az * f2; acc.w = acc.w * f1 + aw * f2;
-    m = mn;
+    if constexpr (HD == 64) {
+      att_merge(o, m, l, acc);
+    } else {
+      const float mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
+      const float ax = __shfl_xor(acc.x, o, 64), ay = __shfl_xor(acc.y, o, 64);
+      const float az = __shfl_xor(acc.z, o, 64), aw = __shfl_xor(acc.w, o, 64);
+      const float mn = fmaxf(m, mo);
+      const float f1 = l > 0.f ? expf(m - mn) : 0.f, f2 = lo > 0.f ? expf(mo - mn) : 0.f;
+      l = l * f1 + lo * f2;
+      acc.x = acc.x * f1 + ax * f2; acc.y = acc.y * f1 + ay * f2;
+      acc.z = acc.z * f1 + az * f2; acc.w = acc.w * f1 + aw * f2;
+      m = mn;
+    }
   }
   if (kig == 0) {
     const float inv = 1.f / l;
@@ -752,11 +792,11 @@ __device__ unsigned long long d2t_row_phase[32];
 // operand as hi + lo (three MFMAs per product, lo*hi + hi*lo + hi*hi: the arithmetic of the encoder's GEMMs):
 //     S^T [16 keys x 16 (8 heads + 8 idle)] = M_tile [16 x 256] . Q'^T      8 K-steps x 3 v_mfma_f32_16x16x32_bf16   (24)
 //     ctx [16 (8 heads + 8 idle) x 256]    += P [16 x 16 keys] . M_tile     16 column blocks x 3 v_mfma_f32_16x16x16_bf16 (48)
-// 72 MFMAs of 16 cycles instead of 128 of 32.  The memory rows arrive as two bf16 planes (hi = upper 16 bits, lo = bf16(x - hi):
-// x to 16 significant bits; launch_split_bf16 at cross_kv time); a tile = 16 rows x 512 B of hi | 16 x 512 B of lo in the wave's
+// 72 MFMAs of 16 cycles instead of 128 of 32.  The memory rows arrive as two bf16 planes (hi = bf16_rne(x), lo =
+// bf16_rne(x - hi): x to 16 or more significant bits; launch_split_bf16 at cross_kv time); a tile = 16 rows x 512 B of hi | 16 x 512 B of lo in the wave's
 // 16 KB stage, 16-byte chunk c of row r at position c ^ r (conflict-free ds_read_b128 of the score product's A operand; the
 // weighted sum's B operand [keys x channels] comes out of the same image with ds_read_b64_tr_b16).  The absorbed queries
-// are split the same way when they are stored.  The score product's result layout (lane = (key group, head), registers =
+// and the probabilities are split in registers (split16 below: hi = upper 16 bits, lo = bf16_rne(x - hi)).  The score product's result layout (lane = (key group, head), registers =
 // keys 4g..4g+3) is the A-operand layout of the 16x16x16 form, so P never moves between lanes, as before.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __bf16 dbf16x8 __attribute__((ext_vector_type(8)));
@@ -887,7 +927,7 @@ struct DecRow2P {
   // beam search (MODE 1 / 2): the row kernel split around the per-SAMPLE cross-attention kernel
   float* qp;            // [rows][8][D]: MODE 1 writes the absorbed queries, beam_cross_kernel replaces them with the context rows
   float* x1;            // [rows][D]: LN1 output (the residual of the cross-attention block), MODE 1 -> MODE 2
-  // round 4: the memory rows as two bf16 planes (hi = upper 16 bits, lo = bf16(x - hi); launch_split_bf16) for the greedy
+  // round 4: the memory rows as two bf16 planes (launch_split_bf16: hi = bf16_rne(x), lo = bf16_rne(x - hi)) for the greedy
   // two-row kernel's split-bf16 cross-attention (nullptr: the fp32 rows above on the fp32 MFMA)
   const uint16_t* mem_hi;   // [samples][T][D]
   const uint16_t* mem_lo;   // [samples][T][D]
@@ -1416,18 +1456,23 @@ __device__ __forceinline__ void row_attention_2h(const float* const (&q)[2], con
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int j = (it0 + u) * KPI + kig;
-        float d = (q4[h].x * k4[h][u].x + q4[h].y * k4[h][u].y) + (q4[h].z * k4[h][u].z + q4[h].w * k4[h][u].w);
+        float d = HD == 64 ? att_dot4(q4[h], k4[h][u])
+                           : (q4[h].x * k4[h][u].x + q4[h].y * k4[h][u].y) + (q4[h].z * k4[h][u].z + q4[h].w * k4[h][u].w);
 #pragma unroll
         for (int o = 1; o < LPK; o <<= 1) d += __shfl_xor(d, o, 64);
         if (j < L) {
-          const float sj = d * scale;
-          const float mn = fmaxf(m[h], sj);
-          const float f = expf(m[h] - mn);
-          const float pj = expf(sj - mn);
-          l[h] = l[h] * f + pj;
-          acc[h].x = acc[h].x * f + pj * v4[h][u].x; acc[h].y = acc[h].y * f + pj * v4[h][u].y;
-          acc[h].z = acc[h].z * f + pj * v4[h][u].z; acc[h].w = acc[h].w * f + pj * v4[h][u].w;
-          m[h] = mn;
+          if constexpr (HD == 64) {
+            att_update(d * scale, v4[h][u], m[h], l[h], acc[h]);
+          } else {
+            const float sj = d * scale;
+            const float mn = fmaxf(m[h], sj);
+            const float f = expf(m[h] - mn);
+            const float pj = expf(sj - mn);
+            l[h] = l[h] * f + pj;
+            acc[h].x = acc[h].x * f + pj * v4[h][u].x; acc[h].y = acc[h].y * f + pj * v4[h][u].y;
+            acc[h].z = acc[h].z * f + pj * v4[h][u].z; acc[h].w = acc[h].w * f + pj * v4[h][u].w;
+            m[h] = mn;
+          }
         }
       }
     WAVE_PHASE(24);  // groups awaited + scored
@@ -1436,15 +1481,19 @@ __device__ __forceinline__ void row_attention_2h(const float* const (&q)[2], con
   for (int h = 0; h < 2; ++h) {
 #pragma unroll
     for (int o = LPK; o < 64; o <<= 1) {
-      const float mo = __shfl_xor(m[h], o, 64), lo = __shfl_xor(l[h], o, 64);
-      const float ax = __shfl_xor(acc[h].x, o, 64), ay = __shfl_xor(acc[h].y, o, 64);
-      const float az = __shfl_xor(acc[h].z, o, 64), aw = __shfl_xor(acc[h].w, o, 64);
-      const float mn = fmaxf(m[h], mo);
-      const float f1 = l[h] > 0.f ? expf(m[h] - mn) : 0.f, f2 = lo > 0.f ? expf(mo - mn) : 0.f;
-      l[h] = l[h] * f1 + lo * f2;
-      acc[h].x = acc[h].x * f1 + ax * f2; acc[h].y = acc[h].y * f1 + ay * f2;
-      acc[h].z = acc[h].z * f1 + az * f2; acc[h].w = acc[h].w * f1 + aw * f2;
-      m[h] = mn;
+      if constexpr (HD == 64) {
+        att_merge(o, m[h], l[h], acc[h]);
+      } else {
+        const float mo = __shfl_xor(m[h], o, 64), lo = __shfl_xor(l[h], o, 64);
+        const float ax = __shfl_xor(acc[h].x, o, 64), ay = __shfl_xor(acc[h].y, o, 64);
+        const float az = __shfl_xor(acc[h].z, o, 64), aw = __shfl_xor(acc[h].w, o, 64);
+        const float mn = fmaxf(m[h], mo);
+        const float f1 = l[h] > 0.f ? expf(m[h] - mn) : 0.f, f2 = lo > 0.f ? expf(mo - mn) : 0.f;
+        l[h] = l[h] * f1 + lo * f2;
+        acc[h].x = acc[h].x * f1 + ax * f2; acc[h].y = acc[h].y * f1 + ay * f2;
+        acc[h].z = acc[h].z * f1 + az * f2; acc[h].w = acc[h].w * f1 + aw * f2;
+        m[h] = mn;
+      }
     }
     if (kig == 0) {
       const float inv = 1.f / l[h];

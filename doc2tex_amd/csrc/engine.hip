@@ -2424,4 +2424,238 @@ int d2t_op_decode_attention(const float* q, const float* k, const float* v, floa
   return launch_decode_attention(p, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
 }
 
+// ---------------------------------------------------------------------------
+// decode-step kernels one at a time (test infrastructure; see include/d2t.h).  Every entry checks its sizes -- and the
+// device-side integers a kernel would index with, read back first -- against the kernel's limits before it launches.
+// ---------------------------------------------------------------------------
+namespace {
+// the stream's earlier work has finished; n ints of device memory on the host
+bool fetch_ints(hipStream_t s, const int* dev, size_t n, std::vector<int>* out) {
+  out->resize(n);
+  if (hipStreamSynchronize(s) != hipSuccess) return false;
+  return n == 0 || hipMemcpy(out->data(), dev, n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+}
+}  // namespace
+
+int d2t_op_skinny(const float* x, const float* w, const float* bias, const float* res, const float* ln_g, const float* ln_b,
+                  float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx, int32_t ldy, int32_t act,
+                  const int32_t* step, int64_t out_step_stride, d2t_stream stream) {
+  if (!x || !w || !y || M < 1 || M > 65535 * 16 || N < 1 || K < 16 || K % 16 || ldx < K || ldx % 4 || ldy < N) return D2T_EINVAL;
+  if (act != ACT_NONE && act != ACT_RELU && act != ACT_GELU) return D2T_EINVAL;
+  if ((ln_g == nullptr) != (ln_b == nullptr) || (ln_out && !ln_g)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (step) {
+    std::vector<int> t;
+    if (out_step_stride < 0 || !fetch_ints(s, step, 1, &t) || t[0] < 0) return D2T_EINVAL;
+  }
+  SkinnyP p{};
+  p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
+  p.M = M; p.K = K; p.N = N; p.ldx = ldx; p.ldy = ldy; p.ldres = N; p.act = act;
+  p.step_ptr = step; p.out_step_stride = out_step_stride;
+  p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_out = ln_out;
+  const hipError_t e = launch_skinny(p, s);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                       const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                       const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps, float* y2,
+                       const int32_t* step, int32_t M, int32_t D, int32_t T, int32_t Lmax, int32_t rows, int32_t samples,
+                       int32_t one_row, const int32_t* row_map, const int32_t* anc, int32_t anc_stride, const int32_t* seg,
+                       int32_t nsamples, d2t_stream stream) {
+  if (!qkv || !xres || !sk || !sv || !mem || !ca_in_w || !ca_in_b || !sa_out_w || !sa_out_b || !ca_out_w || !ca_out_b ||
+      !ln1_g || !ln1_b || !y2 || !step)
+    return D2T_EINVAL;
+  if (kind < 0 || kind > 5 || M < 1 || M > 65535 || rows < M || samples < 1 || T < 1 || T > 4096 || Lmax < 1 || Lmax > 4096)
+    return D2T_EINVAL;
+  if (kind == 0 ? (D != 256 && D != 512) : D != 256) return D2T_EINVAL;
+  if (!row_map && samples < M) return D2T_EINVAL;  // row b attends over sample b
+  if (anc && ((kind != 2 && kind != 4) || Lmax > 512 || anc_stride < Lmax)) return D2T_EINVAL;  // one-row absorbed builds only
+  if (kind == 5 && (!seg || !row_map || nsamples < 1 || nsamples > samples)) return D2T_EINVAL;
+  if (kind != 5 && seg) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> h;
+  if (!fetch_ints(s, step, 1, &h)) return D2T_EHIP;
+  const int t = h[0];
+  if (t < 0 || t >= Lmax) return D2T_EINVAL;
+  if (row_map) {
+    if (!fetch_ints(s, row_map, M, &h)) return D2T_EHIP;
+    for (int v : h) if (v < 0 || v >= samples) return D2T_EINVAL;
+  }
+  if (anc) {
+    if (!fetch_ints(s, anc, (size_t)M * anc_stride, &h)) return D2T_EHIP;
+    for (int b = 0; b < M; ++b)
+      for (int j = 0; j < t; ++j)
+        if (h[(size_t)b * anc_stride + j] < 0 || h[(size_t)b * anc_stride + j] >= rows) return D2T_EINVAL;
+  }
+  if (kind == 5) {  // compact segments in sample order, at most 6 live hypotheses each, every row in exactly one
+    std::vector<int> rm;
+    if (!fetch_ints(s, seg, (size_t)nsamples * 3, &h) || !fetch_ints(s, row_map, M, &rm)) return D2T_EHIP;
+    int next = 0;
+    for (int n = 0; n < nsamples; ++n) {
+      const int first = h[3 * n], cnt = h[3 * n + 1];
+      if (cnt < 0 || cnt > 6 || (cnt > 0 && first != next)) return D2T_EINVAL;
+      for (int r = 0; r < cnt; ++r) if (rm[next + r] != n) return D2T_EINVAL;
+      next += cnt;
+    }
+    if (next != M) return D2T_EINVAL;
+  }
+  const size_t dd = (size_t)D * D, memn = (size_t)samples * T * D;
+  // temporaries: three transposed projections, W_v^T; then projected K / V (kind 0), bf16 planes (3, 4), q' + x1 (5)
+  size_t extra = 0;
+  if (kind == 0) extra = 2 * memn * 4;
+  else if (kind == 3 || kind == 4) extra = memn * 4;
+  else if (kind == 5) extra = (size_t)M * 9 * D * 4;
+  float* buf = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&buf), 4 * dd * 4 + extra) != hipSuccess) return D2T_ENOMEM;
+  float *wo_t = buf, *wq_t = buf + dd, *wco_t = buf + 2 * dd, *wv_t = buf + 3 * dd, *ext = buf + 4 * dd;
+  hipError_t e = launch_transpose(sa_out_w, wo_t, D, D, s);
+  if (e == hipSuccess) e = launch_transpose(ca_in_w, wq_t, D, D, s);
+  if (e == hipSuccess) e = launch_transpose(ca_out_w, wco_t, D, D, s);
+  if (e == hipSuccess) e = launch_transpose(ca_in_w + 2 * dd, wv_t, D, D, s);
+  DecRowP r{};
+  r.qkv = qkv; r.qkv_stride = 3 * D; r.xres = xres;
+  r.sk = sk; r.sv = sv; r.s_batch_stride = (long long)Lmax * D; r.s_Lmax = Lmax;
+  r.c_row_map = row_map; r.T = T;
+  r.wo_t = wo_t; r.bo = sa_out_b; r.ln1_g = ln1_g; r.ln1_b = ln1_b; r.eps = eps;
+  r.wq_t = wq_t; r.bq = ca_in_b; r.wco_t = wco_t; r.bco = ca_out_b;
+  r.y2 = y2; r.step_ptr = step; r.M = M; r.D = D; r.heads = 8;
+  r.anc = anc; r.anc_stride = anc_stride;
+  const float *wk = ca_in_w + dd, *bv = ca_in_b + 2 * D;
+  if (e != hipSuccess) {  // (nothing more to launch)
+  } else if (kind == 0) {  // K / V of the memory rows as cross_kv projects them: [2][samples][8][T][D / 8]
+    ConvP p{};
+    p.in = mem; p.w = wk; p.bias = ca_in_b + D; p.out = ext;
+    p.B = 1; p.H = 1; p.W = samples * T; p.Cin = D; p.OH = 1; p.OW = samples * T; p.Cout = 2 * D;
+    p.KH = p.KW = p.SH = p.SW = 1; p.M = samples * T; p.K = D; p.act = ACT_NONE;
+    p.store_mode = STORE_KV; p.kv_T = T; p.kv_heads = 8; p.kv_hd = D / 8; p.kv_B = samples;
+    e = launch_conv(p, s);
+    r.ck = ext; r.cv = ext + memn; r.c_batch_stride = (long long)T * D;
+    r.one_row = one_row != 0;
+    if (e == hipSuccess) e = launch_decoder_row(r, s);
+  } else if (kind == 5) {
+    r.one_row = 1;
+    e = launch_decoder_row_beam(r, mem, (long long)T * D, wk, wv_t, bv, ext, ext + (size_t)M * 8 * D, seg, nsamples, s);
+  } else {
+    r.one_row = kind == 2 || kind == 4;
+    uint16_t *hi = nullptr, *lo = nullptr;
+    if (kind >= 3) {
+      hi = reinterpret_cast<uint16_t*>(ext); lo = hi + memn;
+      e = launch_split_bf16(mem, hi, lo, memn, s);
+    }
+    if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, (long long)T * D, wk, wv_t, bv, s, hi, lo);
+  }
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(buf);
+  return e == hipErrorInvalidValue ? D2T_EINVAL : (e == hipSuccess && e2 == hipSuccess) ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_argmax_embed(const float* logits, int32_t S, int64_t* tokens, int32_t* ended, int32_t* end_count, int32_t* steps_done,
+                        int32_t* step, int32_t* done_count, int32_t* batch_end_count, int32_t* batch_steps_done,
+                        int32_t* batches_done, int32_t* stop_at, const float* emb, const float* pe, float* x, int32_t B, int32_t V,
+                        int32_t d, int32_t end_token, int32_t rows_per_batch, int32_t n_batches, d2t_stream stream) {
+  if (!logits || !tokens || !ended || !end_count || !steps_done || !step || !done_count || B < 1 || B > 65535 || V < 1 || S < 1)
+    return D2T_EINVAL;
+  if (end_token < 0 || end_token >= V) return D2T_EINVAL;
+  if (x && (!emb || !pe || d < 1)) return D2T_EINVAL;
+  if (n_batches < 0 || n_batches > 64) return D2T_EINVAL;
+  if (n_batches > 0 && (rows_per_batch < 1 || (long long)rows_per_batch * n_batches != B || !batch_end_count || !batch_steps_done ||
+                        !batches_done))
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> t;
+  if (!fetch_ints(s, step, 1, &t)) return D2T_EHIP;
+  if (t[0] < 0 || t[0] >= S) return D2T_EINVAL;  // logits / tokens hold S steps, pe S + 1 rows
+  ArgmaxP p{};
+  p.logits = logits; p.row_stride = (long long)S * V; p.step_stride = V;
+  p.tokens = tokens; p.tok_stride = S;
+  p.ended = ended; p.end_count = end_count; p.steps_done = steps_done; p.step_ptr = step; p.done_count = done_count;
+  p.B = B; p.V = V; p.end_token = end_token;
+  p.emb = emb; p.pe = pe; p.x = x; p.d = d;
+  p.rows_per_batch = rows_per_batch; p.n_batches = n_batches;
+  p.batch_end_count = batch_end_count; p.batch_steps_done = batch_steps_done; p.batches_done = batches_done; p.stop_at = stop_at;
+  return launch_argmax_embed(p, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_beam_topk(const float* logits, const float* scores, const int32_t* seg, int32_t N, int32_t rows, int32_t V, int32_t kmax,
+                     float* topv, int32_t* topi, d2t_stream stream) {
+  if (!logits || !scores || !seg || !topv || !topi || N < 1 || N > 65535 || rows < 1 || V < 1 || kmax < 1 || kmax > 16)
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> h;
+  if (!fetch_ints(s, seg, (size_t)N * 3, &h)) return D2T_EHIP;
+  for (int n = 0; n < N; ++n) {
+    const int off = h[3 * n], m = h[3 * n + 1], k = h[3 * n + 2];
+    if (m <= 0 || k <= 0) continue;  // the kernel leaves such a segment alone
+    if (off < 0 || m > 16 || off + m > rows || k > kmax || (long long)k > (long long)m * V || (long long)m * V > 0x7fffffffLL)
+      return D2T_EINVAL;
+  }
+  const hipError_t e = launch_beam_topk_batch(logits, scores, seg, N, V, kmax, topv, topi, s);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+int d2t_op_beam_advance(int32_t init, int64_t go_token, int32_t* ctrl, int64_t* tok, float* scores, int32_t* map, int32_t* prev,
+                        int32_t* seg, int32_t* comp_n, int32_t* fin, int32_t* comp_t, int32_t* comp_par, float* comp_score,
+                        int32_t* hist_par, int32_t* hist_tok, const float* topv, const int32_t* topi, int32_t N, int32_t beam,
+                        int32_t cap, int32_t V, int32_t S, int32_t end_token, d2t_stream stream) {
+  if (!ctrl || !tok || !scores || !map || !prev || !seg || !comp_n || !fin || !comp_t || !comp_par || !comp_score || !hist_par ||
+      !hist_tok)
+    return D2T_EINVAL;
+  if (N < 1 || N > 1024 || beam < 1 || beam > 16 || (long long)cap < (long long)N * beam || V < 1 || S < 1 || end_token < 0 ||
+      end_token >= V)
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  BeamDev b{};
+  b.ctrl = ctrl; b.tok = tok; b.scores = scores; b.map = map; b.prev = prev; b.seg = seg; b.comp_n = comp_n; b.fin = fin;
+  b.comp_t = comp_t; b.comp_par = comp_par; b.comp_score = comp_score; b.hist_par = hist_par; b.hist_tok = hist_tok;
+  b.topv = topv; b.topi = topi; b.N = N; b.beam = beam; b.cap = cap; b.V = V; b.S = S; b.end_token = end_token;
+  if (init) return launch_beam_dev_init(b, go_token, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+  if (!topv || !topi) return D2T_EINVAL;
+  // the state as the kernel will read it: the step indexes the history, the candidates index rows of their segment
+  std::vector<int> c, sg, cn, fi, ti;
+  if (!fetch_ints(s, ctrl, 4, &c) || !fetch_ints(s, seg, (size_t)N * 3, &sg) || !fetch_ints(s, comp_n, N, &cn) ||
+      !fetch_ints(s, fin, N, &fi) || !fetch_ints(s, topi, (size_t)N * beam, &ti))
+    return D2T_EHIP;
+  if (c[0] < 0 || c[2] < 0) return D2T_EINVAL;
+  if (!(c[2] && c[0] >= c[2])) {  // the launch will do work
+    if (c[0] >= S) return D2T_EINVAL;
+    for (int i = 0; i < N; ++i) {
+      if (fi[i] || sg[3 * i + 1] <= 0) continue;
+      const int live = sg[3 * i + 2], m = sg[3 * i + 1];
+      if (live < 0 || live > beam || cn[i] < 0 || cn[i] + live > beam || sg[3 * i] < 0 || sg[3 * i] + m > cap) return D2T_EINVAL;
+      for (int r = 0; r < live; ++r) {
+        const int idx = ti[(size_t)i * beam + r];
+        if (idx < 0 || idx / V >= m) return D2T_EINVAL;
+      }
+    }
+  }
+  const hipError_t e = launch_beam_dev_advance(b, s);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+int d2t_op_beam_ancestry(const int32_t* anc_old, int32_t* anc_new, const int32_t* prev, int32_t rows, int32_t stride,
+                         const int32_t* step_in, int32_t* step_out, const int32_t* rows_ptr, const int32_t* stop,
+                         d2t_stream stream) {
+  if (!anc_old || !anc_new || !prev || !step_in || !step_out || rows < 1 || rows > 65535 || stride < 1) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> t, pv;
+  if (!fetch_ints(s, step_in, 1, &t) || !fetch_ints(s, prev, rows, &pv)) return D2T_EHIP;
+  if (t[0] < 0 || t[0] > stride) return D2T_EINVAL;  // positions 0 .. t - 1 of a row are written
+  for (int v : pv) if (v < 0 || v >= rows) return D2T_EINVAL;
+  const hipError_t e = launch_beam_ancestry(anc_old, anc_new, prev, rows, stride, step_in, step_out, s, rows_ptr, stop);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+int d2t_op_cache_gather(const float* src, float* dst, const int32_t* prev, int32_t slabs, int32_t cap, int32_t M, int32_t heads,
+                        int32_t Lmax, int32_t hd, int32_t rows, d2t_stream stream) {
+  if (!src || !dst || !prev || src == dst || slabs < 1 || cap < 1 || M < 1 || M > cap || M > 65535 || heads < 1 || heads > 65535 ||
+      Lmax < 1 || hd < 4 || hd % 4 || rows < 1 || rows > Lmax)
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> pv;
+  if (!fetch_ints(s, prev, M, &pv)) return D2T_EHIP;
+  for (int v : pv) if (v < 0 || v >= cap) return D2T_EINVAL;
+  return launch_cache_gather(src, dst, prev, slabs, cap, M, heads, Lmax, hd, rows, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
 }  // extern "C"

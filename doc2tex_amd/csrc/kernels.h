@@ -106,7 +106,8 @@ struct SkinnyP {
   const int* step_ptr;
   long long out_step_stride;
   // optional LayerNorm prologue: the A operand is LN(x)*ln_g + ln_b over the K features of each row
-  // (K = 256 or 512 only).  ln_out, if set, receives the normalised rows [M][K] as a side output.
+  // (the split-K builds only: K = 256, 512 or 1024).  ln_out, if set, receives the normalised rows [M][K] as a side
+  // output; it needs N >= K (launch_skinny refuses it otherwise).
   const float* ln_g; const float* ln_b; float ln_eps; float* ln_out;
 };
 hipError_t launch_skinny(const SkinnyP& p, hipStream_t s);

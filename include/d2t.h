@@ -458,6 +458,64 @@ int d2t_op_vit_attention_probs(const float* qkv, float* y, float* probs, int32_t
 int d2t_op_decode_attention(const float* q, const float* k, const float* v, float* y, int32_t B, int32_t heads,
                             int32_t hd, int32_t L, int32_t Lmax, d2t_stream stream);
 
+/* ---- the decode step's kernels, one at a time ------------------------------------------------------------------
+ * TEST INFRASTRUCTURE (tests/test_decode_ops_gpu.py): the serving paths never call these.  No context; tensors are
+ * device pointers in the layouts PyTorch has (weights [N][K] as stored); whatever transposition / splitting a kernel
+ * wants happens in temporary device memory.  Every size -- and every device-side integer a kernel indexes with (step
+ * counters, row maps, ancestry, segments, parents), read back before the launch -- is checked against the kernel's limits:
+ * D2T_EINVAL and nothing launched otherwise.  The entries synchronise the stream for that check. */
+/* Skinny GEMM (launch_skinny): y[M][ldy] (first N columns) = act(A @ w[N][K]^T + bias + res[M][N]), A = x[M][ldx] or, with
+ * ln_g / ln_b, LayerNorm(x) * ln_g + ln_b (K = 256, 512, 1024); ln_out (optional, needs N >= K) receives A [M][K].
+ * step (optional, device): the output base is advanced by *step * out_step_stride floats. */
+int d2t_op_skinny(const float* x, const float* w, const float* bias, const float* res, const float* ln_g, const float* ln_b,
+                  float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx, int32_t ldy, int32_t act,
+                  const int32_t* step, int64_t out_step_stride, d2t_stream stream);
+/* The fused row step of one post-norm decoder layer for M rows at position t = *step (8 heads):
+ *   a = SelfAttn(q, cache[0 .. t-1] + this step's k, v);  x1 = LN1(a @ sa_out_w^T + sa_out_b + xres)
+ *   y2 = CrossAttn(x1, mem of the row's sample) @ ca_out_w^T + ca_out_b + x1          (pre-LN2)
+ * kind: 0 projected K/V (D = 256 or 512; one_row != 0 selects the one-row-per-block build at D = 512), 1 absorbed two rows
+ * per block, 2 absorbed one row, 3 / 4 the same two on split-bf16 MFMAs, 5 beam search's pre / per-sample cross / post
+ * split (D = 256 for 1-5).  qkv [M][3D] (self-attention in-projection of this step), xres [M][D]; sk / sv
+ * [rows][8][Lmax][D/8], read and written (row b's k, v are stored at position t); mem [samples][T][D]; ca_in_w [3D][D] /
+ * ca_in_b [3D] the cross-attention in-projection; row_map (optional) [M]: the sample of a row (default: row b -> sample b);
+ * anc (kinds 2, 4, Lmax <= 512) [M][anc_stride]: the cache row that holds position j < t of row b; seg (kind 5)
+ * [nsamples][3] = (first row, rows <= 6, -) of sample n, compact and in row order, row_map agreeing with it. */
+int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                       const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                       const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps, float* y2,
+                       const int32_t* step, int32_t M, int32_t D, int32_t T, int32_t Lmax, int32_t rows, int32_t samples,
+                       int32_t one_row, const int32_t* row_map, const int32_t* anc, int32_t anc_stride, const int32_t* seg,
+                       int32_t nsamples, d2t_stream stream);
+/* One greedy step (launch_argmax_embed) at t = *step < S: tokens[b][t] = first maximum of logits[b][t][:V] (logits [B][S][V],
+ * tokens [B][S]); end-of-sequence bookkeeping in ended [B], end_count, steps_done; *step becomes t + 1, done_count (zero
+ * before the first launch) is back at zero afterwards; x [B][d] (optional) = emb[token] * sqrt(d) + pe[t + 1] (pe [S + 1][d]).
+ * n_batches > 0: rows are n_batches groups of rows_per_batch with batch_end_count / batch_steps_done [n_batches],
+ * batches_done [1] and stop_at [1] (optional; once *stop_at != 0 and t >= *stop_at a launch changes nothing). */
+int d2t_op_argmax_embed(const float* logits, int32_t S, int64_t* tokens, int32_t* ended, int32_t* end_count, int32_t* steps_done,
+                        int32_t* step, int32_t* done_count, int32_t* batch_end_count, int32_t* batch_steps_done,
+                        int32_t* batches_done, int32_t* stop_at, const float* emb, const float* pe, float* x, int32_t B, int32_t V,
+                        int32_t d, int32_t end_token, int32_t rows_per_batch, int32_t n_batches, d2t_stream stream);
+/* Beam candidates (launch_beam_topk_batch): segment n = seg[n] = (first row, rows <= 16, k <= kmax <= 16) of logits [rows][V] /
+ * scores [rows]; its k best of score[i] + log_softmax(logits[i])[v] (value descending, flat index i * V + v ascending on ties)
+ * at topv / topi [n][kmax].  A segment with no rows or k = 0 leaves its slots untouched. */
+int d2t_op_beam_topk(const float* logits, const float* scores, const int32_t* seg, int32_t N, int32_t rows, int32_t V, int32_t kmax,
+                     float* topv, int32_t* topi, d2t_stream stream);
+/* Device-side Beam.advance for N <= 1024 samples, beam <= 16 (struct BeamDev of csrc/kernels.h: ctrl [4], tok / scores / map /
+ * prev [cap], seg [N][3], comp_n / fin [N], comp_t / comp_par / comp_score [N][beam], hist_par / hist_tok [S][cap]).  init != 0:
+ * launch_beam_dev_init (topv / topi unused); else one launch_beam_dev_advance over the candidates topv / topi [N][beam]. */
+int d2t_op_beam_advance(int32_t init, int64_t go_token, int32_t* ctrl, int64_t* tok, float* scores, int32_t* map, int32_t* prev,
+                        int32_t* seg, int32_t* comp_n, int32_t* fin, int32_t* comp_t, int32_t* comp_par, float* comp_score,
+                        int32_t* hist_par, int32_t* hist_tok, const float* topv, const int32_t* topi, int32_t N, int32_t beam,
+                        int32_t cap, int32_t V, int32_t S, int32_t end_token, d2t_stream stream);
+/* anc_new[row][0 .. t-2] = anc_old[prev[row]][...], anc_new[row][t-1] = prev[row], t = *step_in <= stride, published to
+ * *step_out; rows >= *rows_ptr are skipped and nothing is written once *stop != 0 and t >= *stop (both optional). */
+int d2t_op_beam_ancestry(const int32_t* anc_old, int32_t* anc_new, const int32_t* prev, int32_t rows, int32_t stride,
+                         const int32_t* step_in, int32_t* step_out, const int32_t* rows_ptr, const int32_t* stop,
+                         d2t_stream stream);
+/* dst[slab][i][head][0 .. rows)[:] = src[slab][prev[i]][head][0 .. rows)[:] for i < M; caches [slabs][cap][heads][Lmax][hd]. */
+int d2t_op_cache_gather(const float* src, float* dst, const int32_t* prev, int32_t slabs, int32_t cap, int32_t M, int32_t heads,
+                        int32_t Lmax, int32_t hd, int32_t rows, d2t_stream stream);
+
 /* ---- fused cross-entropy ------------------------------------------------------------------------------------------
  * The criterion of the reference's training step -- nn.CrossEntropyLoss(ignore_index = PAD, reduction = 'none') on
  * preds.view(-1, V) / target.view(-1) (engine/training.py:50-53, 83, 90; modules/loss/builder.py:18-24) -- as one kernel

@@ -1,5 +1,11 @@
-"""GPU: every HIP kernel, called through the C-ABI, against a plain fp32 CPU
-PyTorch evaluation of the same op (tolerances written per test)."""
+"""GPU: the encoder-side HIP kernels and the plain single-query attention, called through the C-ABI, against a plain
+fp32 CPU PyTorch evaluation of the same op (tolerances written per test): the convolutions (fp32 MFMA, split-bf16,
+split records, fused max-pool), the big linear (d2t_op_linear: every K % 32 == 0 goes to the convolution GEMM, so the
+skinny split-K kernels are NOT reached from here), max-pool, layer norm, the ViT attention, d2t_op_decode_attention.
+The other kernel families have their own operator tests: the decode step (skinny GEMM + LayerNorm prologue, fused
+decoder-row kernels, argmax + embed, beam top-k / advance / ancestry / cache gather) in test_decode_ops_gpu.py, the
+training operators in test_train_ops_gpu.py, pre- / post-processing in test_prep_gpu.py, fp16x2 records in
+test_fp16x2_gpu.py."""
 import ctypes as C
 
 import pytest
