@@ -69,6 +69,9 @@ SIGNATURES = {
     "d2t_decode_greedy_async": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "d2t_decode_wait": (_I, [_P, _P, _I]),
     "d2t_decode_greedy_submit": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, C.POINTER(_L)]),
+    "d2t_decode_greedy_submit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), _P, _I, _P, _P, _P, C.POINTER(_L)]),
+    "d2t_decode_graph_count": (_I, [_P]),
+    "d2t_decode_supports_ragged": (_I, [_P]),
     "d2t_decode_attn_greedy_submit": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_L)]),
     "d2t_decode_steps": (_I, [_P, _L, C.POINTER(_I), _I, C.POINTER(_I)]),
     "d2t_decode_last_ticket": (_L, [_P]),
@@ -118,6 +121,7 @@ SIGNATURES = {
     # the decode step's kernels one at a time (test infrastructure)
     "d2t_op_skinny": (_I, [_P] * 6 + [C.c_float, _P, _P] + [_I] * 6 + [_P, _L, _P]),
     "d2t_op_decoder_row": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 7 + [_P, _P, _I, _P, _I, _P]),
+    "d2t_op_decoder_row_ragged": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 4 + [C.POINTER(_I), C.POINTER(_I), _P]),
     "d2t_op_argmax_embed": (_I, [_P, _I] + [_P] * 13 + [_I] * 6 + [_P]),
     "d2t_op_beam_topk": (_I, [_P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
     "d2t_op_beam_advance": (_I, [_I, _L] + [_P] * 15 + [_I] * 6 + [_P]),

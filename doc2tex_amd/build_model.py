@@ -203,6 +203,14 @@ class Model(nn.Module):
         # dispatched by layer shape only, so each row's tokens / logits are bit-identical to an ungrouped decode.  Results
         # of a group become valid after synchronize() (which also launches a group that is still incomplete).
         self.decode_group = 1
+        # decode groups over crops of DIFFERENT sizes (opt-in; TFM head with d_model 256, the absorbed cross-attention): a
+        # group then takes consecutive forward() calls of any (rows, memory length) -- every row reads its own slice of one
+        # packed memory buffer and stays bit-identical to its single-batch decode -- and is launched when it holds
+        # `decode_group` batches or the next batch would exceed `decode_group_rows` rows (the row count up to which the step
+        # loop's duration stays flat).  Off: a change of the row count or memory length launches the
+        # group collected so far, as before.  Other decoders (d_model 512) keep that behaviour whatever the switch says.
+        self.decode_group_mixed = False
+        self.decode_group_rows = 384
         self._grp = None
         # Arithmetic of the backbone / large GEMMs:
         #   'bf16x3'  (default) split-bf16: 3 bf16 MFMAs per product, fp32 accumulate; max |dlogit| ~5e-5 against the 1e-3 bar
@@ -265,6 +273,8 @@ class Model(nn.Module):
         G = int(self.decode_group)
         B, T, d = memory.shape
         S, V = eng.cfg.max_seq_len + 1, eng.cfg.vocab
+        if self.decode_group_mixed and eng.supports_ragged_groups():
+            return self._group_decode_mixed(eng, memory, start, is_test)
         key = (G, B, T, d, S, V, memory.device, bool(is_test))
         g = self._grp
         if g is not None and g["key"] != key:
@@ -288,9 +298,54 @@ class Model(nn.Module):
             self._flush_group(eng)
         return out
 
+    def _group_decode_mixed(self, eng, memory, start, is_test):
+        """decode_group_mixed: the group is keyed on (d, S, V, device, is_test) only; memories of any (B, T) are packed
+        back to back into one flat [rows, d] buffer, outputs are views of [decode_group_rows, S] / [.., S, V] tensors."""
+        import torch
+        G, R = int(self.decode_group), max(1, int(self.decode_group_rows))
+        B, T, d = memory.shape
+        S, V = eng.cfg.max_seq_len + 1, eng.cfg.vocab
+        key = ("mixed", d, S, V, memory.device, bool(is_test))
+        g = self._grp
+        if g is not None and (g["key"] != key or g["rows"] + B > g["cap"]):
+            self._flush_group(eng)
+            g = None
+        if g is None:
+            cap = max(R, B)  # a single batch beyond the row budget is a group of its own
+            # the packed memory starts at what `decode_group` batches like this one need and grows with longer / larger ones
+            g = self._grp = {"key": key, "n": 0, "handles": [], "rows": 0, "cap": cap, "layout": [], "mem_rows": 0,
+                             "mem": torch.empty((min(cap, max(1, G) * B) * T, d), dtype=torch.float32, device=memory.device),
+                             "start": torch.empty((cap,), dtype=torch.int64, device=memory.device),
+                             "tokens": torch.empty((cap, S), dtype=torch.int64, device=memory.device),
+                             "logits": torch.empty((cap, S, V), dtype=torch.float32, device=memory.device)}
+        r0, m0 = g["rows"], g["mem_rows"]
+        if m0 + B * T > g["mem"].shape[0]:  # longer memories than the first batch's: grow the packed buffer
+            grown = torch.empty((max(2 * g["mem"].shape[0], m0 + B * T), d), dtype=torch.float32, device=memory.device)
+            grown[:m0].copy_(g["mem"][:m0])
+            g["mem"] = grown
+        g["mem"][m0:m0 + B * T].copy_(memory.reshape(B * T, d))
+        g["start"][r0:r0 + B].copy_(start.to(device=memory.device, dtype=torch.int64))
+        views = g["tokens"][r0:r0 + B], g["logits"][r0:r0 + B]
+        handle = DecodeHandle(self, eng, None, g["n"], views)
+        g["handles"].append(handle)
+        g["layout"].append((B, T))
+        g["rows"], g["mem_rows"] = r0 + B, m0 + B * T
+        g["n"] += 1
+        if g["n"] >= G:
+            self._flush_group(eng)
+        return views + (handle,)
+
     def _flush_group(self, eng):
         g = self._grp
         if g is None or g["n"] == 0:
+            return
+        if g["key"][0] == "mixed":
+            rows = g["rows"]
+            ticket = eng.decode_greedy_ragged_into(g["mem"][:g["mem_rows"]], g["layout"], g["start"][:rows], g["tokens"][:rows],
+                                                   g["logits"][:rows], is_test=g["key"][-1])
+            for h in g["handles"]:
+                h.ticket = ticket
+            self._grp = None
             return
         rows = g["n"] * g["key"][1]
         ticket = eng.decode_greedy_async_into(g["mem"][:rows], g["start"][:rows], g["tokens"][:rows], g["logits"][:rows],

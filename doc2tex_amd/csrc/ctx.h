@@ -198,7 +198,15 @@ struct d2t_ctx {
   float* dout = nullptr; size_t dout_cap = 0;
   int active_chain = 0, n_chains = 1;
   hipEvent_t ev_in = nullptr;
-  struct GraphKey { int B, T, steps; const void* tok; const void* logits; const void* ckv; const void* dws; const void* skv; const void* dstate; long long variant; };
+  // ragged decode groups: per memory slot the device tables [row0 | len | row_batch] (rg_cap rows each) | batch_rows [64] |
+  // n_batches, and the pinned host buffer they are copied from on the caller's stream (rg_ev: that copy has run, the host
+  // buffer may be rewritten).  Per slot, because a decode still in flight on another chain reads its own slot's tables.
+  int* rg_tab[MAXC] = {}; int* rg_host[MAXC] = {}; int rg_cap = 0;
+  hipEvent_t rg_ev[MAXC] = {}; bool rg_ev_valid[MAXC] = {};
+  // ragged decode groups (rtab != nullptr): B is the row total, T is 0 and the batch layout is NOT part of the key -- the loop
+  // reads lengths and offsets from the tables at rtab; aux = the slot's bf16-plane offset (a function of the slot's capacity)
+  struct GraphKey { int B, T, steps; const void* tok; const void* logits; const void* ckv; const void* dws; const void* skv; const void* dstate; long long variant;
+                    const void* rtab; long long aux; };
   struct GraphEnt { GraphKey key; hipGraphExec_t exec; };
   std::vector<GraphEnt> graphs;  // small cache of captured decode steps (most recent last)
   // kernel timing log (d2t_profile_*)

@@ -420,12 +420,17 @@ __global__ __launch_bounds__(64) void argmax_embed_kernel(const ArgmaxP p) {
       p.ended[b] = 1;
       const int c = atomicAdd(p.end_count, 1) + 1;
       if (c == p.B) *p.steps_done = t + 1;
-      if (p.n_batches > 0) {  // decode group: this row's encoder batch may have finished
-        const int k = b / p.rows_per_batch;
-        if (atomicAdd(p.batch_end_count + k, 1) + 1 == p.rows_per_batch) {
+      if (p.n_batches > 0) {  // decode group: this row's encoder batch may have finished (a ragged group passes ARGMAX_GROUPED
+                              // here and its real batch count through n_batches_ptr)
+        // uniform group: batch = b / rows_per_batch; ragged group (row_batch != nullptr): the layout comes from device tables, so
+        // that one captured loop serves every layout with the same row total
+        const int k = p.row_batch ? p.row_batch[b] : b / p.rows_per_batch;
+        const int rows_k = p.batch_rows ? p.batch_rows[k] : p.rows_per_batch;
+        const int nb = p.n_batches_ptr ? *p.n_batches_ptr : p.n_batches;
+        if (atomicAdd(p.batch_end_count + k, 1) + 1 == rows_k) {
           p.batch_steps_done[k] = t + 1;
           // every block of THIS launch read step t before the stop takes effect (t < t + 1); the kernels of step t + 1 see it
-          if (atomicAdd(p.batches_done, 1) + 1 == p.n_batches && p.stop_at) *p.stop_at = t + 1;
+          if (atomicAdd(p.batches_done, 1) + 1 == nb && p.stop_at) *p.stop_at = t + 1;
         }
       }
     }
@@ -441,6 +446,28 @@ __global__ __launch_bounds__(64) void argmax_embed_kernel(const ArgmaxP p) {
 
 hipError_t launch_argmax_embed(const ArgmaxP& p, hipStream_t s) {
   hipLaunchKernelGGL(argmax_embed_kernel, dim3(p.B), dim3(64), 0, s, p);
+  return hipGetLastError();
+}
+
+// Ragged decode group with the device-side early exit: the loop runs until the LAST batch has ended, so the rows of a batch
+// that ended earlier were decoded past their batch's exit.  One block per row clears tokens (PAD = 0) and logits of the steps
+// [batch_steps_done[batch of the row], S): every batch comes back as its single-batch is_test decode leaves its buffers.
+__global__ __launch_bounds__(256) void ragged_finalize_kernel(int64_t* __restrict__ tokens, float* __restrict__ logits,
+                                                              const int* __restrict__ row_batch, const int* __restrict__ batch_steps_done,
+                                                              int S, int V) {
+  const int b = blockIdx.x;
+  const int n = batch_steps_done[row_batch[b]];
+  if (n <= 0 || n >= S) return;  // the batch never ended: all S steps are its result
+  for (int t = n + threadIdx.x; t < S; t += 256) tokens[(size_t)b * S + t] = 0;
+  float* l = logits + ((size_t)b * S + n) * V;
+  const size_t cnt = (size_t)(S - n) * V;
+  for (size_t i = threadIdx.x; i < cnt; i += 256) l[i] = 0.f;
+}
+
+hipError_t launch_ragged_finalize(int64_t* tokens, float* logits, const int* row_batch, const int* batch_steps_done, int B, int S,
+                                  int V, hipStream_t s) {
+  if (B < 1) return hipSuccess;
+  hipLaunchKernelGGL(ragged_finalize_kernel, dim3(B), dim3(256), 0, s, tokens, logits, row_batch, batch_steps_done, S, V);
   return hipGetLastError();
 }
 
@@ -931,6 +958,10 @@ struct DecRow2P {
   // two-row kernel's split-bf16 cross-attention (nullptr: the fp32 rows above on the fp32 MFMA)
   const uint16_t* mem_hi;   // [samples][T][D]
   const uint16_t* mem_lo;   // [samples][T][D]
+  // ragged decode group (the RAGGED builds of the greedy kernels): `mem` / `mem_hi` / `mem_lo` are ONE packed [sum B_i T_i][D]
+  // buffer, row b attends over the len[b] memory rows that start at row row0[b] (device tables; r.T, mem_stride, c_row_map unused)
+  const int* row0;
+  const int* len;
 };
 
 #ifdef D2T_PROBES
@@ -941,7 +972,8 @@ struct DecRow2P {
 // MODE 0: the whole row step (greedy).  MODE 1: up to the absorbed queries, which go to q.qp (+ x1 to q.x1).  MODE 2: from
 // the context rows in q.qp on (value projection, output projection, residual) -- the two halves around beam_cross_kernel.
 constexpr int ANC_MAX = 512;  // longest ancestry row held in LDS (DecRowP::anc needs s_Lmax <= ANC_MAX)
-template <int NTH, int MODE, bool BX3 = false>  // D = 256, 8 heads of 32; BX3 (MODE 0): the cross-attention on split-bf16 MFMAs
+template <int NTH, int MODE, bool BX3 = false, bool RAGGED = false>  // D = 256, 8 heads of 32; BX3 (MODE 0): the cross-attention on
+                                                                     // split-bf16 MFMAs; RAGGED (MODE 0): per-row memory base and length
 __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecRow2P q) {
   constexpr int D = 256, HD = 32, NW = NTH / 64, G = NTH / (D / 4), HPW = 8 / NW;
   const DecRowP& p = q.r;
@@ -1068,18 +1100,29 @@ __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecR
   }
   // ---- cross-attention over the memory rows of this row's sample ----
   if (MODE == 0 && !ROW_PROBE(4)) {
-    const int cb = p.c_row_map ? p.c_row_map[b] : b;
+    // the keys of this row: a sample of the uniform [samples][T][D] memory, or (RAGGED) its own slice of the packed rows.  A wave
+    // that owns no tile of a short row skips the key loop (no block barrier inside) and hands (-inf, 0) to the merge below
+    int Tb;
+    size_t moff;
+    if constexpr (RAGGED) {
+      Tb = q.len[b];
+      moff = (size_t)q.row0[b] * D;
+    } else {
+      const int cb = p.c_row_map ? p.c_row_map[b] : b;
+      Tb = p.T;
+      moff = (size_t)cb * q.mem_stride;
+    }
     float m_run, l_run;
     unsigned char* stage = stage_s + wave * 16384;
     const int col = lane & 15, g = lane >> 4;
     float* mine = reinterpret_cast<float*>(stage);
     if constexpr (BX3) {
-      const uint16_t* mh = q.mem_hi + (size_t)cb * q.mem_stride;
-      const uint16_t* ml = q.mem_lo + (size_t)cb * q.mem_stride;
+      const uint16_t* mh = q.mem_hi + moff;
+      const uint16_t* ml = q.mem_lo + moff;
       f32x4 acc[16];
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (wave < ((p.T + 15) >> 4)) bx3_tile_dma(mh, ml, p.T, wave, stage, lane);  // (the stage held GEMV partials until now)
-      cross_absorbed_wave_bx3<NW>(mh, ml, p.T, reinterpret_cast<const unsigned char*>(qp_s), stage, wave, lane, m_run, l_run, acc);
+      if (wave < ((Tb + 15) >> 4)) bx3_tile_dma(mh, ml, Tb, wave, stage, lane);  // (the stage held GEMV partials until now)
+      cross_absorbed_wave_bx3<NW>(mh, ml, Tb, reinterpret_cast<const unsigned char*>(qp_s), stage, wave, lane, m_run, l_run, acc);
       if (g == 0 && col < 8) { wm_s[wave][col] = m_run; wl_s[wave][col] = l_run; }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (g < 2) {
@@ -1090,7 +1133,7 @@ __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecR
       }
     } else {
       f32x4 acc[4][4];
-      cross_absorbed_wave<NW>(q.mem + (size_t)cb * q.mem_stride, p.T, qp_s, stage, wave, lane, m_run, l_run, acc);
+      cross_absorbed_wave<NW>(q.mem + moff, Tb, qp_s, stage, wave, lane, m_run, l_run, acc);
       if (g == 0 && col < 8) { wm_s[wave][col] = m_run; wl_s[wave][col] = l_run; }
       // this wave's un-normalised ctx [8 heads][256] into its (now idle) staging area: lane (g, col) holds heads 4g + reg
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1607,7 +1650,14 @@ __device__ __forceinline__ void cross_absorbed_wave_pf(const float* __restrict__
   l_run += __shfl_xor(l_run, 32, 64);
 }
 
-template <bool BX3>  // BX3: the cross-attention on split-bf16 MFMAs over DecRow2P::mem_hi / mem_lo (cross_absorbed_wave_bx3)
+// RAGGED (decode groups of batches with different row counts and memory lengths): row b reads its keys from the packed memory
+// rows [row0[b], row0[b] + len[b]); the two halves of a block get independent lengths.  Every block barrier (ROW_SYNC) and every
+// s_waitcnt of the body lies OUTSIDE the key loop and is reached by all eight waves whatever the two lengths are: the first-tile
+// LDS-DMA is a wave-uniform `if` without a barrier, the key loop is private to a wave, and a wave that owns no tile hands
+// (-inf, 0) and zero accumulators to the merge.  A row's arithmetic depends on its own length alone (tile -> wave assignment),
+// so it is bit-identical to the uniform kernel's on the same memory.  A template parameter, not a branch: the uniform builds
+// compile to the code they were.
+template <bool BX3, bool RAGGED = false>  // BX3: the cross-attention on split-bf16 MFMAs over DecRow2P::mem_hi / mem_lo (cross_absorbed_wave_bx3)
 __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q) {
   constexpr int D = 256, HD = 32, G = 8;
   const DecRowP& p = q.r;
@@ -1631,11 +1681,20 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
   const int t = *p.step_ptr;
   const int lr = lane, gg = wave;  // GEMV thread coordinates: columns 4 lr .. 4 lr + 3, K group gg
   // ---- this wave's first memory tile, and the first GEMV's weight rows, are requested before anything else ----
-  const int cb = p.c_row_map ? p.c_row_map[b] : b;
-  const float* const mem = q.mem + (size_t)cb * q.mem_stride;
+  int Tb;        // keys of this wave's row (wave-uniform: b is)
+  size_t moff;   // its first memory row, in elements
+  if constexpr (RAGGED) {
+    Tb = q.len[b];
+    moff = (size_t)q.row0[b] * D;
+  } else {
+    const int cb = p.c_row_map ? p.c_row_map[b] : b;
+    Tb = p.T;
+    moff = (size_t)cb * q.mem_stride;
+  }
+  const float* const mem = q.mem + moff;
   unsigned char* const stage = stage_s + wave * 16384;
-  const uint16_t* const mh = BX3 ? q.mem_hi + (size_t)cb * q.mem_stride : nullptr;
-  const uint16_t* const ml = BX3 ? q.mem_lo + (size_t)cb * q.mem_stride : nullptr;
+  const uint16_t* const mh = BX3 ? q.mem_hi + moff : nullptr;
+  const uint16_t* const ml = BX3 ? q.mem_lo + moff : nullptr;
   // the element-wise phases' few global operands, requested BEFORE the weight prefetches: the vector-memory counter retires in
   // order, so a small load issued behind a 256 KB prefetch would wait for all of it
   const float bo_v = p.bo[tcol] + p.xres[(size_t)brow * D + tcol], bq_v = p.bq[tcol], bv_v = q.bv[tcol], bco_v = p.bco[tcol];
@@ -1647,9 +1706,9 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
   // behind its first K / V loads (their 48 instructions' issue time -- ~100 ns each with the CU's vector-memory path busy --
   // then passes under that first round trip instead of in front of it)
   auto prefetch = [&]() {
-    if (w4i < ((p.T + 15) >> 4)) {
-      if constexpr (BX3) bx3_tile_dma(mh, ml, p.T, w4i, stage, lane);
-      else cross_tile_dma(mem, p.T, w4i, stage, lane);
+    if (w4i < ((Tb + 15) >> 4)) {
+      if constexpr (BX3) bx3_tile_dma(mh, ml, Tb, w4i, stage, lane);
+      else cross_tile_dma(mem, Tb, w4i, stage, lane);
     }
     gemv2_load(p.wo_t, gg, lr, W);
   };
@@ -1764,7 +1823,7 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
     float* mine = reinterpret_cast<float*>(stage);
     if constexpr (BX3) {
       f32x4 acc[16];
-      cross_absorbed_wave_bx3<4>(mh, ml, p.T, reinterpret_cast<const unsigned char*>(qp_s[half]), stage, w4i, lane, m_run, l_run, acc);
+      cross_absorbed_wave_bx3<4>(mh, ml, Tb, reinterpret_cast<const unsigned char*>(qp_s[half]), stage, w4i, lane, m_run, l_run, acc);
       ROW_PHASE(12);
       if (g == 0 && col < 8) { wm_s[half][w4i][col] = m_run; wl_s[half][w4i][col] = l_run; }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1776,7 +1835,7 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
       }
     } else {
       f32x4 acc[4][4];
-      cross_absorbed_wave_pf<4>(mem, p.T, qp_s[half], stage, w4i, lane, m_run, l_run, acc);
+      cross_absorbed_wave_pf<4>(mem, Tb, qp_s[half], stage, w4i, lane, m_run, l_run, acc);
       ROW_PHASE(12);
       if (g == 0 && col < 8) { wm_s[half][w4i][col] = m_run; wl_s[half][w4i][col] = l_run; }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1852,6 +1911,8 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
 
 __global__ __launch_bounds__(512, 1) void decoder_row2_absorbed_pf_kernel(const DecRow2P q) { decoder_row2_absorbed_pf_body<false>(q); }
 __global__ __launch_bounds__(512, 1) void decoder_row2_absorbed_bx3_kernel(const DecRow2P q) { decoder_row2_absorbed_pf_body<true>(q); }
+__global__ __launch_bounds__(512, 1) void decoder_row2_absorbed_pf_ragged_kernel(const DecRow2P q) { decoder_row2_absorbed_pf_body<false, true>(q); }
+__global__ __launch_bounds__(512, 1) void decoder_row2_absorbed_bx3_ragged_kernel(const DecRow2P q) { decoder_row2_absorbed_pf_body<true, true>(q); }
 
 #ifdef D2T_PROBES
 }  // namespace d2t
@@ -1867,13 +1928,25 @@ extern "C" int d2t_debug_row_phases(unsigned long long* out, int reset) {  // pr
 namespace d2t {
 #endif
 hipError_t launch_decoder_row_absorbed(const DecRowP& r, const float* mem, long long mem_stride, const float* wk, const float* wv_t,
-                                       const float* bv, hipStream_t s, const uint16_t* mem_hi, const uint16_t* mem_lo) {
-  if (r.heads != 8 || r.D != 256 || r.T < 1) return hipErrorInvalidValue;
-  DecRow2P q{r, mem, mem_stride, wk, wv_t, bv, nullptr, nullptr, mem_hi, mem_lo};
+                                       const float* bv, hipStream_t s, const uint16_t* mem_hi, const uint16_t* mem_lo,
+                                       const int* row0, const int* len) {
+  const bool ragged = row0 != nullptr;
+  if (r.heads != 8 || r.D != 256 || (!ragged && r.T < 1)) return hipErrorInvalidValue;
+  if (ragged && (!len || r.c_row_map || r.anc || r.rows_ptr)) return hipErrorInvalidValue;  // greedy rows only
+  DecRow2P q{r, mem, mem_stride, wk, wv_t, bv, nullptr, nullptr, mem_hi, mem_lo, row0, len};
   static const int probe = D2T_PROBE_ENV("D2T_ROW_PROBE");  // probe builds only: skip phases (results are garbage by construction)
   q.r.probe = probe;
   static const bool one_row = D2T_PROBE_ENV_STR("D2T_DECODE_ONE_ROW_BLOCKS") != nullptr;  // A/B: the one-row-per-block form for every row
   if (r.anc && (!r.one_row || r.s_Lmax > ANC_MAX)) return hipErrorInvalidValue;  // the two-row kernel reads the cache directly
+  if (ragged) {  // the ragged builds of the same two forms (no probe-build A/B variants)
+    const bool bx3 = mem_hi && mem_lo;
+    if (r.one_row) {
+      if (bx3) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true, true>), dim3(r.M), dim3(256), 0, s, q);
+      else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, false, true>), dim3(r.M), dim3(256), 0, s, q);
+    } else if (bx3) hipLaunchKernelGGL(decoder_row2_absorbed_bx3_ragged_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
+    else hipLaunchKernelGGL(decoder_row2_absorbed_pf_ragged_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
+    return hipGetLastError();
+  }
   if (one_row || r.one_row) {
     if (mem_hi && mem_lo) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true>), dim3(r.M), dim3(256), 0, s, q);
     else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0>), dim3(r.M), dim3(256), 0, s, q);

@@ -464,6 +464,11 @@ void d2t_destroy(d2t_ctx* c) {
   if (c->zero_page) hipFree(c->zero_page);
   if (c->gc_ws) hipFree(c->gc_ws);
   if (c->ev_in) hipEventDestroy(c->ev_in);
+  for (int i = 0; i < d2t_ctx::MAXC; ++i) {
+    if (c->rg_tab[i]) hipFree(c->rg_tab[i]);
+    if (c->rg_host[i]) hipHostFree(c->rg_host[i]);
+    if (c->rg_ev[i]) hipEventDestroy(c->rg_ev[i]);
+  }
   if (c->h_steps) hipHostFree(c->h_steps);
   for (hipEvent_t ev : c->ticket_ev) if (ev) hipEventDestroy(ev);
   if (c->dout) hipFree(c->dout);
@@ -1068,13 +1073,15 @@ hipError_t sync_chains(d2t_ctx* c) {
   return e;
 }
 
-int dec_prepare(d2t_ctx* c, int B, int T, DecBufs* bufs) {
+// mem_rows > 0 (ragged decode group, absorbed form): the slot holds that many packed memory rows instead of B * T
+int dec_prepare(d2t_ctx* c, int B, int T, DecBufs* bufs, size_t mem_rows = 0) {
   const d2t_config& g = c->cfg;
   const int d = g.dec_dim, Lmax = g.max_seq_len + 2;
   int rc;
   // a slot holds the encoder memory copy [B][T][d] (absorbed cross-attention) or the projected K/V of every layer
   // (absorbed form: the fp32 rows, and behind them the same rows as bf16 hi / lo planes for the greedy two-row kernel)
-  const size_t slot_bytes = c->dec_absorbed ? (size_t)B * T * d * 8 + 64 : (size_t)g.dec_layers * 2 * B * T * d * 4;
+  const size_t slot_rows = mem_rows ? mem_rows : (size_t)B * T;
+  const size_t slot_bytes = c->dec_absorbed ? slot_rows * d * 8 + 64 : (size_t)g.dec_layers * 2 * slot_rows * d * 4;
   for (int i = 0; i < (c->n_chains > 2 ? c->n_chains : 2); ++i)
     if ((rc = ensure(c, &c->ckv2[i], &c->ckv2_cap[i], slot_bytes))) return rc;
   if (!c->ckv) c->ckv = c->ckv2[0];
@@ -1091,6 +1098,11 @@ int dec_prepare(d2t_ctx* c, int B, int T, DecBufs* bufs) {
   bufs->f = p;
   return D2T_OK;
 }
+
+// device side of a ragged decode group (absorbed form): per-row tables, and where the slot keeps the bf16 planes of the packed
+// memory rows -- hi at ckv + plane_elems floats, lo plane_elems elements behind it: fixed by the slot's capacity, not by the
+// group's memory total, so that one captured loop serves every layout
+struct RaggedDev { const int* row0; const int* len; size_t plane_elems; };
 
 struct Lin { const float* x; int ldx; const LinW* w; const float* res; float* y; int ldy; int act; };
 
@@ -1148,7 +1160,7 @@ hipError_t cross_kv(d2t_ctx* c, hipStream_t s, const float* memory, int B, int T
 hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int T, int kvB,
                        float* logits, long long logit_row_stride, long long logit_step_stride, int ckvB = -1,
                        const int* row_map = nullptr, const int* stop = nullptr, int beam = 0, const int* seg = nullptr,
-                       const int* anc = nullptr, const int* rows_ptr = nullptr) {
+                       const int* anc = nullptr, const int* rows_ptr = nullptr, const RaggedDev* rg = nullptr) {
   const d2t_config& g = c->cfg;
   const int d = g.dec_dim, heads = g.dec_heads, hd = d / heads, Lmax = g.max_seq_len + 2;
   const int* step = c->dstate;
@@ -1182,6 +1194,10 @@ hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, int M, int 
     if (c->dec_absorbed && c->beam_shared_tile && beam > 0 && beam <= 6 && c->beam_qp && row_map)
       TRY(launch_decoder_row_beam(r, c->ckv, (long long)T * d, L.ca_wk, L.ca_v_t, L.ca_bv, c->beam_qp,
                                   c->beam_qp + (size_t)kvB * 8 * d, seg, ckvB, s));
+    else if (c->dec_absorbed && rg) {
+      const uint16_t* mhi = c->cross_fp32 ? nullptr : reinterpret_cast<const uint16_t*>(c->ckv + rg->plane_elems);
+      TRY(launch_decoder_row_absorbed(r, c->ckv, 0, L.ca_wk, L.ca_v_t, L.ca_bv, s, mhi, mhi ? mhi + rg->plane_elems : nullptr, rg->row0, rg->len));
+    }
     else if (c->dec_absorbed) {
       // the split-bf16 cross-attention reads the planes behind the slot's fp32 rows (cross_kv): greedy rows (two per block) and beam
       // rows (one per block, ancestry) alike
@@ -1252,10 +1268,66 @@ int ensure_host_beam(d2t_ctx* c, size_t bytes) {
 // rows_per_batch > 0 (async only): the B rows are rows_per_batch-row encoder batches decoded by one loop (a decode group);
 // with is_test every batch gets its own "first step at which all ITS rows had ended", and the captured loop stops working
 // once every batch has one (device-side early exit: the remaining kernels of the graph return at their first instruction).
+// rg != nullptr (async only, absorbed form): a RAGGED group -- the B rows are rg->n batches of rg->rows[i] rows whose memories of
+// rg->T[i] tokens lie packed in `memory` ([sum rows_i T_i][d]); T and rows_per_batch are unused.  Lengths, offsets and the
+// batch layout reach the kernels through per-slot device tables, so the captured loop depends on the row total alone.
+struct RaggedGroup { int n; const int32_t* rows; const int32_t* T; size_t mem_rows; };
+
+// Fill slot `slot`'s tables for the group (host side, then one asynchronous copy on the caller's stream, which the decode
+// stream is ordered behind).  The caller's stream already waits for the decode that last read this slot.
+int ragged_tables(d2t_ctx* c, int slot, int B, const RaggedGroup& rg, hipStream_t user, int** tab_out) {
+  if (c->rg_cap < B) {  // grow all slots together (fixed addresses between growths: they are part of the graph key)
+    int cap = 1024;
+    while (cap < B) cap *= 2;
+    HIPCHK(c, hipDeviceSynchronize());
+    for (int i = 0; i < d2t_ctx::MAXC; ++i) {
+      if (c->rg_tab[i]) hipFree(c->rg_tab[i]);
+      if (c->rg_host[i]) hipHostFree(c->rg_host[i]);
+      c->rg_tab[i] = nullptr; c->rg_host[i] = nullptr; c->rg_ev_valid[i] = false;
+    }
+    c->rg_cap = 0;
+    const size_t bytes = ((size_t)3 * cap + GRP_MAXB + 1) * 4;
+    for (int i = 0; i < d2t_ctx::MAXC; ++i) {
+      int rc = dev_alloc(c, reinterpret_cast<void**>(&c->rg_tab[i]), bytes);
+      if (rc) return rc;
+      if (hipHostMalloc(reinterpret_cast<void**>(&c->rg_host[i]), bytes, hipHostMallocDefault) != hipSuccess)
+        return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
+    }
+    c->rg_cap = cap;
+  }
+  const int cap = c->rg_cap;
+  if (c->rg_ev_valid[slot]) HIPCHK(c, hipEventSynchronize(c->rg_ev[slot]));  // the previous copy out of this host buffer has run
+  int* h = c->rg_host[slot];
+  int *row0 = h, *len = h + cap, *row_batch = h + 2 * cap, *batch_rows = h + 3 * cap;
+  int b = 0;
+  long long mrow = 0;
+  for (int k = 0; k < rg.n; ++k) {
+    for (int i = 0; i < rg.rows[k]; ++i, ++b) {
+      row0[b] = (int)(mrow + (long long)i * rg.T[k]);
+      len[b] = rg.T[k];
+      row_batch[b] = k;
+    }
+    mrow += (long long)rg.rows[k] * rg.T[k];
+    batch_rows[k] = rg.rows[k];
+  }
+  for (int k = rg.n; k < GRP_MAXB; ++k) batch_rows[k] = 0;
+  batch_rows[GRP_MAXB] = rg.n;
+  HIPCHK(c, hipMemcpyAsync(c->rg_tab[slot], h, ((size_t)3 * cap + GRP_MAXB + 1) * 4, hipMemcpyHostToDevice, user));
+  if (!c->rg_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->rg_ev[slot], hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(c->rg_ev[slot], user));
+  c->rg_ev_valid[slot] = true;
+  *tab_out = c->rg_tab[slot];
+  return D2T_OK;
+}
+
 int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* start_tokens, int is_test,
-                int64_t* tokens, float* logits, int* steps_out, hipStream_t user, bool async, int rows_per_batch = 0) {
+                int64_t* tokens, float* logits, int* steps_out, hipStream_t user, bool async, int rows_per_batch = 0,
+                const RaggedGroup* rg = nullptr) {
   const d2t_config& g = c->cfg;
   const int S = g.max_seq_len + 1, V = g.vocab;
+  if (rows_per_batch <= 0 || B % rows_per_batch) rows_per_batch = B;
+  const int n_batches = rg ? rg->n : B / rows_per_batch;
+  if (n_batches > GRP_MAXB) return fail(c, D2T_EINVAL, "a decode group holds at most %d batches", GRP_MAXB);  // (nothing enqueued yet)
   // memory slots rotate (at least two: the next batch's copy is written while the previous decode still reads its own);
   // async decodes rotate over the chains (chain == slot); everything else runs on chain 0
   const int nslots = c->n_chains > 2 ? c->n_chains : 2;
@@ -1263,7 +1335,7 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
   select_chain(c, (async && c->n_chains > 1) ? slot % c->n_chains : 0);
   hipStream_t s = c->dstream;
   DecBufs bf;
-  int rc = dec_prepare(c, B, T, &bf);
+  int rc = dec_prepare(c, B, T, &bf, rg ? rg->mem_rows : 0);
   if (rc) return rc;
   c->skv_cur = c->skv;
   c->ckv = c->ckv2[slot];
@@ -1279,15 +1351,24 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
   }
   // the decode that last read this K/V slot must be finished before it is overwritten
   if (c->ev_done_valid[slot]) HIPCHK(c, hipStreamWaitEvent(user, c->ev_done[slot], 0));
-  HIPCHK(c, cross_kv(c, user, memory, B, T));
-  // order the internal stream after the caller's work (K/V slot, start tokens)
+  RaggedDev rgd{};
+  int* rtab = nullptr;
+  if (rg) {  // tables first, then the packed rows and their bf16 planes at the slot's capacity-fixed offsets
+    if ((rc = ragged_tables(c, slot, B, *rg, user, &rtab))) return rc;
+    rgd.row0 = rtab; rgd.len = rtab + c->rg_cap;
+    rgd.plane_elems = ((c->ckv2_cap[slot] - 64) / 8) & ~(size_t)255;
+    const size_t n = rg->mem_rows * g.dec_dim;
+    HIPCHK(c, hipMemcpyAsync(c->ckv, memory, n * sizeof(float), hipMemcpyDeviceToDevice, user));
+    uint16_t* hi = reinterpret_cast<uint16_t*>(c->ckv + rgd.plane_elems);
+    HIPCHK(c, launch_split_bf16(memory, hi, hi + rgd.plane_elems, n, user));
+  } else {
+    HIPCHK(c, cross_kv(c, user, memory, B, T));
+  }
+  // order the internal stream after the caller's work (K/V slot, start tokens, a ragged group's tables)
   HIPCHK(c, hipEventRecord(c->ev_in, user));
   HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
   HIPCHK(c, hipMemsetAsync(c->dstate, 0, (size_t)(4 + B + GRP_WORDS) * 4, s));
   const bool dev_exit = async && is_test;  // early exit decided on the device inside the whole-loop graph
-  if (rows_per_batch <= 0 || B % rows_per_batch) rows_per_batch = B;
-  const int n_batches = B / rows_per_batch;
-  if (n_batches > GRP_MAXB) return fail(c, D2T_EINVAL, "a decode group holds at most %d batches", GRP_MAXB);
   int* grp = c->dstate + 4 + B;
   const int* stop = dev_exit ? grp + 2 * GRP_MAXB + 1 : nullptr;
   // step 0 input: Embedding([GO]) * sqrt(d) + pe[0]; later inputs are written by argmax_embed
@@ -1303,8 +1384,14 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
   am.rows_per_batch = rows_per_batch; am.n_batches = n_batches;
   am.batch_end_count = grp; am.batch_steps_done = grp + GRP_MAXB; am.batches_done = grp + 2 * GRP_MAXB;
   am.stop_at = dev_exit ? grp + 2 * GRP_MAXB + 1 : nullptr;
+  if (rg) {  // the layout is read from the slot's tables at run time; nothing of it is baked into the captured launch
+    // ArgmaxP::n_batches > 0 only says "grouped" here (ARGMAX_GROUPED): the group's real batch count is *n_batches_ptr
+    am.rows_per_batch = 0; am.n_batches = ARGMAX_GROUPED;
+    am.row_batch = rtab + 2 * c->rg_cap; am.batch_rows = rtab + 3 * c->rg_cap; am.n_batches_ptr = rtab + 3 * c->rg_cap + GRP_MAXB;
+  }
   auto one_step = [&](hipStream_t st) -> hipError_t {
-    hipError_t e = decode_step(c, st, bf, B, T, B, logits, (long long)S * V, V, -1, nullptr, stop);
+    hipError_t e = decode_step(c, st, bf, B, rg ? 1 : T, B, logits, (long long)S * V, V, -1, nullptr, stop, 0, nullptr, nullptr, nullptr,
+                               rg ? &rgd : nullptr);
     if (e != hipSuccess) return e;
     am.trace = trace_slot(c);
     return launch_argmax_embed(am, st);
@@ -1321,6 +1408,9 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
     k.B = B; k.T = T; k.steps = steps_per_graph; k.tok = tokens; k.logits = logits; k.ckv = c->ckv; k.dws = c->dws;
     k.skv = c->skv; k.dstate = c->dstate;
     k.variant = (dev_exit ? 1 : 0) | ((long long)rows_per_batch << 1);
+    if (rg) {  // row total + the "ragged" bit; neither T nor the batch layout
+      k.T = 0; k.variant = (dev_exit ? 1 : 0) | ((long long)c->rg_cap << 8) | (1LL << 62); k.rtab = rtab; k.aux = (long long)rgd.plane_elems;
+    }
     if (D2T_PROBE_ENV_STR("D2T_DECODE_TRACE") && !c->dtrace)  // debug timeline of the kernel nodes of a captured loop
       HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->dtrace), (size_t)d2t_ctx::DTRACE_SLOTS * 16));
     rc = cached_graph(c, s, k, "decode", [&](hipStream_t st) {
@@ -1352,6 +1442,9 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
     HIPCHK(c, hipEventRecord(drec.b, s));
     c->prof.push_back(drec);
   }
+  // a ragged group's batches are consumed one by one: each gets PAD / zeros from ITS OWN exit step on, as its single-batch
+  // decode leaves them (the loop itself ran every row until the last batch had ended)
+  if (rg && dev_exit) HIPCHK(c, launch_ragged_finalize(tokens, logits, am.row_batch, grp + GRP_MAXB, B, S, V, s));
   if (tokens != user_tokens) {
     HIPCHK(c, hipMemcpyAsync(user_logits, logits, log_bytes, hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipMemcpyAsync(user_tokens, tokens, tok_bytes, hipMemcpyDeviceToDevice, s));
@@ -1757,6 +1850,43 @@ int d2t_decode_greedy_submit(d2t_ctx* c, const float* memory, int32_t B, int32_t
   if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
   return rc;
 }
+
+int d2t_decode_greedy_submit_ragged(d2t_ctx* c, const float* memory, int32_t n_batches, const int32_t* batch_rows,
+                                    const int32_t* batch_T, const int64_t* start_tokens, int32_t is_test, int64_t* tokens,
+                                    float* logits, d2t_stream stream, int64_t* ticket_out) {
+  DevGuard dg_(c);
+  if (!c || !memory || !batch_rows || !batch_T || !start_tokens || !tokens || !logits) return fail(c, D2T_EINVAL, "bad argument");
+  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
+  if (c->cfg.decoder != D2T_DEC_TFM) return fail(c, D2T_ESTATE, "context was not created with the TFM decoder");
+  if (n_batches > GRP_MAXB) return fail(c, D2T_EINVAL, "a decode group holds at most %d batches", GRP_MAXB);
+  long long B = 0, mem_rows = 0;
+  for (int k = 0; k < n_batches; ++k) {
+    if (batch_rows[k] < 1) return fail(c, D2T_EINVAL, "batch %d of the group has %d rows", k, batch_rows[k]);
+    if (batch_T[k] < 1) return fail(c, D2T_EINVAL, "batch %d of the group has memory length %d", k, batch_T[k]);
+    if (batch_T[k] > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d > %d unsupported", batch_T[k], memory_cap(c));
+    B += batch_rows[k];
+    mem_rows += (long long)batch_rows[k] * batch_T[k];
+  }
+  if (n_batches < 1 || B < 1) return fail(c, D2T_EINVAL, "a decode group needs at least one row");
+  if (B > 65535 || mem_rows > 0x7fffffffLL / 256) return fail(c, D2T_EINVAL, "decode group too large (%lld rows, %lld memory rows)", B, mem_rows);
+  if (!c->dec_absorbed)
+    return fail(c, D2T_ESTATE, "ragged decode groups need the absorbed cross-attention (d_model 256, 8 heads): this decoder lays its "
+                               "projected cross K/V out by memory length, so batches of different lengths cannot share a loop");
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, logits, "logits")) return rc;
+  if (int rc = check_dev_ptr(c, tokens, "tokens")) return rc;
+  if (int rc = check_dev_ptr(c, start_tokens, "start_tokens")) return rc;
+  const RaggedGroup rg{n_batches, batch_rows, batch_T, (size_t)mem_rows};
+  const int rc = greedy_impl(c, memory, (int)B, 0, start_tokens, is_test, tokens, logits, nullptr, (hipStream_t)stream, true, 0, &rg);
+  if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
+  return rc;
+}
+
+// 1: this context decodes ragged groups (TFM decoder on the absorbed cross-attention); 0: d2t_decode_greedy_submit_ragged refuses
+int32_t d2t_decode_supports_ragged(const d2t_ctx* c) { return c && c->cfg.decoder == D2T_DEC_TFM && c->dec_absorbed ? 1 : 0; }
+
+// captured decode loops the context holds (tests: a ragged group re-uses one loop for every layout with the same row total)
+int32_t d2t_decode_graph_count(const d2t_ctx* c) { return c ? (int32_t)c->graphs.size() : 0; }
 
 int d2t_decode_wait(d2t_ctx* c, d2t_stream stream, int32_t host_sync) {
   DevGuard dg_(c);
@@ -2457,6 +2587,34 @@ int d2t_op_skinny(const float* x, const float* w, const float* bias, const float
   return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
 }
 
+namespace {
+// Set-up the decoder-row operator entries share: one temporary buffer [W_o^T | W_q^T | W_co^T | W_v^T | extra bytes] with the
+// four transposes enqueued, and the DecRowP fields every kind sets alike.  *buf is allocated here (nullptr on D2T_ENOMEM)
+// and freed by the caller after its stream has drained.
+struct RowOpTmp { float* buf; float* wv_t; float* ext; };
+int row_op_setup(const float* qkv, const float* xres, float* sk, float* sv, const float* ca_in_w, const float* ca_in_b,
+                 const float* sa_out_w, const float* sa_out_b, const float* ca_out_w, const float* ca_out_b, const float* ln1_g,
+                 const float* ln1_b, float eps, float* y2, const int32_t* step, int M, int D, int Lmax, size_t extra,
+                 hipStream_t s, RowOpTmp* t, DecRowP* r, hipError_t* e) {
+  const size_t dd = (size_t)D * D;
+  t->buf = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&t->buf), 4 * dd * 4 + extra) != hipSuccess) return D2T_ENOMEM;
+  float *wo_t = t->buf, *wq_t = t->buf + dd, *wco_t = t->buf + 2 * dd;
+  t->wv_t = t->buf + 3 * dd; t->ext = t->buf + 4 * dd;
+  *e = launch_transpose(sa_out_w, wo_t, D, D, s);
+  if (*e == hipSuccess) *e = launch_transpose(ca_in_w, wq_t, D, D, s);
+  if (*e == hipSuccess) *e = launch_transpose(ca_out_w, wco_t, D, D, s);
+  if (*e == hipSuccess) *e = launch_transpose(ca_in_w + 2 * dd, t->wv_t, D, D, s);
+  *r = DecRowP{};
+  r->qkv = qkv; r->qkv_stride = 3 * D; r->xres = xres;
+  r->sk = sk; r->sv = sv; r->s_batch_stride = (long long)Lmax * D; r->s_Lmax = Lmax;
+  r->wo_t = wo_t; r->bo = sa_out_b; r->ln1_g = ln1_g; r->ln1_b = ln1_b; r->eps = eps;
+  r->wq_t = wq_t; r->bq = ca_in_b; r->wco_t = wco_t; r->bco = ca_out_b;
+  r->y2 = y2; r->step_ptr = step; r->M = M; r->D = D; r->heads = 8;
+  return D2T_OK;
+}
+}  // namespace
+
 int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
                        const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
                        const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps, float* y2,
@@ -2506,20 +2664,14 @@ int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float*
   if (kind == 0) extra = 2 * memn * 4;
   else if (kind == 3 || kind == 4) extra = memn * 4;
   else if (kind == 5) extra = (size_t)M * 9 * D * 4;
-  float* buf = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&buf), 4 * dd * 4 + extra) != hipSuccess) return D2T_ENOMEM;
-  float *wo_t = buf, *wq_t = buf + dd, *wco_t = buf + 2 * dd, *wv_t = buf + 3 * dd, *ext = buf + 4 * dd;
-  hipError_t e = launch_transpose(sa_out_w, wo_t, D, D, s);
-  if (e == hipSuccess) e = launch_transpose(ca_in_w, wq_t, D, D, s);
-  if (e == hipSuccess) e = launch_transpose(ca_out_w, wco_t, D, D, s);
-  if (e == hipSuccess) e = launch_transpose(ca_in_w + 2 * dd, wv_t, D, D, s);
-  DecRowP r{};
-  r.qkv = qkv; r.qkv_stride = 3 * D; r.xres = xres;
-  r.sk = sk; r.sv = sv; r.s_batch_stride = (long long)Lmax * D; r.s_Lmax = Lmax;
+  RowOpTmp tmp;
+  DecRowP r;
+  hipError_t e = hipSuccess;
+  if (int rc = row_op_setup(qkv, xres, sk, sv, ca_in_w, ca_in_b, sa_out_w, sa_out_b, ca_out_w, ca_out_b, ln1_g, ln1_b, eps, y2, step,
+                            M, D, Lmax, extra, s, &tmp, &r, &e))
+    return rc;
+  float *const buf = tmp.buf, *const wv_t = tmp.wv_t, *const ext = tmp.ext;
   r.c_row_map = row_map; r.T = T;
-  r.wo_t = wo_t; r.bo = sa_out_b; r.ln1_g = ln1_g; r.ln1_b = ln1_b; r.eps = eps;
-  r.wq_t = wq_t; r.bq = ca_in_b; r.wco_t = wco_t; r.bco = ca_out_b;
-  r.y2 = y2; r.step_ptr = step; r.M = M; r.D = D; r.heads = 8;
   r.anc = anc; r.anc_stride = anc_stride;
   const float *wk = ca_in_w + dd, *bv = ca_in_b + 2 * D;
   if (e != hipSuccess) {  // (nothing more to launch)
@@ -2545,6 +2697,51 @@ int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float*
     }
     if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, (long long)T * D, wk, wv_t, bv, s, hi, lo);
   }
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(buf);
+  return e == hipErrorInvalidValue ? D2T_EINVAL : (e == hipSuccess && e2 == hipSuccess) ? D2T_OK : D2T_EHIP;
+}
+
+// The ragged builds of the greedy absorbed row kernels (kind as d2t_op_decoder_row: 1 / 2 = fp32 MFMA two-row / one-row,
+// 3 / 4 = split-bf16 two-row / one-row): mem is ONE packed [mem_rows][256] buffer, row b attends over the len[b] rows from
+// row0[b] on (host arrays, validated here, uploaded for the launch).
+int d2t_op_decoder_row_ragged(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                              const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                              const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps,
+                              float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
+                              const int32_t* row0_host, const int32_t* len_host, d2t_stream stream) {
+  if (!qkv || !xres || !sk || !sv || !mem || !ca_in_w || !ca_in_b || !sa_out_w || !sa_out_b || !ca_out_w || !ca_out_b ||
+      !ln1_g || !ln1_b || !y2 || !step || !row0_host || !len_host)
+    return D2T_EINVAL;
+  if (kind < 1 || kind > 4 || M < 1 || M > 65535 || rows < M || mem_rows < 1 || mem_rows > (1 << 22) || Lmax < 1 || Lmax > 4096)
+    return D2T_EINVAL;
+  for (int b = 0; b < M; ++b)
+    if (row0_host[b] < 0 || len_host[b] < 1 || len_host[b] > 4096 || (long long)row0_host[b] + len_host[b] > mem_rows) return D2T_EINVAL;
+  constexpr int D = 256;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> h;
+  if (!fetch_ints(s, step, 1, &h)) return D2T_EHIP;
+  if (h[0] < 0 || h[0] >= Lmax) return D2T_EINVAL;
+  const size_t dd = (size_t)D * D, memn = (size_t)mem_rows * D;
+  const size_t extra = kind >= 3 ? memn * 4 : 0;
+  RowOpTmp tmp;
+  DecRowP r;
+  hipError_t e = hipSuccess;
+  if (int rc = row_op_setup(qkv, xres, sk, sv, ca_in_w, ca_in_b, sa_out_w, sa_out_b, ca_out_w, ca_out_b, ln1_g, ln1_b, eps, y2, step,
+                            M, D, Lmax, extra + (size_t)2 * M * 4, s, &tmp, &r, &e))
+    return rc;
+  float *const buf = tmp.buf, *const wv_t = tmp.wv_t, *const ext = tmp.ext;
+  int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ext) + extra);  // [row0 | len] behind the bf16 planes
+  if (e == hipSuccess) e = hipMemcpyAsync(tab, row0_host, (size_t)M * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tab + M, len_host, (size_t)M * 4, hipMemcpyHostToDevice, s);
+  r.T = 1;  // (unused by the ragged builds)
+  r.one_row = kind == 2 || kind == 4;
+  uint16_t *hi = nullptr, *lo = nullptr;
+  if (e == hipSuccess && kind >= 3) {
+    hi = reinterpret_cast<uint16_t*>(ext); lo = hi + memn;
+    e = launch_split_bf16(mem, hi, lo, memn, s);
+  }
+  if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, 0, ca_in_w + dd, wv_t, ca_in_b + 2 * D, s, hi, lo, tab, tab + M);
   const hipError_t e2 = hipStreamSynchronize(s);
   hipFree(buf);
   return e == hipErrorInvalidValue ? D2T_EINVAL : (e == hipSuccess && e2 == hipSuccess) ? D2T_OK : D2T_EHIP;

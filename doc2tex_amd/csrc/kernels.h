@@ -269,9 +269,11 @@ hipError_t launch_decoder_row(const DecRowP& p, hipStream_t s);
 // mem [samples][T][256] (row b attends over sample c_row_map[b] or b), wk [256][256] as stored, wv_t [c][o], bv [256]
 // mem_hi / mem_lo (optional, greedy two-row kernel only): the same rows as bf16 hi / lo planes (launch_split_bf16) -> the
 // cross-attention runs on split-bf16 MFMAs
+// row0 / len (optional, greedy rows only; device arrays [M]): the RAGGED builds -- mem (and the planes) are one packed
+// [rows][256] buffer and row b attends over the len[b] >= 1 rows from row0[b] on; p.T, mem_stride and c_row_map are unused
 hipError_t launch_decoder_row_absorbed(const DecRowP& p, const float* mem, long long mem_stride, const float* wk,
                                        const float* wv_t, const float* bv, hipStream_t s, const uint16_t* mem_hi = nullptr,
-                                       const uint16_t* mem_lo = nullptr);
+                                       const uint16_t* mem_lo = nullptr, const int* row0 = nullptr, const int* len = nullptr);
 // beam search (at most 6 live hypotheses per sample): the row step split around ONE cross-attention block per sample that
 // stages the sample's memory tiles once for all its hypotheses; qp [rows][8][256] and x1 [rows][256] are scratch;
 // seg [nsamples][3] = (first row, live hypotheses, -) per sample, or nullptr / 1 for a single sample (rows [0, p.M))
@@ -300,8 +302,17 @@ struct ArgmaxP {
   // stop_at != nullptr, *stop_at = t + 1 makes the remaining kernels of a captured loop return immediately
   int rows_per_batch, n_batches;
   int* batch_end_count; int* batch_steps_done; int* batches_done; int* stop_at;
+  // ragged decode group (batches of different row counts): row_batch[b] = batch of row b, batch_rows[k] = rows of batch k,
+  // *n_batches_ptr = batches of the group -- device tables, read at run time (n_batches must still be > 0); nullptr = the
+  // uniform rule above
+  const int* row_batch; const int* batch_rows; const int* n_batches_ptr;
 };
+constexpr int ARGMAX_GROUPED = 1;  // ArgmaxP::n_batches of a launch whose batch count is read from n_batches_ptr
 hipError_t launch_argmax_embed(const ArgmaxP& p, hipStream_t s);
+// after an early-exit loop over a ragged group: tokens [B][S] / logits [B][S][V] of row b cleared from step
+// batch_steps_done[row_batch[b]] on (0 = the batch never ended: untouched)
+hipError_t launch_ragged_finalize(int64_t* tokens, float* logits, const int* row_batch, const int* batch_steps_done, int B, int S,
+                                  int V, hipStream_t s);
 
 // ---- beam search helpers (tools/beam.py semantics) ----
 // x[i] = emb[tok[i]]*sqrt(d) + pe[*step]

@@ -107,6 +107,26 @@ def device_index(device):
     return torch.cuda.current_device() if d.index is None else int(d.index)
 
 
+def ragged_tables(layout):
+    """The tables of a ragged decode group, as the engine writes them for its kernels: layout = [(rows_i, T_i)] per batch ->
+    dict(row0, len, row_batch, batch_rows, rows, mem_rows).  Row b (batch order) attends over the len[b] memory rows that
+    start at row row0[b] of the packed [sum rows_i * T_i][d] buffer; row_batch[b] is its batch, batch_rows[k] the rows of
+    batch k.  Pure host arithmetic (lists of ints)."""
+    row0, length, row_batch, batch_rows = [], [], [], []
+    base = 0
+    for k, (rows, T) in enumerate(layout):
+        rows, T = int(rows), int(T)
+        if rows < 1 or T < 1:
+            raise ValueError(f"batch {k} of the group has {rows} rows of memory length {T}")
+        for i in range(rows):
+            row0.append(base + i * T)
+            length.append(T)
+            row_batch.append(k)
+        batch_rows.append(rows)
+        base += rows * T
+    return {"row0": row0, "len": length, "row_batch": row_batch, "batch_rows": batch_rows, "rows": len(row0), "mem_rows": base}
+
+
 class Engine:
     def __init__(self, opt, device=None):
         self.lib = _lib.require_device()
@@ -445,6 +465,38 @@ class Engine:
                                                       int(rows_per_batch), _lib.ptr(tokens), _lib.ptr(logits),
                                                       _lib.stream_of(memory), C.byref(t)), "decode_greedy_submit")
         return self._hold(int(t.value), memory, (memory, start, tokens, logits))
+
+    def decode_greedy_ragged_into(self, memory, layout, start, tokens, logits, is_test=False):
+        """d2t_decode_greedy_submit_ragged on caller-held buffers: memory [sum rows_i * T_i, d] holds the batches' memories
+        back to back, layout = [(rows_i, T_i)], start [B], tokens [B, S], logits [B, S, V] with B = sum rows_i.  Returns the
+        ticket; decode_steps(ticket) has one entry per batch."""
+        self._on_device(memory, "memory")
+        n = len(layout)
+        tab = ragged_tables(layout) if n else {"rows": 0, "mem_rows": 0}
+        d, S, V, B = self.cfg.dec_dim, self.cfg.max_seq_len + 1, self.cfg.vocab, tab["rows"]
+        if tuple(memory.shape) != (tab["mem_rows"], d) or not memory.is_contiguous() or memory.dtype != torch.float32:
+            raise ValueError(f"packed memory must be a contiguous float32 [{tab['mem_rows']}, {d}] tensor, got "
+                             f"{memory.dtype} {tuple(memory.shape)}")
+        for what, t, shape, dtype in (("start", start, (B,), torch.int64), ("tokens", tokens, (B, S), torch.int64),
+                                      ("logits", logits, (B, S, V), torch.float32)):
+            self._on_device(t, what)
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+        rows = (C.c_int32 * max(n, 1))(*[int(r) for r, _ in layout])
+        Ts = (C.c_int32 * max(n, 1))(*[int(t) for _, t in layout])
+        t = C.c_int64(0)
+        self._check(self.lib.d2t_decode_greedy_submit_ragged(self.ctx, _lib.ptr(memory), n, rows, Ts, _lib.ptr(start),
+                                                             int(bool(is_test)), _lib.ptr(tokens), _lib.ptr(logits),
+                                                             _lib.stream_of(memory), C.byref(t)), "decode_greedy_submit_ragged")
+        return self._hold(int(t.value), memory, (memory, start, tokens, logits))
+
+    def supports_ragged_groups(self):
+        """Whether this context decodes ragged groups (TFM head on the absorbed cross-attention: d_model 256, 8 heads); the
+        context itself answers (d2t_decode_supports_ragged), once the weights are finalized."""
+        return bool(self.lib.d2t_decode_supports_ragged(self.ctx))
+
+    def graph_count(self):
+        return int(self.lib.d2t_decode_graph_count(self.ctx))
 
     def _hold(self, ticket, memory, tensors):
         """Keep the buffers of the asynchronous decode `ticket` referenced until it completes; returns the ticket."""

@@ -209,8 +209,13 @@ int d2t_decode_attn_greedy_alpha(d2t_ctx* ctx, const float* memory_dev, int32_t 
  * alive and untouched until d2t_decode_wait: it makes `stream` wait for every outstanding decode
  * (and, if host_sync != 0, blocks the host until they are complete). */
 /* Decode groups: B need not be one encoder batch.  A serving loop may collect the memories of several consecutive batches
- * (same T) in one buffer and decode their rows with ONE call -- the step loop's duration hardly depends on the row count,
- * and every row's result is bit-identical to its single-batch decode (doc2tex_amd.Model.decode_group does exactly this). */
+ * in one buffer and decode their rows with ONE call -- the step loop's duration hardly depends on the row count, and every
+ * row's result is bit-identical to its single-batch decode (doc2tex_amd.Model.decode_group does exactly this).  Two forms:
+ *   d2t_decode_greedy_submit         UNIFORM group: every batch has the same row count (rows_per_batch) and the same memory
+ *                                    length T; memory_dev is [B][T][d];
+ *   d2t_decode_greedy_submit_ragged  RAGGED group: batch i has batch_rows[i] rows and memory length batch_T[i] (crops of
+ *                                    different sizes); memory_dev is the batches' memories packed back to back,
+ *                                    [sum_i batch_rows[i] * batch_T[i]][d] (Model.decode_group_mixed). */
 int d2t_decode_greedy_async(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T,
                             const int64_t* start_tokens_dev, int64_t* tokens_dev, float* logits_dev, d2t_stream stream);
 int d2t_decode_wait(d2t_ctx* ctx, d2t_stream stream, int32_t host_sync);
@@ -230,6 +235,28 @@ int d2t_decode_wait(d2t_ctx* ctx, d2t_stream stream, int32_t host_sync);
 int d2t_decode_greedy_submit(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T, const int64_t* start_tokens_dev,
                              int32_t is_test, int32_t rows_per_batch, int64_t* tokens_dev, float* logits_dev,
                              d2t_stream stream, int64_t* ticket_out);
+/* A decode group whose batches differ in row count and memory length (d_model 256 / 8 heads, the absorbed cross-attention:
+ * each row reads its own slice of the packed memory rows, so it is bit-identical to its single-batch decode).
+ *   memory_dev         [sum_i batch_rows[i] * batch_T[i]][d], batch after batch, each batch [rows][T][d];
+ *   batch_rows/batch_T HOST arrays [n_batches] (1 .. 64 batches, every entry >= 1, batch_T[i] <= 4096); read before the call
+ *                      returns;
+ *   start_tokens_dev   [B], tokens_dev [B][S], logits_dev [B][S][V] with B = sum_i batch_rows[i], rows in batch order.
+ * is_test, tickets, d2t_decode_steps (one entry per batch) and the PAD / zero output behind the group's stop step are those
+ * of d2t_decode_greedy_submit.  The captured step loop depends on B alone: lengths, offsets and the batch layout are read
+ * from engine-owned device tables (filled on `stream` by an asynchronous copy), so any mix with the same row total replays
+ * one graph.  Refused before anything is enqueued (D2T_EINVAL unless stated): no batch / no row, more than 64 batches, a
+ * batch without rows, a memory length < 1 or > 4096, a pointer of another device; a context without the TFM decoder
+ * (D2T_ESTATE); a decoder with projected cross K/V (d_model 512: D2T_ESTATE -- its K/V layout depends on T; decode such
+ * batches with d2t_decode_greedy_submit, one group per size). */
+int d2t_decode_greedy_submit_ragged(d2t_ctx* ctx, const float* memory_dev, int32_t n_batches, const int32_t* batch_rows,
+                                    const int32_t* batch_T, const int64_t* start_tokens_dev, int32_t is_test,
+                                    int64_t* tokens_dev, float* logits_dev, d2t_stream stream, int64_t* ticket_out);
+/* 1 if this context decodes ragged groups (d2t_decode_greedy_submit_ragged: TFM decoder whose cross-attention reads the
+ * encoder memory itself), 0 if that entry point refuses (LSTM-attention heads; projected cross K/V, d_model 512).  Valid
+ * once the weights are finalized. */
+int32_t d2t_decode_supports_ragged(const d2t_ctx* ctx);
+/* Captured decode loops the context currently holds (at most 40, least recently used evicted). */
+int32_t d2t_decode_graph_count(const d2t_ctx* ctx);
 /* The LSTM-attention heads (Attn / Attnv2) through the same serving machinery: d2t_decode_attn_greedy[_alpha] without
  * the wait.  The key projection, the one-launch step loop and a small finalize kernel are enqueued on the stream of one of
  * the d2t_set_decode_chains chains (they take turns), ordered behind `stream` by an event; the call returns once that is
@@ -486,6 +513,15 @@ int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float*
                        const int32_t* step, int32_t M, int32_t D, int32_t T, int32_t Lmax, int32_t rows, int32_t samples,
                        int32_t one_row, const int32_t* row_map, const int32_t* anc, int32_t anc_stride, const int32_t* seg,
                        int32_t nsamples, d2t_stream stream);
+/* The ragged builds of the greedy absorbed row kernels (D = 256; kind 1 - 4 as above): mem is ONE packed [mem_rows][256]
+ * buffer and row b attends over the len[b] rows from row row0[b] on (HOST arrays [M]; 1 <= len[b] <= 4096,
+ * row0[b] + len[b] <= mem_rows).  Everything else as d2t_op_decoder_row.  With row0[b] = b * T and len[b] = T the result
+ * equals d2t_op_decoder_row's bit for bit. */
+int d2t_op_decoder_row_ragged(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                              const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                              const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps,
+                              float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
+                              const int32_t* row0, const int32_t* len, d2t_stream stream);
 /* One greedy step (launch_argmax_embed) at t = *step < S: tokens[b][t] = first maximum of logits[b][t][:V] (logits [B][S][V],
  * tokens [B][S]); end-of-sequence bookkeeping in ended [B], end_count, steps_done; *step becomes t + 1, done_count (zero
  * before the first launch) is back at zero afterwards; x [B][d] (optional) = emb[token] * sqrt(d) + pe[t + 1] (pe [S + 1][d]).

@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""tools/serve_bench.py's end-to-end loop on MIXED-SIZE traffic: every page set holds pages that land on the three crop
+sizes of config C4 (96x384, 128x512, 160x640), a few per size, so `Preprocessor.batch` hands back three small batches per
+set and consecutive forwards differ in row count and memory length.
+
+  --mixed 0   decode groups as they were: a change of size launches the group collected so far, so every small batch pays
+              for a step loop of its own (this mode only touches what Model had before decode_group_mixed existed);
+  --mixed 1   Model.decode_group_mixed: batches of any size share a loop until the group holds --group batches or
+              --group-rows rows.
+
+Prints one JSON line: formulas/s end to end (uint8 pages -> LaTeX strings)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+from doc2tex_amd import Model, synth
+from doc2tex_amd.postprocess import LabelDecoder
+from doc2tex_amd.preprocess import Preprocessor
+
+SYMBOLS = ["\\frac", "{", "}", "x", "y", "a", "b", "1", "2", "^", "_", "\\mathrm", "\\operatorname", "*", "\\alpha", "+", "=",
+           "(", ")", "\\,", "d", "\\hspace", "\\mathbf", "\\left", "\\right", ".", "~", "\\\\", "&", "e", "\\sum", "\\int", "|"]
+BUCKETS = {(96, 384), (128, 512), (160, 640)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20, help="page sets timed")
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--per-size", type=int, default=8, help="pages per crop size in a page set")
+    ap.add_argument("--mixed", type=int, default=0, choices=[0, 1])
+    ap.add_argument("--group", type=int, default=6, help="batches per decode step loop")
+    ap.add_argument("--group-rows", type=int, default=384, help="--mixed 1: row budget of a group")
+    ap.add_argument("--chains", type=int, default=3)
+    ap.add_argument("--page-sets", type=int, default=4, help="distinct page sets cycled through")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    cfg = synth.make_config("C4", device=str(dev))
+    model = Model(cfg)
+    tmpl = {k: v for k, v in model.state_dict().items() if not k.endswith("image_positional_encoder.pe")}
+    model.load_state_dict(synth.synth_state_dict(tmpl), strict=False)
+    model.eval().to(dev)
+    model.pipelined, model.decode_chains, model.decode_group, model.reserved_blocks = True, args.chains, args.group, 0
+    if args.mixed:
+        model.decode_group_mixed, model.decode_group_rows = True, args.group_rows
+    opt = {"imgH": None, "imgW": None, "max_dimension": cfg["max_dimension"], "min_dimension": [32, 32], "mean": 0.5,
+           "std": 0.5, "rgb": False, "pad": False, "device": str(dev)}
+    pre = Preprocessor(opt, "demo")
+    vocab = [SYMBOLS[i % len(SYMBOLS)] + ("" if i < len(SYMBOLS) else f"_{i}") for i in range(synth.VOCAB - 4)]
+    dec = LabelDecoder(vocab, head="TFM")
+    rng = np.random.default_rng(3)
+    n = args.per_size
+
+    def page_set(s):
+        # scanned pages that are scaled down onto 160x640, and crops that already have one of the two smaller sizes
+        pages = [synth.synth_formula_image(int(rng.integers(380, 396)), int(rng.integers(1580, 1601)), 9000 + s * 64 + i) for i in range(n)]
+        pages += [synth.synth_formula_image(128, 512, 9100 + s * 64 + i) for i in range(n)]
+        pages += [synth.synth_formula_image(96, 384, 9200 + s * 64 + i) for i in range(n)]
+        order = rng.permutation(len(pages))
+        return [pages[i] for i in order]
+
+    sets = [page_set(s) for s in range(args.page_sets)]
+    go = torch.full((3 * n, 1), 1, dtype=torch.long, device=dev)
+    side = torch.cuda.Stream(dev)
+    L = cfg["Prediction"]["params"]["max_seq_len"] + 1
+    ring = [torch.empty((3 * n, L), dtype=torch.int64).pin_memory() for _ in range(64)]
+    state = {"done": 0, "t_post": 0.0, "seq": 0, "sample": ""}
+    waiting, pending = [], []  # forwards whose decode may not be launched yet; copies in flight (pinned slot, rows, event)
+
+    def copy_out(force):
+        ready = [w for w in waiting if force or w[1].ticket is not None]
+        if not ready:
+            return
+        if force:
+            model.synchronize(host_sync=False)  # launches an incomplete group
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for tokens, handle in ready:
+                handle.wait()  # the side stream waits for exactly that decode
+                slot = ring[state["seq"] % len(ring)]
+                state["seq"] += 1
+                slot[:tokens.shape[0]].copy_(tokens, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending.append((slot, tokens.shape[0], ev))
+        for w in ready:
+            waiting.remove(w)
+
+    def consume(block):
+        while pending and (block or pending[0][2].query()):
+            slot, rows, ev = pending.pop(0)
+            ev.synchronize()
+            t = time.perf_counter()
+            latex = dec.to_latex(slot[:rows], "word", postprocess=True)
+            state["t_post"] += time.perf_counter() - t
+            state["done"] += len(latex)
+            state["sample"] = latex[0]
+
+    def step(i):
+        tensors, errors = pre.batch(sets[i % len(sets)])
+        assert all(e is None for e in errors)
+        buckets = {}
+        for t in tensors:
+            buckets.setdefault(t._base.data_ptr(), t._base)
+        assert len(buckets) == 3 and {tuple(x.shape[2:]) for x in buckets.values()} == BUCKETS, [x.shape for x in buckets.values()]
+        for x in buckets.values():
+            with torch.no_grad():
+                tokens, _, extra = model(x, go[:x.shape[0]], is_train=False, is_test=False)
+            waiting.append((tokens, extra["decode"]))
+        copy_out(False)
+        consume(False)
+
+    for i in range(args.warmup):
+        step(i)
+    copy_out(True)
+    consume(True)
+    torch.cuda.synchronize(dev)
+    state["done"], state["t_post"] = 0, 0.0
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        step(args.warmup + i)
+    copy_out(True)
+    consume(True)
+    torch.cuda.synchronize(dev)
+    el = time.perf_counter() - t0
+    assert state["done"] == 3 * n * args.steps, (state["done"], 3 * n * args.steps)
+    print(json.dumps({"metric": "formulas/s end to end on mixed-size pages (uint8 pages -> LaTeX strings)",
+                      "value": round(state["done"] / el, 1), "unit": "formulas/s", "mixed": args.mixed, "steps": args.steps,
+                      "per_size": n, "group": args.group, "ms_per_page_set": round(el / args.steps * 1e3, 2),
+                      "postprocess_ms_per_page_set": round(state["t_post"] / args.steps * 1e3, 2),
+                      "sizes": sorted(BUCKETS), "sample_latex_chars": len(state["sample"])}))
+
+
+if __name__ == "__main__":
+    main()
