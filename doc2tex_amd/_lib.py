@@ -129,6 +129,8 @@ SIGNATURES = {
     "d2t_op_cache_gather": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "d2t_ce_forward": (_I, [_P, _P, _P, _P, _I, _I, _L, _P]),
     "d2t_ce_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _P]),
+    "d2t_ce_smooth_forward": (_I, [_P] * 6 + [_I, _I, _L, C.c_float, C.c_float, _I, _L, _P]),
+    "d2t_ce_smooth_backward": (_I, [_P] * 7 + [_I, _I, _L, C.c_float, C.c_float, _I, _L, _P]),
     "d2t_op_train_conv": (_I, [_P] * 14 + [_I] * 13 + [_P]),
     "d2t_op_train_linear": (_I, [_P] * 10 + [_I] * 5 + [_P]),
     "d2t_op_train_layernorm": (_I, [_P] * 8 + [_I, _I, C.c_float, _P]),

@@ -482,6 +482,13 @@ hipError_t launch_ce_fwd(const float* x, const int64_t* tgt, float* loss, float*
                          hipStream_t s);
 hipError_t launch_ce_bwd(const float* x, const int64_t* tgt, const float* lse, const float* dloss, float* dx, int rows, int V,
                          long long ignore, hipStream_t s);
+// class-weighted / label-smoothed cross-entropy (ref = 0: nn.CrossEntropyLoss(weight, label_smoothing); ref = 1: the
+// reference's LabelSmoothingLoss, no mass on the target's and the padding column beside `on`); w may be nullptr
+hipError_t launch_ce_smooth_fwd(const float* x, const int64_t* tgt, const float* w, float* loss, float* lse, float* mass,
+                                int rows, int V, long long ignore, float on, float off, int ref, long long pad, hipStream_t s);
+hipError_t launch_ce_smooth_bwd(const float* x, const int64_t* tgt, const float* w, const float* lse, const float* mass,
+                                const float* dloss, float* dx, int rows, int V, long long ignore, float on, float off, int ref,
+                                long long pad, hipStream_t s);
 hipError_t launch_relu_mask(const float* y, uint8_t* m, size_t n, hipStream_t s);
 hipError_t launch_pool_argmax(const float* x, uint8_t* k, int B, int H, int W, int C, int SH, int SW, int PH, int PW,
                               hipStream_t s, int KW = 2);

@@ -1663,6 +1663,24 @@ int d2t_ce_backward(const float* logits, const int64_t* target, const float* lse
   if (!logits || !target || !lse || !dloss || !dlogits || rows < 0 || V < 1) return D2T_EINVAL;
   return launch_ce_bwd(logits, target, lse, dloss, dlogits, rows, V, ignore_index, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
 }
+// The same with class weights and / or label smoothing (nn.CrossEntropyLoss(weight, label_smoothing)), and the reference's
+// LabelSmoothingLoss (modules/loss/labelsmoothing.py): include/d2t.h.
+int d2t_ce_smooth_forward(const float* logits, const int64_t* target, const float* weight, float* loss, float* lse, float* mass,
+                          int32_t rows, int32_t V, int64_t ignore_index, float on, float off, int32_t mode, int64_t pad_index,
+                          d2t_stream stream) {
+  if (!logits || !target || !loss || !lse || !mass || rows < 0 || V < 1) return D2T_EINVAL;
+  if ((mode != D2T_CE_TORCH && mode != D2T_CE_REFERENCE) || (mode == D2T_CE_REFERENCE && weight)) return D2T_EINVAL;
+  return launch_ce_smooth_fwd(logits, target, weight, loss, lse, mass, rows, V, ignore_index, on, off, mode == D2T_CE_REFERENCE,
+                              pad_index, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+int d2t_ce_smooth_backward(const float* logits, const int64_t* target, const float* weight, const float* lse, const float* mass,
+                           const float* dloss, float* dlogits, int32_t rows, int32_t V, int64_t ignore_index, float on,
+                           float off, int32_t mode, int64_t pad_index, d2t_stream stream) {
+  if (!logits || !target || !lse || !mass || !dloss || !dlogits || rows < 0 || V < 1) return D2T_EINVAL;
+  if ((mode != D2T_CE_TORCH && mode != D2T_CE_REFERENCE) || (mode == D2T_CE_REFERENCE && weight)) return D2T_EINVAL;
+  return launch_ce_smooth_bwd(logits, target, weight, lse, mass, dloss, dlogits, rows, V, ignore_index, on, off,
+                              mode == D2T_CE_REFERENCE, pad_index, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
 
 int d2t_op_train_conv(const float* x, const float* w, const float* bias, const float* gamma, const float* beta,
                       const float* residual, const float* dy, float* y, float* dx, float* dw, float* dbias,

@@ -969,6 +969,147 @@ hipError_t launch_ce_bwd(const float* x, const int64_t* tgt, const float* lse, c
 }
 
 // ---------------------------------------------------------------------------
+// Smoothed / class-weighted cross-entropy: the other criteria modules/loss/builder.py:18-24 can build.  Per live row with
+// target t the criterion spreads a mass m[v] over the classes,
+//     m[v] = on * w[t] * [v == t]  +  off * w[v] * [v in S],        M = sum_v m[v],
+//     loss = sum_v m[v] * (lse - x[v]),        dx[v] = dloss * (M * exp(x[v] - lse) - m[v]),
+//   mode 0 (nn.CrossEntropyLoss(weight, label_smoothing = e)):  on = 1 - e, off = e / V, S = every class, w = weight or 1;
+//   mode 1 (LabelSmoothingLoss, labelsmoothing.py:15-30):  on = 1 - s, off = s / (classes - 2), S = every class but t and
+//          the padding column, w = 1 -- M is then not 1, and the gradient carries it.
+// One wave per row as above, but ONE pass over the logits each way: the forward keeps a running maximum with the rescaled
+// exp-sum (online softmax) beside U = sum off-mass and UX = sum off-mass * x, so loss = on*w[t]*(lse - x[t]) + U*lse - UX
+// and M = on*w[t] + U; it saves lse and M per row, the backward redoes no reduction.  A row is read as float4 from its first
+// 16-byte boundary on (up to three scalar elements in front and behind), whatever V is.  Ignored rows (target ==
+// ignore_index or outside [0, V)) are not read: loss 0, gradient row 0.
+// (tools/probe/ce_smooth_host.cpp runs the code between the two markers lane by lane on the host, under AddressSanitizer.)
+// ---------------------------------------------------------------------------
+// [ce_smooth: begin]
+namespace {
+struct CeSmooth {
+  const float* w;  // class weights or nullptr (mode 0)
+  float on, off;
+  int ref;          // mode 1
+  long long t, pad;
+  // off-target mass of class v (the target's own `on` share is added by the caller)
+  __device__ __forceinline__ float u(int v, float wv) const { return (ref && (v == t || v == pad)) ? 0.f : off * wv; }
+  __device__ __forceinline__ float wt(int v) const { return w ? w[v] : 1.f; }
+};
+// elements in front of the first 16-byte boundary of a row
+__device__ __forceinline__ int ce_head(const float* p, int V) {
+  return min(V, (int)((4u - (unsigned)(((uintptr_t)p >> 2) & 3u)) & 3u));
+}
+__device__ __forceinline__ float4 ce_w4(const CeSmooth& c, int v, bool wvec) {
+  if (!c.w) return make_float4(1.f, 1.f, 1.f, 1.f);
+  if (wvec) return *reinterpret_cast<const float4*>(c.w + v);
+  return make_float4(c.w[v], c.w[v + 1], c.w[v + 2], c.w[v + 3]);
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void ce_smooth_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ tgt,
+                                                            const float* __restrict__ w, float* __restrict__ loss,
+                                                            float* __restrict__ lse, float* __restrict__ mass, int rows, int V,
+                                                            long long ignore, float on, float off, int ref, long long pad) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  const long long t = tgt[row];
+  if (t == ignore || t < 0 || t >= V) {
+    if (lane == 0) loss[row] = 0.f, lse[row] = 0.f, mass[row] = 0.f;
+    return;
+  }
+  const CeSmooth c{w, on, off, ref, t, pad};
+  const float* xr = x + (size_t)row * V;
+  float m = -INFINITY, sum = 0.f, U = 0.f, UX = 0.f;  // per lane: running maximum, sum exp(x - m), off-mass, off-mass * x
+  auto take = [&](float xv, int v) {
+    if (xv > m) sum *= expf(m - xv), m = xv;
+    if (m > -INFINITY) sum += expf(xv - m);
+    const float u = c.u(v, c.wt(v));
+    if (u != 0.f) U += u, UX = fmaf(u, xv, UX);  // (a class without mass may sit at -inf)
+  };
+  const int head = ce_head(xr, V), nvec = (V - head) >> 2, tail = head + (nvec << 2);
+  const bool wvec = w && (((uintptr_t)(w + head)) & 15) == 0;
+  if (lane < head) take(xr[lane], lane);
+#pragma unroll 2
+  for (int i = lane; i < nvec; i += 64) {
+    const int v = head + (i << 2);
+    const float4 q = *reinterpret_cast<const float4*>(xr + v);
+    const float4 wq = ce_w4(c, v, wvec);
+    const float mx = fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w));
+    if (mx > m) sum *= expf(m - mx), m = mx;
+    if (m > -INFINITY) sum += (expf(q.x - m) + expf(q.y - m)) + (expf(q.z - m) + expf(q.w - m));
+    const float u0 = c.u(v, wq.x), u1 = c.u(v + 1, wq.y), u2 = c.u(v + 2, wq.z), u3 = c.u(v + 3, wq.w);
+    if (u0 != 0.f) U += u0, UX = fmaf(u0, q.x, UX);
+    if (u1 != 0.f) U += u1, UX = fmaf(u1, q.y, UX);
+    if (u2 != 0.f) U += u2, UX = fmaf(u2, q.z, UX);
+    if (u3 != 0.f) U += u3, UX = fmaf(u3, q.w, UX);
+  }
+  if (tail + lane < V) take(xr[tail + lane], tail + lane);
+  const float mrow = wmax(m);
+  sum = wsum(m > -INFINITY ? sum * expf(m - mrow) : 0.f);  // lanes that held no element (V < 64) add nothing
+  U = wsum(U);
+  UX = wsum(UX);
+  if (lane == 0) {
+    const float l = mrow + logf(sum), hit = on * c.wt((int)t);
+    lse[row] = l;
+    mass[row] = hit + U;
+    loss[row] = hit * (l - xr[t]) + (U != 0.f ? U * l - UX : 0.f);
+  }
+}
+__global__ __launch_bounds__(256) void ce_smooth_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ tgt,
+                                                            const float* __restrict__ w, const float* __restrict__ lse,
+                                                            const float* __restrict__ mass, const float* __restrict__ dloss,
+                                                            float* __restrict__ dx, int rows, int V, long long ignore, float on,
+                                                            float off, int ref, long long pad) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  const float* xr = x + (size_t)row * V;
+  float* dr = dx + (size_t)row * V;
+  const long long t = tgt[row];
+  const bool live = !(t == ignore || t < 0 || t >= V);
+  const CeSmooth c{w, on, off, ref, t, pad};
+  const float g = live ? dloss[row] : 0.f, l = live ? lse[row] : 0.f, M = live ? mass[row] : 0.f;
+  const float hit = live ? on * c.wt((int)t) : 0.f;
+  auto grad = [&](float xv, int v, float wv) { return (M * expf(xv - l) - (c.u(v, wv) + (v == t ? hit : 0.f))) * g; };
+  // float4 only where the row of x and the row of dx reach a 16-byte boundary together
+  const bool same = ((((uintptr_t)xr) ^ ((uintptr_t)dr)) & 15) == 0;
+  const int head = same ? ce_head(xr, V) : V, nvec = (V - head) >> 2, tail = head + (nvec << 2);
+  if (!live) {
+    for (int v = lane; v < head; v += 64) dr[v] = 0.f;
+    for (int i = lane; i < nvec; i += 64) *reinterpret_cast<float4*>(dr + head + (i << 2)) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tail + lane < V) dr[tail + lane] = 0.f;
+    return;
+  }
+  const bool wvec = w && (((uintptr_t)(w + head)) & 15) == 0;
+  for (int v = lane; v < head; v += 64) dr[v] = grad(xr[v], v, c.wt(v));
+#pragma unroll 2
+  for (int i = lane; i < nvec; i += 64) {
+    const int v = head + (i << 2);
+    const float4 q = *reinterpret_cast<const float4*>(xr + v);
+    const float4 wq = ce_w4(c, v, wvec);
+    *reinterpret_cast<float4*>(dr + v) =
+        make_float4(grad(q.x, v, wq.x), grad(q.y, v + 1, wq.y), grad(q.z, v + 2, wq.z), grad(q.w, v + 3, wq.w));
+  }
+  if (tail + lane < V) dr[tail + lane] = grad(xr[tail + lane], tail + lane, c.wt(tail + lane));
+}
+// [ce_smooth: end]
+hipError_t launch_ce_smooth_fwd(const float* x, const int64_t* tgt, const float* w, float* loss, float* lse, float* mass,
+                                int rows, int V, long long ignore, float on, float off, int ref, long long pad, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ce_smooth_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, tgt, w, loss, lse, mass, rows, V, ignore,
+                     on, off, ref, pad);
+  return hipGetLastError();
+}
+hipError_t launch_ce_smooth_bwd(const float* x, const int64_t* tgt, const float* w, const float* lse, const float* mass,
+                                const float* dloss, float* dx, int rows, int V, long long ignore, float on, float off, int ref,
+                                long long pad, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ce_smooth_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, tgt, w, lse, mass, dloss, dx, rows, V,
+                     ignore, on, off, ref, pad);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // The discrete decisions of a training forward, for tests that replay them in the oracle (d2t_train_read_decision):
 // ReLU keep masks (y > 0) and, per max-pool output element, which window element (kh*2 + kw) the backward routes the
 // gradient to -- the same first-maximum scan as maxpool_bwd_kernel.

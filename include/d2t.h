@@ -562,6 +562,25 @@ int d2t_ce_forward(const float* logits, const int64_t* target, float* loss, floa
                    int64_t ignore_index, d2t_stream stream);
 int d2t_ce_backward(const float* logits, const int64_t* target, const float* lse, const float* dloss, float* dlogits,
                     int32_t rows, int32_t V, int64_t ignore_index, d2t_stream stream);
+/* The other criteria modules/loss/builder.py can build, as a second kernel pair (the plain pair above is untouched).  A
+ * live row with target t puts the mass  m[v] = on * w[t] * [v == t] + off * w[v] * [v in S]  on class v:
+ *     loss = sum_v m[v] * (lse - x[v]),      dlogits[v] = dloss * (M * exp(x[v] - lse) - m[v]),      M = sum_v m[v].
+ *   D2T_CE_TORCH      nn.CrossEntropyLoss(weight, ignore_index, label_smoothing = e): on = 1 - e, off = e / V, S = every
+ *                     class, w = weight [V] (NULL: all ones); pad_index is not read.
+ *   D2T_CE_REFERENCE  LabelSmoothingLoss(reduction, classes, ignore_index, smoothing = s) (modules/loss/labelsmoothing.py):
+ *                     on = 1 - s, off = s / (classes - 2), S = every class except t and column pad_index, weight NULL;
+ *                     the row mass M is then not 1.
+ * The forward writes loss [rows], lse [rows] and mass [rows] (M; lse and mass feed the backward, which repeats no
+ * reduction).  Rows whose target equals ignore_index or lies outside [0, V) give loss 0 and a zero gradient row.  One pass
+ * over the logits each way. */
+#define D2T_CE_TORCH 0
+#define D2T_CE_REFERENCE 1
+int d2t_ce_smooth_forward(const float* logits, const int64_t* target, const float* weight, float* loss, float* lse, float* mass,
+                          int32_t rows, int32_t V, int64_t ignore_index, float on, float off, int32_t mode, int64_t pad_index,
+                          d2t_stream stream);
+int d2t_ce_smooth_backward(const float* logits, const int64_t* target, const float* weight, const float* lse, const float* mass,
+                           const float* dloss, float* dlogits, int32_t rows, int32_t V, int64_t ignore_index, float on,
+                           float off, int32_t mode, int64_t pad_index, d2t_stream stream);
 
 /* ---- op-level TRAINING test entry points ---------------------------------------------------------------------
  * One node of the training tape, forward + backward, on caller tensors (fp32, device, row-major [rows][cols]; maps
