@@ -79,6 +79,10 @@ SIGNATURES = {
     "d2t_decode_wait_ticket": (_I, [_P, _L, _P, _I]),
     "d2t_decode_beam": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_decode_beam_batch": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
+    "d2t_decode_beam_batch_ragged": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float),
+                                          _P]),
+    "d2t_decode_supports_ragged_beam": (_I, [_P]),
+    "d2t_ragged_beam_tables": (_L, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "d2t_decode_attn_beam_batch": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_decode_attn_beam_batch_alpha": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P,
                                                _P]),
@@ -122,6 +126,8 @@ SIGNATURES = {
     "d2t_op_skinny": (_I, [_P] * 6 + [C.c_float, _P, _P] + [_I] * 6 + [_P, _L, _P]),
     "d2t_op_decoder_row": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 7 + [_P, _P, _I, _P, _I, _P]),
     "d2t_op_decoder_row_ragged": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 4 + [C.POINTER(_I), C.POINTER(_I), _P]),
+    "d2t_op_decoder_row_ragged_beam": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 5 +
+                                       [C.POINTER(_I), C.POINTER(_I), _P, _P, _I, _P]),
     "d2t_op_argmax_embed": (_I, [_P, _I] + [_P] * 13 + [_I] * 6 + [_P]),
     "d2t_op_beam_topk": (_I, [_P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
     "d2t_op_beam_advance": (_I, [_I, _L] + [_P] * 15 + [_I] * 6 + [_P]),

@@ -246,10 +246,15 @@ class Model(nn.Module):
         and advance the hypotheses of all samples in one step loop.  Returns [(LongTensor [1, len], score)] per
         sample, each identical to `forward(input[i:i+1], ...)` with `beam_size` set.
 
+        input may also be a list or tuple of image tensors of different sizes: one search over all of them
+        (_beam_search_mixed), the results as one flat list in input order.
+
         return_attn (LSTM-attention heads): [(seq, score, decoder_attn)] per sample, decoder_attn [len, Tk] being what
         forward_decoder returns for that sample alone with viz_attn set (decoder_attn_outputs lays it on the feature grid).
         A batch whose alignment history would exceed _lib.ATTN_MAP_BUDGET bytes is searched in several parts."""
         beam = int(beam_size or self.opt.get("beam_size", 1))
+        if isinstance(input, (list, tuple)):
+            return self._beam_search_mixed(input, beam, return_attn)
         memory, _, _ = self.forward_encoder(input)
         if self.stages["Pred"] == "TFM":
             if return_attn:
@@ -264,6 +269,24 @@ class Model(nn.Module):
         for a in range(0, memory.shape[0], per):
             out += eng.decode_attn_beam_batch(memory[a:a + per].contiguous(), beam, return_alpha=True)
         return out
+
+    def _beam_search_mixed(self, inputs, beam, return_attn=False):
+        """beam_search_batch for a list of image tensors [n_i, C, H_i, W_i] (crops of different sizes, e.g. the buckets of
+        Preprocessor.batch): every tensor is encoded on its own, the memories are packed and ONE search advances the
+        hypotheses of all samples (Engine.decode_beam_batch_ragged).  Returns the flat list of results in input order, each
+        identical to the single-tensor call on its tensor.  Where the engine has no ragged beam search (d_model 512,
+        beam_shared_tile, the LSTM-attention heads) the tensors are searched one after the other by that call."""
+        if len(inputs) == 0:
+            return []
+        eng = self.engine()
+        if self.stages["Pred"] != "TFM" or return_attn or not eng.supports_ragged_beam():
+            out = []
+            for x in inputs:
+                out += self.beam_search_batch(x, beam, return_attn)
+            return out
+        from .engine import pack_memories
+        packed, lengths = pack_memories([self.forward_encoder(x)[0] for x in inputs])
+        return eng.decode_beam_batch_ragged(packed, lengths, beam)
 
     def _group_decode(self, eng, memory, start, is_test=False):
         """pipelined + decode_group > 1: collect the encoder memories of consecutive calls, launch one decode per group.

@@ -203,8 +203,13 @@ struct d2t_ctx {
   // buffer may be rewritten).  Per slot, because a decode still in flight on another chain reads its own slot's tables.
   int* rg_tab[MAXC] = {}; int* rg_host[MAXC] = {}; int rg_cap = 0;
   hipEvent_t rg_ev[MAXC] = {}; bool rg_ev_valid[MAXC] = {};
+  // ragged beam search (d2t_decode_beam_batch_ragged): the per-SAMPLE tables [row0 | len] (brg_cap samples each) and their
+  // pinned host copy.  Its own buffer: a greedy slot's tables may belong to a decode still in flight on another chain.  The
+  // search synchronises before it returns, so both are idle between calls
+  int* brg_tab = nullptr; int* brg_host = nullptr; int brg_cap = 0;
   // ragged decode groups (rtab != nullptr): B is the row total, T is 0 and the batch layout is NOT part of the key -- the loop
   // reads lengths and offsets from the tables at rtab; aux = the slot's bf16-plane offset (a function of the slot's capacity)
+  // ragged beam search: B = N * beam, T = 0, variant = the uniform beam loop's with bit 62 set, rtab = the beam tables
   struct GraphKey { int B, T, steps; const void* tok; const void* logits; const void* ckv; const void* dws; const void* skv; const void* dstate; long long variant;
                     const void* rtab; long long aux; };
   struct GraphEnt { GraphKey key; hipGraphExec_t exec; };

@@ -959,7 +959,8 @@ struct DecRow2P {
   const uint16_t* mem_hi;   // [samples][T][D]
   const uint16_t* mem_lo;   // [samples][T][D]
   // ragged decode group (the RAGGED builds of the greedy kernels): `mem` / `mem_hi` / `mem_lo` are ONE packed [sum B_i T_i][D]
-  // buffer, row b attends over the len[b] memory rows that start at row row0[b] (device tables; r.T, mem_stride, c_row_map unused)
+  // buffer, row b attends over the len[b] memory rows that start at row row0[b] (device tables; r.T, mem_stride, c_row_map unused).
+  // Ragged beam search (RAGGED == 2 of the one-row kernel): the tables are indexed by SAMPLE, row b reads entry r.c_row_map[b]
   const int* row0;
   const int* len;
 };
@@ -972,8 +973,10 @@ struct DecRow2P {
 // MODE 0: the whole row step (greedy).  MODE 1: up to the absorbed queries, which go to q.qp (+ x1 to q.x1).  MODE 2: from
 // the context rows in q.qp on (value projection, output projection, residual) -- the two halves around beam_cross_kernel.
 constexpr int ANC_MAX = 512;  // longest ancestry row held in LDS (DecRowP::anc needs s_Lmax <= ANC_MAX)
-template <int NTH, int MODE, bool BX3 = false, bool RAGGED = false>  // D = 256, 8 heads of 32; BX3 (MODE 0): the cross-attention on
-                                                                     // split-bf16 MFMAs; RAGGED (MODE 0): per-row memory base and length
+// D = 256, 8 heads of 32; BX3 (MODE 0): the cross-attention on split-bf16 MFMAs; RAGGED (MODE 0): memory base and length from the
+// device tables -- 1: indexed by ROW (greedy decode groups), 2: indexed by the row's SAMPLE c_row_map[b] (beam search over crops of
+// different sizes: rows move as hypotheses complete and compact, the row map follows them, the tables stay put)
+template <int NTH, int MODE, bool BX3 = false, int RAGGED = 0>
 __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecRow2P q) {
   constexpr int D = 256, HD = 32, NW = NTH / 64, G = NTH / (D / 4), HPW = 8 / NW;
   const DecRowP& p = q.r;
@@ -1104,9 +1107,13 @@ __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecR
     // that owns no tile of a short row skips the key loop (no block barrier inside) and hands (-inf, 0) to the merge below
     int Tb;
     size_t moff;
-    if constexpr (RAGGED) {
+    if constexpr (RAGGED == 1) {
       Tb = q.len[b];
       moff = (size_t)q.row0[b] * D;
+    } else if constexpr (RAGGED == 2) {  // (the launcher guarantees a row map)
+      const int cb = p.c_row_map[b];
+      Tb = q.len[cb];
+      moff = (size_t)q.row0[cb] * D;
     } else {
       const int cb = p.c_row_map ? p.c_row_map[b] : b;
       Tb = p.T;
@@ -1932,7 +1939,10 @@ hipError_t launch_decoder_row_absorbed(const DecRowP& r, const float* mem, long 
                                        const int* row0, const int* len) {
   const bool ragged = row0 != nullptr;
   if (r.heads != 8 || r.D != 256 || (!ragged && r.T < 1)) return hipErrorInvalidValue;
-  if (ragged && (!len || r.c_row_map || r.anc || r.rows_ptr)) return hipErrorInvalidValue;  // greedy rows only
+  const bool by_sample = ragged && r.c_row_map;  // beam rows: tables per sample, reached through the row map
+  if (ragged && !len) return hipErrorInvalidValue;
+  if (ragged && !by_sample && (r.anc || r.rows_ptr)) return hipErrorInvalidValue;  // tables per row: greedy rows only
+  if (by_sample && !r.one_row) return hipErrorInvalidValue;  // the two-row builds know neither row map nor ancestry
   DecRow2P q{r, mem, mem_stride, wk, wv_t, bv, nullptr, nullptr, mem_hi, mem_lo, row0, len};
   static const int probe = D2T_PROBE_ENV("D2T_ROW_PROBE");  // probe builds only: skip phases (results are garbage by construction)
   q.r.probe = probe;
@@ -1940,9 +1950,12 @@ hipError_t launch_decoder_row_absorbed(const DecRowP& r, const float* mem, long 
   if (r.anc && (!r.one_row || r.s_Lmax > ANC_MAX)) return hipErrorInvalidValue;  // the two-row kernel reads the cache directly
   if (ragged) {  // the ragged builds of the same two forms (no probe-build A/B variants)
     const bool bx3 = mem_hi && mem_lo;
-    if (r.one_row) {
-      if (bx3) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true, true>), dim3(r.M), dim3(256), 0, s, q);
-      else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, false, true>), dim3(r.M), dim3(256), 0, s, q);
+    if (by_sample) {
+      if (bx3) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true, 2>), dim3(r.M), dim3(256), 0, s, q);
+      else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, false, 2>), dim3(r.M), dim3(256), 0, s, q);
+    } else if (r.one_row) {
+      if (bx3) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true, 1>), dim3(r.M), dim3(256), 0, s, q);
+      else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, false, 1>), dim3(r.M), dim3(256), 0, s, q);
     } else if (bx3) hipLaunchKernelGGL(decoder_row2_absorbed_bx3_ragged_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
     else hipLaunchKernelGGL(decoder_row2_absorbed_pf_ragged_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
     return hipGetLastError();

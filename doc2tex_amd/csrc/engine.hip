@@ -464,6 +464,8 @@ void d2t_destroy(d2t_ctx* c) {
   if (c->zero_page) hipFree(c->zero_page);
   if (c->gc_ws) hipFree(c->gc_ws);
   if (c->ev_in) hipEventDestroy(c->ev_in);
+  if (c->brg_tab) hipFree(c->brg_tab);
+  if (c->brg_host) hipHostFree(c->brg_host);
   for (int i = 0; i < d2t_ctx::MAXC; ++i) {
     if (c->rg_tab[i]) hipFree(c->rg_tab[i]);
     if (c->rg_host[i]) hipHostFree(c->rg_host[i]);
@@ -1967,6 +1969,18 @@ int d2t_decode_wait_ticket(d2t_ctx* c, int64_t ticket, d2t_stream stream, int32_
 }
 
 
+// Host arithmetic of the ragged beam search's per-sample tables: sample i's memory occupies the T[i] packed rows from
+// row0[i] = T[0] + .. + T[i-1] on.  Returns the packed row total (no device, no context: also the tests' reference point).
+int64_t d2t_ragged_beam_tables(int32_t N, const int32_t* T, int32_t* row0_out, int32_t* len_out) {
+  int64_t at = 0;
+  for (int i = 0; i < N; ++i) {
+    if (row0_out) row0_out[i] = (int32_t)at;
+    if (len_out) len_out[i] = T[i];
+    at += T[i];
+  }
+  return at;
+}
+
 namespace {
 // forward_beam (tfm.py:145-186) + Beam (tools/beam.py:38-140) for N samples with the bookkeeping ON THE DEVICE (round 4):
 // the hypotheses of all samples are rows of one step loop, every kernel of a step is launched for the full N x beam row slots
@@ -1974,16 +1988,35 @@ namespace {
 // Beam.advance for every sample after the per-sample top-k -- no host round trip in the loop, which is therefore ONE captured
 // graph per (N, T, beam).  The host walks the (parent, token) history back once at the end.  Needs the absorbed row kernel
 // with ancestry rows (no cache copy).  Row results are those of the host-side loop bit for bit (same kernels per row).
+//
+// Ts != nullptr (host [N]): the RAGGED search -- sample i's memory has Ts[i] tokens and `memory` holds the N memories packed
+// ([sum Ts][d]); T is unused.  The only kernel of the loop that knows a memory length is the row kernel's cross-attention, and
+// its per-sample ragged build reads (first packed row, length) of row b's sample map[b] from the context's beam tables
+// (d2t_ctx::brg_tab), so the captured loop depends on N and the beam width alone and every sample's rows compute what its own
+// d2t_decode_beam call computes.  The tables are written on the caller's stream in front of ev_in; the search synchronises
+// before it returns, so no loop in flight ever sees them change.
+constexpr int BEAM_MAX_N = 1024;
 int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_size, int64_t* seq_out, int32_t* len_out,
-                     float* score_out, hipStream_t user) {
+                     float* score_out, hipStream_t user, const int32_t* Ts = nullptr) {
   const d2t_config& g = c->cfg;
   const int S = g.max_seq_len + 1, V = g.vocab, d = g.dec_dim, cap = N * beam_size, Lmax = g.max_seq_len + 2;
-  if (N > 1024) return fail(c, D2T_EINVAL, "batched beam search takes at most 1024 samples per call");
+  if (N > BEAM_MAX_N) return fail(c, D2T_EINVAL, "batched beam search takes at most 1024 samples per call");
   select_chain(c, 0);
   hipStream_t s = c->dstream;
   DecBufs bf;
-  int rc = dec_prepare(c, cap, T, &bf);
+  size_t mem_rows = 0;
+  for (int i = 0; Ts && i < N; ++i) mem_rows += (size_t)Ts[i];
+  int rc = dec_prepare(c, cap, Ts ? 1 : T, &bf, mem_rows);
   if (rc) return rc;
+  if (Ts && !c->brg_cap) {  // [row0 | len] for the largest N, allocated once: the address is part of the graph key
+    if (!c->brg_tab && (rc = dev_alloc(c, reinterpret_cast<void**>(&c->brg_tab), (size_t)2 * BEAM_MAX_N * 4))) return rc;
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->brg_host), (size_t)2 * BEAM_MAX_N * 4, hipHostMallocDefault) != hipSuccess) {
+      c->brg_host = nullptr;
+      return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
+    }
+    memset(c->brg_host, 0, (size_t)2 * BEAM_MAX_N * 4);
+    c->brg_cap = BEAM_MAX_N;
+  }
   // workspace (4-byte words unless noted): logits [cap][V] | topv [cap] | topi [cap] | tok [cap] i64 | scores | map | prev [cap]
   // | seg [N][3] | ctrl [8] | comp_n, fin [N] | comp_t, comp_par, comp_score [N][beam] | hist_par, hist_tok [S][cap] | anc [2][cap][Lmax]
   size_t w = 0;
@@ -2019,10 +2052,24 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
   const int* rows_ptr = b.ctrl + 1;
   const int* stop = b.ctrl + 2;
   if ((rc = ensure_host_beam(c, res_words * 4))) return rc;
+  RaggedDev rgd{};
+  if (Ts) {  // (the previous search has synchronised: neither copy of the tables is in use)
+    d2t_ragged_beam_tables(N, Ts, c->brg_host, c->brg_host + c->brg_cap);
+    HIPCHK(c, hipMemcpyAsync(c->brg_tab, c->brg_host, (size_t)2 * c->brg_cap * 4, hipMemcpyHostToDevice, user));
+    rgd.row0 = c->brg_tab; rgd.len = c->brg_tab + c->brg_cap;
+    rgd.plane_elems = ((c->ckv2_cap[0] - 64) / 8) & ~(size_t)255;
+  }
   HIPCHK(c, hipEventRecord(c->ev_in, user));
   HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
   c->ckv = c->ckv2[0];  // the internal stream is in order, so earlier decodes are done with the slot
-  HIPCHK(c, cross_kv(c, s, memory, N, T));
+  if (Ts) {  // the packed rows once, their bf16 planes at the slot's capacity-fixed offsets (as a ragged greedy group)
+    const size_t n = mem_rows * d;
+    HIPCHK(c, hipMemcpyAsync(c->ckv, memory, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    uint16_t* hi = reinterpret_cast<uint16_t*>(c->ckv + rgd.plane_elems);
+    HIPCHK(c, launch_split_bf16(memory, hi, hi + rgd.plane_elems, n, s));
+  } else {
+    HIPCHK(c, cross_kv(c, s, memory, N, T));
+  }
   c->skv_cur = c->skv;
   auto enqueue_loop = [&](hipStream_t st) -> hipError_t {
     hipError_t e;
@@ -2032,7 +2079,8 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
     for (int step = 0; step < S; ++step) {
       LTRY(launch_beam_ancestry(d_anc[(step + 1) & 1], d_anc[step & 1], b.prev, cap, Lmax, b.ctrl, c->dstate, st, rows_ptr, stop));
       LTRY(launch_embed_tokens(c->word_embed, c->word_pe, b.tok, c->dstate, bf.x, cap, d, st, rows_ptr, stop));
-      LTRY(decode_step(c, st, bf, cap, T, cap, d_logits, V, 0, N, b.map, stop, beam_size, b.seg, d_anc[step & 1], rows_ptr));
+      LTRY(decode_step(c, st, bf, cap, Ts ? 1 : T, cap, d_logits, V, 0, N, b.map, stop, beam_size, b.seg, d_anc[step & 1], rows_ptr,
+                       Ts ? &rgd : nullptr));
       LTRY(launch_beam_topk_batch(d_logits, b.scores, b.seg, N, V, beam_size, base + o_topv, reinterpret_cast<int*>(base + o_topi), st,
                                   c->dstate, stop));
       LTRY(launch_beam_dev_advance(b, st));
@@ -2046,6 +2094,9 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
     memset(&k, 0, sizeof k);
     k.B = cap; k.T = T; k.steps = S; k.tok = nullptr; k.logits = base; k.ckv = c->ckv; k.dws = c->dws; k.skv = c->skv; k.dstate = c->dstate;
     k.variant = 3 | ((long long)N << 8) | ((long long)beam_size << 40);  // (bits 0-1 = 3: the device-side beam loop)
+    if (Ts) {  // N, beam and the "ragged" bit; no memory length
+      k.T = 0; k.variant |= 1LL << 62; k.rtab = c->brg_tab; k.aux = (long long)rgd.plane_elems;
+    }
     hipGraphExec_t exec = nullptr;
     if ((rc = cached_graph(c, s, k, "beam", enqueue_loop, &exec))) return rc;
     HIPCHK(c, hipGraphLaunch(exec, s));
@@ -2096,6 +2147,34 @@ int beam_device_impl(d2t_ctx* c, const float* memory, int N, int T, int beam_siz
   return D2T_OK;
 }
 }  // namespace
+
+// 1: d2t_decode_beam_batch_ragged serves this context (the device-side beam loop: TFM decoder, absorbed cross-attention, one
+// row per block with ancestry rows); 0: it refuses with D2T_ESTATE
+int32_t d2t_decode_supports_ragged_beam(const d2t_ctx* c) {
+  return c && c->cfg.decoder == D2T_DEC_TFM && c->dec_absorbed && !c->beam_shared_tile && c->cfg.max_seq_len + 2 <= 512 ? 1 : 0;
+}
+
+int d2t_decode_beam_batch_ragged(d2t_ctx* c, const float* memory, int32_t N, const int32_t* T, int32_t beam_size, int64_t* seq_out,
+                                 int32_t* len_out, float* score_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  // d2t_decode_beam_batch for N samples whose memories have DIFFERENT lengths, packed in `memory` -- one step loop, one captured
+  // graph per (N, beam).  Everything is checked before anything is enqueued; the context stays usable after a refusal.
+  if (!c || !memory || !T || !seq_out || !len_out || !score_out) return fail(c, D2T_EINVAL, "bad argument");
+  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
+  if (c->cfg.decoder != D2T_DEC_TFM) return fail(c, D2T_ESTATE, "beam search is implemented for the TFM decoder only");
+  if (N < 1 || N > BEAM_MAX_N) return fail(c, D2T_EINVAL, "ragged beam search takes 1 to %d samples per call, got %d", BEAM_MAX_N, N);
+  if (beam_size < 1 || beam_size > 16) return fail(c, D2T_EINVAL, "beam_size must be in [1,16]");
+  for (int i = 0; i < N; ++i)
+    if (T[i] < 1 || T[i] > memory_cap(c))
+      return fail(c, D2T_EINVAL, "sample %d has memory length %d, supported are 1 to %d", i, T[i], memory_cap(c));
+  if ((long long)beam_size * c->cfg.vocab > 16 * 4096) return fail(c, D2T_EINVAL, "beam_size * vocab too large");
+  if (!d2t_decode_supports_ragged_beam(c))
+    return fail(c, D2T_ESTATE, "ragged beam search needs the device-side beam loop (d_model 256 with 8 heads on the absorbed "
+                               "cross-attention, no beam_shared_tile, max_seq_len + 2 <= 512): call d2t_decode_beam_batch once per "
+                               "memory length instead");
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  return beam_device_impl(c, memory, N, 0, beam_size, seq_out, len_out, score_out, (hipStream_t)stream, T);
+}
 
 int d2t_decode_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out, int32_t* len_out,
                     float* score_out, d2t_stream stream) {
@@ -2742,6 +2821,65 @@ int d2t_op_decoder_row_ragged(int32_t kind, const float* qkv, const float* xres,
     e = launch_split_bf16(mem, hi, lo, memn, s);
   }
   if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, 0, ca_in_w + dd, wv_t, ca_in_b + 2 * D, s, hi, lo, tab, tab + M);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(buf);
+  return e == hipErrorInvalidValue ? D2T_EINVAL : (e == hipSuccess && e2 == hipSuccess) ? D2T_OK : D2T_EHIP;
+}
+
+// The per-sample ragged builds of the one-row absorbed kernel (ragged beam search; kind 2 = fp32 MFMA, 4 = split-bf16): mem is
+// ONE packed [mem_rows][256] buffer, row b attends over the len[row_map[b]] rows from row0[row_map[b]] on.  row0 / len: host
+// arrays [samples]; row_map (required) and anc (optional, the hypotheses' ancestry rows): device arrays as d2t_op_decoder_row.
+int d2t_op_decoder_row_ragged_beam(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                                   const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                                   const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps,
+                                   float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
+                                   int32_t samples, const int32_t* row0_host, const int32_t* len_host, const int32_t* row_map,
+                                   const int32_t* anc, int32_t anc_stride, d2t_stream stream) {
+  if (!qkv || !xres || !sk || !sv || !mem || !ca_in_w || !ca_in_b || !sa_out_w || !sa_out_b || !ca_out_w || !ca_out_b ||
+      !ln1_g || !ln1_b || !y2 || !step || !row0_host || !len_host || !row_map)
+    return D2T_EINVAL;
+  if ((kind != 2 && kind != 4) || M < 1 || M > 65535 || rows < M || samples < 1 || samples > 65535 || mem_rows < 1 ||
+      mem_rows > (1 << 22) || Lmax < 1 || Lmax > 4096)
+    return D2T_EINVAL;
+  for (int i = 0; i < samples; ++i)
+    if (row0_host[i] < 0 || len_host[i] < 1 || len_host[i] > 4096 || (long long)row0_host[i] + len_host[i] > mem_rows) return D2T_EINVAL;
+  if (anc && (Lmax > 512 || anc_stride < Lmax)) return D2T_EINVAL;
+  constexpr int D = 256;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> h;
+  if (!fetch_ints(s, step, 1, &h)) return D2T_EHIP;
+  const int t = h[0];
+  if (t < 0 || t >= Lmax) return D2T_EINVAL;
+  if (!fetch_ints(s, row_map, M, &h)) return D2T_EHIP;
+  for (int v : h) if (v < 0 || v >= samples) return D2T_EINVAL;
+  if (anc) {
+    if (!fetch_ints(s, anc, (size_t)M * anc_stride, &h)) return D2T_EHIP;
+    for (int b = 0; b < M; ++b)
+      for (int j = 0; j < t; ++j)
+        if (h[(size_t)b * anc_stride + j] < 0 || h[(size_t)b * anc_stride + j] >= rows) return D2T_EINVAL;
+  }
+  const size_t dd = (size_t)D * D, memn = (size_t)mem_rows * D;
+  const size_t extra = kind == 4 ? memn * 4 : 0;
+  RowOpTmp tmp;
+  DecRowP r;
+  hipError_t e = hipSuccess;
+  if (int rc = row_op_setup(qkv, xres, sk, sv, ca_in_w, ca_in_b, sa_out_w, sa_out_b, ca_out_w, ca_out_b, ln1_g, ln1_b, eps, y2, step,
+                            M, D, Lmax, extra + (size_t)2 * samples * 4, s, &tmp, &r, &e))
+    return rc;
+  float *const buf = tmp.buf, *const wv_t = tmp.wv_t, *const ext = tmp.ext;
+  int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ext) + extra);  // [row0 | len] behind the bf16 planes
+  if (e == hipSuccess) e = hipMemcpyAsync(tab, row0_host, (size_t)samples * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tab + samples, len_host, (size_t)samples * 4, hipMemcpyHostToDevice, s);
+  r.T = 1;  // (unused by the ragged builds)
+  r.one_row = true;
+  r.c_row_map = row_map;
+  r.anc = anc; r.anc_stride = anc_stride;
+  uint16_t *hi = nullptr, *lo = nullptr;
+  if (e == hipSuccess && kind == 4) {
+    hi = reinterpret_cast<uint16_t*>(ext); lo = hi + memn;
+    e = launch_split_bf16(mem, hi, lo, memn, s);
+  }
+  if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, 0, ca_in_w + dd, wv_t, ca_in_b + 2 * D, s, hi, lo, tab, tab + samples);
   const hipError_t e2 = hipStreamSynchronize(s);
   hipFree(buf);
   return e == hipErrorInvalidValue ? D2T_EINVAL : (e == hipSuccess && e2 == hipSuccess) ? D2T_OK : D2T_EHIP;

@@ -270,7 +270,9 @@ hipError_t launch_decoder_row(const DecRowP& p, hipStream_t s);
 // mem_hi / mem_lo (optional, greedy two-row kernel only): the same rows as bf16 hi / lo planes (launch_split_bf16) -> the
 // cross-attention runs on split-bf16 MFMAs
 // row0 / len (optional, greedy rows only; device arrays [M]): the RAGGED builds -- mem (and the planes) are one packed
-// [rows][256] buffer and row b attends over the len[b] >= 1 rows from row0[b] on; p.T, mem_stride and c_row_map are unused
+// [rows][256] buffer and row b attends over the len[b] >= 1 rows from row0[b] on; p.T, mem_stride and c_row_map are unused.
+// With p.c_row_map (one-row kernel only: ragged beam search) the tables are indexed by SAMPLE: row b reads entry
+// c_row_map[b], and p.anc / p.rows_ptr work as in the uniform build
 hipError_t launch_decoder_row_absorbed(const DecRowP& p, const float* mem, long long mem_stride, const float* wk,
                                        const float* wv_t, const float* bv, hipStream_t s, const uint16_t* mem_hi = nullptr,
                                        const uint16_t* mem_lo = nullptr, const int* row0 = nullptr, const int* len = nullptr);

@@ -127,6 +127,33 @@ def ragged_tables(layout):
     return {"row0": row0, "len": length, "row_batch": row_batch, "batch_rows": batch_rows, "rows": len(row0), "mem_rows": base}
 
 
+def ragged_beam_tables(lengths):
+    """The per-SAMPLE tables of a ragged beam search, as the engine writes them (d2t_ragged_beam_tables): sample i's memory
+    occupies the lengths[i] rows from row0[i] on of the packed [sum lengths][d] buffer -> dict(row0, len, mem_rows).  Pure
+    host arithmetic (lists of ints)."""
+    row0, base = [], 0
+    for i, T in enumerate(lengths):
+        T = int(T)
+        if T < 1:
+            raise ValueError(f"sample {i} has memory length {T}")
+        row0.append(base)
+        base += T
+    return {"row0": row0, "len": [int(T) for T in lengths], "mem_rows": base}
+
+
+def pack_memories(memories):
+    """Encoder memories [n_i, T_i, d] of different lengths -> (packed [sum n_i * T_i, d], lengths): the samples' rows one
+    behind the other in input order, lengths[j] the memory length of flat sample j."""
+    d = memories[0].shape[-1]
+    lengths = []
+    for m in memories:
+        if m.dim() != 3 or m.shape[-1] != d:
+            raise ValueError(f"expected memories [n, T, {d}], got {tuple(m.shape)}")
+        lengths += [int(m.shape[1])] * int(m.shape[0])
+    packed = torch.cat([m.float().reshape(-1, d) for m in memories], 0).contiguous()
+    return packed, lengths
+
+
 class Engine:
     def __init__(self, opt, device=None):
         self.lib = _lib.require_device()
@@ -596,6 +623,28 @@ class Engine:
         self._check(self.lib.d2t_decode_beam_batch(self.ctx, _lib.ptr(memory), N, memory.shape[1], int(beam_size), seq, n,
                                                    score, _lib.stream_of(memory)), "decode_beam_batch")
         return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), float(score[i])) for i in range(N)]
+
+    def decode_beam_batch_ragged(self, packed, lengths, beam_size):
+        """decode_beam_batch for samples whose memories have different lengths: packed [sum lengths, d] holds sample i's
+        lengths[i] rows behind sample i-1's.  One shared step loop (one captured graph per sample count and beam width,
+        whatever the lengths): [(LongTensor [1,len], score)] per sample, each equal to decode_beam on that sample alone."""
+        packed = packed.float().contiguous()
+        lengths = [int(T) for T in lengths]
+        N, S = len(lengths), self.cfg.max_seq_len + 1
+        if packed.dim() != 2 or packed.shape[0] != sum(lengths):
+            raise ValueError(f"packed memory {tuple(packed.shape)} does not hold the {sum(lengths)} rows of `lengths`")
+        seq = (C.c_int64 * max(1, N * S))()
+        n = (C.c_int32 * max(1, N))()
+        score = (C.c_float * max(1, N))()
+        Ts = (C.c_int32 * max(1, N))(*lengths)
+        self._check(self.lib.d2t_decode_beam_batch_ragged(self.ctx, _lib.ptr(packed), N, Ts, int(beam_size), seq, n, score,
+                                                          _lib.stream_of(packed)), "decode_beam_batch_ragged")
+        return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), float(score[i])) for i in range(N)]
+
+    def supports_ragged_beam(self):
+        """Whether decode_beam_batch_ragged serves this context (the device-side beam loop: TFM head, d_model 256 on the
+        absorbed cross-attention, no beam_shared_tile); the context itself answers, once the weights are finalized."""
+        return bool(self.lib.d2t_decode_supports_ragged_beam(self.ctx))
 
     def decode_beam(self, memory, beam_size):
         memory = memory.float().contiguous()

@@ -26,7 +26,7 @@
  *        <- Model.forward under module.train() and loss.backward(): forward_step / train_one_step
  *           engine/training.py:76-164 (tfm.py:103-118, seq2seq.py:224-331 with is_train)
  *   d2t_decode_greedy_async / d2t_decode_greedy_submit / d2t_decode_attn_greedy_submit / d2t_decode_wait,
- *   d2t_set_reserved_blocks / d2t_set_decode_chains, d2t_decode_beam_batch / d2t_decode_attn_beam_batch
+ *   d2t_set_reserved_blocks / d2t_set_decode_chains, d2t_decode_beam_batch[_ragged] / d2t_decode_attn_beam_batch
  *        -- serving extensions without a reference counterpart (cross-batch pipelining, batched beam search);
  *           their results equal the corresponding reference-shaped calls bit for bit
  *   d2t_op_*  -- single-kernel entry points used by the parity tests.
@@ -315,6 +315,24 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* ctx, const float* memory, int32_t 
 int d2t_decode_beam_batch(d2t_ctx* ctx, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
                           int32_t* len_out, float* score_out, d2t_stream stream);
 
+/* d2t_decode_beam_batch for N samples whose memories have DIFFERENT lengths (crops of different sizes), in one step loop:
+ * memory_packed_dev [T[0] + .. + T[N-1]][d], sample i's rows behind sample i-1's; T: HOST array [N]; outputs as
+ * d2t_decode_beam_batch.  Every sample's sequence, length and score are those of its own d2t_decode_beam call, bit for bit.
+ * The captured loop depends on N and beam_size alone: lengths and offsets are read from engine-owned per-sample device
+ * tables (filled on `stream` by an asynchronous copy in front of the loop), so any mix of lengths with the same N and beam
+ * replays one graph.  Refused before anything is enqueued (D2T_EINVAL unless stated): N < 1 or N > 1024, a length < 1 or
+ * > 4096, beam_size outside [1, 16], beam_size * vocab over d2t_decode_beam_batch's cap, a pointer of another device; a
+ * context without the TFM decoder (D2T_ESTATE); a context whose beam search does not run on the device -- d_model 512,
+ * d2t_set_beam_shared_tile(1), max_seq_len + 2 > 512 (D2T_ESTATE: call d2t_decode_beam_batch once per length). */
+int d2t_decode_beam_batch_ragged(d2t_ctx* ctx, const float* memory_packed_dev, int32_t N, const int32_t* T, int32_t beam_size,
+                                 int64_t* seq_out, int32_t* len_out, float* score_out, d2t_stream stream);
+/* 1 if d2t_decode_beam_batch_ragged serves this context, 0 if it refuses with D2T_ESTATE.  Valid once the weights are
+ * finalized; follows d2t_set_beam_shared_tile. */
+int32_t d2t_decode_supports_ragged_beam(const d2t_ctx* ctx);
+/* The table arithmetic of d2t_decode_beam_batch_ragged (host only, no context): row0_out[i] = T[0] + .. + T[i-1],
+ * len_out[i] = T[i] (either may be NULL); returns the packed row total. */
+int64_t d2t_ragged_beam_tables(int32_t N, const int32_t* T, int32_t* row0_out, int32_t* len_out);
+
 /* LSTM-attention beam search for ONE sample (reference: Attention.forward_beam, prediction_head/seq2seq.py:83-222;
  * AttentionV2.forward_beam, seq2seq_v2.py:12-174 -- what config/test.yaml runs with beam_size 5 / 10).  Coverage
  * attention only.  memory [1][T][256]; seq_out (host, >= batch_max_length + 1 entries) receives the token ids without
@@ -522,6 +540,17 @@ int d2t_op_decoder_row_ragged(int32_t kind, const float* qkv, const float* xres,
                               const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps,
                               float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
                               const int32_t* row0, const int32_t* len, d2t_stream stream);
+/* The per-sample ragged builds of the one-row absorbed kernel (ragged beam search; kind 2 = fp32 MFMA, 4 = split-bf16):
+ * mem is ONE packed [mem_rows][256] buffer, row b attends over the len[row_map[b]] rows from row row0[row_map[b]] on.
+ * row0 / len: HOST arrays [samples] (1 <= len[i] <= 4096, row0[i] + len[i] <= mem_rows); row_map (required, device [M],
+ * values < samples); anc (optional, Lmax <= 512) as d2t_op_decoder_row.  A sample's rows equal d2t_op_decoder_row's on
+ * that sample's memory alone bit for bit. */
+int d2t_op_decoder_row_ragged_beam(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                                   const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                                   const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps,
+                                   float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
+                                   int32_t samples, const int32_t* row0, const int32_t* len, const int32_t* row_map,
+                                   const int32_t* anc, int32_t anc_stride, d2t_stream stream);
 /* One greedy step (launch_argmax_embed) at t = *step < S: tokens[b][t] = first maximum of logits[b][t][:V] (logits [B][S][V],
  * tokens [B][S]); end-of-sequence bookkeeping in ended [B], end_count, steps_done; *step becomes t + 1, done_count (zero
  * before the first launch) is back at zero afterwards; x [B][d] (optional) = emb[token] * sqrt(d) + pe[t + 1] (pe [S + 1][d]).

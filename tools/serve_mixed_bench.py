@@ -8,6 +8,11 @@ set and consecutive forwards differ in row count and memory length.
   --mixed 1   Model.decode_group_mixed: batches of any size share a loop until the group holds --group batches or
               --group-rows rows.
 
+  --beam K    beam search (width K) instead of greedy decoding, synchronous as Model.beam_search_batch is:
+              --mixed 0   one beam_search_batch call per size bucket (three searches per page set, a captured loop per size);
+              --mixed 1   the list form: the buckets are encoded one by one, their memories packed, ONE search per page set
+                          (d2t_decode_beam_batch_ragged).
+
 Prints one JSON line: formulas/s end to end (uint8 pages -> LaTeX strings)."""
 import argparse
 import json
@@ -40,6 +45,7 @@ def main():
     ap.add_argument("--group-rows", type=int, default=384, help="--mixed 1: row budget of a group")
     ap.add_argument("--chains", type=int, default=3)
     ap.add_argument("--page-sets", type=int, default=4, help="distinct page sets cycled through")
+    ap.add_argument("--beam", type=int, default=0, help="beam width; 0 = greedy decoding through the decode groups")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cfg = synth.make_config("C4", device=str(dev))
@@ -110,6 +116,21 @@ def main():
         for t in tensors:
             buckets.setdefault(t._base.data_ptr(), t._base)
         assert len(buckets) == 3 and {tuple(x.shape[2:]) for x in buckets.values()} == BUCKETS, [x.shape for x in buckets.values()]
+        if args.beam:
+            with torch.no_grad():
+                if args.mixed:
+                    found = model.beam_search_batch(list(buckets.values()), args.beam)
+                else:
+                    found = [r for x in buckets.values() for r in model.beam_search_batch(x, args.beam)]
+            tokens = torch.zeros((len(found), L), dtype=torch.int64)  # PAD behind every hypothesis
+            for r, (seq, _) in enumerate(found):
+                tokens[r, :seq.shape[1]] = seq[0]
+            t = time.perf_counter()
+            latex = dec.to_latex(tokens, "word", postprocess=True)
+            state["t_post"] += time.perf_counter() - t
+            state["done"] += len(latex)
+            state["sample"] = latex[0]
+            return
         for x in buckets.values():
             with torch.no_grad():
                 tokens, _, extra = model(x, go[:x.shape[0]], is_train=False, is_test=False)
@@ -133,7 +154,7 @@ def main():
     assert state["done"] == 3 * n * args.steps, (state["done"], 3 * n * args.steps)
     print(json.dumps({"metric": "formulas/s end to end on mixed-size pages (uint8 pages -> LaTeX strings)",
                       "value": round(state["done"] / el, 1), "unit": "formulas/s", "mixed": args.mixed, "steps": args.steps,
-                      "per_size": n, "group": args.group, "ms_per_page_set": round(el / args.steps * 1e3, 2),
+                      "per_size": n, "group": args.group, "beam": args.beam, "ms_per_page_set": round(el / args.steps * 1e3, 2),
                       "postprocess_ms_per_page_set": round(state["t_post"] / args.steps * 1e3, 2),
                       "sizes": sorted(BUCKETS), "sample_latex_chars": len(state["sample"])}))
 
