@@ -1,4 +1,4 @@
-// Shared between engine.hip (inference) and train.hip (training step): the context struct, packed-weight
+// Shared between the engine*.hip files (inference) and train.hip (training step): the context struct, packed-weight
 // records and small host helpers.  Internal to libd2t; the public surface is include/d2t.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -153,7 +153,6 @@ struct d2t_ctx {
   // decoder state
   static constexpr int MAXC = 4;                                     // decode chains / memory slots at most
   float* ckv2[MAXC] = {}; size_t ckv2_cap[MAXC] = {};                // memory copy (or projected cross K/V) per slot: a decode reads one
-  float* ckv = nullptr;                                              // the slot the current decode reads
   // d_model 256 / 8 heads: the decode attends over the encoder memory itself (absorbed K / V projections); the slots then
   // hold a COPY OF THE MEMORY [B][T][d] instead of the projected K / V of every layer [layers*2][B][heads][T][hd]
   bool dec_absorbed = false;
@@ -167,9 +166,7 @@ struct d2t_ctx {
   hipEvent_t ticket_ev[TICKET_RING] = {};
   int* h_steps = nullptr;               // pinned [TICKET_RING][64]: per-batch step counts of early-exit decodes
   int ticket_batches[TICKET_RING] = {};  // batches of that decode's group (< 0: not an early-exit decode)
-  float* skv = nullptr; size_t skv_cap = 0;
-  float* skv_alt = nullptr; size_t skv_alt_cap = 0;  // beam: reorder target (ping-pong with skv_cur)
-  float* skv_cur = nullptr;                          // cache decode_step reads / appends
+  float* skv_alt = nullptr; size_t skv_alt_cap = 0;  // host-side beam loop: reorder target (ping-pong with chain 0's cache)
   float* beam_ws = nullptr; size_t beam_ws_cap = 0;  // beam logits / scores / tokens / top-k
   char* h_beam = nullptr; size_t h_beam_cap = 0;     // pinned host staging of the beam searches (ensure_host_beam)
   float* beam_hist = nullptr; size_t beam_hist_cap = 0;  // LSTM beam search with maps: alignment history + chosen paths
@@ -180,23 +177,24 @@ struct d2t_ctx {
   int no_shortcut_fusion = 0;  // debug / A-B: 1 = the 1x1 shortcuts as their own kernels (d2t_set_conv_fusion)
   int no_pool_fusion = 0;  // debug / A-B: 1 = the two 2x2 max-pools as their own kernels (d2t_set_conv_fusion)
   float* beam_qp = nullptr; size_t beam_qp_cap = 0;  // beam, absorbed cross-attention: q' / context rows + LN1 rows (decode.hip)
-  float* dws = nullptr; size_t dws_cap = 0;
-  int* dstate = nullptr;   // TFM: [0]=step [1]=end_count [2]=steps_done [3..]=ended[B]
-                           // LSTM-attention heads: [0..1]=exit word (AttnDecP::exit_state) [2]=steps [3]=pad [4..]=end_step[B]
-  size_t dstate_cap = 0;
   int* h_pinned = nullptr;
   void* zero_page = nullptr;  // 256 zero bytes: out-of-image taps of the split-bf16 convolution
-  hipStream_t dstream = nullptr;
-  // Second decode chain (own stream, self-attention cache, workspace, state): with two chains the decode
-  // loops of consecutive async batches run side by side.  The members above are the ACTIVE chain; the
-  // inactive ones are parked here (select_chain swaps).
-  struct Chain { hipStream_t stream = nullptr; float* skv = nullptr; size_t skv_cap = 0; float* dws = nullptr;
-                 size_t dws_cap = 0; int* dstate = nullptr; size_t dstate_cap = 0;
-                 float* out = nullptr; size_t out_cap = 0; } chains[MAXC];  // chains[active_chain] is stale: its state lives in the members above
-  // async decodes write tokens / logits here (fixed addresses, so one captured graph per chain serves every
-  // caller buffer) and copy them out afterwards
-  float* dout = nullptr; size_t dout_cap = 0;
-  int active_chain = 0, n_chains = 1;
+  // Decode chains: each owns its stream, self-attention cache, workspace, state block and output staging, so that with two
+  // or more the decode loops of consecutive async batches run side by side.  Chain i keeps its stream and buffers between
+  // calls (their addresses are part of GraphKey); a decode entry picks its chain once and passes it down.  Everything
+  // synchronous and every beam search runs on chain 0.
+  struct Chain {
+    hipStream_t stream = nullptr;
+    float* skv = nullptr; size_t skv_cap = 0;  // self-attention cache
+    float* dws = nullptr; size_t dws_cap = 0;  // step workspace (LSTM-attention heads: the key projection)
+    int* dstate = nullptr;   // TFM: [0]=step [1]=end_count [2]=steps_done [3..]=ended[B]
+                             // LSTM-attention heads: [0..1]=exit word (AttnDecP::exit_state) [2]=steps [3]=pad [4..]=end_step[B]
+    size_t dstate_cap = 0;
+    // decodes write logits | tokens here (fixed addresses, so one captured graph per chain serves every caller buffer) and
+    // copy them out afterwards
+    float* out = nullptr; size_t out_cap = 0;
+  } chains[MAXC];
+  int n_chains = 1;
   hipEvent_t ev_in = nullptr;
   // ragged decode groups: per memory slot the device tables [row0 | len | row_batch] (rg_cap rows each) | batch_rows [64] |
   // n_batches, and the pinned host buffer they are copied from on the caller's stream (rg_ev: that copy has run, the host

@@ -1,0 +1,336 @@
+// libd2t engine, LSTM-attention heads: the greedy decode (synchronous and pipelined) and the beam search of the C-ABI.
+// Host code only: the kernels are recurrent.hip's.
+#include "engine_impl.h"
+
+extern "C" {
+
+namespace {
+// The fields of the LSTM-attention decoder launch that every caller sets alike: memory [*][T][H], its key projection kp,
+// the weights.  The caller adds its outputs, row count, step count and (beam search) the step-mode fields.
+AttnDecP attn_dec_params(const d2t_ctx* c, const float* memory, int T, const float* kp) {
+  const d2t_config& g = c->cfg;
+  AttnDecP p{};
+  p.mem = memory; p.T = T; p.D = g.attn_hidden; p.key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  p.init_mode = !g.attn_enc_init ? 0 : (g.attn_keys == D2T_ATTN_KEYS_ALL_INIT_MEAN ? 1 : 2);
+  p.kp = kp; p.wq_t = c->attn.wq_t; p.bq = c->attn.bq; p.wloc = c->attn.wloc; p.bloc = c->attn.bloc;
+  p.taps = c->attn.taps; p.wscore = c->attn.wscore; p.bscore = c->attn.bscore;
+  p.wx_t = c->attn.wx_t; p.bx = c->attn.bx; p.wg_t = c->attn.wg_t; p.bg = c->attn.bg;
+  p.wih_t = c->attn.wih_t; p.bih = c->attn.bih; p.wic_t = c->attn.wic_t; p.bic = c->attn.bic;
+  p.emb = c->attn.emb; p.tokgate = c->attn.tokgate;
+  p.V = g.vocab; p.H = g.attn_hidden; p.E = g.attn_hidden; p.coverage = g.attn_coverage; p.end_token = 1;  // attn_converter.py:8
+  return p;
+}
+// What every greedy call of the LSTM-attention heads refuses, before anything is enqueued.
+int attn_greedy_check(d2t_ctx* c, const float* memory, int B, int T, const int64_t* tokens, const float* probs) {
+  if (!c || !memory || !tokens || !probs || B < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
+  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
+  const d2t_config& g = c->cfg;
+  if (g.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "context was not created with the Attn decoder");
+  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  if (T - key_off < 1 || T - key_off > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
+  if (g.vocab > D2T_ATTN_MAX_CLASSES) return fail(c, D2T_EINVAL, "Attn decoder supports num_class <= %d, got %d", D2T_ATTN_MAX_CLASSES, g.vocab);
+  return D2T_OK;
+}
+
+// Greedy decode of the LSTM-attention heads.  Synchronous (async == false): everything on the caller's stream, in chain
+// 0's workspace.  Asynchronous: the chains take turns; the key projection, the one-launch step loop and the finalize
+// kernel run on the chain's stream, ordered behind the caller's stream by an event, and the call returns once they are
+// enqueued (no host synchronisation).  A chain's stream is in order, so its workspace (key projection, state block) is
+// never rewritten under a loop that still reads it.
+// is_test: the reference's early exit is taken inside the kernel (AttnDecP::exit_state) and the finalize kernel zeroes
+// what lies behind it and leaves the step count in the state block: one path for the rule, synchronous or not.
+int attn_greedy_impl(d2t_ctx* c, const float* memory, int B, int T, int is_test, int64_t* tokens, float* probs, float* alpha,
+                     int* steps_out, hipStream_t user, bool async) {
+  const d2t_config& g = c->cfg;
+  const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab;
+  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  const int chain = async ? (int)(c->decode_seq++ % (unsigned)c->n_chains) : 0;
+  d2t_ctx::Chain& ch = c->chains[chain];
+  hipStream_t s = async ? ch.stream : user;
+  int rc;
+  // workspace of the chain: key_proj(memory) [B*T][H]; state: exit word | steps | pad (16 bytes) | end_step [B]
+  if ((rc = ensure(c, &ch.dws, &ch.dws_cap, ((size_t)B * T * Hh + 16) * 4))) return rc;
+  if ((rc = ensure(c, &ch.dstate, &ch.dstate_cap, ((size_t)B + 4) * 4))) return rc;
+  float* kp = ch.dws;
+  unsigned long long* exit_state = reinterpret_cast<unsigned long long*>(ch.dstate);
+  int* steps_dev = ch.dstate + 2;
+  int* end_step = ch.dstate + 4;
+  if (async) {  // the chain's stream starts behind the caller's work (the memory)
+    HIPCHK(c, hipEventRecord(c->ev_in, user));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
+  } else if (c->ev_done_valid[chain]) {  // an asynchronous decode of this chain may still read the workspace
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_done[chain], 0));
+  }
+  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, B * T, ACT_NONE));
+  HIPCHK(c, hipMemsetAsync(ch.dstate, 0, 16, s));
+  HIPCHK(c, hipMemsetAsync(end_step, 0xFF, (size_t)B * 4, s));  // -1 = never emitted [s]
+  AttnDecP p = attn_dec_params(c, memory, T, kp);
+  p.probs = probs; p.tokens = tokens; p.end_step = end_step;
+  p.sv_alpha = alpha;  // optional [B][S][Tk]: the alignment of every step (viz_attn, seq2seq.py:267-272,300-301)
+  p.B = B; p.S = S;
+  p.exit_state = is_test ? exit_state : nullptr;
+  HIPCHK(c, launch_attn_decode(p, s));
+  // reference: break after the first step at which every row has emitted [s]; its pre-zeroed outputs keep zeros behind it
+  if (is_test) HIPCHK(c, launch_attn_decode_finalize(exit_state, steps_dev, B, S, V, T - key_off, tokens, probs, alpha, s));
+  int steps = S;
+  if (async) {
+    HIPCHK(c, hipEventRecord(c->ev_done[chain], s));
+    c->ev_done_valid[chain] = true;
+    if ((rc = issue_ticket(c, s, is_test ? 1 : -S, steps_dev))) return rc;  // the ticket counter and ring of the TFM decodes
+  } else if (is_test) {
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned, steps_dev, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    steps = c->h_pinned[0];
+  }
+  if (steps_out) *steps_out = steps;
+  return D2T_OK;
+}
+}  // namespace
+
+int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                           float* probs, int32_t* steps_out, d2t_stream stream) {
+  return d2t_decode_attn_greedy_alpha(c, memory, B, T, is_test, tokens, probs, nullptr, steps_out, stream);
+}
+
+int d2t_decode_attn_greedy_alpha(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                                 float* probs, float* alpha, int32_t* steps_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  if (!steps_out) return fail(c, D2T_EINVAL, "bad argument");
+  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
+  return attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, steps_out, (hipStream_t)stream, false);
+}
+
+int d2t_decode_attn_greedy_submit(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                                  float* probs, float* alpha, d2t_stream stream, int64_t* ticket_out) {
+  DevGuard dg_(c);
+  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, probs, "probs")) return rc;
+  const int rc = attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, nullptr, (hipStream_t)stream, true);
+  if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
+  return rc;
+}
+
+int d2t_decode_attn_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out, int32_t* len_out,
+                         float* score_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  // Attention.forward_beam (prediction_head/seq2seq.py:83-222) / AttentionV2.forward_beam (seq2seq_v2.py:12-174) for
+  // one sample: the batched search with N = 1.
+  return d2t_decode_attn_beam_batch(c, memory, 1, T, beam_size, seq_out, len_out, score_out, stream);
+}
+
+int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
+                               int32_t* len_out, float* score_out, d2t_stream stream) {
+  return d2t_decode_attn_beam_batch_alpha(c, memory, N, T, beam_size, seq_out, len_out, score_out, nullptr, stream);
+}
+
+int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
+                                     int32_t* len_out, float* score_out, float* alpha_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  // Attention / AttentionV2.forward_beam for N samples in one step loop: rows = live hypotheses of all samples, each
+  // attending over its own sample's keys (row map).  The attention cell + LSTMCell + generator of every live hypothesis run
+  // as ONE launch per step (the greedy kernel in step mode, one block per hypothesis), log_softmax + top-k per sample
+  // segment on the device, the reference's bookkeeping per sample on the host -- including its quirks: step 0 ranks row 0
+  // only; the LSTM state follows prev_word_inds[incomplete] but the coverage memory only `incomplete`; if the last executed
+  // step completed nothing the first live sequence is returned; otherwise the best score/len sequence with the MAXIMUM raw
+  // score.
+  if (!c || !memory || !seq_out || !len_out || !score_out || N < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
+  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
+  const d2t_config& g = c->cfg;
+  if (g.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "context was not created with the Attn decoder");
+  if (!g.attn_coverage && g.attn_cell != D2T_ATTN_CELL_BAHDANAU)
+    return fail(c, D2T_ESTATE, "LSTM beam search is implemented for the coverage and Bahdanau cells (the reference's 'loc_aware' beam "
+                "hands the previous beam's un-reordered alignment to the next step, seq2seq.py:207)");
+  if (beam_size < 1 || beam_size > 16) return fail(c, D2T_EINVAL, "beam_size must be in [1,16]");
+  const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab, cap = N * beam_size;
+  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  const int Tk = T - key_off;
+  if (Tk < 1 || Tk > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  // alignment maps (viz_attn): every step's launch writes its rows' alignments into its own slice of a history
+  // [S][cap][Tk], kept apart from the workspace below; the chosen paths [N][S] and lengths [N] follow it
+  float* d_hist = nullptr;
+  int* d_path = nullptr;
+  if (alpha_out) {
+    const size_t hist_bytes = (size_t)S * cap * Tk * 4;
+    if (hist_bytes > D2T_ATTN_MAP_BUDGET)
+      return fail(c, D2T_EINVAL, "beam alignment history of %zu bytes (%d steps x %d samples x beam %d x %d keys x 4) exceeds the "
+                  "%llu-byte budget: decode fewer samples per call", hist_bytes, S, N, beam_size, Tk, (unsigned long long)D2T_ATTN_MAP_BUDGET);
+    if ((rc = ensure(c, &c->beam_hist, &c->beam_hist_cap, hist_bytes + ((size_t)N * (S + 1) + 16) * 4))) return rc;
+    d_hist = c->beam_hist;
+    d_path = reinterpret_cast<int*>(d_hist + (size_t)S * cap * Tk);
+  }
+  // the key projection lives in chain 0's workspace, like the synchronous greedy call's: behind that chain's last
+  // asynchronous greedy decode (d2t_decode_attn_greedy_submit), which may still read it
+  d2t_ctx::Chain& ch = c->chains[0];
+  if (c->ev_done_valid[0]) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done[0], 0));
+  if ((rc = ensure(c, &ch.dws, &ch.dws_cap, ((size_t)N * T * Hh + 16) * 4))) return rc;
+  float* kp = ch.dws;
+  // workspace: logits [cap][V] | topv [cap] | topi [cap] (one device -> host copy per step) | h_in c_in h_out c_out [cap][H]
+  //            | mem_in mem_out [cap][Tk] | end_step [cap] | dummy tokens i64 [cap] | step pack (one host -> device copy per
+  //            step): tok i64 [cap] | scores [cap] | map [cap] | idx_h [cap] | idx_m [cap] | seg [N][3]
+  const size_t nf = (size_t)cap * V + 2 * (size_t)cap + 4 * (size_t)cap * Hh + 2 * (size_t)cap * Tk + cap;
+  const size_t pack_off = ((nf * 4 + 15) & ~(size_t)15) + (size_t)cap * 8;
+  const size_t pack_bytes = ((size_t)cap * (8 + 4 * 4) + (size_t)N * 12 + 15) & ~(size_t)15;
+  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, pack_off + pack_bytes + 64))) return rc;
+  float* d_logits = c->beam_ws;
+  float* d_topv = d_logits + (size_t)cap * V;
+  int* d_topi = reinterpret_cast<int*>(d_topv + cap);
+  float* st[6];
+  st[0] = reinterpret_cast<float*>(d_topi + cap);  // h_in
+  st[1] = st[0] + (size_t)cap * Hh;               // c_in
+  st[2] = st[1] + (size_t)cap * Hh;               // h_out
+  st[3] = st[2] + (size_t)cap * Hh;               // c_out
+  st[4] = st[3] + (size_t)cap * Hh;               // mem_in
+  st[5] = st[4] + (size_t)cap * Tk;               // mem_out
+  int* d_end = reinterpret_cast<int*>(st[5] + (size_t)cap * Tk);
+  char* d_pack = reinterpret_cast<char*>(c->beam_ws) + pack_off;
+  int64_t* d_dummy = reinterpret_cast<int64_t*>(d_pack) - cap;
+  int64_t* d_tok = reinterpret_cast<int64_t*>(d_pack);
+  float* d_scores = reinterpret_cast<float*>(d_tok + cap);
+  int* d_map = reinterpret_cast<int*>(d_scores + cap);
+  int* d_idxh = d_map + cap;
+  int* d_idxm = d_idxh + cap;
+  int* d_seg = d_idxm + cap;
+  // pinned host mirror: the step pack | topv [cap] | topi [cap]
+  if ((rc = ensure_host_beam(c, pack_bytes + 2 * (size_t)cap * 4))) return rc;
+  char* hp = c->h_beam;
+  int64_t* h_tok = reinterpret_cast<int64_t*>(hp);
+  float* h_scores = reinterpret_cast<float*>(h_tok + cap);
+  int* h_map = reinterpret_cast<int*>(h_scores + cap);
+  int* h_idxh = h_map + cap;
+  int* h_idxm = h_idxh + cap;
+  int* h_seg = h_idxm + cap;
+  float* h_topv = reinterpret_cast<float*>(hp + pack_bytes);
+  int* h_topi = reinterpret_cast<int*>(h_topv + cap);
+  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, N * T, ACT_NONE));
+  AttnDecP p = attn_dec_params(c, memory, T, kp);
+  p.probs = d_logits; p.tokens = d_dummy; p.end_step = d_end;
+  p.S = 1; p.coverage = 1;
+  p.step_mode = 1;
+  p.st_h_in = st[0]; p.st_c_in = st[1]; p.st_mem_in = st[4];
+  p.st_h_out = st[2]; p.st_c_out = st[3]; p.st_mem_out = st[5];
+  p.tok_in = d_tok; p.row_sample = d_map;
+
+  struct Smp {
+    std::vector<std::vector<int64_t>> seqs, complete;
+    std::vector<std::vector<int>> paths, cpaths;  // maps only: per hypothesis, the launch row of its parent at every step
+    std::vector<float> live, cscores;
+    int k;
+    bool last_completed = false, finished = false;
+  };
+  std::vector<Smp> sm((size_t)N);
+  for (auto& x : sm) {
+    x.seqs.assign((size_t)beam_size, std::vector<int64_t>{0});  // each starts with [GO] = 0
+    x.live.assign((size_t)beam_size, 0.f);
+    x.k = beam_size;
+    if (alpha_out) x.paths.assign((size_t)beam_size, std::vector<int>{});
+  }
+  // the rows of a step in sample order: segments, scores and row map into the pack; returns the row count
+  auto stage = [&](int step) {
+    int rows = 0;
+    for (int i = 0; i < N; ++i) {
+      Smp& x = sm[i];
+      const int M = x.finished ? 0 : (int)x.seqs.size();
+      // step 0: all rows of a sample are identical and the reference ranks its row 0 only (seq2seq.py:145-146)
+      h_seg[3 * i] = rows; h_seg[3 * i + 1] = M ? (step == 0 ? 1 : M) : 0; h_seg[3 * i + 2] = x.finished ? 0 : x.k;
+      for (int j = 0; j < M; ++j) { h_scores[rows + j] = x.live[j]; h_map[rows + j] = i; }
+      rows += M;
+    }
+    return rows;
+  };
+  int rows = stage(0);
+  HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
+  for (int step = 0; step < S; ++step) {
+    p.B = rows; p.first = step == 0;
+    if (d_hist) p.sv_alpha = d_hist + (size_t)step * cap * Tk;
+    HIPCHK(c, launch_attn_decode(p, s));
+    HIPCHK(c, launch_beam_topk_batch(d_logits, d_scores, d_seg, N, V, beam_size, d_topv, d_topi, s));
+    HIPCHK(c, hipMemcpyAsync(h_topv, d_topv, 2 * (size_t)cap * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    int nrows = 0;
+    for (int i = 0; i < N; ++i) {
+      Smp& x = sm[i];
+      if (x.finished) continue;
+      const int off = h_seg[3 * i];
+      std::vector<std::vector<int64_t>> nseqs;
+      std::vector<std::vector<int>> npaths;
+      std::vector<float> nscores;
+      x.last_completed = false;
+      for (int r = 0; r < x.k; ++r) {
+        const int idx = h_topi[(size_t)i * beam_size + r], prev = idx / V, word = idx % V;
+        std::vector<int64_t> sq = x.seqs[prev];
+        sq.push_back(word);
+        std::vector<int> pa;
+        if (alpha_out) {  // the step's alignment row of this hypothesis = its parent's row: seqs_alpha[prev_word_inds]
+          pa = x.paths[prev];
+          pa.push_back(off + prev);
+        }
+        if (word == 1) {  // [s] (attn_converter.py:8)
+          x.complete.push_back(std::move(sq));
+          if (alpha_out) x.cpaths.push_back(std::move(pa));
+          x.cscores.push_back(h_topv[(size_t)i * beam_size + r]);
+          x.last_completed = true;
+        } else {
+          h_idxh[nrows] = off + prev;  // LSTM state: hidden[prev_word_inds[incomplete]]
+          h_idxm[nrows] = off + r;     // coverage memory: (alpha_cum + alpha)[incomplete]
+          h_tok[nrows] = word;
+          ++nrows;
+          nseqs.push_back(std::move(sq));
+          if (alpha_out) npaths.push_back(std::move(pa));
+          nscores.push_back(h_topv[(size_t)i * beam_size + r]);
+        }
+      }
+      x.seqs.swap(nseqs);
+      x.paths.swap(npaths);
+      x.live.swap(nscores);
+      x.k = (int)x.seqs.size();
+      if (x.k == 0) x.finished = true;
+    }
+    if (!nrows || step + 1 == S) break;
+    rows = stage(step + 1);  // == nrows: the survivors, in the order of their gather indices
+    HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, launch_gather_rows(st[2], st[0], d_idxh, rows, Hh, s));
+    HIPCHK(c, launch_gather_rows(st[3], st[1], d_idxh, rows, Hh, s));
+    HIPCHK(c, launch_gather_rows(st[5], st[4], d_idxm, rows, Tk, s));
+  }
+  HIPCHK(c, hipStreamSynchronize(s));
+  std::vector<int> h_path;  // maps: [N][S] chosen paths | [N] lengths, uploaded in one copy
+  if (alpha_out) h_path.assign((size_t)N * (S + 1), 0);
+  for (int i = 0; i < N; ++i) {
+    Smp& x = sm[i];
+    std::vector<int64_t> out;
+    const std::vector<int>* path = nullptr;
+    float score;
+    if (!x.last_completed) {  // seq2seq.py:209-216
+      out.assign(x.seqs[0].begin() + 1, x.seqs[0].end());
+      score = x.live[0];
+      if (alpha_out) path = &x.paths[0];
+    } else {
+      size_t best = 0;
+      for (size_t j = 1; j < x.complete.size(); ++j)
+        if ((double)x.cscores[j] / (double)x.complete[j].size() > (double)x.cscores[best] / (double)x.complete[best].size()) best = j;
+      out.assign(x.complete[best].begin() + 1, x.complete[best].end());
+      score = *std::max_element(x.cscores.begin(), x.cscores.end());
+      if (alpha_out) path = &x.cpaths[best];
+    }
+    const int n = (int)std::min<size_t>(out.size(), (size_t)S);
+    for (int j = 0; j < n; ++j) seq_out[(size_t)i * S + j] = out[j];
+    len_out[i] = n;
+    score_out[i] = score;
+    if (alpha_out) {  // one path entry per emitted token; entries index rows of that step's launch (< cap)
+      const int m = (int)std::min<size_t>(path->size(), (size_t)n);
+      for (int j = 0; j < m; ++j) h_path[(size_t)i * S + j] = (*path)[j];
+      h_path[(size_t)N * S + i] = m;
+    }
+  }
+  if (alpha_out) {  // seqs_alpha[best][1:] of every sample: one upload, one gather over all samples
+    HIPCHK(c, hipMemcpyAsync(d_path, h_path.data(), h_path.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, launch_attn_alpha_gather(d_hist, d_path, d_path + (size_t)N * S, alpha_out, N, S, cap, Tk, s));
+    HIPCHK(c, hipStreamSynchronize(s));  // h_path is pageable and local
+  }
+  return D2T_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,518 @@
+// libd2t engine: the d2t_op_* entries of the C-ABI -- single kernels behind argument checks, for the operator tests and tools.
+#include "engine_impl.h"
+
+extern "C" {
+
+int d2t_op_conv2d(const float* x, const float* w, const float* bias, const float* residual, float* y, int32_t B,
+                  int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t SH, int32_t SW,
+                  int32_t PH, int32_t PW, int32_t act, d2t_stream stream) {
+  if (!x || !w || !y || SH < 1 || SW < 1) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (Cin == 1 || Cin == 3) {  // the stem kernels: x is the image as the encoder takes it, NCHW planar [B][Cin][H][W]
+    if (KH != 3 || KW != 3 || SH != 1 || SW != 1 || PH != 1 || PW != 1 || residual) return D2T_EINVAL;
+    return launch_stem(x, w, bias, y, B, Cin, H, W, Cout, act, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+  }
+  if (Cin % 32) return D2T_EINVAL;
+  float* wp = nullptr;  // the kernel's K order (test entry point: temporary repack, synchronous)
+  if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)Cout * KH * KW * Cin * 4) != hipSuccess) return D2T_ENOMEM;
+  ConvP p{};
+  p.in = x; p.w = wp; p.bias = bias; p.res = residual; p.out = y;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+  p.OH = (H + 2 * PH - KH) / SH + 1; p.OW = (W + 2 * PW - KW) / SW + 1;
+  p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
+  p.M = B * p.OH * p.OW; p.K = KH * KW * Cin; p.act = act;
+  hipError_t e = launch_repack_ohwi(w, wp, Cout, KH, KW, Cin, s);
+  if (e == hipSuccess) e = launch_conv(p, s);
+  hipStreamSynchronize(s);
+  hipFree(wp);
+  return e == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_conv2d_bf16x3(const float* x, const float* w, const float* bias, const float* residual, float* y, int32_t B,
+                         int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t SH, int32_t SW,
+                         int32_t PH, int32_t PW, int32_t act, d2t_stream stream) {
+  if (!x || !w || !y || SH < 1 || SW < 1 || Cin % 32) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)Cout * KH * KW * Cin;
+  uint16_t *hi = nullptr, *lo = nullptr;
+  float* wp = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&hi), n * 2) != hipSuccess) return D2T_ENOMEM;
+  if (hipMalloc(reinterpret_cast<void**>(&lo), n * 2) != hipSuccess) { hipFree(hi); return D2T_ENOMEM; }
+  if (hipMalloc(reinterpret_cast<void**>(&wp), n * 4) != hipSuccess) { hipFree(hi); hipFree(lo); return D2T_ENOMEM; }
+  ConvP p{};
+  p.in = x; p.w = wp; p.w_hi = hi; p.w_lo = lo; p.bias = bias; p.res = residual; p.out = y;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+  p.OH = (H + 2 * PH - KH) / SH + 1; p.OW = (W + 2 * PW - KW) / SW + 1;
+  p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
+  p.M = B * p.OH * p.OW; p.K = KH * KW * Cin; p.act = act;
+  hipError_t e = launch_repack_ohwi(w, wp, Cout, KH, KW, Cin, s);
+  if (e == hipSuccess) e = launch_split_bf16(wp, hi, lo, n, s);
+  if (e == hipSuccess) e = launch_conv_bf16x3(p, s);
+  hipStreamSynchronize(s);
+  hipFree(hi);
+  hipFree(lo);
+  hipFree(wp);
+  return e == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+// kernel selection of d2t_op_conv2d_bf16x3_split (process-wide; op-level tests and tools/conv_bench.py only)
+static int g_op_conv_kind = 3, g_op_reserved_cus = 0;
+int d2t_op_set_conv_kernel(int32_t kind, int32_t reserved_cus) {
+  if ((kind != 0 && kind != 3 && kind != 8) || reserved_cus < 0 || reserved_cus > 128) return D2T_EINVAL;  // 0 / 3 as d2t_set_conv_kernel; 8: kind 3 in fp16x2 arithmetic (ConvP::f16)
+  g_op_conv_kind = kind;
+  g_op_reserved_cus = reserved_cus;
+  return D2T_OK;
+}
+
+// The split-activation kernel: input, residual and output travel as bf16 hi / lo (conv kind 8: fp16) records.
+// pool: with the fused 2x2 / stride 2 max-pool (ConvP::pool2, conv kernel 3 only); y is the POOLED map [B][OH/2][OW/2][Cout]
+static int op_conv_split(bool pool, const float* x, const float* w, const float* bias, const float* residual, float* y, int B, int H,
+                         int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PH, int PW, int act, hipStream_t s) {
+  if (!x || !w || !y || SH < 1 || SW < 1 || Cin % 32 || Cout % 32 || (pool && Cout > 64 && Cout < 128)) return D2T_EINVAL;
+  const int OH = (H + 2 * PH - KH) / SH + 1, OW = (W + 2 * PW - KW) / SW + 1;
+  const size_t nw = (size_t)Cout * KH * KW * Cin, rx = (size_t)B * H * W, ry = (size_t)B * OH * OW;
+  const size_t nx = rx * Cin, ny = ry * Cout, rp = (size_t)B * (OH / 2) * (OW / 2);
+  void* buf = nullptr;
+  const size_t bytes = nw * 4 + nw * 4 + nx * 4 + ny * 4 + (residual ? ny * 4 : 0) + 256;
+  if (hipMalloc(&buf, bytes) != hipSuccess) return D2T_ENOMEM;
+  char* q = (char*)buf;
+  float* wp = (float*)q; q += nw * 4;
+  uint16_t* whi = (uint16_t*)q; q += nw * 2;
+  uint16_t* wlo = (uint16_t*)q; q += nw * 2;
+  uint16_t* xs = (uint16_t*)q; q += nx * 4;
+  uint16_t* ys = (uint16_t*)q; q += ny * 4;
+  uint16_t* rs = nullptr;
+  if (residual) { rs = (uint16_t*)q; q += ny * 4; }
+  void* zero = q;
+  ConvP p{};
+  p.w = wp; p.w_hi = whi; p.w_lo = wlo; p.bias = bias;
+  p.in_hi = xs; p.out_hi = ys; p.res_hi = rs; p.zero16 = zero;
+  const int f16 = g_op_conv_kind == 8;  // fp16 records, fp16 hi / lo weights, two MFMAs per product
+  p.f16 = f16;
+  p.pipelined = (f16 || pool) ? 3 : g_op_conv_kind; p.reserved_cus = g_op_reserved_cus; p.split_tail = !pool;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.OH = OH; p.OW = OW;
+  p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
+  p.M = pool ? (int)(4 * rp) : B * OH * OW; p.K = KH * KW * Cin; p.act = act; p.pool2 = pool;
+  hipError_t e = hipMemsetAsync(zero, 0, 256, s);
+  if (e == hipSuccess) e = launch_repack_ohwi(w, wp, Cout, KH, KW, Cin, s);
+  if (e == hipSuccess) e = f16 ? launch_split_f16(wp, whi, wlo, nw, s) : launch_split_bf16(wp, whi, wlo, nw, s);
+  if (e == hipSuccess) e = launch_split_act(x, xs, rx, Cin, s, f16);
+  if (e == hipSuccess && residual) e = launch_split_act(residual, rs, ry, Cout, s, f16);
+  if (e == hipSuccess) e = launch_conv_bf16x3(p, s);
+  if (e == hipSuccess) e = launch_merge_act(ys, y, pool ? rp : ry, Cout, s, f16);
+  hipStreamSynchronize(s);
+  hipFree(buf);
+  return e == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_conv2d_bf16x3_split(const float* x, const float* w, const float* bias, const float* residual, float* y,
+                               int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW,
+                               int32_t SH, int32_t SW, int32_t PH, int32_t PW, int32_t act, d2t_stream stream) {
+  return op_conv_split(false, x, w, bias, residual, y, B, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW, act, (hipStream_t)stream);
+}
+
+int d2t_op_conv2d_bf16x3_split_pool(const float* x, const float* w, const float* bias, float* y,
+                               int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW,
+                               int32_t SH, int32_t SW, int32_t PH, int32_t PW, int32_t act, d2t_stream stream) {
+  return op_conv_split(true, x, w, bias, nullptr, y, B, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW, act, (hipStream_t)stream);
+}
+
+int d2t_op_linear(const float* x, const float* w, const float* bias, const float* residual, float* y, int32_t M,
+                  int32_t K, int32_t N, int32_t act, d2t_stream stream) {
+  if (!x || !w || !y || K % 16) return D2T_EINVAL;
+  LinW lw{w, bias, N, K};
+  return linear_any(nullptr, (hipStream_t)stream, x, lw, residual, y, M, act) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_maxpool2x2(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t SH, int32_t SW,
+                      int32_t PH, int32_t PW, d2t_stream stream) {
+  if (!x || !y) return D2T_EINVAL;
+  return launch_maxpool(x, y, B, H, W, C, SH, SW, PH, PW, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t rows, int32_t D,
+                     float eps, d2t_stream stream) {
+  if (!x || !gamma || !beta || !y) return D2T_EINVAL;
+  return launch_layernorm(x, gamma, beta, y, rows, D, eps, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_vit_attention(const float* qkv, float* y, int32_t B, int32_t N, int32_t heads, d2t_stream stream) {
+  if (!qkv || !y) return D2T_EINVAL;
+  return launch_vit_attention(qkv, y, B, N, heads, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_vit_attention_probs(const float* qkv, float* y, float* probs, int32_t B, int32_t N, int32_t heads,
+                               d2t_stream stream) {
+  if (!qkv || !y || !probs || B < 1 || N < 1 || heads < 1) return D2T_EINVAL;
+  return launch_vit_attention_probs(qkv, y, probs, B, N, heads, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_decode_attention(const float* q, const float* k, const float* v, float* y, int32_t B, int32_t heads,
+                            int32_t hd, int32_t L, int32_t Lmax, d2t_stream stream) {
+  if (!q || !k || !v || !y || L > Lmax) return D2T_EINVAL;
+  DecAttnP p{};
+  p.q = q; p.q_stride = heads * hd; p.k = const_cast<float*>(k); p.v = const_cast<float*>(v);
+  p.y = y; p.y_stride = heads * hd; p.B = B; p.heads = heads; p.hd = hd; p.Lmax = Lmax; p.L = L;
+  p.kv_batch_stride = (long long)heads * Lmax * hd;
+  return launch_decode_attention(p, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+// ---------------------------------------------------------------------------
+// decode-step kernels one at a time (test infrastructure; see include/d2t.h).  Every entry checks its sizes -- and the
+// device-side integers a kernel would index with, read back first -- against the kernel's limits before it launches.
+// ---------------------------------------------------------------------------
+namespace {
+// the stream's earlier work has finished; n ints of device memory on the host
+bool fetch_ints(hipStream_t s, const int* dev, size_t n, std::vector<int>* out) {
+  out->resize(n);
+  if (hipStreamSynchronize(s) != hipSuccess) return false;
+  return n == 0 || hipMemcpy(out->data(), dev, n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+}
+}  // namespace
+
+int d2t_op_skinny(const float* x, const float* w, const float* bias, const float* res, const float* ln_g, const float* ln_b,
+                  float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx, int32_t ldy, int32_t act,
+                  const int32_t* step, int64_t out_step_stride, d2t_stream stream) {
+  if (!x || !w || !y || M < 1 || M > 65535 * 16 || N < 1 || K < 16 || K % 16 || ldx < K || ldx % 4 || ldy < N) return D2T_EINVAL;
+  if (act != ACT_NONE && act != ACT_RELU && act != ACT_GELU) return D2T_EINVAL;
+  if ((ln_g == nullptr) != (ln_b == nullptr) || (ln_out && !ln_g)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (step) {
+    std::vector<int> t;
+    if (out_step_stride < 0 || !fetch_ints(s, step, 1, &t) || t[0] < 0) return D2T_EINVAL;
+  }
+  SkinnyP p{};
+  p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
+  p.M = M; p.K = K; p.N = N; p.ldx = ldx; p.ldy = ldy; p.ldres = N; p.act = act;
+  p.step_ptr = step; p.out_step_stride = out_step_stride;
+  p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_out = ln_out;
+  const hipError_t e = launch_skinny(p, s);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+namespace {
+// Set-up the decoder-row operator entries share: one temporary buffer [W_o^T | W_q^T | W_co^T | W_v^T | extra bytes] with the
+// four transposes enqueued, and the DecRowP fields every kind sets alike.  *buf is allocated here (nullptr on D2T_ENOMEM)
+// and freed by the caller after its stream has drained.
+struct RowOpTmp { float* buf; float* wv_t; float* ext; };
+int row_op_setup(const float* qkv, const float* xres, float* sk, float* sv, const float* ca_in_w, const float* ca_in_b,
+                 const float* sa_out_w, const float* sa_out_b, const float* ca_out_w, const float* ca_out_b, const float* ln1_g,
+                 const float* ln1_b, float eps, float* y2, const int32_t* step, int M, int D, int Lmax, size_t extra,
+                 hipStream_t s, RowOpTmp* t, DecRowP* r, hipError_t* e) {
+  const size_t dd = (size_t)D * D;
+  t->buf = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&t->buf), 4 * dd * 4 + extra) != hipSuccess) return D2T_ENOMEM;
+  float *wo_t = t->buf, *wq_t = t->buf + dd, *wco_t = t->buf + 2 * dd;
+  t->wv_t = t->buf + 3 * dd; t->ext = t->buf + 4 * dd;
+  *e = launch_transpose(sa_out_w, wo_t, D, D, s);
+  if (*e == hipSuccess) *e = launch_transpose(ca_in_w, wq_t, D, D, s);
+  if (*e == hipSuccess) *e = launch_transpose(ca_out_w, wco_t, D, D, s);
+  if (*e == hipSuccess) *e = launch_transpose(ca_in_w + 2 * dd, t->wv_t, D, D, s);
+  *r = DecRowP{};
+  r->qkv = qkv; r->qkv_stride = 3 * D; r->xres = xres;
+  r->sk = sk; r->sv = sv; r->s_batch_stride = (long long)Lmax * D; r->s_Lmax = Lmax;
+  r->wo_t = wo_t; r->bo = sa_out_b; r->ln1_g = ln1_g; r->ln1_b = ln1_b; r->eps = eps;
+  r->wq_t = wq_t; r->bq = ca_in_b; r->wco_t = wco_t; r->bco = ca_out_b;
+  r->y2 = y2; r->step_ptr = step; r->M = M; r->D = D; r->heads = 8;
+  return D2T_OK;
+}
+// The device-side integers a row kernel indexes with, read back: the step (a cache position), the row map (optional: samples)
+// and the ancestry rows (optional: cache rows at positions below the step).
+static int row_op_check(hipStream_t s, const int32_t* step, int Lmax, const int32_t* row_map, int M, int samples, const int32_t* anc,
+                 int anc_stride, int rows) {
+  std::vector<int> h;
+  if (!fetch_ints(s, step, 1, &h)) return D2T_EHIP;
+  const int t = h[0];
+  if (t < 0 || t >= Lmax) return D2T_EINVAL;
+  if (row_map) {
+    if (!fetch_ints(s, row_map, M, &h)) return D2T_EHIP;
+    for (int v : h) if (v < 0 || v >= samples) return D2T_EINVAL;
+  }
+  if (anc) {
+    if (!fetch_ints(s, anc, (size_t)M * anc_stride, &h)) return D2T_EHIP;
+    for (int b = 0; b < M; ++b)
+      for (int j = 0; j < t; ++j)
+        if (h[(size_t)b * anc_stride + j] < 0 || h[(size_t)b * anc_stride + j] >= rows) return D2T_EINVAL;
+  }
+  return D2T_OK;
+}
+// every (row0, len) slice of a ragged table lies inside the packed memory and within the kernels' longest memory
+static bool ragged_slices_ok(const int32_t* row0, const int32_t* len, int n, int mem_rows) {
+  for (int i = 0; i < n; ++i)
+    if (row0[i] < 0 || len[i] < 1 || len[i] > 4096 || (long long)row0[i] + len[i] > mem_rows) return false;
+  return true;
+}
+// the stream drained, the temporaries freed, the launches' status as a return code
+static int row_op_finish(hipStream_t s, float* buf, hipError_t e) {
+  const hipError_t e2 = hipStreamSynchronize(s);
+  hipFree(buf);
+  return e == hipErrorInvalidValue ? D2T_EINVAL : (e == hipSuccess && e2 == hipSuccess) ? D2T_OK : D2T_EHIP;
+}
+}  // namespace
+
+int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                       const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                       const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps, float* y2,
+                       const int32_t* step, int32_t M, int32_t D, int32_t T, int32_t Lmax, int32_t rows, int32_t samples,
+                       int32_t one_row, const int32_t* row_map, const int32_t* anc, int32_t anc_stride, const int32_t* seg,
+                       int32_t nsamples, d2t_stream stream) {
+  if (!qkv || !xres || !sk || !sv || !mem || !ca_in_w || !ca_in_b || !sa_out_w || !sa_out_b || !ca_out_w || !ca_out_b ||
+      !ln1_g || !ln1_b || !y2 || !step)
+    return D2T_EINVAL;
+  if (kind < 0 || kind > 5 || M < 1 || M > 65535 || rows < M || samples < 1 || T < 1 || T > 4096 || Lmax < 1 || Lmax > 4096)
+    return D2T_EINVAL;
+  if (kind == 0 ? (D != 256 && D != 512) : D != 256) return D2T_EINVAL;
+  if (!row_map && samples < M) return D2T_EINVAL;  // row b attends over sample b
+  if (anc && ((kind != 2 && kind != 4) || Lmax > 512 || anc_stride < Lmax)) return D2T_EINVAL;  // one-row absorbed builds only
+  if (kind == 5 && (!seg || !row_map || nsamples < 1 || nsamples > samples)) return D2T_EINVAL;
+  if (kind != 5 && seg) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = row_op_check(s, step, Lmax, row_map, M, samples, anc, anc_stride, rows)) return rc;
+  if (kind == 5) {  // compact segments in sample order, at most 6 live hypotheses each, every row in exactly one
+    std::vector<int> h, rm;
+    if (!fetch_ints(s, seg, (size_t)nsamples * 3, &h) || !fetch_ints(s, row_map, M, &rm)) return D2T_EHIP;
+    int next = 0;
+    for (int n = 0; n < nsamples; ++n) {
+      const int first = h[3 * n], cnt = h[3 * n + 1];
+      if (cnt < 0 || cnt > 6 || (cnt > 0 && first != next)) return D2T_EINVAL;
+      for (int r = 0; r < cnt; ++r) if (rm[next + r] != n) return D2T_EINVAL;
+      next += cnt;
+    }
+    if (next != M) return D2T_EINVAL;
+  }
+  const size_t dd = (size_t)D * D, memn = (size_t)samples * T * D;
+  // temporaries: three transposed projections, W_v^T; then projected K / V (kind 0), bf16 planes (3, 4), q' + x1 (5)
+  size_t extra = 0;
+  if (kind == 0) extra = 2 * memn * 4;
+  else if (kind == 3 || kind == 4) extra = memn * 4;
+  else if (kind == 5) extra = (size_t)M * 9 * D * 4;
+  RowOpTmp tmp;
+  DecRowP r;
+  hipError_t e = hipSuccess;
+  if (int rc = row_op_setup(qkv, xres, sk, sv, ca_in_w, ca_in_b, sa_out_w, sa_out_b, ca_out_w, ca_out_b, ln1_g, ln1_b, eps, y2, step,
+                            M, D, Lmax, extra, s, &tmp, &r, &e))
+    return rc;
+  float *const buf = tmp.buf, *const wv_t = tmp.wv_t, *const ext = tmp.ext;
+  r.c_row_map = row_map; r.T = T;
+  r.anc = anc; r.anc_stride = anc_stride;
+  const float *wk = ca_in_w + dd, *bv = ca_in_b + 2 * D;
+  if (e != hipSuccess) {  // (nothing more to launch)
+  } else if (kind == 0) {  // K / V of the memory rows as cross_kv projects them: [2][samples][8][T][D / 8]
+    ConvP p{};
+    p.in = mem; p.w = wk; p.bias = ca_in_b + D; p.out = ext;
+    p.B = 1; p.H = 1; p.W = samples * T; p.Cin = D; p.OH = 1; p.OW = samples * T; p.Cout = 2 * D;
+    p.KH = p.KW = p.SH = p.SW = 1; p.M = samples * T; p.K = D; p.act = ACT_NONE;
+    p.store_mode = STORE_KV; p.kv_T = T; p.kv_heads = 8; p.kv_hd = D / 8; p.kv_B = samples;
+    e = launch_conv(p, s);
+    r.ck = ext; r.cv = ext + memn; r.c_batch_stride = (long long)T * D;
+    r.one_row = one_row != 0;
+    if (e == hipSuccess) e = launch_decoder_row(r, s);
+  } else if (kind == 5) {
+    r.one_row = 1;
+    e = launch_decoder_row_beam(r, mem, (long long)T * D, wk, wv_t, bv, ext, ext + (size_t)M * 8 * D, seg, nsamples, s);
+  } else {
+    r.one_row = kind == 2 || kind == 4;
+    uint16_t *hi = nullptr, *lo = nullptr;
+    if (kind >= 3) {
+      hi = reinterpret_cast<uint16_t*>(ext); lo = hi + memn;
+      e = launch_split_bf16(mem, hi, lo, memn, s);
+    }
+    if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, (long long)T * D, wk, wv_t, bv, s, hi, lo);
+  }
+  return row_op_finish(s, buf, e);
+}
+
+// The ragged builds of the greedy absorbed row kernels (kind as d2t_op_decoder_row: 1 / 2 = fp32 MFMA two-row / one-row,
+// 3 / 4 = split-bf16 two-row / one-row): mem is ONE packed [mem_rows][256] buffer, row b attends over the len[b] rows from
+// row0[b] on (host arrays, validated here, uploaded for the launch).
+int d2t_op_decoder_row_ragged(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                              const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                              const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps,
+                              float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
+                              const int32_t* row0_host, const int32_t* len_host, d2t_stream stream) {
+  if (!qkv || !xres || !sk || !sv || !mem || !ca_in_w || !ca_in_b || !sa_out_w || !sa_out_b || !ca_out_w || !ca_out_b ||
+      !ln1_g || !ln1_b || !y2 || !step || !row0_host || !len_host)
+    return D2T_EINVAL;
+  if (kind < 1 || kind > 4 || M < 1 || M > 65535 || rows < M || mem_rows < 1 || mem_rows > (1 << 22) || Lmax < 1 || Lmax > 4096)
+    return D2T_EINVAL;
+  if (!ragged_slices_ok(row0_host, len_host, M, mem_rows)) return D2T_EINVAL;
+  constexpr int D = 256;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = row_op_check(s, step, Lmax, nullptr, M, 0, nullptr, 0, rows)) return rc;
+  const size_t dd = (size_t)D * D, memn = (size_t)mem_rows * D;
+  const size_t extra = kind >= 3 ? memn * 4 : 0;
+  RowOpTmp tmp;
+  DecRowP r;
+  hipError_t e = hipSuccess;
+  if (int rc = row_op_setup(qkv, xres, sk, sv, ca_in_w, ca_in_b, sa_out_w, sa_out_b, ca_out_w, ca_out_b, ln1_g, ln1_b, eps, y2, step,
+                            M, D, Lmax, extra + (size_t)2 * M * 4, s, &tmp, &r, &e))
+    return rc;
+  float *const buf = tmp.buf, *const wv_t = tmp.wv_t, *const ext = tmp.ext;
+  int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ext) + extra);  // [row0 | len] behind the bf16 planes
+  if (e == hipSuccess) e = hipMemcpyAsync(tab, row0_host, (size_t)M * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tab + M, len_host, (size_t)M * 4, hipMemcpyHostToDevice, s);
+  r.T = 1;  // (unused by the ragged builds)
+  r.one_row = kind == 2 || kind == 4;
+  uint16_t *hi = nullptr, *lo = nullptr;
+  if (e == hipSuccess && kind >= 3) {
+    hi = reinterpret_cast<uint16_t*>(ext); lo = hi + memn;
+    e = launch_split_bf16(mem, hi, lo, memn, s);
+  }
+  if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, 0, ca_in_w + dd, wv_t, ca_in_b + 2 * D, s, hi, lo, tab, tab + M);
+  return row_op_finish(s, buf, e);
+}
+
+// The per-sample ragged builds of the one-row absorbed kernel (ragged beam search; kind 2 = fp32 MFMA, 4 = split-bf16): mem is
+// ONE packed [mem_rows][256] buffer, row b attends over the len[row_map[b]] rows from row0[row_map[b]] on.  row0 / len: host
+// arrays [samples]; row_map (required) and anc (optional, the hypotheses' ancestry rows): device arrays as d2t_op_decoder_row.
+int d2t_op_decoder_row_ragged_beam(int32_t kind, const float* qkv, const float* xres, float* sk, float* sv, const float* mem,
+                                   const float* ca_in_w, const float* ca_in_b, const float* sa_out_w, const float* sa_out_b,
+                                   const float* ca_out_w, const float* ca_out_b, const float* ln1_g, const float* ln1_b, float eps,
+                                   float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
+                                   int32_t samples, const int32_t* row0_host, const int32_t* len_host, const int32_t* row_map,
+                                   const int32_t* anc, int32_t anc_stride, d2t_stream stream) {
+  if (!qkv || !xres || !sk || !sv || !mem || !ca_in_w || !ca_in_b || !sa_out_w || !sa_out_b || !ca_out_w || !ca_out_b ||
+      !ln1_g || !ln1_b || !y2 || !step || !row0_host || !len_host || !row_map)
+    return D2T_EINVAL;
+  if ((kind != 2 && kind != 4) || M < 1 || M > 65535 || rows < M || samples < 1 || samples > 65535 || mem_rows < 1 ||
+      mem_rows > (1 << 22) || Lmax < 1 || Lmax > 4096)
+    return D2T_EINVAL;
+  if (!ragged_slices_ok(row0_host, len_host, samples, mem_rows)) return D2T_EINVAL;
+  if (anc && (Lmax > 512 || anc_stride < Lmax)) return D2T_EINVAL;
+  constexpr int D = 256;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = row_op_check(s, step, Lmax, row_map, M, samples, anc, anc_stride, rows)) return rc;
+  const size_t dd = (size_t)D * D, memn = (size_t)mem_rows * D;
+  const size_t extra = kind == 4 ? memn * 4 : 0;
+  RowOpTmp tmp;
+  DecRowP r;
+  hipError_t e = hipSuccess;
+  if (int rc = row_op_setup(qkv, xres, sk, sv, ca_in_w, ca_in_b, sa_out_w, sa_out_b, ca_out_w, ca_out_b, ln1_g, ln1_b, eps, y2, step,
+                            M, D, Lmax, extra + (size_t)2 * samples * 4, s, &tmp, &r, &e))
+    return rc;
+  float *const buf = tmp.buf, *const wv_t = tmp.wv_t, *const ext = tmp.ext;
+  int* tab = reinterpret_cast<int*>(reinterpret_cast<char*>(ext) + extra);  // [row0 | len] behind the bf16 planes
+  if (e == hipSuccess) e = hipMemcpyAsync(tab, row0_host, (size_t)samples * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tab + samples, len_host, (size_t)samples * 4, hipMemcpyHostToDevice, s);
+  r.T = 1;  // (unused by the ragged builds)
+  r.one_row = true;
+  r.c_row_map = row_map;
+  r.anc = anc; r.anc_stride = anc_stride;
+  uint16_t *hi = nullptr, *lo = nullptr;
+  if (e == hipSuccess && kind == 4) {
+    hi = reinterpret_cast<uint16_t*>(ext); lo = hi + memn;
+    e = launch_split_bf16(mem, hi, lo, memn, s);
+  }
+  if (e == hipSuccess) e = launch_decoder_row_absorbed(r, mem, 0, ca_in_w + dd, wv_t, ca_in_b + 2 * D, s, hi, lo, tab, tab + samples);
+  return row_op_finish(s, buf, e);
+}
+
+int d2t_op_argmax_embed(const float* logits, int32_t S, int64_t* tokens, int32_t* ended, int32_t* end_count, int32_t* steps_done,
+                        int32_t* step, int32_t* done_count, int32_t* batch_end_count, int32_t* batch_steps_done,
+                        int32_t* batches_done, int32_t* stop_at, const float* emb, const float* pe, float* x, int32_t B, int32_t V,
+                        int32_t d, int32_t end_token, int32_t rows_per_batch, int32_t n_batches, d2t_stream stream) {
+  if (!logits || !tokens || !ended || !end_count || !steps_done || !step || !done_count || B < 1 || B > 65535 || V < 1 || S < 1)
+    return D2T_EINVAL;
+  if (end_token < 0 || end_token >= V) return D2T_EINVAL;
+  if (x && (!emb || !pe || d < 1)) return D2T_EINVAL;
+  if (n_batches < 0 || n_batches > 64) return D2T_EINVAL;
+  if (n_batches > 0 && (rows_per_batch < 1 || (long long)rows_per_batch * n_batches != B || !batch_end_count || !batch_steps_done ||
+                        !batches_done))
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> t;
+  if (!fetch_ints(s, step, 1, &t)) return D2T_EHIP;
+  if (t[0] < 0 || t[0] >= S) return D2T_EINVAL;  // logits / tokens hold S steps, pe S + 1 rows
+  ArgmaxP p{};
+  p.logits = logits; p.row_stride = (long long)S * V; p.step_stride = V;
+  p.tokens = tokens; p.tok_stride = S;
+  p.ended = ended; p.end_count = end_count; p.steps_done = steps_done; p.step_ptr = step; p.done_count = done_count;
+  p.B = B; p.V = V; p.end_token = end_token;
+  p.emb = emb; p.pe = pe; p.x = x; p.d = d;
+  p.rows_per_batch = rows_per_batch; p.n_batches = n_batches;
+  p.batch_end_count = batch_end_count; p.batch_steps_done = batch_steps_done; p.batches_done = batches_done; p.stop_at = stop_at;
+  return launch_argmax_embed(p, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+int d2t_op_beam_topk(const float* logits, const float* scores, const int32_t* seg, int32_t N, int32_t rows, int32_t V, int32_t kmax,
+                     float* topv, int32_t* topi, d2t_stream stream) {
+  if (!logits || !scores || !seg || !topv || !topi || N < 1 || N > 65535 || rows < 1 || V < 1 || kmax < 1 || kmax > 16)
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> h;
+  if (!fetch_ints(s, seg, (size_t)N * 3, &h)) return D2T_EHIP;
+  for (int n = 0; n < N; ++n) {
+    const int off = h[3 * n], m = h[3 * n + 1], k = h[3 * n + 2];
+    if (m <= 0 || k <= 0) continue;  // the kernel leaves such a segment alone
+    if (off < 0 || m > 16 || off + m > rows || k > kmax || (long long)k > (long long)m * V || (long long)m * V > 0x7fffffffLL)
+      return D2T_EINVAL;
+  }
+  const hipError_t e = launch_beam_topk_batch(logits, scores, seg, N, V, kmax, topv, topi, s);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+int d2t_op_beam_advance(int32_t init, int64_t go_token, int32_t* ctrl, int64_t* tok, float* scores, int32_t* map, int32_t* prev,
+                        int32_t* seg, int32_t* comp_n, int32_t* fin, int32_t* comp_t, int32_t* comp_par, float* comp_score,
+                        int32_t* hist_par, int32_t* hist_tok, const float* topv, const int32_t* topi, int32_t N, int32_t beam,
+                        int32_t cap, int32_t V, int32_t S, int32_t end_token, d2t_stream stream) {
+  if (!ctrl || !tok || !scores || !map || !prev || !seg || !comp_n || !fin || !comp_t || !comp_par || !comp_score || !hist_par ||
+      !hist_tok)
+    return D2T_EINVAL;
+  if (N < 1 || N > 1024 || beam < 1 || beam > 16 || (long long)cap < (long long)N * beam || V < 1 || S < 1 || end_token < 0 ||
+      end_token >= V)
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  BeamDev b{};
+  b.ctrl = ctrl; b.tok = tok; b.scores = scores; b.map = map; b.prev = prev; b.seg = seg; b.comp_n = comp_n; b.fin = fin;
+  b.comp_t = comp_t; b.comp_par = comp_par; b.comp_score = comp_score; b.hist_par = hist_par; b.hist_tok = hist_tok;
+  b.topv = topv; b.topi = topi; b.N = N; b.beam = beam; b.cap = cap; b.V = V; b.S = S; b.end_token = end_token;
+  if (init) return launch_beam_dev_init(b, go_token, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+  if (!topv || !topi) return D2T_EINVAL;
+  // the state as the kernel will read it: the step indexes the history, the candidates index rows of their segment
+  std::vector<int> c, sg, cn, fi, ti;
+  if (!fetch_ints(s, ctrl, 4, &c) || !fetch_ints(s, seg, (size_t)N * 3, &sg) || !fetch_ints(s, comp_n, N, &cn) ||
+      !fetch_ints(s, fin, N, &fi) || !fetch_ints(s, topi, (size_t)N * beam, &ti))
+    return D2T_EHIP;
+  if (c[0] < 0 || c[2] < 0) return D2T_EINVAL;
+  if (!(c[2] && c[0] >= c[2])) {  // the launch will do work
+    if (c[0] >= S) return D2T_EINVAL;
+    for (int i = 0; i < N; ++i) {
+      if (fi[i] || sg[3 * i + 1] <= 0) continue;
+      const int live = sg[3 * i + 2], m = sg[3 * i + 1];
+      if (live < 0 || live > beam || cn[i] < 0 || cn[i] + live > beam || sg[3 * i] < 0 || sg[3 * i] + m > cap) return D2T_EINVAL;
+      for (int r = 0; r < live; ++r) {
+        const int idx = ti[(size_t)i * beam + r];
+        if (idx < 0 || idx / V >= m) return D2T_EINVAL;
+      }
+    }
+  }
+  const hipError_t e = launch_beam_dev_advance(b, s);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+int d2t_op_beam_ancestry(const int32_t* anc_old, int32_t* anc_new, const int32_t* prev, int32_t rows, int32_t stride,
+                         const int32_t* step_in, int32_t* step_out, const int32_t* rows_ptr, const int32_t* stop,
+                         d2t_stream stream) {
+  if (!anc_old || !anc_new || !prev || !step_in || !step_out || rows < 1 || rows > 65535 || stride < 1) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> t, pv;
+  if (!fetch_ints(s, step_in, 1, &t) || !fetch_ints(s, prev, rows, &pv)) return D2T_EHIP;
+  if (t[0] < 0 || t[0] > stride) return D2T_EINVAL;  // positions 0 .. t - 1 of a row are written
+  for (int v : pv) if (v < 0 || v >= rows) return D2T_EINVAL;
+  const hipError_t e = launch_beam_ancestry(anc_old, anc_new, prev, rows, stride, step_in, step_out, s, rows_ptr, stop);
+  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+}
+
+int d2t_op_cache_gather(const float* src, float* dst, const int32_t* prev, int32_t slabs, int32_t cap, int32_t M, int32_t heads,
+                        int32_t Lmax, int32_t hd, int32_t rows, d2t_stream stream) {
+  if (!src || !dst || !prev || src == dst || slabs < 1 || cap < 1 || M < 1 || M > cap || M > 65535 || heads < 1 || heads > 65535 ||
+      Lmax < 1 || hd < 4 || hd % 4 || rows < 1 || rows > Lmax)
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> pv;
+  if (!fetch_ints(s, prev, M, &pv)) return D2T_EHIP;
+  for (int v : pv) if (v < 0 || v >= cap) return D2T_EINVAL;
+  return launch_cache_gather(src, dst, prev, slabs, cap, M, heads, Lmax, hd, rows, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+}  // extern "C"

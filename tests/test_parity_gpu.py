@@ -560,6 +560,86 @@ def test_pipelined_early_exit_decided_on_the_device(cases, group):
     m.pipelined, m.decode_group = False, 1
 
 
+def _chain_modes(imgs):
+    """The decode modes of test_chain_state_survives_mode_and_count_changes: name -> f(model) -> flat list of result tensors."""
+    a, b = imgs
+    go = lambda x: torch.full((x.shape[0], 1), R.GO, dtype=torch.long, device="cuda")
+
+    def settings(m, pipelined, chains, group=1, mixed=False):
+        m.pipelined, m.decode_chains, m.decode_group, m.decode_group_mixed = pipelined, chains, group, mixed
+
+    def pipelined(m, xs, chains, group=1, mixed=False):
+        settings(m, True, chains, group, mixed)
+        handles = [m(x, go(x), is_train=False)[2]["decode"] for x in xs]
+        if mixed:
+            assert len({h.ticket for h in handles}) == 1 and handles[0].ticket is not None  # ONE ragged decode
+        res = [t for h in handles for t in h.result()]
+        m.synchronize()
+        settings(m, False, chains)
+        return [t.clone() for t in res]
+
+    def sync(m):
+        settings(m, False, m.decode_chains)
+        return [t.clone() for x in (a, b) for t in m(x, go(x), is_train=False)[:2]]
+
+    def beam(m):  # four hypothesis rows: within what the warm-up sized chain 0 for
+        settings(m, False, m.decode_chains)
+        return [t for seq, score in m.beam_search_batch(b, beam_size=2) for t in (seq, torch.tensor(score))]
+
+    return {
+        # both batches on every one of the three chains / memory slots, whatever the context's decode counter stands at
+        "pipelined3": lambda m: pipelined(m, [a, b, a, b, a, b], 3),
+        "sync": sync,
+        "beam": beam,
+        "pipelined1": lambda m: pipelined(m, [a, b, a], 1),
+        "ragged2": lambda m, chains=2: pipelined(m, [a, b], chains, group=2, mixed=True),
+    }
+
+
+def test_chain_state_survives_mode_and_count_changes():
+    """One live context through changes of the decode mode and of the chain count: pipelined greedy on three chains,
+    synchronous greedy, a beam search (chain 0), pipelined greedy on one chain, a ragged group on two chains, then the first
+    call again.  Every call returns the bits of the same call on a fresh model that does nothing else (same kernels, same
+    row counts: no tolerance).
+
+    The sequence runs twice.  On a fresh model, where the calls also grow the chains' buffers between the mode changes.  Then
+    on a model whose three chains were first brought to their final size by three ragged groups (the call with the most rows
+    and memory rows; a grown buffer has a new address, and the addresses are part of a captured loop's key): there a second
+    pass over the modes, the repeat of the first call included, finds every loop of the first pass again -- chain i kept
+    chain i's buffers and stream.  (A pass issues twelve greedy decodes, a multiple of both slot counts, so the second
+    pass meets the same chains and memory slots.)"""
+    L = 40
+    imgs = [synth.synth_images(3, 48, 64, seed=3100).cuda(), synth.synth_images(2, 48, 32, seed=3101).cuda()]
+    modes = _chain_modes(imgs)
+    order = ["pipelined3", "sync", "beam", "pipelined1", "ragged2"]
+
+    def check(m, i, name):
+        got = modes[name](m)
+        assert len(got) == len(ref[name])
+        for k, (x, y) in enumerate(zip(got, ref[name])):
+            assert x.shape == y.shape and torch.equal(x, y), f"call {i} ({name}): output {k} differs from a fresh model's"
+
+    with torch.no_grad():
+        ref = {}
+        for name in order:
+            _, fresh = engine_model("T2", L, 1234, 0.0)
+            assert len({fresh.engine().encoder_shape(*x.shape[2:])[0] for x in imgs}) == 2  # two memory lengths
+            ref[name] = modes[name](fresh)
+            del fresh
+        _, m = engine_model("T2", L, 1234, 0.0)
+        for i, name in enumerate(order + order[:1]):
+            check(m, i, name)
+        _, m = engine_model("T2", L, 1234, 0.0)
+        for _ in range(3):  # chains / slots 0, 1, 2 at their final size
+            modes["ragged2"](m, chains=3)
+        eng = m.engine()
+        for i, name in enumerate(order + order):
+            n0 = eng.graph_count()
+            check(m, i, name)
+            if i >= len(order):
+                assert eng.graph_count() == n0, f"call {i} ({name}) re-captured a decode loop of the first pass"
+
+
 @pytest.mark.parametrize("name", ["t2_greedy", "c2_small_crop", "c2_greedy", "c1_greedy", "s0_greedy"])
 def test_fp32_convolutions_keep_parity(cases, name):
     """The exact-fp32 arithmetic mode (conv_precision = 'fp32'; the default is the split-bf16 path every other test
