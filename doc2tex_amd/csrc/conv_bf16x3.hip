@@ -28,8 +28,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int XBK = 32;             // K-step
 constexpr int XROW = 64;            // bytes per LDS row of one plane (32 bf16)
 
-__device__ __forceinline__ int swz_chunk(int row, int c) { return c ^ ((row >> 2) & 3); }
-
 // four consecutive-k floats -> packed hi (truncation) and lo (RNE of the remainder) bf16 quads
 __device__ __forceinline__ void split4(const float4 v, uint2& hi, uint2& lo) {
   const unsigned x0 = __float_as_uint(v.x), x1 = __float_as_uint(v.y), x2 = __float_as_uint(v.z),
@@ -229,8 +227,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN) / 2) void conv_bf16x3_kerne
         compute(kt2, F_{}, F_{}, ra[1], rbh[1], rbl[1], ra[0], rbh[0], rbl[0]);
       }
     }
-    if (wide_epilogue_full_ok(p)) conv_epilogue_wide_full<BM, BN, NT, MI, NJ>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
-    else conv_epilogue<MI, NJ>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
+    if (wide_epilogue_full_ok(p)) conv_epilogue_tile<Epi::full, BM, BN, NT>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
+    else conv_epilogue<Map32, ElemTwoWay>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
     return;
   }
   // steady state (K-steps kt+1 and kt+2 exist), unrolled by two so the register sets are static
@@ -250,8 +248,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN) / 2) void conv_bf16x3_kerne
   } else if (kt < KT) {     // one left
     compute(kt, F_{}, F_{}, ra[1], rbh[1], rbl[1], ra[0], rbh[0], rbl[0]);
   }
-  if (wide_epilogue_full_ok(p)) conv_epilogue_wide_full<BM, BN, NT, MI, NJ>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
-  else conv_epilogue<MI, NJ>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
+  if (wide_epilogue_full_ok(p)) conv_epilogue_tile<Epi::full, BM, BN, NT>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
+  else conv_epilogue<Map32, ElemTwoWay>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -283,8 +281,8 @@ __device__ __forceinline__ void conv_bf16x3g_body(const ConvP& p, unsigned char*
   constexpr int STAGE = 2 * PLANE_A + 2 * PLANE_B;
 
   const int nt = (p.Cout + BN - 1) / BN;
-  const int ntiles = nt * ((p.M - p.m_base + BM - 1) / BM);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int ntiles = nt * ((p.M + BM - 1) / BM);
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;  // (wave-uniform: wm / wn and the piece offsets stay scalar)
   const int lr = lane >> 2, pos = lane & 3;
   // Persistent over tiles: the grid may be smaller than the tile count (p.max_blocks), which leaves
   // block slots free for the latency-bound decode kernels of the previous batch (pipelined mode).
@@ -294,7 +292,7 @@ __device__ __forceinline__ void conv_bf16x3g_body(const ConvP& p, unsigned char*
   int logical = tile0 + blockIdx.x;
   if ((G & 7) == 0) logical = tile0 + (blockIdx.x & 7) * gx + (blockIdx.x >> 3);
   if (logical >= ntiles) break;  // block-uniform
-  const int m0 = p.m_base + (logical / nt) * BM;
+  const int m0 = (logical / nt) * BM;
   const int n0 = (logical % nt) * BN;
 
   int a_off[AJ];
@@ -420,10 +418,10 @@ __device__ __forceinline__ void conv_bf16x3g_body(const ConvP& p, unsigned char*
   }
   if (wide_epilogue_ok(p)) {  // block-uniform
     static_assert(BM * BN * 4 <= 2 * STAGE, "the fp32 tile must fit in the staging area");
-    if (p.pool2) conv_epilogue_wide_pool<BM, BN, NW * 64, MI, NJ>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
-    else conv_epilogue_wide<BM, BN, NW * 64, MI, NJ>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
+    if (p.pool2) conv_epilogue_tile<Epi::pool, BM, BN, NW * 64>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
+    else conv_epilogue_tile<Epi::lean, BM, BN, NW * 64>(p, acc, smem, m0, n0, wm * WTM, wn * WTN, r, h, tid);
   } else {
-    conv_epilogue<MI, NJ>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
+    conv_epilogue<Map32, ElemTwoWay>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
   }
   }  // tile loop
 }
@@ -458,29 +456,17 @@ __global__ __launch_bounds__(512, 4) void conv_f16x2g_128x128_w8(const ConvP p) 
   conv_bf16x3g_body<128, 128, 4, true>(p, smem);
 }
 
-// The 128-row LDS-DMA kernels over output rows [p.m_base, p.M) with a column tile of `bn` (64 | 128): the pipelined kernel
-// hands the rows of its last, partial round of tiles to this one (conv_bf16x3p.hip).
-hipError_t launch_conv_bf16x3g_rows(const ConvP& p, int bn, hipStream_t s) {
-  if (p.M <= p.m_base) return hipSuccess;
-  if (!p.in_hi || !p.w_hi || !p.w_lo || !p.zero16 || p.m_base < 0 || (bn != 64 && bn != 128)) return hipErrorInvalidValue;
-  const int tiles = ((p.M - p.m_base + 127) / 128) * ((p.Cout + bn - 1) / bn);
-  if (bn == 64) hipLaunchKernelGGL(conv_bf16x3g_128x64, dim3(tiles), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(conv_bf16x3g_128x128_w8, dim3(tiles), dim3(512), 0, s, p);
-  return hipGetLastError();
-}
-
 hipError_t launch_conv_bf16x3(const ConvP& p, hipStream_t s) {
   if (p.M <= 0 || p.Cout <= 0) return hipSuccess;
   if (p.pool2) {  // fused 2x2 max-pool: split-record LDS-DMA kernels with the wide epilogue only (g body, 16x16x32 pipelined body)
     const bool wide = p.store_mode == STORE_ROWS && p.rows_per_img == 0 && !p.row_add && (p.Cout & 31) == 0;
     if (!p.in_hi || !wide || p.res || p.res_hi || (p.M & 3) || p.M != 4 * p.B * (p.OH / 2) * (p.OW / 2) ||
-        (p.Cout >= 128 && p.pipelined != 3 && p.pipelined != 6 && p.pipelined != 7) || (p.Cout > 64 && p.Cout < 128))
+        (p.Cout >= 128 && p.pipelined != 3) || (p.Cout > 64 && p.Cout < 128))
       return hipErrorInvalidValue;
   }
   if (!p.w_hi || !p.w_lo || p.Cin % XBK != 0 || p.K != p.KH * p.KW * p.Cin + p.Cin2 || p.m_base != 0) return hipErrorInvalidValue;
   // a second (1x1) input along K: the DMA issuer of the pipelined 16x16x32 kernel only (no tail hand-over, not the patch forms)
-  if (p.Cin2 && (!p.in_hi || !p.in2_hi || p.Cin2 % XBK || p.Cout < 128 || (p.pipelined != 3 && p.pipelined != 6 && p.pipelined != 7) || p.pool2 ||
-                 p.OH != p.H || p.OW != p.W))
+  if (p.Cin2 && (!p.in_hi || !p.in2_hi || p.Cin2 % XBK || p.Cout < 128 || p.pipelined != 3 || p.pool2 || p.OH != p.H || p.OW != p.W))
     return hipErrorInvalidValue;
   if (p.f16 && (!p.in_hi || (p.Cout >= 128 && p.pipelined != 3))) return hipErrorInvalidValue;  // fp16 records: split-record kernels only
   const int mt = (p.M + 127) / 128;
@@ -496,9 +482,8 @@ hipError_t launch_conv_bf16x3(const ConvP& p, hipStream_t s) {
       // (conv0_2: 9 K-steps per tile) uses to overlap one tile's prologue / epilogue with another's MFMAs whenever the
       // grid is not capped (no slots reserved for the decode stream): 1.35 -> 0.96 ms alone.  With a cap it stays at
       // the cap (three per CU measured 0.5 % slower end to end in pipelined serving).
-      const int grid3 = grid;
-      if (p.f16) hipLaunchKernelGGL(conv_f16x2g_128x64, dim3(grid3), dim3(256), 0, s, p);
-      else hipLaunchKernelGGL(conv_bf16x3g_128x64, dim3(grid3), dim3(256), 0, s, p);
+      if (p.f16) hipLaunchKernelGGL(conv_f16x2g_128x64, dim3(grid), dim3(256), 0, s, p);
+      else hipLaunchKernelGGL(conv_bf16x3g_128x64, dim3(grid), dim3(256), 0, s, p);
     } else {
       // 8 waves per tile (4 per SIMD at two blocks per CU) measured 1-2 % faster end to end than 4 waves
       static const bool w4 = D2T_PROBE_ENV("D2T_BF16X3_WAVES") == 4;
@@ -523,6 +508,9 @@ hipError_t launch_conv_bf16x3(const ConvP& p, hipStream_t s) {
   }
   return hipGetLastError();
 }
+
+// grid of the element-wise kernels below: 256 threads per block, grid-stride loops, at most `cap` blocks
+static dim3 grid_1d(size_t n, size_t cap) { return dim3((unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap)); }
 
 __global__ void split_bf16_kernel(const float* __restrict__ w, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
                                   size_t n) {
@@ -580,28 +568,28 @@ hipError_t launch_split_act(const float* x, uint16_t* planes, size_t rows, int C
   const size_t n = rows * C;
   if (C % 32 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
     const size_t n8 = n / 8;
-    hipLaunchKernelGGL(split_act8_kernel, dim3((unsigned)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192)), dim3(256), 0, s, x,
+    hipLaunchKernelGGL(split_act8_kernel, grid_1d(n8, 8192), dim3(256), 0, s, x,
                        planes, n8, f16);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(split_act_kernel, dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(split_act_kernel, grid_1d(n, 4096), dim3(256), 0,
                      s, x, planes, rows, C, f16);
   return hipGetLastError();
 }
 hipError_t launch_merge_act(const uint16_t* planes, float* x, size_t rows, int C, hipStream_t s, int f16) {
   const size_t n = rows * C;
-  hipLaunchKernelGGL(merge_act_kernel, dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(merge_act_kernel, grid_1d(n, 4096), dim3(256), 0,
                      s, planes, x, rows, C, f16);
   return hipGetLastError();
 }
 
 hipError_t launch_split_f16(const float* w, uint16_t* hi, uint16_t* lo, size_t n, hipStream_t s) {
-  hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(split_f16_kernel, grid_1d(n, 4096), dim3(256), 0,
                      s, w, hi, lo, n);
   return hipGetLastError();
 }
 hipError_t launch_split_bf16(const float* w, uint16_t* hi, uint16_t* lo, size_t n, hipStream_t s) {
-  hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(split_bf16_kernel, grid_1d(n, 4096), dim3(256), 0,
                      s, w, hi, lo, n);
   return hipGetLastError();
 }

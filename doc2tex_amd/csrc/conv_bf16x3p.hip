@@ -43,8 +43,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 namespace {
 constexpr int PBK = 32;   // K-step
 constexpr int PROW = 64;  // bytes per LDS row of one plane (32 bf16)
-__device__ __forceinline__ int pswz(int row, int c) { return c ^ ((row >> 2) & 3); }
-// the same for the 16x16x32 fragment pattern (lane -> row lane & 15, 16-byte k-chunk lane >> 4): the 16-lane service groups
+// swz_chunk (conv_common.h) for the 16x16x32 fragment pattern (lane -> row lane & 15, 16-byte k-chunk lane >> 4): the 16-lane service groups
 // of a ds_read_b128 then pair rows 0-3 / 12-15 at chunk c with rows 4-11 at chunk c ^ 1, and XOR-ing bit 1 of the chunk
 // with bit 3 of the row spreads every group over all 64 banks (tools/probe/lds_swizzle_check.py)
 __device__ __forceinline__ int pswz16(int row, int c) { return c ^ ((row >> 2) & 2); }
@@ -69,185 +68,6 @@ __device__ unsigned long long d2t_conv_phase[16];
 #define CONV_PHASE_TILE() do { } while (0)
 #endif
 }  // namespace
-
-// Second phase of the wide epilogue (conv_common.h conv_epilogue_wide), run by EVERY thread of the block, loader waves
-// included: the fp32 [BM][BN] tile is in LDS (32-float column blocks XOR-ed with bit 2 of the row); a thread owns four
-// consecutive channels of one output row.  Same arithmetic per element in the same order as conv_epilogue:
-// v = acc + bias; v += res | (res_hi + res_lo); activation; split.
-template <int BM, int BN, int NT, int ROWS = BM>  // ROWS < BM: only the first ROWS rows of the tile are real output rows
-__device__ __forceinline__ void epilogue_rows(const ConvP& p, const unsigned char* smem, int m0, int n0, int tid) {
-  const float* tile = reinterpret_cast<const float*>(smem);
-  constexpr int OPR = BN / 8;  // 8-channel octets per tile row: 16-byte accesses to each half of a record
-  const uint16_t* __restrict__ res_hi = p.res_hi;
-  const float* __restrict__ res = p.res;
-  const float* __restrict__ bias = p.bias;
-  uint16_t* __restrict__ out_hi = p.out_hi;
-  float* __restrict__ out = p.out;
-#pragma unroll 2
-  for (int idx = tid; idx < ROWS * OPR; idx += NT) {
-    const int row = idx / OPR, o = idx % OPR;
-    const int m = m0 + row, n = n0 + o * 8;
-    if (m >= p.M || n >= p.Cout) continue;
-    const int col = (o * 8) ^ (((row >> 2) & 1) << 5);
-    const float4 a0 = *reinterpret_cast<const float4*>(tile + row * BN + col);
-    const float4 a1 = *reinterpret_cast<const float4*>(tile + row * BN + col + 4);
-    float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    if (bias) {
-      const float4 b0 = *reinterpret_cast<const float4*>(bias + n), b1 = *reinterpret_cast<const float4*>(bias + n + 4);
-      v[0] += b0.x, v[1] += b0.y, v[2] += b0.z, v[3] += b0.w, v[4] += b1.x, v[5] += b1.y, v[6] += b1.z, v[7] += b1.w;
-    }
-    const size_t off = (size_t)m * p.Cout + n;
-    const size_t pi = plane_idx((size_t)m, n, p.Cout);
-    if (res) {
-      const float4 r0 = *reinterpret_cast<const float4*>(res + off), r1 = *reinterpret_cast<const float4*>(res + off + 4);
-      v[0] += r0.x, v[1] += r0.y, v[2] += r0.z, v[3] += r0.w, v[4] += r1.x, v[5] += r1.y, v[6] += r1.z, v[7] += r1.w;
-    }
-    if (res_hi) {
-      const uint4 rh = *reinterpret_cast<const uint4*>(res_hi + pi);
-      const unsigned h[4] = {rh.x, rh.y, rh.z, rh.w};
-      const int rf = res_fmt(p);
-      if (rf == REC_F16) {  // one fp16 per element: the value is the hi half
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[2 * e] += f16_bits_to_f32((uint16_t)(h[e] & 0xFFFFu));
-          v[2 * e + 1] += f16_bits_to_f32((uint16_t)(h[e] >> 16));
-        }
-      } else {
-        const uint4 rl = *reinterpret_cast<const uint4*>(res_hi + pi + 32);
-        const unsigned l[4] = {rl.x, rl.y, rl.z, rl.w};
-        if (rf == REC_F16_PAIR) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[2 * e] += f16_bits_to_f32((uint16_t)(h[e] & 0xFFFFu)) + f16_bits_to_f32((uint16_t)(l[e] & 0xFFFFu));
-            v[2 * e + 1] += f16_bits_to_f32((uint16_t)(h[e] >> 16)) + f16_bits_to_f32((uint16_t)(l[e] >> 16));
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[2 * e] += __uint_as_float(h[e] << 16) + __uint_as_float(l[e] << 16);
-            v[2 * e + 1] += __uint_as_float(h[e] & 0xFFFF0000u) + __uint_as_float(l[e] & 0xFFFF0000u);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = apply_act(v[e], p.act);
-    if (out_hi) {
-      uint16_t hi[8], lo[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) split_rec(v[e], hi[e], lo[e], out_fmt(p));
-      uint4 oh, ol;
-      oh.x = (unsigned)hi[0] | ((unsigned)hi[1] << 16), oh.y = (unsigned)hi[2] | ((unsigned)hi[3] << 16);
-      oh.z = (unsigned)hi[4] | ((unsigned)hi[5] << 16), oh.w = (unsigned)hi[6] | ((unsigned)hi[7] << 16);
-      ol.x = (unsigned)lo[0] | ((unsigned)lo[1] << 16), ol.y = (unsigned)lo[2] | ((unsigned)lo[3] << 16);
-      ol.z = (unsigned)lo[4] | ((unsigned)lo[5] << 16), ol.w = (unsigned)lo[6] | ((unsigned)lo[7] << 16);
-      *reinterpret_cast<uint4*>(out_hi + pi) = oh;
-      if (out_fmt(p) != REC_F16) *reinterpret_cast<uint4*>(out_hi + pi + 32) = ol;  // (one-fp16 records: the lo half is never read)
-    } else {
-      *reinterpret_cast<float4*>(out + off) = make_float4(v[0], v[1], v[2], v[3]);
-      *reinterpret_cast<float4*>(out + off + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
-  }
-}
-
-// The fused 2x2 max-pool form of epilogue_rows (ConvP::pool2): tile rows 4r .. 4r+3 are one pooling window (pooled row order of
-// the GEMM's rows); a thread owns eight channels of one POOLED row.  max, then bias, then activation -- the pool of the
-// activated outputs, bit for bit (both monotone); no residual (the layers in front of a pool have none).
-template <int BM, int BN, int NT>
-__device__ __forceinline__ void epilogue_rows_pool(const ConvP& p, const unsigned char* smem, int m0, int n0, int tid) {
-  const float* tile = reinterpret_cast<const float*>(smem);
-  constexpr int OPR = BN / 8;
-  const float* __restrict__ bias = p.bias;
-  uint16_t* __restrict__ out_hi = p.out_hi;
-  float* __restrict__ out = p.out;
-  for (int idx = tid; idx < (BM / 4) * OPR; idx += NT) {
-    const int pr = idx / OPR, o = idx % OPR;
-    const int m = m0 + 4 * pr, n = n0 + o * 8;
-    if (m >= p.M || n >= p.Cout) continue;
-    const int col = (o * 8) ^ ((pr & 1) << 5);  // rows 4 pr .. 4 pr + 3 share (row >> 2) & 1 = pr & 1
-    float v[8];
-    {
-      const float4 a0 = *reinterpret_cast<const float4*>(tile + (4 * pr) * BN + col);
-      const float4 a1 = *reinterpret_cast<const float4*>(tile + (4 * pr) * BN + col + 4);
-      v[0] = a0.x, v[1] = a0.y, v[2] = a0.z, v[3] = a0.w, v[4] = a1.x, v[5] = a1.y, v[6] = a1.z, v[7] = a1.w;
-    }
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-      const float4 a0 = *reinterpret_cast<const float4*>(tile + (4 * pr + k) * BN + col);
-      const float4 a1 = *reinterpret_cast<const float4*>(tile + (4 * pr + k) * BN + col + 4);
-      v[0] = fmaxf(v[0], a0.x), v[1] = fmaxf(v[1], a0.y), v[2] = fmaxf(v[2], a0.z), v[3] = fmaxf(v[3], a0.w);
-      v[4] = fmaxf(v[4], a1.x), v[5] = fmaxf(v[5], a1.y), v[6] = fmaxf(v[6], a1.z), v[7] = fmaxf(v[7], a1.w);
-    }
-    if (bias) {
-      const float4 b0 = *reinterpret_cast<const float4*>(bias + n), b1 = *reinterpret_cast<const float4*>(bias + n + 4);
-      v[0] += b0.x, v[1] += b0.y, v[2] += b0.z, v[3] += b0.w, v[4] += b1.x, v[5] += b1.y, v[6] += b1.z, v[7] += b1.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = apply_act(v[e], p.act);
-    const size_t mp = (size_t)(m >> 2);
-    const size_t pi = plane_idx(mp, n, p.Cout);
-    if (out_hi) {
-      uint16_t hi[8], lo[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) split_rec(v[e], hi[e], lo[e], out_fmt(p));
-      uint4 oh, ol;
-      oh.x = (unsigned)hi[0] | ((unsigned)hi[1] << 16), oh.y = (unsigned)hi[2] | ((unsigned)hi[3] << 16);
-      oh.z = (unsigned)hi[4] | ((unsigned)hi[5] << 16), oh.w = (unsigned)hi[6] | ((unsigned)hi[7] << 16);
-      ol.x = (unsigned)lo[0] | ((unsigned)lo[1] << 16), ol.y = (unsigned)lo[2] | ((unsigned)lo[3] << 16);
-      ol.z = (unsigned)lo[4] | ((unsigned)lo[5] << 16), ol.w = (unsigned)lo[6] | ((unsigned)lo[7] << 16);
-      *reinterpret_cast<uint4*>(out_hi + pi) = oh;
-      if (out_fmt(p) != REC_F16) *reinterpret_cast<uint4*>(out_hi + pi + 32) = ol;  // (one-fp16 records: the lo half is never read)
-    } else {
-      *reinterpret_cast<float4*>(out + mp * p.Cout + n) = make_float4(v[0], v[1], v[2], v[3]);
-      *reinterpret_cast<float4*>(out + mp * p.Cout + n + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
-  }
-}
-
-// Element-wise epilogue of one wave's MI x NJ grid of 16x16 accumulators (the layers the wide epilogue does not take: row
-// remap, positional add, Cout % 32 != 0): same arithmetic per element as conv_epilogue.
-template <int MI, int NJ>
-__device__ __forceinline__ void conv_epilogue16(const ConvP& p, float __attribute__((ext_vector_type(4))) (&acc)[MI][NJ], int mw, int nw,
-                                                int r, int q) {
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int n = nw + j * 16 + r;
-    if (n >= p.Cout) continue;
-    const float bias = p.bias ? p.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int m = mw + i * 16 + 4 * q + reg;
-        if (m >= p.M) continue;
-        float v = acc[i][j][reg] + bias;
-        size_t row = (size_t)m;
-        int in_img = 0;
-        if (p.rows_per_img > 0) {
-          const int img = m / p.rows_per_img;
-          in_img = m - img * p.rows_per_img;
-          row = (size_t)img * p.img_stride + p.row_off + in_img;
-        }
-        const size_t off = row * p.Cout + n;
-        if (p.res) v += p.res[off];
-        if (p.res_hi) {
-          const size_t ri = plane_idx(row, n, p.Cout);
-          v += join_rec(p.res_hi[ri], p.res_hi[ri + 32], res_fmt(p));
-        }
-        v = apply_act(v, p.act);
-        if (p.row_add) v += p.row_add[(size_t)(p.row_add_off + in_img) * p.Cout + n];
-        if (p.out_hi) {
-          uint16_t hi, lo;
-          split_rec(v, hi, lo, out_fmt(p));
-          const size_t oi = plane_idx(row, n, p.Cout);
-          p.out_hi[oi] = hi;
-          p.out_hi[oi + 32] = lo;
-        } else {
-          p.out[off] = v;
-        }
-      }
-  }
-}
 
 // The vector-memory side of a tile for ONE issuing wave: which 16-row pieces of the A / B planes it copies, their per-lane
 // source addresses (XOR-swizzled k-chunk applied on the SOURCE: the LDS destination of a wave's LDS-DMA is linear) and the
@@ -302,7 +122,7 @@ struct DmaIssuer {
 #pragma unroll
     for (int j = 0; j < BJ; ++j) {
       const int row = (lw * BJ + j) * 16 + lr;
-      const int c = S16 ? pswz16(row, pos) : pswz(row, pos);
+      const int c = S16 ? pswz16(row, pos) : swz_chunk(row, pos);
       const int n = n0 + row;
       const bool ok = n < p.Cout;
       b_hi[j] = ok ? p.w_hi + (size_t)n * p.K + c * 8 : nullptr;
@@ -355,8 +175,6 @@ struct DmaIssuer {
 // rounding; every kernel that may compute rows of the same layer must use the same shape -- see launch_conv_bf16x3p).
 // The stagger splits a K-step by ROW BLOCKS (first two of A, then the other two) since it can no longer be split by k:
 // waves 4-7 carry the B fragments and the second pair of A fragments across the barrier.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 
 // F16 (ConvP::f16, fp16x2 mode): A = the fp16 hi halves of the records only (12 instead of 16 fragment reads, 8 instead of
@@ -402,7 +220,7 @@ __device__ __forceinline__ void conv_bf16x3p16_body(const ConvP& p, unsigned cha
       if (ABL == 4) wait_vm<0>();
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_s_barrier();
-      if (wide_epilogue_ok(p)) { if (p.pool2) epilogue_rows_pool<BM, BN, NT>(p, smem, m0, n0, tid); else epilogue_rows<BM, BN, NT>(p, smem, m0, n0, tid); }
+      if (wide_epilogue_ok(p)) { if (p.pool2) tile_rows_epilogue<Epi::pool, 8, BM, BN, NT>(p, smem, m0, n0, tid); else tile_rows_epilogue<Epi::lean, 8, BM, BN, NT>(p, smem, m0, n0, tid); }
       __builtin_amdgcn_s_barrier();
       continue;
     }
@@ -516,28 +334,17 @@ __device__ __forceinline__ void conv_bf16x3p16_body(const ConvP& p, unsigned cha
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every wave is done with the last stages: the staging area becomes the epilogue's fp32 tile
     CONV_PHASE(3);  // waiting for the other waves (staggered partners finish half a K-step later)
-    // C/D map of v_mfma_f32_16x16x32: col = lane & 15 -> n, row = 4 * (lane >> 4) + reg -> m
     if (wide_epilogue_ok(p)) {  // block-uniform
-      float* tile_f = reinterpret_cast<float*>(smem);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            const int row = wm * WTM + i * 16 + 4 * q + reg;
-            const int col = (wn * WTN + j * 16 + r) ^ (((row >> 2) & 1) << 5);
-            tile_f[row * BN + col] = acc[i][j][reg];
-          }
+      acc_to_tile<Map16, BN>(acc, reinterpret_cast<float*>(smem), wm * WTM, wn * WTN, r, q);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       CONV_PHASE(4);  // accumulators to the LDS tile + barrier
-      if (p.pool2) epilogue_rows_pool<BM, BN, NT>(p, smem, m0, n0, tid);
-      else epilogue_rows<BM, BN, NT>(p, smem, m0, n0, tid);
+      if (p.pool2) tile_rows_epilogue<Epi::pool, 8, BM, BN, NT>(p, smem, m0, n0, tid);
+      else tile_rows_epilogue<Epi::lean, 8, BM, BN, NT>(p, smem, m0, n0, tid);
       CONV_PHASE(5);  // this thread's rows: LDS reads, bias / residual / activation / split, stores issued
-    } else {
+    } else {  // (row remap, positional add, Cout % 32 != 0)
       __builtin_amdgcn_s_barrier();
-      conv_epilogue16<MI, NJ>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, q);
+      conv_epilogue<Map16, ElemThreeWay>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, q);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // the tile is staging memory again (next tile's LDS-DMA)
@@ -603,7 +410,7 @@ hipError_t launch_conv_bf16x3p(const ConvP& p, hipStream_t s) {
       return hipErrorInvalidDevice;
     cus = n;
   }
-  if (p.pipelined != 3) return hipErrorInvalidValue;
+  if (p.pipelined != 3 || p.store_mode != STORE_ROWS) return hipErrorInvalidValue;  // (no head-split store in this kernel's epilogues)
   ConvP q = p;
   q.wave_prio = D2T_PROBE_ENV("D2T_CONV_PRIO");
   const int nt = (p.Cout + 127) / 128;

@@ -5,6 +5,7 @@
 namespace d2t {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+using f32x4v = __attribute__((ext_vector_type(4))) float;
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   if (act == ACT_RELU) return fmaxf(v, 0.f);
@@ -46,23 +47,73 @@ __device__ __forceinline__ float join_rec(uint16_t hi, uint16_t lo, int fmt) {
   if (fmt == REC_BF16) return bf16_bits_to_f32(hi) + bf16_bits_to_f32(lo);
   return fmt == REC_F16_PAIR ? f16_bits_to_f32(hi) + f16_bits_to_f32(lo) : f16_bits_to_f32(hi);
 }
-// four consecutive elements: rh / rl = the 8-byte hi / lo words of the record
-__device__ __forceinline__ void add_rec4(float (&v)[4], const uint2 rh, const uint2 rl, int fmt) {
-  if (fmt != REC_BF16) {
-    const unsigned h[2] = {rh.x, rh.y}, l[2] = {rl.x, rl.y};
+// W (4 | 8) consecutive elements of a record, W / 2 packed words per half.  `rec` points at the hi half; the lo half lies 32
+// elements further.
+template <int W>
+using rec_words = unsigned __attribute__((ext_vector_type(W / 2)));
+// residual add: v += hi (+ lo).  One-fp16 records: the value is the hi half, the lo half is not read.
+template <int W>
+__device__ __forceinline__ void add_rec(float (&v)[W], const uint16_t* rec, int fmt) {
+  const rec_words<W> h = *reinterpret_cast<const rec_words<W>*>(rec);
+  if (fmt == REC_F16) {
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      float a = f16_bits_to_f32((uint16_t)(h[e] & 0xFFFFu)), b = f16_bits_to_f32((uint16_t)(h[e] >> 16));
-      if (fmt == REC_F16_PAIR) { a += f16_bits_to_f32((uint16_t)(l[e] & 0xFFFFu)); b += f16_bits_to_f32((uint16_t)(l[e] >> 16)); }
-      v[2 * e] += a;
-      v[2 * e + 1] += b;
+    for (int e = 0; e < W / 2; ++e) {
+      v[2 * e] += f16_bits_to_f32((uint16_t)(h[e] & 0xFFFFu));
+      v[2 * e + 1] += f16_bits_to_f32((uint16_t)(h[e] >> 16));
+    }
+    return;
+  }
+  const rec_words<W> l = *reinterpret_cast<const rec_words<W>*>(rec + 32);
+  if (fmt == REC_F16_PAIR) {
+#pragma unroll
+    for (int e = 0; e < W / 2; ++e) {
+      v[2 * e] += f16_bits_to_f32((uint16_t)(h[e] & 0xFFFFu)) + f16_bits_to_f32((uint16_t)(l[e] & 0xFFFFu));
+      v[2 * e + 1] += f16_bits_to_f32((uint16_t)(h[e] >> 16)) + f16_bits_to_f32((uint16_t)(l[e] >> 16));
     }
   } else {
-    v[0] += __uint_as_float(rh.x << 16) + __uint_as_float(rl.x << 16);
-    v[1] += __uint_as_float(rh.x & 0xFFFF0000u) + __uint_as_float(rl.x & 0xFFFF0000u);
-    v[2] += __uint_as_float(rh.y << 16) + __uint_as_float(rl.y << 16);
-    v[3] += __uint_as_float(rh.y & 0xFFFF0000u) + __uint_as_float(rl.y & 0xFFFF0000u);
+#pragma unroll
+    for (int e = 0; e < W / 2; ++e) {
+      v[2 * e] += __uint_as_float(h[e] << 16) + __uint_as_float(l[e] << 16);
+      v[2 * e + 1] += __uint_as_float(h[e] & 0xFFFF0000u) + __uint_as_float(l[e] & 0xFFFF0000u);
+    }
   }
+}
+// split, pack and store.  The 8-wide store skips the lo half of one-fp16 records (it is never read); the 4-wide store
+// writes its zeros.
+template <int W>
+__device__ __forceinline__ void store_rec(const float (&v)[W], uint16_t* rec, int fmt) {
+  rec_words<W> oh, ol;
+#pragma unroll
+  for (int e = 0; e < W / 2; ++e) {
+    uint16_t h0, l0, h1, l1;
+    split_rec(v[2 * e], h0, l0, fmt);
+    split_rec(v[2 * e + 1], h1, l1, fmt);
+    oh[e] = (unsigned)h0 | ((unsigned)h1 << 16);
+    ol[e] = (unsigned)l0 | ((unsigned)l1 << 16);
+  }
+  *reinterpret_cast<rec_words<W>*>(rec) = oh;
+  if (W == 4 || fmt != REC_F16) *reinterpret_cast<rec_words<W>*>(rec + 32) = ol;
+}
+// W consecutive floats (16-byte accesses): the epilogue tile in LDS, bias / residual / positional rows, fp32 output rows
+template <int W>
+__device__ __forceinline__ void load_tile(const float* src, float (&v)[W]) {
+#pragma unroll
+  for (int e = 0; e < W; e += 4) {
+    const float4 a = *reinterpret_cast<const float4*>(src + e);
+    v[e] = a.x, v[e + 1] = a.y, v[e + 2] = a.z, v[e + 3] = a.w;
+  }
+}
+template <int W>
+__device__ __forceinline__ void add_row(float (&v)[W], const float* src) {
+  float a[W];
+  load_tile<W>(src, a);
+#pragma unroll
+  for (int e = 0; e < W; ++e) v[e] += a[e];
+}
+template <int W>
+__device__ __forceinline__ void store_row(const float (&v)[W], float* dst) {
+#pragma unroll
+  for (int e = 0; e < W; e += 4) *reinterpret_cast<float4*>(dst + e) = make_float4(v[e], v[e + 1], v[e + 2], v[e + 3]);
 }
 
 // Split-activation layout ("planes"): per row and per 32-channel group one 128-byte record
@@ -71,6 +122,10 @@ __device__ __forceinline__ void add_rec4(float (&v)[4], const uint2 rh, const ui
 __device__ __forceinline__ size_t plane_idx(size_t row, int c, int C) {
   return (row * C + (size_t)(c & ~31)) * 2 + (c & 31);
 }
+
+// LDS rows of one operand plane are 64 bytes (32 x 16 bit); the 16-byte k-chunk index is XOR-swizzled with (row >> 2) & 3 so
+// that the 16-lane groups of a ds_read_b128 of the 32x32x16 fragment pattern touch all 64 banks exactly once
+__device__ __forceinline__ int swz_chunk(int row, int c) { return c ^ ((row >> 2) & 3); }
 
 // GEMM row m -> output pixel (b, oh, ow): row-major, or pooled order when a 2x2 max-pool is fused (ConvP::pool2)
 __device__ __forceinline__ void conv_row_coords(const ConvP& p, int m, int& b, int& oh, int& ow) {
@@ -96,21 +151,52 @@ __device__ __forceinline__ int xcd_logical_tile() {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
 }
 
-// Epilogue of one wave's MI x NJ grid of 32x32 accumulators whose top-left output element is
-// (mw, nw): bias (folded BN), residual, activation, positional-table add, row / head-split remaps.
-// C/D map of v_mfma_*_32x32*: col = lane&31 -> n, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) -> m.
-// (Records here are bf16 hi | lo or, with ConvP::f16, one fp16: the 32x32 kernels never see the mixed-precision formats
-// ConvP::out_fmt / res_fmt -- launch_conv / launch_conv_bf16x3 reject them -- and the three-way format code costs the fp32
-// kernel, which runs at the VGPR limit, 700 bytes of scratch per lane and half its speed.)
-template <int MI, int NJ>
-__device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x16 (&acc)[MI][NJ], int mw, int nw, int r, int h) {
+// C/D register maps of the MFMAs: row of register `reg` of a lane in the result block whose first row is `base`.  A lane's
+// column in the block is lc, its row group lr -- the kernels hold both already (their fragment reads use them), and
+// recomputing them from the lane id here costs the 16x16x32 tail kernels 4 VGPRs and one wave of occupancy.
+struct Map32 {  // v_mfma_*_32x32*: lc = lane & 31 -> n, lr = lane >> 5, row = (reg & 3) + 8 * (reg >> 2) + 4 * lr -> m
+  using acc_t = f32x16;
+  static constexpr int BLK = 32, REGS = 16;
+  static __device__ __forceinline__ int row(int base, int lr, int reg) { return base + (reg & 3) + 8 * (reg >> 2) + 4 * lr; }
+};
+struct Map16 {  // v_mfma_f32_16x16x32_*: lc = lane & 15 -> n, lr = lane >> 4, row = 4 * lr + reg -> m
+  using acc_t = f32x4v;
+  static constexpr int BLK = 16, REGS = 4;
+  static __device__ __forceinline__ int row(int base, int lr, int reg) { return base + 4 * lr + reg; }
+};
+
+// What the element-wise epilogue below compiles in, by what a kernel's launcher lets through.
+// The 32x32 kernels: records are bf16 hi | lo or, with ConvP::f16, one fp16 -- they never see the mixed-precision formats
+// ConvP::out_fmt / res_fmt (launch_conv / launch_conv_bf16x3 reject them), and the three-way format code costs the fp32
+// kernel, which runs at the VGPR limit, 700 bytes of scratch per lane and half its speed.
+struct ElemTwoWay {
+  static constexpr bool kv_store = true;
+  static __device__ __forceinline__ float res_at(const ConvP& p, size_t ri) {
+    return p.f16 ? f16_bits_to_f32(p.res_hi[ri]) : bf16_bits_to_f32(p.res_hi[ri]) + bf16_bits_to_f32(p.res_hi[ri + 32]);
+  }
+  static __device__ __forceinline__ void split(const ConvP& p, float v, uint16_t& hi, uint16_t& lo) {
+    if (p.f16) { hi = f32_to_f16_bits(v); lo = 0; } else split_f32(v, hi, lo);
+  }
+};
+// The pipelined 16x16x32 kernels: all three record formats; no head-split store (launch_conv_bf16x3p rejects it).
+struct ElemThreeWay {
+  static constexpr bool kv_store = false;
+  static __device__ __forceinline__ float res_at(const ConvP& p, size_t ri) { return join_rec(p.res_hi[ri], p.res_hi[ri + 32], res_fmt(p)); }
+  static __device__ __forceinline__ void split(const ConvP& p, float v, uint16_t& hi, uint16_t& lo) { split_rec(v, hi, lo, out_fmt(p)); }
+};
+
+// Element-wise epilogue of one wave's MI x NJ grid of accumulator blocks whose top-left output element is (mw, nw): bias
+// (folded BN), residual, activation, positional-table add, row / head-split remaps.  The layers the tile epilogue below
+// does not take (Cout % 32 != 0, head_dim % 4 != 0; in the LDS-DMA kernels also every remap).
+template <class Map, class Elem, int MI, int NJ>
+__device__ __forceinline__ void conv_epilogue(const ConvP& p, typename Map::acc_t (&acc)[MI][NJ], int mw, int nw, int lc, int lr) {
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    const int n = nw + j * 32 + r;
+    const int n = nw + j * Map::BLK + lc;
     if (n >= p.Cout) continue;
     const float bias = p.bias ? p.bias[n] : 0.f;
     int slab = 0, head = 0, e = 0;
-    if (p.store_mode == STORE_KV) {
+    if (Elem::kv_store && p.store_mode == STORE_KV) {
       const int d = p.kv_heads * p.kv_hd;
       slab = n / d;
       const int within = n - slab * d;
@@ -120,11 +206,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x16 (&acc)[MI][
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int m = mw + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+      for (int reg = 0; reg < Map::REGS; ++reg) {
+        const int m = Map::row(mw + i * Map::BLK, lr, reg);
         if (m >= p.M) continue;
         float v = acc[i][j][reg] + bias;
-        if (p.store_mode == STORE_KV) {
+        if (Elem::kv_store && p.store_mode == STORE_KV) {
           const int bb = m / p.kv_T, jj = m - bb * p.kv_T;
           p.out[((((size_t)slab * p.kv_B + bb) * p.kv_heads + head) * p.kv_T + jj) * p.kv_hd + e] = v;
           continue;
@@ -138,15 +224,12 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x16 (&acc)[MI][
         }
         const size_t off = row * p.Cout + n;
         if (p.res) v += p.res[off];
-        if (p.res_hi) {
-          const size_t ri = plane_idx(row, n, p.Cout);
-          v += p.f16 ? f16_bits_to_f32(p.res_hi[ri]) : bf16_bits_to_f32(p.res_hi[ri]) + bf16_bits_to_f32(p.res_hi[ri + 32]);
-        }
+        if (p.res_hi) v += Elem::res_at(p, plane_idx(row, n, p.Cout));
         v = apply_act(v, p.act);
         if (p.row_add) v += p.row_add[(size_t)(p.row_add_off + in_img) * p.Cout + n];
         if (p.out_hi) {
           uint16_t hi, lo;
-          if (p.f16) { hi = f32_to_f16_bits(v); lo = 0; } else split_f32(v, hi, lo);
+          Elem::split(p, v, hi, lo);
           const size_t oi = plane_idx(row, n, p.Cout);
           p.out_hi[oi] = hi;
           p.out_hi[oi + 32] = lo;
@@ -158,209 +241,121 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x16 (&acc)[MI][
   }
 }
 
-// Wide epilogue for block tiles whose LDS staging area is free after the K loop (the split-bf16 LDS-DMA kernel): the
-// accumulators go through LDS once so that a thread afterwards owns FOUR CONSECUTIVE CHANNELS of one output row, and the
-// residual is read and the result written with 8/16-byte accesses instead of one 2-byte (or 4-byte) access per element --
-// the element-wise epilogue above costs a residual layer ~10 % of its run time and dominates the short-K layers.
+// Tile epilogue for block tiles whose LDS staging area is free after the K loop: the accumulators go through LDS once so
+// that a thread afterwards owns W (4 | 8) CONSECUTIVE CHANNELS of one output row, and the residual is read and the result
+// written with 8/16-byte accesses instead of one 2-byte (or 4-byte) access per element -- the element-wise epilogue above
+// costs a residual layer ~10 % of its run time and dominates the short-K layers.
 // Same arithmetic per element, in the same order, as conv_epilogue: v = acc + bias; v += res | (res_hi + res_lo);
-// activation; split.  Requires: no row remap, no positional add, no head-split store, Cout % 32 == 0.
+// activation; positional add; split.
 // LDS tile: fp32 [BM][BN], the 32-float column block XOR-ed with bit 2 of the row so that the two half-waves of an MFMA
 // result (rows 4 apart, same columns) hit different banks.
+__device__ __forceinline__ int tile_col(int row, int col) { return col ^ (((row >> 2) & 1) << 5); }
+
+// phase one: one wave's MI x NJ accumulator blocks, top-left tile element (wrow, wcol), into the tile
+template <class Map, int BN, int MI, int NJ>
+__device__ __forceinline__ void acc_to_tile(typename Map::acc_t (&acc)[MI][NJ], float* tile, int wrow, int wcol, int lc, int lr) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int reg = 0; reg < Map::REGS; ++reg) {
+        const int row = Map::row(wrow + i * Map::BLK, lr, reg);
+        tile[row * BN + tile_col(row, wcol + j * Map::BLK + lc)] = acc[i][j][reg];
+      }
+}
+
+// The three forms of phase two:
+//   lean  no row remap, no positional add, no head-split store (wide_epilogue_ok): the LDS-DMA kernels;
+//   pool  lean with the fused 2x2 max-pool (ConvP::pool2): tile rows 4r .. 4r+3 are one pooling window (pooled row order of
+//         the GEMM's rows), a thread owns W channels of one POOLED row.  max, then bias, then activation = the pool of the
+//         activated convolution outputs (both monotone), bit for bit; no residual (the layers in front of a pool have none);
+//   full  with the row remap (rows_per_img), the positional-table add and the head-split K/V store, for the kernels whose
+//         register budget does not matter (the on-the-fly split-bf16 kernel, the fp32 kernel).  Kept out of the lean form
+//         on purpose: with the remap code compiled in, the split-bf16 LDS-DMA kernel needs 107-121 VGPRs instead of 101;
+//         above 104 a decode wave no longer fits on a SIMD next to four convolution waves and the decode streams starve
+//         (measured: 1139 instead of 1210 formulas/s).
+// All need Cout % 32 == 0; the head-split store also head_dim % W == 0.
+enum class Epi { lean, pool, full };
 __device__ __forceinline__ bool wide_epilogue_ok(const ConvP& p) {
   return p.store_mode == STORE_ROWS && p.rows_per_img == 0 && !p.row_add && (p.Cout & 31) == 0;
 }
-
-template <int BM, int BN, int NT, int MI, int NJ>
-__device__ __forceinline__ void conv_epilogue_wide(const ConvP& p, f32x16 (&acc)[MI][NJ], unsigned char* smem, int m0, int n0,
-                                                   int wrow, int wcol, int r, int h, int tid) {
-  float* tile = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = wrow + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        const int col = (wcol + j * 32 + r) ^ (((row >> 2) & 1) << 5);
-        tile[row * BN + col] = acc[i][j][reg];
-      }
-  __syncthreads();
-  constexpr int QPR = BN / 4;  // 4-channel quads per tile row
-#pragma unroll 2  // more would cost the registers that let a decode wave share the SIMD with four convolution waves
-  for (int idx = tid; idx < BM * QPR; idx += NT) {
-    const int row = idx / QPR, q = idx % QPR;
-    const int m = m0 + row, n = n0 + q * 4;
-    if (m >= p.M || n >= p.Cout) continue;
-    const int col = (q * 4) ^ (((row >> 2) & 1) << 5);
-    const float4 a = *reinterpret_cast<const float4*>(tile + row * BN + col);
-    float v[4] = {a.x, a.y, a.z, a.w};
-    if (p.bias) {
-      const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
-      v[0] += b.x, v[1] += b.y, v[2] += b.z, v[3] += b.w;
-    }
-    const size_t off = (size_t)m * p.Cout + n;
-    const size_t pi = plane_idx((size_t)m, n, p.Cout);
-    if (p.res) {
-      const float4 rr = *reinterpret_cast<const float4*>(p.res + off);
-      v[0] += rr.x, v[1] += rr.y, v[2] += rr.z, v[3] += rr.w;
-    }
-    if (p.res_hi) {
-      const uint2 rh = *reinterpret_cast<const uint2*>(p.res_hi + pi), rl = *reinterpret_cast<const uint2*>(p.res_hi + pi + 32);
-      add_rec4(v, rh, rl, res_fmt(p));
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], p.act);
-    if (p.out_hi) {
-      uint16_t hi[4], lo[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) split_rec(v[e], hi[e], lo[e], out_fmt(p));
-      uint2 oh, ol;
-      oh.x = (unsigned)hi[0] | ((unsigned)hi[1] << 16), oh.y = (unsigned)hi[2] | ((unsigned)hi[3] << 16);
-      ol.x = (unsigned)lo[0] | ((unsigned)lo[1] << 16), ol.y = (unsigned)lo[2] | ((unsigned)lo[3] << 16);
-      *reinterpret_cast<uint2*>(p.out_hi + pi) = oh;
-      *reinterpret_cast<uint2*>(p.out_hi + pi + 32) = ol;
-    } else {
-      *reinterpret_cast<float4*>(p.out + off) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
-  __syncthreads();  // the tile is staging memory again (next tile's LDS-DMA)
-}
-
-// The fused 2x2 max-pool form (ConvP::pool2): tile rows 4r .. 4r+3 are one pooling window; a thread owns four channels of one
-// POOLED row.  max, then bias, then activation = the pool of the activated convolution outputs (both monotone), bit for bit.
-template <int BM, int BN, int NT, int MI, int NJ>
-__device__ __forceinline__ void conv_epilogue_wide_pool(const ConvP& p, f32x16 (&acc)[MI][NJ], unsigned char* smem, int m0, int n0,
-                                                        int wrow, int wcol, int r, int h, int tid) {
-  float* tile = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = wrow + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        const int col = (wcol + j * 32 + r) ^ (((row >> 2) & 1) << 5);
-        tile[row * BN + col] = acc[i][j][reg];
-      }
-  __syncthreads();
-  constexpr int QPR = BN / 4;
-  for (int idx = tid; idx < (BM / 4) * QPR; idx += NT) {
-    const int pr = idx / QPR, q = idx % QPR;
-    const int m = m0 + 4 * pr, n = n0 + q * 4;
-    if (m >= p.M || n >= p.Cout) continue;
-    const int col = (q * 4) ^ ((pr & 1) << 5);  // rows 4 pr .. 4 pr + 3 share (row >> 2) & 1 = pr & 1
-    float4 a = *reinterpret_cast<const float4*>(tile + (4 * pr) * BN + col);
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-      const float4 t = *reinterpret_cast<const float4*>(tile + (4 * pr + k) * BN + col);
-      a.x = fmaxf(a.x, t.x); a.y = fmaxf(a.y, t.y); a.z = fmaxf(a.z, t.z); a.w = fmaxf(a.w, t.w);
-    }
-    float v[4] = {a.x, a.y, a.z, a.w};
-    if (p.bias) {
-      const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
-      v[0] += b.x, v[1] += b.y, v[2] += b.z, v[3] += b.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], p.act);
-    const size_t mp = (size_t)(m >> 2);
-    const size_t pi = plane_idx(mp, n, p.Cout);
-    if (p.out_hi) {
-      uint16_t hi[4], lo[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) split_rec(v[e], hi[e], lo[e], out_fmt(p));
-      uint2 oh, ol;
-      oh.x = (unsigned)hi[0] | ((unsigned)hi[1] << 16), oh.y = (unsigned)hi[2] | ((unsigned)hi[3] << 16);
-      ol.x = (unsigned)lo[0] | ((unsigned)lo[1] << 16), ol.y = (unsigned)lo[2] | ((unsigned)lo[3] << 16);
-      *reinterpret_cast<uint2*>(p.out_hi + pi) = oh;
-      *reinterpret_cast<uint2*>(p.out_hi + pi + 32) = ol;
-    } else {
-      *reinterpret_cast<float4*>(p.out + mp * p.Cout + n) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
-  __syncthreads();
-}
-
-// The same with the row remap (rows_per_img), the positional-table add and the head-split K/V store, for the kernels whose
-// register budget does not matter (the on-the-fly split-bf16 kernel, the fp32 kernel).  Kept apart from the lean function
-// above on purpose: with the remap code compiled in, the split-bf16 LDS-DMA kernel needs 107-121 VGPRs instead of 101; above
-// 104 a decode wave no longer fits on a SIMD next to four convolution waves and the decode streams starve (measured: 1139
-// instead of 1210 formulas/s).  Requires Cout % 32 == 0 and, for the head-split store, head_dim % 4 == 0.
 __device__ __forceinline__ bool wide_epilogue_full_ok(const ConvP& p) {
   return (p.Cout & 31) == 0 && (p.store_mode == STORE_ROWS || (p.kv_hd & 3) == 0);
 }
 
-template <int BM, int BN, int NT, int MI, int NJ>
-__device__ __forceinline__ void conv_epilogue_wide_full(const ConvP& p, f32x16 (&acc)[MI][NJ], unsigned char* smem, int m0, int n0,
-                                                   int wrow, int wcol, int r, int h, int tid) {
-  float* tile = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = wrow + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        const int col = (wcol + j * 32 + r) ^ (((row >> 2) & 1) << 5);
-        tile[row * BN + col] = acc[i][j][reg];
-      }
-  __syncthreads();
-  constexpr int QPR = BN / 4;  // 4-channel quads per tile row
-#pragma unroll 2  // more would cost the registers that let a decode wave share the SIMD with four convolution waves
-  for (int idx = tid; idx < BM * QPR; idx += NT) {
-    const int row = idx / QPR, q = idx % QPR;
-    const int m = m0 + row, n = n0 + q * 4;
+// phase two, run by every thread of the block (NT; in the pipelined kernel the loader waves included): LDS reads to global
+// stores.  The caller puts a barrier in front (the tile is complete) and behind (the tile is staging memory again).
+template <Epi KIND, int W, int BM, int BN, int NT>
+__device__ __forceinline__ void tile_rows_epilogue(const ConvP& p, const unsigned char* smem, int m0, int n0, int tid) {
+  static_assert(KIND != Epi::full || W == 4, "the head-split store is checked for four channels (wide_epilogue_full_ok)");
+  const float* tile = reinterpret_cast<const float*>(smem);
+  constexpr int GPR = BN / W;                    // W-channel groups per tile row
+  constexpr int RS = KIND == Epi::pool ? 4 : 1;  // tile rows per output row
+  const uint16_t* __restrict__ res_hi = p.res_hi;
+  const float* __restrict__ res = p.res;
+  const float* __restrict__ bias = p.bias;
+  uint16_t* __restrict__ out_hi = p.out_hi;
+  float* __restrict__ out = p.out;
+  // unroll 2, not more: more would cost the registers that let a decode wave share the SIMD with four convolution waves;
+  // the pooled loop is not unrolled at all (109-115 instead of 102-108 VGPRs in the LDS-DMA kernels)
+#pragma unroll KIND == Epi::pool ? 1 : 2
+  for (int idx = tid; idx < (BM / RS) * GPR; idx += NT) {
+    const int row = RS * (idx / GPR), g = idx % GPR;
+    const int m = m0 + row, n = n0 + g * W;
     if (m >= p.M || n >= p.Cout) continue;
-    const int col = (q * 4) ^ (((row >> 2) & 1) << 5);
-    const float4 a = *reinterpret_cast<const float4*>(tile + row * BN + col);
-    float v[4] = {a.x, a.y, a.z, a.w};
-    if (p.bias) {
-      const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
-      v[0] += b.x, v[1] += b.y, v[2] += b.z, v[3] += b.w;
+    const float* src = tile + row * BN + tile_col(row, g * W);  // (rows 4 r .. 4 r + 3 share the column XOR)
+    float v[W];
+    load_tile<W>(src, v);
+    if constexpr (KIND == Epi::pool) {
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {
+        float t[W];
+        load_tile<W>(src + k * BN, t);
+#pragma unroll
+        for (int e = 0; e < W; ++e) v[e] = fmaxf(v[e], t[e]);
+      }
     }
-    if (p.store_mode == STORE_KV) {  // n -> (slab, head, e), m -> (b, j): four consecutive e of one head
-      const int d = p.kv_heads * p.kv_hd, slab = n / d, within = n - slab * d;
-      const int head = within / p.kv_hd, e = within - head * p.kv_hd;
-      const int bb = m / p.kv_T, jj = m - bb * p.kv_T;
-      *reinterpret_cast<float4*>(p.out + ((((size_t)slab * p.kv_B + bb) * p.kv_heads + head) * p.kv_T + jj) * p.kv_hd + e) =
-          make_float4(v[0], v[1], v[2], v[3]);
-      continue;
-    }
-    size_t orow = (size_t)m;
+    if (bias) add_row<W>(v, bias + n);
+    size_t orow = (size_t)(KIND == Epi::pool ? m >> 2 : m);
     int in_img = 0;
-    if (p.rows_per_img > 0) {
-      const int img = m / p.rows_per_img;
-      in_img = m - img * p.rows_per_img;
-      orow = (size_t)img * p.img_stride + p.row_off + in_img;
+    if constexpr (KIND == Epi::full) {
+      if (p.store_mode == STORE_KV) {  // n -> (slab, head, e), m -> (b, j): W consecutive e of one head
+        const int d = p.kv_heads * p.kv_hd, slab = n / d, within = n - slab * d;
+        const int head = within / p.kv_hd, e = within - head * p.kv_hd;
+        const int bb = m / p.kv_T, jj = m - bb * p.kv_T;
+        store_row<W>(v, out + ((((size_t)slab * p.kv_B + bb) * p.kv_heads + head) * p.kv_T + jj) * p.kv_hd + e);
+        continue;
+      }
+      if (p.rows_per_img > 0) {
+        const int img = m / p.rows_per_img;
+        in_img = m - img * p.rows_per_img;
+        orow = (size_t)img * p.img_stride + p.row_off + in_img;
+      }
     }
     const size_t off = orow * p.Cout + n;
     const size_t pi = plane_idx(orow, n, p.Cout);
-    if (p.res) {
-      const float4 rr = *reinterpret_cast<const float4*>(p.res + off);
-      v[0] += rr.x, v[1] += rr.y, v[2] += rr.z, v[3] += rr.w;
-    }
-    if (p.res_hi) {
-      const uint2 rh = *reinterpret_cast<const uint2*>(p.res_hi + pi), rl = *reinterpret_cast<const uint2*>(p.res_hi + pi + 32);
-      add_rec4(v, rh, rl, res_fmt(p));
+    if constexpr (KIND != Epi::pool) {
+      if (res) add_row<W>(v, res + off);
+      if (res_hi) add_rec<W>(v, res_hi + pi, res_fmt(p));
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], p.act);
-    if (p.row_add) {
-      const float4 ra = *reinterpret_cast<const float4*>(p.row_add + (size_t)(p.row_add_off + in_img) * p.Cout + n);
-      v[0] += ra.x, v[1] += ra.y, v[2] += ra.z, v[3] += ra.w;
+    for (int e = 0; e < W; ++e) v[e] = apply_act(v[e], p.act);
+    if constexpr (KIND == Epi::full) {
+      if (p.row_add) add_row<W>(v, p.row_add + (size_t)(p.row_add_off + in_img) * p.Cout + n);
     }
-    if (p.out_hi) {
-      uint16_t hi[4], lo[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) split_rec(v[e], hi[e], lo[e], out_fmt(p));
-      uint2 oh, ol;
-      oh.x = (unsigned)hi[0] | ((unsigned)hi[1] << 16), oh.y = (unsigned)hi[2] | ((unsigned)hi[3] << 16);
-      ol.x = (unsigned)lo[0] | ((unsigned)lo[1] << 16), ol.y = (unsigned)lo[2] | ((unsigned)lo[3] << 16);
-      *reinterpret_cast<uint2*>(p.out_hi + pi) = oh;
-      *reinterpret_cast<uint2*>(p.out_hi + pi + 32) = ol;
-    } else {
-      *reinterpret_cast<float4*>(p.out + off) = make_float4(v[0], v[1], v[2], v[3]);
-    }
+    if (out_hi) store_rec<W>(v, out_hi + pi, out_fmt(p));
+    else store_row<W>(v, out + off);
   }
+}
+
+// both phases for the kernels whose every wave holds accumulators (four channels per thread)
+template <Epi KIND, int BM, int BN, int NT, int MI, int NJ>
+__device__ __forceinline__ void conv_epilogue_tile(const ConvP& p, f32x16 (&acc)[MI][NJ], unsigned char* smem, int m0, int n0,
+                                                   int wrow, int wcol, int lc, int lr, int tid) {
+  acc_to_tile<Map32, BN>(acc, reinterpret_cast<float*>(smem), wrow, wcol, lc, lr);
+  __syncthreads();
+  tile_rows_epilogue<KIND, 4, BM, BN, NT>(p, smem, m0, n0, tid);
   __syncthreads();  // the tile is staging memory again (next tile's LDS-DMA)
 }
 

@@ -151,9 +151,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvP p) {
 
   static_assert((size_t)BM * BN <= 2 * (BM + BN) * LDS_LD, "the wide epilogue's fp32 tile must fit in the staging area");
   if (wide_epilogue_full_ok(p))
-    conv_epilogue_wide_full<BM, BN, 256, MI, NJ>(p, acc, reinterpret_cast<unsigned char*>(smem), m0, n0, wm * WTM, wn * WTN, r, h, tid);
+    conv_epilogue_tile<Epi::full, BM, BN, 256>(p, acc, reinterpret_cast<unsigned char*>(smem), m0, n0, wm * WTM, wn * WTN, r, h, tid);
   else
-    conv_epilogue<MI, NJ>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
+    conv_epilogue<Map32, ElemTwoWay>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, h);
 }
 
 template <int BM, int BN>

@@ -122,6 +122,21 @@ hipError_t conv_timed(d2t_ctx* c, const ConvP& p, hipStream_t s) {
   return e != hipSuccess ? e : e2;
 }
 
+// How a convolution behind the stem is routed (conv() and the patch embedding): split-record input brings the zero page and
+// the block cap; fp16 records in select the two-MFMA kernels (x16 * w_lo + x16 * w_hi) on the layer's fp16 hi / lo weight
+// planes, made on first use; the pipelined kernel's switches come from the context.
+int conv_route(d2t_ctx* c, hipStream_t s, ConvP& p, ConvW& w, bool split_in, bool f16_in) {
+  if (split_in) { p.zero16 = c->zero_page; p.max_blocks = c->conv_max_blocks; }
+  if (split_in && f16_in) {
+    if (int rc = f16_planes(c, w, s)) return rc;
+    p.f16 = 1;
+    p.w_hi = w.w_h16; p.w_lo = w.w_l16;
+  }
+  p.pipelined = c->conv_pipelined; p.reserved_cus = c->reserved_cus;
+  p.split_tail = !c->decode_in_flight || D2T_PROBE_ENV("D2T_CONV_TAIL_ALWAYS");
+  return D2T_OK;
+}
+
 // One convolution of the backbone.  `res` may be nullptr; `out_split` asks for split-bf16 output planes
 // (only meaningful on the bf16x3 path; the consumer must be another bf16x3 convolution or the split pool).
 // pool2: fuse the 2x2 / stride 2 max-pool that follows (split-record path only: see ConvP::pool2); y is then the POOLED map.
@@ -135,25 +150,23 @@ Act conv(d2t_ctx* c, hipStream_t s, hipError_t* err, const Act& x, const ConvW& 
   if (extra) p = *extra;
   p.w = w.w; p.bias = w.bias;
   if (c->conv_bf16x3) { p.w_hi = w.w_hi; p.w_lo = w.w_lo; }
-  if (x.split) { p.in_hi = x.planes(); p.zero16 = c->zero_page; p.max_blocks = c->conv_max_blocks; } else { p.in = x.p; }
-  if (x.split && x.fmt != 0) {  // fp16 records in: the two-MFMA kernels (x16 * w_lo + x16 * w_hi), fp16 hi / lo weight planes
-    if (f16_planes(c, const_cast<ConvW&>(w), s) != D2T_OK) { if (*err == hipSuccess) *err = hipErrorOutOfMemory; return y; }  // (w lives in *c)
-    p.f16 = 1;
-    p.w_hi = w.w_h16; p.w_lo = w.w_l16;
+  if (x.split) p.in_hi = x.planes(); else p.in = x.p;
+  if (conv_route(c, s, p, const_cast<ConvW&>(w), x.split, x.fmt != 0) != D2T_OK) {  // (w lives in *c)
+    if (*err == hipSuccess) *err = hipErrorOutOfMemory;
+    return y;
   }
   if (out_split) {
     y.fmt = out_fmt >= 0 ? out_fmt : (x.split ? (x.fmt ? 1 : 0) : (c->conv_f16 ? 1 : 0));
     p.out_fmt = 1 + y.fmt;
   }
   if (res && res->split) p.res_fmt = 1 + res->fmt;
-  p.pipelined = c->conv_pipelined; p.reserved_cus = c->reserved_cus; p.split_tail = !c->decode_in_flight || D2T_PROBE_ENV("D2T_CONV_TAIL_ALWAYS");
   if (out_split) { p.out_hi = y.planes(); } else { p.out = outbuf; }
   if (res) {
     if (res->split) { p.res_hi = res->planes(); } else { p.res = res->p; }
   }
-  p.B = x.B; p.H = x.H; p.W = x.W; p.Cin = x.C; p.OH = y.H; p.OW = y.W; p.Cout = w.Cout;
-  p.KH = w.KH; p.KW = w.KW; p.SH = sh; p.SW = sw; p.PH = ph; p.PW = pw;
-  p.M = y.B * y.H * y.W; p.K = w.KH * w.KW * x.C + p.Cin2; p.act = act;  // (Cin2: a second 1x1 input from `extra`)
+  conv_shape(p, x.B, x.H, x.W, x.C, w.Cout, w.KH, w.KW, sh, sw, ph, pw);
+  p.K += p.Cin2;  // (a second 1x1 input from `extra`)
+  p.act = act;
   if (pool2) {  // rows in pooled order (floor: a last odd row / column belongs to no window and is never computed)
     p.pool2 = 1;
     p.M = 4 * y.B * (y.H / 2) * (y.W / 2);
@@ -967,15 +980,9 @@ int d2t_encode_attn(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_
     ConvP p{};
     p.w = c->patch.w; p.bias = c->patch.bias; p.out = X;
     if (c->conv_bf16x3) { p.w_hi = c->patch.w_hi; p.w_lo = c->patch.w_lo; }
-    if (f.split) { p.in_hi = f.planes(); p.zero16 = c->zero_page; p.max_blocks = c->conv_max_blocks; } else { p.in = f.p; }
-    if (f.split && f.fmt != 0) {  // fp16 records from the backbone
-      if ((rc = f16_planes(c, c->patch, s))) return rc;
-      p.f16 = 1; p.w_hi = c->patch.w_h16; p.w_lo = c->patch.w_l16;
-    }
-    p.pipelined = c->conv_pipelined; p.reserved_cus = c->reserved_cus; p.split_tail = !c->decode_in_flight || D2T_PROBE_ENV("D2T_CONV_TAIL_ALWAYS");
-    p.B = f.B; p.H = f.H; p.W = f.W; p.Cin = f.C; p.OH = gh; p.OW = gw; p.Cout = dim;
-    p.KH = g.patch_h; p.KW = g.patch_w; p.SH = g.patch_h; p.SW = g.patch_w; p.PH = 0; p.PW = 0;
-    p.M = B * gh * gw; p.K = p.KH * p.KW * f.C; p.act = ACT_NONE;
+    if (f.split) p.in_hi = f.planes(); else p.in = f.p;
+    if ((rc = conv_route(c, s, p, c->patch, f.split, f.fmt != 0))) return rc;  // (fp16 records from the backbone)
+    conv_shape(p, f.B, f.H, f.W, f.C, dim, g.patch_h, g.patch_w, g.patch_h, g.patch_w, 0, 0, gh, gw);
     const float* pos;
     if ((rc = pos_table_for(c, gh, gw, s, &pos))) return rc;
     p.row_add = pos; p.rows_per_img = gh * gw; p.img_stride = T; p.row_off = 1; p.row_add_off = 1;

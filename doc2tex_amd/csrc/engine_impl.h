@@ -19,8 +19,8 @@ inline hipError_t linear_big(d2t_ctx* c, hipStream_t s, const float* x, const Li
   ConvP p{};
   p.in = x; p.w = w.w; p.bias = w.b; p.res = res; p.out = y;
   if (c && c->conv_bf16x3 && w.w_hi) { p.w_hi = w.w_hi; p.w_lo = w.w_lo; }  // launch_conv picks the bf16x3 GEMM
-  p.B = 1; p.H = 1; p.W = M; p.Cin = w.K; p.OH = 1; p.OW = M; p.Cout = w.N;
-  p.KH = p.KW = p.SH = p.SW = 1; p.PH = p.PW = 0; p.M = M; p.K = w.K; p.act = act;
+  linear_shape(p, M, w.K, w.N);
+  p.act = act;
   return c ? d2t_internal_conv_timed(c, p, s) : launch_conv(p, s);
 }
 

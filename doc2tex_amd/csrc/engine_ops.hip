@@ -17,10 +17,8 @@ int d2t_op_conv2d(const float* x, const float* w, const float* bias, const float
   if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)Cout * KH * KW * Cin * 4) != hipSuccess) return D2T_ENOMEM;
   ConvP p{};
   p.in = x; p.w = wp; p.bias = bias; p.res = residual; p.out = y;
-  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-  p.OH = (H + 2 * PH - KH) / SH + 1; p.OW = (W + 2 * PW - KW) / SW + 1;
-  p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
-  p.M = B * p.OH * p.OW; p.K = KH * KW * Cin; p.act = act;
+  conv_shape(p, B, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW);
+  p.act = act;
   hipError_t e = launch_repack_ohwi(w, wp, Cout, KH, KW, Cin, s);
   if (e == hipSuccess) e = launch_conv(p, s);
   hipStreamSynchronize(s);
@@ -41,10 +39,8 @@ int d2t_op_conv2d_bf16x3(const float* x, const float* w, const float* bias, cons
   if (hipMalloc(reinterpret_cast<void**>(&wp), n * 4) != hipSuccess) { hipFree(hi); hipFree(lo); return D2T_ENOMEM; }
   ConvP p{};
   p.in = x; p.w = wp; p.w_hi = hi; p.w_lo = lo; p.bias = bias; p.res = residual; p.out = y;
-  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-  p.OH = (H + 2 * PH - KH) / SH + 1; p.OW = (W + 2 * PW - KW) / SW + 1;
-  p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
-  p.M = B * p.OH * p.OW; p.K = KH * KW * Cin; p.act = act;
+  conv_shape(p, B, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW);
+  p.act = act;
   hipError_t e = launch_repack_ohwi(w, wp, Cout, KH, KW, Cin, s);
   if (e == hipSuccess) e = launch_split_bf16(wp, hi, lo, n, s);
   if (e == hipSuccess) e = launch_conv_bf16x3(p, s);
@@ -90,9 +86,9 @@ static int op_conv_split(bool pool, const float* x, const float* w, const float*
   const int f16 = g_op_conv_kind == 8;  // fp16 records, fp16 hi / lo weights, two MFMAs per product
   p.f16 = f16;
   p.pipelined = (f16 || pool) ? 3 : g_op_conv_kind; p.reserved_cus = g_op_reserved_cus; p.split_tail = !pool;
-  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.OH = OH; p.OW = OW;
-  p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
-  p.M = pool ? (int)(4 * rp) : B * OH * OW; p.K = KH * KW * Cin; p.act = act; p.pool2 = pool;
+  conv_shape(p, B, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW);
+  p.act = act;
+  if (pool) { p.pool2 = 1; p.M = (int)(4 * rp); }  // rows in pooled order
   hipError_t e = hipMemsetAsync(zero, 0, 256, s);
   if (e == hipSuccess) e = launch_repack_ohwi(w, wp, Cout, KH, KW, Cin, s);
   if (e == hipSuccess) e = f16 ? launch_split_f16(wp, whi, wlo, nw, s) : launch_split_bf16(wp, whi, wlo, nw, s);
@@ -300,8 +296,7 @@ int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float*
   } else if (kind == 0) {  // K / V of the memory rows as cross_kv projects them: [2][samples][8][T][D / 8]
     ConvP p{};
     p.in = mem; p.w = wk; p.bias = ca_in_b + D; p.out = ext;
-    p.B = 1; p.H = 1; p.W = samples * T; p.Cin = D; p.OH = 1; p.OW = samples * T; p.Cout = 2 * D;
-    p.KH = p.KW = p.SH = p.SW = 1; p.M = samples * T; p.K = D; p.act = ACT_NONE;
+    linear_shape(p, samples * T, D, 2 * D);
     p.store_mode = STORE_KV; p.kv_T = T; p.kv_heads = 8; p.kv_hd = D / 8; p.kv_B = samples;
     e = launch_conv(p, s);
     r.ck = ext; r.cv = ext + memn; r.c_batch_stride = (long long)T * D;

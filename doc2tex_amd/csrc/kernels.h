@@ -73,7 +73,7 @@ struct ConvP {
   int B, H, W, Cin, OH, OW, Cout;
   int KH, KW, SH, SW, PH, PW;
   int M;    // B*OH*OW
-  int m_base;  // LDS-DMA split-bf16 kernel only: this launch covers output rows [m_base, M) (tiles count from m_base)
+  int m_base;  // pipelined kernel and its tail only (launch_conv_bf16x3p sets it): this launch covers output rows [m_base, M)
   int K;    // KH*KW*Cin
   int act;
   // output row remap: row(m) = (m / rows_per_img) * img_stride + row_off + m % rows_per_img
@@ -83,10 +83,21 @@ struct ConvP {
   //   out[(((slab*kv_B + b)*kv_heads + head)*kv_T + j)*kv_hd + e]
   int store_mode, kv_T, kv_heads, kv_hd, kv_B;
 };
+// The shape fields of a ConvP in one place: M = B*OH*OW, K = KH*KW*Cin.  OH / OW < 0: what the convolution formula gives.
+// Callers that append a second input (Cin2) or use pooled-order rows (pool2) adjust K / M afterwards.
+inline void conv_shape(ConvP& p, int B, int H, int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PH, int PW,
+                       int OH = -1, int OW = -1) {
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+  p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW;
+  p.OH = OH >= 0 ? OH : (H + 2 * PH - KH) / SH + 1;
+  p.OW = OW >= 0 ? OW : (W + 2 * PW - KW) / SW + 1;
+  p.M = B * p.OH * p.OW; p.K = KH * KW * Cin;
+}
+// a linear layer out[M][N] = in[M][K] @ w[N][K]^T is a 1x1 convolution over a 1 x M image
+inline void linear_shape(ConvP& p, int M, int K, int N) { conv_shape(p, 1, 1, M, K, N, 1, 1, 1, 1, 0, 0); }
 hipError_t launch_conv(const ConvP& p, hipStream_t s);         // fp32 MFMA, or bf16x3 when p.w_hi != nullptr
 hipError_t launch_conv_bf16x3(const ConvP& p, hipStream_t s);
 hipError_t launch_conv_bf16x3p(const ConvP& p, hipStream_t s);  // 256x128 tile, 3 LDS stages, one block per CU
-hipError_t launch_conv_bf16x3g_rows(const ConvP& p, int bn, hipStream_t s);  // 128-row LDS-DMA kernel over rows [m_base, M)
 // hi = bf16(w) (round-to-nearest-even), lo = bf16(w - hi)
 hipError_t launch_split_bf16(const float* w, uint16_t* hi, uint16_t* lo, size_t n, hipStream_t s);
 // hi = fp16(w), lo = fp16(w - hi) (fp16x2 mode, ConvP::f16)

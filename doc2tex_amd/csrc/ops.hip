@@ -190,9 +190,8 @@ __global__ __launch_bounds__(256) void maxpool_split_kernel(const uint16_t* __re
         const int ih = oh * SH - PH + kh, iw = ow * SW - PW + kw;
         if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
           const size_t o = plane_idx((size_t)((b * H + ih) * W + iw), c4 * 4, C);
-          const uint2 h2 = *reinterpret_cast<const uint2*>(xp + o), l2 = *reinterpret_cast<const uint2*>(xp + o + 32);
           float v[4] = {0.f, 0.f, 0.f, 0.f};
-          add_rec4(v, h2, l2, f16);
+          add_rec<4>(v, xp + o, f16);
           m[0] = fmaxf(m[0], v[0]); m[1] = fmaxf(m[1], v[1]); m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
         }
       }

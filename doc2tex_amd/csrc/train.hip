@@ -183,8 +183,8 @@ struct Tr {  // builder / runner bound to one context and stream
               int act) {
     ConvP p{};
     p.in = a; p.w = w; p.bias = bias; p.res = res; p.out = out;
-    p.B = 1; p.H = 1; p.W = (int)M; p.Cin = K; p.OH = 1; p.OW = (int)M; p.Cout = N;
-    p.KH = p.KW = p.SH = p.SW = 1; p.M = (int)M; p.K = K; p.act = act;
+    linear_shape(p, (int)M, K, N);
+    p.act = act;
     TCHK(d2t_internal_conv_timed(c, p, s));
     return D2T_OK;
   }
@@ -315,8 +315,7 @@ struct Tr {  // builder / runner bound to one context and stream
       p.w_hi = hi; p.w_lo = hi + wn;
     }
     p.in = x.p; p.w = wp; p.bias = bias; p.out = n.z;
-    p.B = x.B; p.H = x.H; p.W = x.W; p.Cin = x.cols; p.OH = OH; p.OW = OW; p.Cout = Cout;
-    p.KH = KH; p.KW = KW; p.SH = SH; p.SW = SW; p.PH = PH; p.PW = PW; p.M = (int)P; p.K = n.K; p.act = ACT_NONE;
+    conv_shape(p, x.B, x.H, x.W, x.cols, Cout, KH, KW, SH, SW, PH, PW, OH, OW);
     RC(split_input(&p, x.p, x.rows, x.cols, x.planes));
     if (p.in_hi && !x.planes) st->t[in].planes = p.in_hi;  // records made here: the weight gradient reads them again
     TCHK(d2t_internal_conv_timed(c, p, s));
@@ -1179,9 +1178,7 @@ struct Tr {  // builder / runner bound to one context and stream
       p.w_hi = hi; p.w_lo = hi + (size_t)Cin * Kd;
     }
     p.in = src; p.w = wp; p.out = dx;
-    p.B = x.B; p.H = DH; p.W = DW; p.Cin = Cout; p.OH = x.H; p.OW = x.W; p.Cout = Cin;
-    p.KH = n.KH; p.KW = n.KW; p.SH = p.SW = 1; p.PH = n.KH - 1 - n.PH; p.PW = n.KW - 1 - n.PW;
-    p.M = (int)x.rows; p.K = Kd; p.act = ACT_NONE;
+    conv_shape(p, x.B, DH, DW, Cout, Cin, n.KH, n.KW, 1, 1, n.KH - 1 - n.PH, n.KW - 1 - n.PW, x.H, x.W);
     RC(split_input(&p, src, (long long)x.B * DH * DW, Cout, src == dz ? dz_planes : nullptr));
     TCHK(d2t_internal_conv_timed(c, p, s));
     return add_grad(n.in, dx);
