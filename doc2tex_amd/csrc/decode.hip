@@ -471,9 +471,6 @@ hipError_t launch_ragged_finalize(int64_t* tokens, float* logits, const int* row
   return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// Fused row kernel (see DecRowP).  512 threads = 8 waves = 8 heads.
-// ---------------------------------------------------------------------------
 // The online-softmax arithmetic of the d_model 512 row kernels' attention loops (head dim 64), spelled with explicit fmaf.
 // decoder_row2_kernel promises the one-row kernel's bits per row; written as a * b + c * d the compiler's contraction may fuse
 // either product, and chose differently in the two loops (tests/test_decode_ops_gpu.py: the builds differed by 1-3 ulp).
@@ -573,90 +570,158 @@ __device__ __forceinline__ void row_attention(const float* q, const float* Kc, c
   }
 }
 
-// out_part[g][n] = sum_{k in group g} in[k] * Wt[k][n]; caller reduces over g after a barrier
-template <int D, int NTH>
+// ---------------------------------------------------------------------------------------------------------------------
+// The phases of the per-row decoder step, one copy each.  Every row kernel below is a sequence of these calls and barriers:
+// self-attention over the cache, W_o + residual, LN1, W_q, cross-attention, W_co + residual.
+// ---------------------------------------------------------------------------------------------------------------------
+// Entry of a row kernel.  A finished step loop (stop_at: set by an EARLIER launch only) and a dead row slot return at once, both
+// block-uniform; the rest runs at the decode priority inside the launch's trace record.
+#define ROW_KERNEL_ENTRY(p, dead_row)                                       \
+  if ((p).stop_at && *(p).stop_at && *(p).step_ptr >= *(p).stop_at) return; \
+  if (dead_row) return;                                                     \
+  decode_wave_priority();                                                   \
+  TraceScope trace_((p).trace)
+
+__device__ __forceinline__ void fma4(float a, const float4& w, float4& acc) {
+  acc.x = fmaf(a, w.x, acc.x); acc.y = fmaf(a, w.y, acc.y); acc.z = fmaf(a, w.z, acc.z); acc.w = fmaf(a, w.w, acc.w);
+}
+__device__ __forceinline__ float4 scale4(const float4& a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
+
+// out_part[g][n] = sum_{k in group g} in[k] * Wt[k][n]; caller reduces over g after a barrier (sum_parts).
+// CTX_HD != 0: in_s holds [heads][D] context rows and column n reads the row of ITS head n / CTX_HD (the value projection behind
+// the absorbed cross-attention)
+template <int D, int NTH, int CTX_HD = 0>
 __device__ __forceinline__ void row_gemv(const float* in_s, const float* __restrict__ Wt, float* part_s, int tid) {
   constexpr int LPR = D / 4, G = NTH / LPR, KG = D / G;
   const int lr = tid % LPR, g = tid / LPR;
   const float* w = Wt + (size_t)(g * KG) * D + lr * 4;
-  const float* in = in_s + g * KG;
+  const float* in = in_s + (CTX_HD ? ((lr * 4) / CTX_HD) * D : 0) + g * KG;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-  for (int k = 0; k < KG; ++k) {
-    const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)k * D);
-    const float a = in[k];
-    acc.x = fmaf(a, w4.x, acc.x); acc.y = fmaf(a, w4.y, acc.y);
-    acc.z = fmaf(a, w4.z, acc.z); acc.w = fmaf(a, w4.w, acc.w);
-  }
+  for (int k = 0; k < KG; ++k) fma4(in[k], *reinterpret_cast<const float4*>(w + (size_t)k * D), acc);
   *reinterpret_cast<float4*>(part_s + g * D + lr * 4) = acc;
 }
+// one GEMV for two rows: every weight element is fetched once and applied to both inputs.  Thread (lr, g) -> columns
+// 4 lr .. 4 lr + 3, k in [g KG, (g + 1) KG): per row the products and their order are row_gemv's
+template <int D, int NTH, int UNROLL>
+__device__ __forceinline__ void gemv2(const float* in0, const float* in1, const float* __restrict__ Wt, float* part0, float* part1,
+                                      int tid) {
+  constexpr int LPR = D / 4, G = NTH / LPR, KG = D / G;
+  const int lr = tid % LPR, g = tid / LPR;
+  const float* w = Wt + (size_t)(g * KG) * D + lr * 4;
+  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+#pragma unroll UNROLL
+  for (int k = 0; k < KG; ++k) {
+    const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)k * D);
+    const float x0 = in0[g * KG + k], x1 = in1[g * KG + k];
+    fma4(x0, w4, a0);
+    fma4(x1, w4, a1);
+  }
+  *reinterpret_cast<float4*>(part0 + g * D + lr * 4) = a0;
+  *reinterpret_cast<float4*>(part1 + g * D + lr * 4) = a1;
+}
 
+// v0 + the G partial sums of column c, in ascending g
+template <int G, int D>
+__device__ __forceinline__ float sum_parts(const float* part, int c, float v) {
+#pragma unroll
+  for (int g = 0; g < G; ++g) v += part[g * D + c];
+  return v;
+}
+
+// LN1 of one row by one wave, two-pass; gamma / beta: (i, c) -> the scale / shift of channel c = 64 i + lane
+template <int D, class Gamma, class Beta>
+__device__ __forceinline__ void row_ln1(const float* y_row, float* x1_row, int lane, float eps, Gamma gamma, Beta beta) {
+  constexpr int V = D / 64;
+  float v[V], s = 0.f;
+#pragma unroll
+  for (int i = 0; i < V; ++i) { v[i] = y_row[i * 64 + lane]; s += v[i]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const float mean = s * (1.f / D);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < V; ++i) { v[i] -= mean; q += v[i] * v[i]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  const float rstd = 1.f / sqrtf(q * (1.f / D) + eps);
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const int c = i * 64 + lane;
+    x1_row[c] = v[i] * rstd * gamma(i, c) + beta(i, c);
+  }
+}
+template <int D>
+__device__ __forceinline__ void row_ln1(const float* y_row, float* x1_row, int lane, const DecRowP& p) {
+  row_ln1<D>(y_row, x1_row, lane, p.eps, [&](int, int c) { return p.ln1_g[c]; }, [&](int, int c) { return p.ln1_b[c]; });
+}
+
+// Head `head` of row b in front of the self-attention: this step's K / V go into the cache at position t (store == false: the
+// repeated last row of an odd row count keeps its stores to itself); returns the head's operands for row_attention[_2h]
+struct HeadPtrs { const float *q, *K, *V, *curk, *curv; };
+template <int D, int HD>
+__device__ __forceinline__ HeadPtrs cache_append_and_heads(const DecRowP& p, int b, int head, int t, int lane, bool store) {
+  const float* qkv = p.qkv + (size_t)b * p.qkv_stride;
+  float* Kc = p.sk + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
+  float* Vc = p.sv + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
+  const float* curk = qkv + D + head * HD;
+  const float* curv = qkv + 2 * D + head * HD;
+  if (lane < HD && store) {
+    Kc[(size_t)t * HD + lane] = curk[lane];
+    Vc[(size_t)t * HD + lane] = curv[lane];
+  }
+  return {qkv + head * HD, Kc, Vc, curk, curv};
+}
+// the operands of row_attention_2h: two heads of one row, or one head of two rows
+struct HeadPair {
+  const float *q[2], *K[2], *V[2], *curk[2], *curv[2];
+  float* out[2];
+  __device__ __forceinline__ void set(int i, const HeadPtrs& h, float* o) {
+    q[i] = h.q; K[i] = h.K; V[i] = h.V; curk[i] = h.curk; curv[i] = h.curv; out[i] = o;
+  }
+};
+// one head of the one-row kernels: cache append + attention over positions 0 .. t.  ANC (beam search, DecRowP::anc): position
+// j < t of this hypothesis lives in cache row anc_s[j] (no cache copy per step)
+template <int D, int HD, bool ANC = false>
+__device__ __forceinline__ void row_self_attention(const DecRowP& p, int b, int head, int t, int lane, float* out,
+                                                   const int* anc_s = nullptr) {
+  const HeadPtrs h = cache_append_and_heads<D, HD>(p, b, head, t, lane, true);
+  if (ANC && p.anc)
+    row_attention<HD, 4>(h.q, p.sk + (size_t)head * p.s_Lmax * HD, p.sv + (size_t)head * p.s_Lmax * HD, h.curk, h.curv, t, t + 1, out,
+                         lane, anc_s, p.s_batch_stride);
+  else
+    row_attention<HD, 4>(h.q, h.K, h.V, h.curk, h.curv, t, t + 1, out, lane);
+}
+
+// ---------------------------------------------------------------------------
+// Fused row kernel (see DecRowP).  512 threads = 8 waves = 8 heads.
+// ---------------------------------------------------------------------------
 template <int D, int HD, int NTH>  // NTH = 512: one wave per head; 256: four waves, two heads each (<= 128 VGPRs, so that a
                                     // block fits on a CU next to the pipelined convolution's three waves per SIMD)
 __global__ __launch_bounds__(NTH, NTH == 256 ? 4 : 2) void decoder_row_kernel(const DecRowP p) {
   constexpr int G = NTH / (D / 4);
   constexpr int HPW = 8 * 64 / NTH;  // heads per wave
-  if (p.stop_at && *p.stop_at && *p.step_ptr >= *p.stop_at) return;  // block-uniform
-  decode_wave_priority();
-  TraceScope trace_(p.trace);
+  ROW_KERNEL_ENTRY(p, false);
   __shared__ __attribute__((aligned(16))) float a_s[D], y_s[D], x1_s[D], q2_s[D], part_s[G * D];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x;
   const int t = *p.step_ptr;
-  const float* qkv = p.qkv + (size_t)b * p.qkv_stride;
   // ---- self-attention, one head per wave (and pass) ----
 #pragma unroll
   for (int hp = 0; hp < HPW; ++hp) {
     const int head = wave + hp * (NTH / 64);
-    float* Kc = p.sk + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-    float* Vc = p.sv + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-    const float* curk = qkv + D + head * HD;
-    const float* curv = qkv + 2 * D + head * HD;
-    if (lane < HD) {
-      Kc[(size_t)t * HD + lane] = curk[lane];
-      Vc[(size_t)t * HD + lane] = curv[lane];
-    }
-    row_attention<HD, 4>(qkv + head * HD, Kc, Vc, curk, curv, t, t + 1, a_s + head * HD, lane);
+    row_self_attention<D, HD>(p, b, head, t, lane, a_s + head * HD);
   }
   __syncthreads();
   row_gemv<D, NTH>(a_s, p.wo_t, part_s, tid);
   __syncthreads();
-  if (tid < D) {
-    float v = p.bo[tid] + p.xres[(size_t)b * D + tid];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[g * D + tid];
-    y_s[tid] = v;
-  }
+  if (tid < D) y_s[tid] = sum_parts<G, D>(part_s, tid, p.bo[tid] + p.xres[(size_t)b * D + tid]);
   __syncthreads();
-  if (wave == 0) {  // LN1, two-pass, one wave
-    constexpr int V = D / 64;
-    float v[V], s = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] = y_s[i * 64 + lane]; s += v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s * (1.f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] -= mean; q += v[i] * v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    const float rstd = 1.f / sqrtf(q * (1.f / D) + p.eps);
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const int c = i * 64 + lane;
-      x1_s[c] = v[i] * rstd * p.ln1_g[c] + p.ln1_b[c];
-    }
-  }
+  if (wave == 0) row_ln1<D>(y_s, x1_s, lane, p);
   __syncthreads();
   row_gemv<D, NTH>(x1_s, p.wq_t, part_s, tid);
   __syncthreads();
-  if (tid < D) {
-    float v = p.bq[tid];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[g * D + tid];
-    q2_s[tid] = v;
-  }
+  if (tid < D) q2_s[tid] = sum_parts<G, D>(part_s, tid, p.bq[tid]);
   __syncthreads();
   // ---- cross-attention over the memory K/V, one head per wave (and pass) ----
 #pragma unroll
@@ -670,12 +735,7 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 4 : 2) void decoder_row_kernel(co
   __syncthreads();
   row_gemv<D, NTH>(a_s, p.wco_t, part_s, tid);
   __syncthreads();
-  if (tid < D) {
-    float v = p.bco[tid] + x1_s[tid];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[g * D + tid];
-    p.y2[(size_t)b * D + tid] = v;
-  }
+  if (tid < D) p.y2[(size_t)b * D + tid] = sum_parts<G, D>(part_s, tid, p.bco[tid] + x1_s[tid]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -700,15 +760,74 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? 4 : 2) void decoder_row_kernel(co
 // partial (max, sum, ctx) triples are merged through LDS.  The S^T product is taken transposed on purpose: its result
 // layout (lane = (key group g, head), registers = keys 4g..4g+3) IS the A-operand layout of the second product with
 // k-step s <-> register s, so P never moves between lanes.
-// Everything else (self-attention over the cache, the three row GEMVs, LN1) is the code of decoder_row_kernel.
+// Everything else (self-attention over the cache, the row GEMVs, LN1) is the phase helpers above.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* lds_ptr_dec;
+
+#ifdef D2T_PROBES
+// probe builds: block 0 / thread 0 adds the time between consecutive marks (s_memrealtime, 10 ns ticks) to d2t_row_phase[k]
+__device__ unsigned long long d2t_row_phase[32];
+#define ROW_PHASE(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); \
+    atomicAdd(&d2t_row_phase[k], now_ - phase_t_); phase_t_ = now_; } } while (0)
+#define ROW_PHASE_INIT() unsigned long long phase_t_ = __builtin_amdgcn_s_memrealtime(); if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&d2t_row_phase[31], 1ull)
+#define WAVE_PHASE(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); \
+    atomicAdd(&d2t_row_phase[k], now_ - wave_t_); wave_t_ = now_; } } while (0)
+#define WAVE_PHASE_INIT() unsigned long long wave_t_ = __builtin_amdgcn_s_memrealtime()
+#define ROW_PROBE(bit) (p.probe & (bit))
+#else
+#define ROW_PHASE(k) do { } while (0)
+#define ROW_PHASE_INIT() do { } while (0)
+#define WAVE_PHASE(k) do { } while (0)
+#define WAVE_PHASE_INIT() do { } while (0)
+#define ROW_PROBE(bit) 0
+#endif
+
+// LDS-DMA of key tile `tile` of `mem` into a wave's 16 KB stage: row i -> stage + i * 1024, physical 16-byte chunk c holds
+// logical chunk c ^ i
+__device__ __forceinline__ void cross_tile_dma(const float* __restrict__ mem, int T, int tile, unsigned char* stage, int lane) {
+  const int j0 = tile << 4;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int j = j0 + i < T ? j0 + i : T - 1;  // rows past the end: a valid row, its probability is forced to zero
+    __builtin_amdgcn_global_load_lds(mem + (size_t)j * 256 + ((lane ^ i) << 2), (lds_ptr_dec)(stage + i * 1024), 16, 0, 0);
+  }
+}
+
+// Online softmax of one 16-key score tile: this lane holds keys j0 + 4 g + reg of one query row (head) in sacc.  Updates the
+// row's running max / sum; pv = the keys' probabilities against the new max, ar[reg] = the rescale of accumulator register reg
+// (the accumulators hold ctx[row 4 g + reg][...]: their scale is the alpha of THAT row, lane 4 g + reg has it)
+__device__ __forceinline__ void online_softmax_tile(const f32x4& sacc, int j0, int g, int T, float& m_run, float& l_run,
+                                                    float (&pv)[4], float (&ar)[4]) {
+  float sv[4], mx = -INFINITY;
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    sv[reg] = (j0 + 4 * g + reg < T) ? sacc[reg] : -INFINITY;
+    mx = fmaxf(mx, sv[reg]);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // a tile holds at least one valid key: finite
+  const float m_new = fmaxf(m_run, mx);
+  const float alpha = expf(m_run - m_new);  // exp(-inf) = 0 for the first tile
+  float ps = 0.f;
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    pv[reg] = expf(sv[reg] - m_new);  // exp(-inf) = 0 for keys past the end
+    ps += pv[reg];
+  }
+  l_run = l_run * alpha + ps;
+  m_run = m_new;
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) ar[reg] = __shfl(alpha, 4 * g + reg, 64);
+}
 
 // this wave's share of the cross-attention of ONE query row set: heads x T keys of `mem` [T][256].
 // qp_s: LDS [8][256] absorbed queries (already scaled by 1/sqrt(head_dim); the 16-byte chunks of row h XOR-ed with h like
 // the tile rows); stage: this wave's 16 KB; results: the wave's
 // running max / sum per head (lanes with col < 8, reduced over the key groups) and ctx accumulators acc[w][e] (D layout).
-template <int NW>
+// How a tile arrives: PF == false, by LDS-DMA in front of its arithmetic; PF == true, the wave's first tile was started with
+// cross_tile_dma long before, and every following tile travels to registers during the arithmetic on the current one and moves
+// to LDS when its reads are done.  Same products, same order.
+template <int NW, bool PF>
 __device__ __forceinline__ void cross_absorbed_wave(const float* __restrict__ mem, int T, const float* qp_s, unsigned char* stage,
                                                     int wave, int lane, float& m_run, float& l_run, f32x4 (&acc)[4][4]) {
   const int col = lane & 15, g = lane >> 4;
@@ -723,17 +842,30 @@ __device__ __forceinline__ void cross_absorbed_wave(const float* __restrict__ me
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[w][e] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int ntiles = (T + 15) >> 4;
+  if constexpr (PF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the first tile (issued at kernel entry) has landed
+  WAVE_PHASE_INIT();
   for (int tile = wave; tile < ntiles; tile += NW) {
     const int j0 = tile << 4;
-    // ---- stage the tile: row i -> stage + i * 1024, physical 16-byte chunk p holds logical chunk p ^ i ----
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous tile's fragment reads have returned
+    const int nxt = tile + NW;
+    WAVE_PHASE(13);
+    f32x4 pf[16];
+    if constexpr (PF) {
+      if (nxt < ntiles) {  // wave-uniform
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int j = j0 + i < T ? j0 + i : T - 1;  // rows past the end: a valid row, its probability is forced to zero
-      const float* src = mem + (size_t)j * 256 + ((lane ^ i) << 2);
-      __builtin_amdgcn_global_load_lds(src, (lds_ptr_dec)(stage + i * 1024), 16, 0, 0);
+        for (int i = 0; i < 16; ++i) {
+          const int j = (nxt << 4) + i < T ? (nxt << 4) + i : T - 1;
+          pf[i] = *reinterpret_cast<const f32x4*>(mem + (size_t)j * 256 + ((lane ^ i) << 2));
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pf[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    } else {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous tile's fragment reads have returned
+      cross_tile_dma(mem, T, tile, stage, lane);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    WAVE_PHASE(14);
     // ---- S^T[key = 4g' + reg][head = col] = sum_c m[key][c] q'[head][c] ----
     f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -746,35 +878,16 @@ __device__ __forceinline__ void cross_absorbed_wave(const float* __restrict__ me
       sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, q4.z, sacc, 0, 0, 0);
       sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, q4.w, sacc, 0, 0, 0);
     }
-    // ---- online softmax: this lane holds keys j0 + 4g + reg of head `col` ----
-    float sv[4], mx = -INFINITY;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      sv[reg] = (j0 + 4 * g + reg < T) ? sacc[reg] : -INFINITY;
-      mx = fmaxf(mx, sv[reg]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // a tile holds at least one valid key: finite
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = expf(m_run - m_new);  // exp(-inf) = 0 for the first tile
-    float pv[4], ps = 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      pv[reg] = expf(sv[reg] - m_new);  // exp(-inf) = 0 for keys past the end
-      ps += pv[reg];
-    }
-    l_run = l_run * alpha + ps;
-    m_run = m_new;
-    // the accumulators hold ctx[head = 4g + reg][...]: their scale is the alpha of THAT head (lane 4g + reg has it)
-    float ar[4];
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) ar[reg] = __shfl(alpha, 4 * g + reg, 64);
+    WAVE_PHASE(15);
+    float pv[4], ar[4];
+    online_softmax_tile(sacc, j0, g, T, m_run, l_run, pv, ar);
 #pragma unroll
     for (int w = 0; w < 4; ++w)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) acc[w][e][reg] *= ar[reg];
+    WAVE_PHASE(16);
     // ---- ctx[head][64w + 4 col' + e] += sum_keys P[head][key] m[key][chan]; k-step s <-> keys 4g + s ----
 #pragma unroll
     for (int sk = 0; sk < 4; ++sk) {
@@ -789,29 +902,20 @@ __device__ __forceinline__ void cross_absorbed_wave(const float* __restrict__ me
         acc[w][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[sk], b4.w, acc[w][3], 0, 0, 0);
       }
     }
+    WAVE_PHASE(17);
+    if constexpr (PF) {
+      if (nxt < ntiles) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this tile's fragment reads have returned: the stage may be overwritten
+#pragma unroll
+        for (int i = 0; i < 16; ++i) *reinterpret_cast<f32x4*>(stage + i * 1024 + lane * 16) = pf[i];
+      }
+    }
+    WAVE_PHASE(18);
   }
   l_run += __shfl_xor(l_run, 16, 64);
   l_run += __shfl_xor(l_run, 32, 64);
 }
 
-#ifdef D2T_PROBES
-// probe builds: block 0 / thread 0 adds the time between consecutive marks (s_memrealtime, 10 ns ticks) to d2t_row_phase[k]
-__device__ unsigned long long d2t_row_phase[32];
-#define ROW_PHASE(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); \
-    atomicAdd(&d2t_row_phase[k], now_ - phase_t_); phase_t_ = now_; } } while (0)
-#define ROW_PHASE_INIT() unsigned long long phase_t_ = __builtin_amdgcn_s_memrealtime(); if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&d2t_row_phase[31], 1ull)
-#else
-#define ROW_PHASE(k) do { } while (0)
-#define ROW_PHASE_INIT() do { } while (0)
-#endif
-#ifdef D2T_PROBES
-#define WAVE_PHASE(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); \
-    atomicAdd(&d2t_row_phase[k], now_ - wave_t_); wave_t_ = now_; } } while (0)
-#define WAVE_PHASE_INIT() unsigned long long wave_t_ = __builtin_amdgcn_s_memrealtime()
-#else
-#define WAVE_PHASE(k) do { } while (0)
-#define WAVE_PHASE_INIT() do { } while (0)
-#endif
 // ---------------------------------------------------------------------------------------------------------------------
 // Cross-attention on split-bf16 MFMAs (round 4).  Inside the loop below the fp32-MFMA form is bound by the matrix pipe:
 // 128 v_mfma_f32_16x16x4_f32 per tile at 32 cycles, two waves per SIMD, and only 8 of the 16 columns (heads) of every tile
@@ -891,31 +995,12 @@ __device__ __forceinline__ void cross_absorbed_wave_bx3(const uint16_t* __restri
       sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, sacc, 0, 0, 0);
       sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, sacc, 0, 0, 0);
     }
-    // ---- online softmax: this lane holds keys j0 + 4 g + reg of head `col` ----
-    float sv[4], mx = -INFINITY;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      sv[reg] = (j0 + 4 * g + reg < T) ? sacc[reg] : -INFINITY;
-      mx = fmaxf(mx, sv[reg]);
-    }
     WAVE_PHASE(15);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // a tile holds at least one valid key: finite
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = expf(m_run - m_new);  // exp(-inf) = 0 for the first tile
-    float ps = 0.f;
+    float pv[4], ar[4];
+    online_softmax_tile(sacc, j0, g, T, m_run, l_run, pv, ar);
     unsigned ph[4], pl[4];
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const float pv = expf(sv[reg] - m_new);  // exp(-inf) = 0 for keys past the end
-      ps += pv;
-      split16(pv, ph[reg], pl[reg]);
-    }
-    l_run = l_run * alpha + ps;
-    m_run = m_new;
-    float ar[4];  // the accumulators hold ctx[head = 4 g + reg][...]: their scale is the alpha of THAT head (lane 4 g + reg has it)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) ar[reg] = __shfl(alpha, 4 * g + reg, 64);
+    for (int reg = 0; reg < 4; ++reg) split16(pv[reg], ph[reg], pl[reg]);
 #pragma unroll
     for (int cb = 0; cb < 16; ++cb)
 #pragma unroll
@@ -944,6 +1029,84 @@ __device__ __forceinline__ void cross_absorbed_wave_bx3(const uint16_t* __restri
   l_run += __shfl_xor(l_run, 32, 64);
 }
 
+// ---- what surrounds the key loop: the absorbed queries on their way in, the waves' partial results on their way out ----
+// absorbed query q'[h][c4 .. c4 + 3] into the [8][256] fp32 image the fp32 MFMA form reads (16-byte chunks of row h XOR-ed with h)
+__device__ __forceinline__ void store_absorbed_query(float* qp, int h, int c4, const float4& qv) {
+  *reinterpret_cast<float4*>(qp + h * 256 + (((c4 >> 2) ^ h) << 2)) = qv;
+}
+// split16 of x = a * s.  The lo plane's x - hi is spelled out, not left to the compiler's contraction: FUSED_LO takes it as
+// fma(a, s, -hi), from the unrounded product -- what contraction had made of the one-row kernel's copy of this code and not of
+// the two-row body's.  The two kernels' results are pinned separately (they promise each other fp32 rounding only), so each
+// keeps its form.
+template <bool FUSED_LO>
+__device__ __forceinline__ void split16_scaled(float a, float s, unsigned& hi, unsigned& lo) {
+#pragma clang fp contract(off)
+  const float x = a * s;
+  const unsigned u = __float_as_uint(x);
+  hi = u >> 16;
+  const float h = __uint_as_float(u & 0xFFFF0000u);
+  const __bf16 l = (__bf16)(FUSED_LO ? fmaf(a, s, -h) : x - h);
+  lo = *reinterpret_cast<const unsigned short*>(&l);
+}
+// ... and q' = a * scale as hi / lo bf16 planes (cross_absorbed_wave_bx3): head h's row of 512 B, chunk (c4 >> 3) ^ h, half
+// (c4 >> 2) & 1
+template <bool FUSED_LO>
+__device__ __forceinline__ void store_absorbed_query_bx3(float* qp, int h, int c4, const float4& a, float scale) {
+  const float v[4] = {a.x, a.y, a.z, a.w};
+  unsigned hi[4], lo[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) split16_scaled<FUSED_LO>(v[e], scale, hi[e], lo[e]);
+  unsigned char* base = reinterpret_cast<unsigned char*>(qp) + h * 512 + (((c4 >> 3) ^ h) << 4) + ((c4 >> 2) & 1) * 8;
+  *reinterpret_cast<uint2*>(base) = make_uint2(hi[0] | hi[1] << 16, hi[2] | hi[3] << 16);
+  *reinterpret_cast<uint2*>(base + 4096) = make_uint2(lo[0] | lo[1] << 16, lo[2] | lo[3] << 16);
+}
+// a wave's running max / sum per head for the merge: the lanes that hold one (`holds`: g == 0 and col < 8, head = col) write
+// element `slot` = 8 * wave + head of wm / wl [waves][8]; behind it the wave's LDS traffic has drained (its stage is idle)
+__device__ __forceinline__ void store_wave_ml(float* wm, float* wl, int slot, bool holds, float m_run, float l_run) {
+  if (holds) { wm[slot] = m_run; wl[slot] = l_run; }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+// this wave's un-normalised ctx [8 heads][256] into its (now idle) staging area: lane (g, col) holds heads 4 g + reg.
+// fp32 form: acc[w][e][reg] = ctx[head 4 g + reg][channel 64 w + 4 col + e]
+__device__ __forceinline__ void store_wave_ctx(const f32x4 (&acc)[4][4], float* mine, int g, int col) {
+  if (g < 2) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg)
+        *reinterpret_cast<float4*>(mine + (4 * g + reg) * 256 + 64 * w + 4 * col) =
+            make_float4(acc[w][0][reg], acc[w][1][reg], acc[w][2][reg], acc[w][3][reg]);
+  }
+}
+// split-bf16 form: acc[cb][reg] = ctx[head 4 g + reg][channel 16 cb + col]
+__device__ __forceinline__ void store_wave_ctx(const f32x4 (&acc)[16], float* mine, int g, int col) {
+  if (g < 2) {
+#pragma unroll
+    for (int cb = 0; cb < 16; ++cb)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) mine[(4 * g + reg) * 256 + 16 * cb + col] = acc[cb][reg];
+  }
+}
+// log-sum-exp combine of the NW waves' partial softmaxes of one query row: channels c4 .. c4 + 3 of head h.  wm / wl: [NW][8];
+// stage_base: the first of the NW stages that hold the waves' ctx; the normalised context goes to ctx_out [8][256]
+template <int NW>
+__device__ __forceinline__ void merge_wave_softmax(const float (*wm)[8], const float (*wl)[8], const unsigned char* stage_base,
+                                                   float* ctx_out, int h, int c4) {
+  float M = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) M = fmaxf(M, wm[w][h]);
+  float L = 0.f;
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const float f = wl[w][h] > 0.f ? expf(wm[w][h] - M) : 0.f;  // waves without keys contribute nothing
+    L += wl[w][h] * f;
+    const float4 c = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(stage_base + w * 16384) + h * 256 + c4);
+    o.x += c.x * f; o.y += c.y * f; o.z += c.z * f; o.w += c.w * f;
+  }
+  *reinterpret_cast<float4*>(ctx_out + h * 256 + c4) = scale4(o, 1.f / L);
+}
+
 struct DecRow2P {
   DecRowP r;            // as decoder_row_kernel (ck / cv unused)
   const float* mem;     // [samples][T][D] encoder memory (engine-owned copy)
@@ -965,11 +1128,6 @@ struct DecRow2P {
   const int* len;
 };
 
-#ifdef D2T_PROBES
-#define ROW_PROBE(bit) (p.probe & (bit))
-#else
-#define ROW_PROBE(bit) 0
-#endif
 // MODE 0: the whole row step (greedy).  MODE 1: up to the absorbed queries, which go to q.qp (+ x1 to q.x1).  MODE 2: from
 // the context rows in q.qp on (value projection, output projection, residual) -- the two halves around beam_cross_kernel.
 constexpr int ANC_MAX = 512;  // longest ancestry row held in LDS (DecRowP::anc needs s_Lmax <= ANC_MAX)
@@ -980,10 +1138,7 @@ template <int NTH, int MODE, bool BX3 = false, int RAGGED = 0>
 __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecRow2P q) {
   constexpr int D = 256, HD = 32, NW = NTH / 64, G = NTH / (D / 4), HPW = 8 / NW;
   const DecRowP& p = q.r;
-  if (p.stop_at && *p.stop_at && *p.step_ptr >= *p.stop_at) return;  // block-uniform
-  if (p.rows_ptr && (int)blockIdx.x >= *p.rows_ptr) return;        // device-side beam search: a dead row slot
-  decode_wave_priority();
-  TraceScope trace_(p.trace);
+  ROW_KERNEL_ENTRY(p, p.rows_ptr && (int)blockIdx.x >= *p.rows_ptr);  // (device-side beam search: a dead row slot)
   // 77 KB: two blocks per CU.  The GEMV partial sums live in the (then idle) tile staging area, the merged context rows
   // in the absorbed queries' place (the queries are in registers by then).
   __shared__ __attribute__((aligned(1024))) unsigned char stage_s[NW * 16384];
@@ -996,7 +1151,6 @@ __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecR
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x;
   const int t = *p.step_ptr;
-  const float* qkv = p.qkv + (size_t)b * p.qkv_stride;
   if (MODE != 2) {
   // beam search: the hypothesis' earlier positions stay in the cache rows they were written to (no cache copy per step)
   __shared__ int anc_s[ANC_MAX];
@@ -1008,59 +1162,18 @@ __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecR
 #pragma unroll
   for (int hp = 0; hp < (ROW_PROBE(1) ? 0 : HPW); ++hp) {
     const int head = wave + hp * NW;
-    float* Kc = p.sk + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-    float* Vc = p.sv + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-    const float* curk = qkv + D + head * HD;
-    const float* curv = qkv + 2 * D + head * HD;
-    if (lane < HD) {
-      Kc[(size_t)t * HD + lane] = curk[lane];
-      Vc[(size_t)t * HD + lane] = curv[lane];
-    }
-    if (p.anc)
-      row_attention<HD, 4>(qkv + head * HD, p.sk + (size_t)head * p.s_Lmax * HD, p.sv + (size_t)head * p.s_Lmax * HD, curk, curv,
-                           t, t + 1, a_s + head * HD, lane, anc_s, p.s_batch_stride);
-    else
-      row_attention<HD, 4>(qkv + head * HD, Kc, Vc, curk, curv, t, t + 1, a_s + head * HD, lane);
+    row_self_attention<D, HD, true>(p, b, head, t, lane, a_s + head * HD, anc_s);
   }
   __syncthreads();
   if (!ROW_PROBE(2)) row_gemv<D, NTH>(a_s, p.wo_t, part_s, tid);
   __syncthreads();
-  if (tid < D) {
-    float v = p.bo[tid] + p.xres[(size_t)b * D + tid];
-#pragma unroll
-    for (int gI = 0; gI < G; ++gI) v += part_s[gI * D + tid];
-    y_s[tid] = v;
-  }
+  if (tid < D) y_s[tid] = sum_parts<G, D>(part_s, tid, p.bo[tid] + p.xres[(size_t)b * D + tid]);
   __syncthreads();
-  if (wave == 0) {  // LN1, two-pass, one wave
-    constexpr int V = D / 64;
-    float v[V], s = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] = y_s[i * 64 + lane]; s += v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s * (1.f / D);
-    float qq = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] -= mean; qq += v[i] * v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) qq += __shfl_xor(qq, o, 64);
-    const float rstd = 1.f / sqrtf(qq * (1.f / D) + p.eps);
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const int c = i * 64 + lane;
-      x1_s[c] = v[i] * rstd * p.ln1_g[c] + p.ln1_b[c];
-    }
-  }
+  if (wave == 0) row_ln1<D>(y_s, x1_s, lane, p);
   __syncthreads();
   if (!ROW_PROBE(2)) row_gemv<D, NTH>(x1_s, p.wq_t, part_s, tid);
   __syncthreads();
-  if (tid < D) {
-    float v = p.bq[tid];
-#pragma unroll
-    for (int gI = 0; gI < G; ++gI) v += part_s[gI * D + tid];
-    q2_s[tid] = v;
-  }
+  if (tid < D) q2_s[tid] = sum_parts<G, D>(part_s, tid, p.bq[tid]);
   __syncthreads();
   // ---- absorbed queries: q'[h][c] = scale * sum_e q2[h*32 + e] * W_k[h*32 + e][c] ----
   if (!ROW_PROBE(2)) {
@@ -1070,23 +1183,11 @@ __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecR
       const float* w = q.wk + (size_t)(h * HD) * D + c4;
       float4 accq = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 8
-      for (int e = 0; e < HD; ++e) {
-        const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)e * D);
-        const float a = q2_s[h * HD + e];
-        accq.x = fmaf(a, w4.x, accq.x); accq.y = fmaf(a, w4.y, accq.y);
-        accq.z = fmaf(a, w4.z, accq.z); accq.w = fmaf(a, w4.w, accq.w);
-      }
-      const float4 qv = make_float4(accq.x * scale, accq.y * scale, accq.z * scale, accq.w * scale);
+      for (int e = 0; e < HD; ++e) fma4(q2_s[h * HD + e], *reinterpret_cast<const float4*>(w + (size_t)e * D), accq);
+      const float4 qv = scale4(accq, scale);
       if (MODE == 1) *reinterpret_cast<float4*>(q.qp + ((size_t)b * 8 + h) * D + c4) = qv;
-      else if (BX3) {  // hi / lo bf16 planes (cross_absorbed_wave_bx3): head h's row of 512 B, chunk (c4 >> 3) ^ h, half (c4 >> 2) & 1
-        const float v[4] = {qv.x, qv.y, qv.z, qv.w};
-        unsigned hi[4], lo[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) split16(v[e], hi[e], lo[e]);
-        unsigned char* base = reinterpret_cast<unsigned char*>(qp_s) + h * 512 + (((c4 >> 3) ^ h) << 4) + ((c4 >> 2) & 1) * 8;
-        *reinterpret_cast<uint2*>(base) = make_uint2(hi[0] | hi[1] << 16, hi[2] | hi[3] << 16);
-        *reinterpret_cast<uint2*>(base + 4096) = make_uint2(lo[0] | lo[1] << 16, lo[2] | lo[3] << 16);
-      } else *reinterpret_cast<float4*>(qp_s + h * D + ((((c4 >> 2) ^ h)) << 2)) = qv;
+      else if (BX3) store_absorbed_query_bx3<true>(qp_s, h, c4, accq, scale);
+      else store_absorbed_query(qp_s, h, c4, qv);
     }
   }
   __syncthreads();
@@ -1130,300 +1231,42 @@ __global__ __launch_bounds__(NTH, 2) void decoder_row_absorbed_kernel(const DecR
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (wave < ((Tb + 15) >> 4)) bx3_tile_dma(mh, ml, Tb, wave, stage, lane);  // (the stage held GEMV partials until now)
       cross_absorbed_wave_bx3<NW>(mh, ml, Tb, reinterpret_cast<const unsigned char*>(qp_s), stage, wave, lane, m_run, l_run, acc);
-      if (g == 0 && col < 8) { wm_s[wave][col] = m_run; wl_s[wave][col] = l_run; }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (g < 2) {
-#pragma unroll
-        for (int cbk = 0; cbk < 16; ++cbk)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) mine[(4 * g + reg) * D + 16 * cbk + col] = acc[cbk][reg];
-      }
+      store_wave_ml(&wm_s[0][0], &wl_s[0][0], wave * 8 + col, g == 0 && col < 8, m_run, l_run);
+      store_wave_ctx(acc, mine, g, col);
     } else {
       f32x4 acc[4][4];
-      cross_absorbed_wave<NW>(q.mem + moff, Tb, qp_s, stage, wave, lane, m_run, l_run, acc);
-      if (g == 0 && col < 8) { wm_s[wave][col] = m_run; wl_s[wave][col] = l_run; }
-      // this wave's un-normalised ctx [8 heads][256] into its (now idle) staging area: lane (g, col) holds heads 4g + reg
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (g < 2) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg)
-            *reinterpret_cast<float4*>(mine + (4 * g + reg) * D + 64 * w + 4 * col) =
-                make_float4(acc[w][0][reg], acc[w][1][reg], acc[w][2][reg], acc[w][3][reg]);
-      }
+      cross_absorbed_wave<NW, false>(q.mem + moff, Tb, qp_s, stage, wave, lane, m_run, l_run, acc);
+      store_wave_ml(&wm_s[0][0], &wl_s[0][0], wave * 8 + col, g == 0 && col < 8, m_run, l_run);
+      store_wave_ctx(acc, mine, g, col);
     }
   }
   __syncthreads();
-  for (int idx = tid; idx < (MODE != 0 || ROW_PROBE(4) ? 0 : 8 * (D / 4)); idx += NTH) {  // merge the waves' partial softmaxes (log-sum-exp combine)
-    const int h = idx / (D / 4), c4 = (idx % (D / 4)) * 4;
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) M = fmaxf(M, wm_s[w][h]);
-    float L = 0.f;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float f = wl_s[w][h] > 0.f ? expf(wm_s[w][h] - M) : 0.f;  // waves without keys contribute nothing
-      L += wl_s[w][h] * f;
-      const float4 c = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(stage_s + w * 16384) + h * D + c4);
-      o.x += c.x * f; o.y += c.y * f; o.z += c.z * f; o.w += c.w * f;
-    }
-    const float inv = 1.f / L;
-    *reinterpret_cast<float4*>(ctx_s + h * D + c4) = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);
-  }
+  for (int idx = tid; idx < (MODE != 0 || ROW_PROBE(4) ? 0 : 8 * (D / 4)); idx += NTH)  // merge the waves' partial softmaxes
+    merge_wave_softmax<NW>(wm_s, wl_s, stage_s, ctx_s, idx / (D / 4), (idx % (D / 4)) * 4);
   __syncthreads();
   // ---- a2[o] = b_v[o] + sum_c ctx[head(o)][c] * W_v^T[c][o] ----
-  if (!ROW_PROBE(2)) {
-    constexpr int LPR = D / 4, KG = D / G;
-    const int lr = tid % LPR, gI = tid / LPR;
-    const float* w = q.wv_t + (size_t)(gI * KG) * D + lr * 4;
-    const float* in = ctx_s + ((lr * 4) / HD) * D + gI * KG;
-    float4 accv = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < KG; ++k) {
-      const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)k * D);
-      const float a = in[k];
-      accv.x = fmaf(a, w4.x, accv.x); accv.y = fmaf(a, w4.y, accv.y);
-      accv.z = fmaf(a, w4.z, accv.z); accv.w = fmaf(a, w4.w, accv.w);
-    }
-    *reinterpret_cast<float4*>(part_s + gI * D + lr * 4) = accv;
-  }
+  if (!ROW_PROBE(2)) row_gemv<D, NTH, HD>(ctx_s, q.wv_t, part_s, tid);
   __syncthreads();
-  if (tid < D) {
-    float v = q.bv[tid];
-#pragma unroll
-    for (int gI = 0; gI < G; ++gI) v += part_s[gI * D + tid];
-    a_s[tid] = v;
-  }
+  if (tid < D) a_s[tid] = sum_parts<G, D>(part_s, tid, q.bv[tid]);
   __syncthreads();
   if (!ROW_PROBE(2)) row_gemv<D, NTH>(a_s, p.wco_t, part_s, tid);
   __syncthreads();
-  if (tid < D) {
-    float v = p.bco[tid] + x1_s[tid];
-#pragma unroll
-    for (int gI = 0; gI < G; ++gI) v += part_s[gI * D + tid];
-    p.y2[(size_t)b * D + tid] = v;
-  }
+  if (tid < D) p.y2[(size_t)b * D + tid] = sum_parts<G, D>(part_s, tid, p.bco[tid] + x1_s[tid]);
 }
 
-#ifdef D2T_PROBES  // round 3's issue order of the two-row kernel, kept for A/B timing (D2T_DECODE_ROW2_NO_PREFETCH) in probe builds
 // ---------------------------------------------------------------------------------------------------------------------
-// The same step for TWO rows per block (greedy decode).  The five row GEMVs read 5 x 256 KB of weights per row, and with two
-// one-row blocks on a CU that is 2.56 MB through the CU's 64 B/clk L2 path per launch -- 18 of the kernel's 69 us (probe
-// build).  Here the block's 512 threads fetch every weight element ONCE and apply it to both rows' inputs (two
-// accumulators, eight K groups of 32 instead of four of 64), the absorbed-query product shares W_k the same way, and the
-// attention phases run as before: waves 0-3 on row 2b, waves 4-7 on row 2b + 1, each wave its own key tiles and 16 KB stage.
-// Per row the arithmetic and its order are those of decoder_row_absorbed_kernel (the K groups of a GEMV are summed in the
-// same ascending order: groups of 32 instead of 64 change the association) -- results agree to fp32 rounding.
-// 152 KB of LDS: one block per CU.
-// ---------------------------------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ void row2_gemv(const float* in0, const float* in1, const float* __restrict__ Wt, float* part_s, int tid) {
-  // part_s[row][g][n]; thread (lr = n / 4, g): k in [g KG, (g + 1) KG)
-  constexpr int LPR = D / 4, G = 512 / LPR, KG = D / G;
-  const int lr = tid % LPR, g = tid / LPR;
-  const float* w = Wt + (size_t)(g * KG) * D + lr * 4;
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-#pragma unroll
-  for (int k = 0; k < KG; ++k) {
-    const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)k * D);
-    const float x0 = in0[g * KG + k], x1 = in1[g * KG + k];
-    a0.x = fmaf(x0, w4.x, a0.x); a0.y = fmaf(x0, w4.y, a0.y); a0.z = fmaf(x0, w4.z, a0.z); a0.w = fmaf(x0, w4.w, a0.w);
-    a1.x = fmaf(x1, w4.x, a1.x); a1.y = fmaf(x1, w4.y, a1.y); a1.z = fmaf(x1, w4.z, a1.z); a1.w = fmaf(x1, w4.w, a1.w);
-  }
-  *reinterpret_cast<float4*>(part_s + (0 * G + g) * D + lr * 4) = a0;
-  *reinterpret_cast<float4*>(part_s + (1 * G + g) * D + lr * 4) = a1;
-}
-
-__global__ __launch_bounds__(512, 1) void decoder_row2_absorbed_kernel(const DecRow2P q) {
-  constexpr int D = 256, HD = 32, G = 8;
-  const DecRowP& p = q.r;
-  if (p.stop_at && *p.stop_at && *p.step_ptr >= *p.stop_at) return;  // block-uniform
-  decode_wave_priority();
-  TraceScope trace_(p.trace);
-  __shared__ __attribute__((aligned(1024))) unsigned char stage_s[8 * 16384];
-  __shared__ __attribute__((aligned(1024))) float qp_s[2][8 * D];
-  __shared__ __attribute__((aligned(16))) float a_s[2][D], y_s[2][D], x1_s[2][D], q2_s[2][D];
-  __shared__ float wm_s[2][4][8], wl_s[2][4][8];
-  float* const part_s = reinterpret_cast<float*>(stage_s);  // [2][G][D] = 16 KB of the (then idle) staging area
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int half = wave >> 2, w4i = wave & 3;   // this wave's row of the pair, its index among the row's four waves
-  // an odd row count: the last block's second half repeats the last row (same kernel for EVERY row, so a row's result never
-  // depends on how many rows share the launch) and keeps its stores to itself
-  const bool valid = 2 * (int)blockIdx.x + half < p.M;
-  const int b = valid ? 2 * blockIdx.x + half : p.M - 1;
-  const int trow = tid >> 8, tcol = tid & 255;  // element-wise phases: thread -> (row of the pair, channel)
-  const bool tvalid = 2 * (int)blockIdx.x + trow < p.M;
-  const int brow = tvalid ? 2 * blockIdx.x + trow : p.M - 1;
-  const int t = *p.step_ptr;
-  // ---- self-attention over the cache, two heads per wave ----
-  {
-    const float* qkv = p.qkv + (size_t)b * p.qkv_stride;
-#pragma unroll
-    for (int hp = 0; hp < 2; ++hp) {
-      const int head = w4i + hp * 4;
-      float* Kc = p.sk + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-      float* Vc = p.sv + (size_t)b * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-      const float* curk = qkv + D + head * HD;
-      const float* curv = qkv + 2 * D + head * HD;
-      if (lane < HD && valid) {
-        Kc[(size_t)t * HD + lane] = curk[lane];
-        Vc[(size_t)t * HD + lane] = curv[lane];
-      }
-      row_attention<HD, 4>(qkv + head * HD, Kc, Vc, curk, curv, t, t + 1, a_s[half] + head * HD, lane);
-    }
-  }
-  __syncthreads();
-  row2_gemv<D>(a_s[0], a_s[1], p.wo_t, part_s, tid);
-  __syncthreads();
-  {
-    float v = p.bo[tcol] + p.xres[(size_t)brow * D + tcol];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[(trow * G + g) * D + tcol];
-    y_s[trow][tcol] = v;
-  }
-  __syncthreads();
-  if (w4i == 0) {  // LN1, two-pass, one wave per row
-    constexpr int V = D / 64;
-    float v[V], s = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] = y_s[half][i * 64 + lane]; s += v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s * (1.f / D);
-    float qq = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] -= mean; qq += v[i] * v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) qq += __shfl_xor(qq, o, 64);
-    const float rstd = 1.f / sqrtf(qq * (1.f / D) + p.eps);
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const int c = i * 64 + lane;
-      x1_s[half][c] = v[i] * rstd * p.ln1_g[c] + p.ln1_b[c];
-    }
-  }
-  __syncthreads();
-  row2_gemv<D>(x1_s[0], x1_s[1], p.wq_t, part_s, tid);
-  __syncthreads();
-  {
-    float v = p.bq[tcol];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[(trow * G + g) * D + tcol];
-    q2_s[trow][tcol] = v;
-  }
-  __syncthreads();
-  // ---- absorbed queries of both rows: q'[h][c] = scale * sum_e q2[h*32 + e] * W_k[h*32 + e][c]; thread -> (head, 4 channels) ----
-  {
-    const float scale = 0.17677669529663687f;  // 1 / sqrt(32)
-    const int h = tid / (D / 4), c4 = (tid % (D / 4)) * 4;
-    const float* w = q.wk + (size_t)(h * HD) * D + c4;
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-#pragma unroll 8
-    for (int e = 0; e < HD; ++e) {
-      const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)e * D);
-      const float x0 = q2_s[0][h * HD + e], x1 = q2_s[1][h * HD + e];
-      a0.x = fmaf(x0, w4.x, a0.x); a0.y = fmaf(x0, w4.y, a0.y); a0.z = fmaf(x0, w4.z, a0.z); a0.w = fmaf(x0, w4.w, a0.w);
-      a1.x = fmaf(x1, w4.x, a1.x); a1.y = fmaf(x1, w4.y, a1.y); a1.z = fmaf(x1, w4.z, a1.z); a1.w = fmaf(x1, w4.w, a1.w);
-    }
-    const int o = h * D + ((((c4 >> 2) ^ h)) << 2);
-    *reinterpret_cast<float4*>(qp_s[0] + o) = make_float4(a0.x * scale, a0.y * scale, a0.z * scale, a0.w * scale);
-    *reinterpret_cast<float4*>(qp_s[1] + o) = make_float4(a1.x * scale, a1.y * scale, a1.z * scale, a1.w * scale);
-  }
-  __syncthreads();
-  // ---- cross-attention over the memory rows of each row's sample: four waves per row ----
-  {
-    const int cb = p.c_row_map ? p.c_row_map[b] : b;
-    float m_run, l_run;
-    f32x4 acc[4][4];
-    unsigned char* stage = stage_s + wave * 16384;
-    cross_absorbed_wave<4>(q.mem + (size_t)cb * q.mem_stride, p.T, qp_s[half], stage, w4i, lane, m_run, l_run, acc);
-    const int col = lane & 15, g = lane >> 4;
-    if (g == 0 && col < 8) { wm_s[half][w4i][col] = m_run; wl_s[half][w4i][col] = l_run; }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    float* mine = reinterpret_cast<float*>(stage);
-    if (g < 2) {
-#pragma unroll
-      for (int w = 0; w < 4; ++w)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg)
-          *reinterpret_cast<float4*>(mine + (4 * g + reg) * D + 64 * w + 4 * col) =
-              make_float4(acc[w][0][reg], acc[w][1][reg], acc[w][2][reg], acc[w][3][reg]);
-    }
-  }
-  __syncthreads();
-  for (int idx = tid; idx < 2 * 8 * (D / 4); idx += 512) {  // merge each row's four partial softmaxes (log-sum-exp combine)
-    const int row = idx / (8 * (D / 4)), rem = idx % (8 * (D / 4));
-    const int h = rem / (D / 4), c4 = (rem % (D / 4)) * 4;
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) M = fmaxf(M, wm_s[row][w][h]);
-    float L = 0.f;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float f = wl_s[row][w][h] > 0.f ? expf(wm_s[row][w][h] - M) : 0.f;
-      L += wl_s[row][w][h] * f;
-      const float4 c = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(stage_s + (row * 4 + w) * 16384) + h * D + c4);
-      o.x += c.x * f; o.y += c.y * f; o.z += c.z * f; o.w += c.w * f;
-    }
-    const float inv = 1.f / L;
-    *reinterpret_cast<float4*>(qp_s[row] + h * D + c4) = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);  // ctx in the queries' place
-  }
-  __syncthreads();
-  // ---- a2[o] = b_v[o] + sum_c ctx[head(o)][c] * W_v^T[c][o], both rows ----
-  {
-    constexpr int LPR = D / 4, KG = D / G;
-    const int lr = tid % LPR, g = tid / LPR;
-    const float* w = q.wv_t + (size_t)(g * KG) * D + lr * 4;
-    const int hoff = ((lr * 4) / HD) * D + g * KG;
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-#pragma unroll
-    for (int k = 0; k < KG; ++k) {
-      const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)k * D);
-      const float x0 = qp_s[0][hoff + k], x1 = qp_s[1][hoff + k];
-      a0.x = fmaf(x0, w4.x, a0.x); a0.y = fmaf(x0, w4.y, a0.y); a0.z = fmaf(x0, w4.z, a0.z); a0.w = fmaf(x0, w4.w, a0.w);
-      a1.x = fmaf(x1, w4.x, a1.x); a1.y = fmaf(x1, w4.y, a1.y); a1.z = fmaf(x1, w4.z, a1.z); a1.w = fmaf(x1, w4.w, a1.w);
-    }
-    // (the merge above still reads the staging area of waves 0 .. 7: it is behind the barrier)
-    *reinterpret_cast<float4*>(part_s + (0 * G + g) * D + lr * 4) = a0;
-    *reinterpret_cast<float4*>(part_s + (1 * G + g) * D + lr * 4) = a1;
-  }
-  __syncthreads();
-  {
-    float v = q.bv[tcol];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[(trow * G + g) * D + tcol];
-    a_s[trow][tcol] = v;
-  }
-  __syncthreads();
-  row2_gemv<D>(a_s[0], a_s[1], p.wco_t, part_s, tid);
-  __syncthreads();
-  {
-    float v = p.bco[tcol] + x1_s[trow][tcol];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[(trow * G + g) * D + tcol];
-    if (tvalid) p.y2[(size_t)brow * D + tcol] = v;
-  }
-}
-
-#endif  // D2T_PROBES
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The row step for TWO rows per block (greedy decode; the shipped form since round 4).
+// The row step for TWO rows per block (greedy decode; the shipped form).
 //
-// Two rows per block (round 3): the five row GEMVs read 5 x 256 KB of weights per row through the CU's 64 B/clk L2 path; the
-// block's 512 threads fetch every weight element ONCE and apply it to both rows' inputs (two accumulators, eight K groups of
-// 32), the absorbed-query product shares W_k the same way, and the attention phases run per row: waves 0-3 on row 2b, waves
-// 4-7 on row 2b + 1, each wave its own key tiles and 16 KB stage.  Per row the arithmetic and its order are those of
+// Two rows per block: the five row GEMVs read 5 x 256 KB of weights per row through the CU's 64 B/clk L2 path; the block's 512
+// threads fetch every weight element ONCE and apply it to both rows' inputs (two accumulators, eight K groups of 32), the
+// absorbed-query product shares W_k the same way, and the attention phases run per row: waves 0-3 on row 2b, waves 4-7 on row
+// 2b + 1, each wave its own key tiles and 16 KB stage.  Per row the arithmetic and its order are those of
 // decoder_row_absorbed_kernel (K groups of 32 instead of 64 change the association: equal to fp32 rounding).  An odd row
 // count: the last block's second half repeats the last row and keeps its stores to itself -- the same kernel for EVERY row, so
 // a row's result never depends on how many rows share the launch.  156 KB of LDS: one block per CU.
 //
-// Issue order (round 4).  PMC of round 3's form at 384 rows (profiles/r04_pmc_decode.txt): matrix pipes 12 % busy, SQ_WAIT_ANY
-// 49 % of the wave cycles -- a serial chain of phases that each began with an exposed round trip.  Same arithmetic per element
-// in the same order (bit-identical results), but
+// Issue order.  Run as a serial chain of phases that each begin with an exposed round trip, the step keeps the matrix pipes
+// 12 % busy with SQ_WAIT_ANY at 49 % of the wave cycles (PMC at 384 rows, profiles/r04_pmc_decode.txt).  So
 //   * a wave's FIRST memory tile is on its way (LDS-DMA) from the kernel's first instruction -- the staging area is idle until
 //     the cross-attention (the GEMV partials of the first two projections live in the absorbed queries' LDS instead);
 //   * inside the cross-attention the NEXT tile travels to registers (16 x 16 bytes per lane) while the matrix cores work on the
@@ -1435,7 +1278,7 @@ __global__ __launch_bounds__(512, 1) void decoder_row2_absorbed_kernel(const Dec
 //   * block barriers are raw s_barrier behind lgkmcnt(0) (LDS only): a __syncthreads() fence would drain the prefetches.
 // Phase timeline at 384 rows, alone on the chip (probe build, tools/probe/row_phases.py; us per launch), with the cross-attention
 // on split-bf16 MFMAs (cross_absorbed_wave_bx3): entry .. self-attention 21.9, five GEMVs 10.6, cross-attention 18.9, element-wise
-// 3.9 -- 55.3 in all (round 3's kernel: 64.4; this issue order on the fp32 MFMA: 62.7).
+// 3.9 -- 55.3 in all (the serial chain of phases, same arithmetic: 64.4; this issue order on the fp32 MFMA: 62.7).
 // ---------------------------------------------------------------------------------------------------------------------
 #define ROW_SYNC() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
 
@@ -1445,7 +1288,7 @@ __device__ __forceinline__ void gemv2_load(const float* __restrict__ Wt, int g, 
 #pragma unroll
   for (int k = 0; k < 32; ++k) w[k] = *reinterpret_cast<const float4*>(src + (size_t)k * 256);
 }
-// part_s[row][g][n] += ... exactly row2_gemv<256>'s products in its order; in0 / in1 = the two rows' inputs at k = 32 g
+// gemv2<256, 512>'s products in its order on rows loaded earlier; in0 / in1 = the two rows' inputs at k = 32 g
 __device__ __forceinline__ void gemv2_fma(const float4 (&w)[32], const float* in0, const float* in1, float4& a0, float4& a1) {
   a0 = make_float4(0.f, 0.f, 0.f, 0.f);
   a1 = a0;
@@ -1453,9 +1296,14 @@ __device__ __forceinline__ void gemv2_fma(const float4 (&w)[32], const float* in
   for (int k = 0; k < 32; ++k) {
     const float4 w4 = w[k];
     const float x0 = in0[k], x1 = in1[k];
-    a0.x = fmaf(x0, w4.x, a0.x); a0.y = fmaf(x0, w4.y, a0.y); a0.z = fmaf(x0, w4.z, a0.z); a0.w = fmaf(x0, w4.w, a0.w);
-    a1.x = fmaf(x1, w4.x, a1.x); a1.y = fmaf(x1, w4.y, a1.y); a1.z = fmaf(x1, w4.z, a1.z); a1.w = fmaf(x1, w4.w, a1.w);
+    fma4(x0, w4, a0);
+    fma4(x1, w4, a1);
   }
+}
+// the two rows' partial sums of thread (lr, g) into part[row][g][n]
+__device__ __forceinline__ void gemv2_store(float* part, int g, int lr, const float4& a0, const float4& a1) {
+  *reinterpret_cast<float4*>(part + (0 * 8 + g) * 256 + lr * 4) = a0;
+  *reinterpret_cast<float4*>(part + (1 * 8 + g) * 256 + lr * 4) = a1;
 }
 
 // row_attention<32, U> for TWO heads of one row in one loop (per head the same keys per lane in the same order)
@@ -1552,111 +1400,6 @@ __device__ __forceinline__ void row_attention_2h(const float* const (&q)[2], con
   }
 }
 
-// LDS-DMA of key tile `tile` of `mem` into a wave's 16 KB stage (the layout cross_absorbed_wave reads)
-__device__ __forceinline__ void cross_tile_dma(const float* __restrict__ mem, int T, int tile, unsigned char* stage, int lane) {
-  const int j0 = tile << 4;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int j = j0 + i < T ? j0 + i : T - 1;
-    __builtin_amdgcn_global_load_lds(mem + (size_t)j * 256 + ((lane ^ i) << 2), (lds_ptr_dec)(stage + i * 1024), 16, 0, 0);
-  }
-}
-
-// cross_absorbed_wave<NW> with the tile stream pipelined: the wave's first tile was started with cross_tile_dma long before;
-// every following tile is loaded to registers during the arithmetic on the current one.  Same products, same order.
-template <int NW>
-__device__ __forceinline__ void cross_absorbed_wave_pf(const float* __restrict__ mem, int T, const float* qp_s, unsigned char* stage,
-                                                       int wave, int lane, float& m_run, float& l_run, f32x4 (&acc)[4][4]) {
-  const int col = lane & 15, g = lane >> 4;
-  const int hrow = col & 7;
-  m_run = -INFINITY;
-  l_run = 0.f;
-#pragma unroll
-  for (int w = 0; w < 4; ++w)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[w][e] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int ntiles = (T + 15) >> 4;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the first tile (issued at kernel entry) has landed
-  WAVE_PHASE_INIT();
-  for (int tile = wave; tile < ntiles; tile += NW) {
-    const int j0 = tile << 4;
-    const int nxt = tile + NW;
-    WAVE_PHASE(13);
-    f32x4 pf[16];
-    if (nxt < ntiles) {  // wave-uniform
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int j = (nxt << 4) + i < T ? (nxt << 4) + i : T - 1;
-        pf[i] = *reinterpret_cast<const f32x4*>(mem + (size_t)j * 256 + ((lane ^ i) << 2));
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) pf[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    WAVE_PHASE(14);
-    f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const float4 a4 = *reinterpret_cast<const float4*>(stage + col * 1024 + (((4 * u + g) ^ col) << 4));
-      const float4 q4 = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(qp_s) + hrow * 1024 + (((4 * u + g) ^ hrow) << 4));
-      sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, q4.x, sacc, 0, 0, 0);
-      sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, q4.y, sacc, 0, 0, 0);
-      sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, q4.z, sacc, 0, 0, 0);
-      sacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, q4.w, sacc, 0, 0, 0);
-    }
-    float sv[4], mx = -INFINITY;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      sv[reg] = (j0 + 4 * g + reg < T) ? sacc[reg] : -INFINITY;
-      mx = fmaxf(mx, sv[reg]);
-    }
-    WAVE_PHASE(15);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    const float alpha = expf(m_run - m_new);
-    float pv[4], ps = 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      pv[reg] = expf(sv[reg] - m_new);
-      ps += pv[reg];
-    }
-    l_run = l_run * alpha + ps;
-    m_run = m_new;
-    float ar[4];
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) ar[reg] = __shfl(alpha, 4 * g + reg, 64);
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) acc[w][e][reg] *= ar[reg];
-    WAVE_PHASE(16);
-#pragma unroll
-    for (int sk = 0; sk < 4; ++sk) {
-      const int key = 4 * g + sk;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const float4 b4 = *reinterpret_cast<const float4*>(stage + key * 1024 + (((16 * w + col) ^ key) << 4));
-        acc[w][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[sk], b4.x, acc[w][0], 0, 0, 0);
-        acc[w][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[sk], b4.y, acc[w][1], 0, 0, 0);
-        acc[w][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[sk], b4.z, acc[w][2], 0, 0, 0);
-        acc[w][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[sk], b4.w, acc[w][3], 0, 0, 0);
-      }
-    }
-    WAVE_PHASE(17);
-    if (nxt < ntiles) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this tile's fragment reads have returned: the stage may be overwritten
-#pragma unroll
-      for (int i = 0; i < 16; ++i) *reinterpret_cast<f32x4*>(stage + i * 1024 + lane * 16) = pf[i];
-    }
-    WAVE_PHASE(18);
-  }
-  l_run += __shfl_xor(l_run, 16, 64);
-  l_run += __shfl_xor(l_run, 32, 64);
-}
-
 // RAGGED (decode groups of batches with different row counts and memory lengths): row b reads its keys from the packed memory
 // rows [row0[b], row0[b] + len[b]); the two halves of a block get independent lengths.  Every block barrier (ROW_SYNC) and every
 // s_waitcnt of the body lies OUTSIDE the key loop and is reached by all eight waves whatever the two lengths are: the first-tile
@@ -1668,9 +1411,7 @@ template <bool BX3, bool RAGGED = false>  // BX3: the cross-attention on split-b
 __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q) {
   constexpr int D = 256, HD = 32, G = 8;
   const DecRowP& p = q.r;
-  if (p.stop_at && *p.stop_at && *p.step_ptr >= *p.stop_at) return;  // block-uniform
-  decode_wave_priority();
-  TraceScope trace_(p.trace);
+  ROW_KERNEL_ENTRY(p, false);
   ROW_PHASE_INIT();
   __shared__ __attribute__((aligned(1024))) unsigned char stage_s[8 * 16384];
   __shared__ __attribute__((aligned(1024))) float qp_s[2][8 * D];
@@ -1722,6 +1463,7 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
   ROW_PHASE(19);  // kernel entry: scalar state, small operands
   // ---- self-attention over the cache, this wave's two heads in one loop ----
   {
+    // (cache_append_and_heads spelled out: through the helper the split-bf16 builds' scratch changes, 36 -> 24 bytes per lane)
     const float* qkv = p.qkv + (size_t)b * p.qkv_stride;
     const float *qh[2], *Kh[2], *Vh[2], *ck[2], *cv[2];
     float* oh[2];
@@ -1746,56 +1488,26 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
     float4 a0, a1;
     gemv2_fma(W, a_s[0] + gg * 32, a_s[1] + gg * 32, a0, a1);
     gemv2_load(p.wq_t, gg, lr, W);  // next projection's rows: on their way during the reduction and LN1
-    *reinterpret_cast<float4*>(part_early + (0 * G + gg) * D + lr * 4) = a0;
-    *reinterpret_cast<float4*>(part_early + (1 * G + gg) * D + lr * 4) = a1;
+    gemv2_store(part_early, gg, lr, a0, a1);
   }
   ROW_SYNC();
   ROW_PHASE(1);
-  {
-    float v = bo_v;
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_early[(trow * G + g) * D + tcol];
-    y_s[trow][tcol] = v;
-  }
+  y_s[trow][tcol] = sum_parts<G, D>(part_early + trow * G * D, tcol, bo_v);
   ROW_SYNC();
   ROW_PHASE(2);
-  if (w4i == 0) {  // LN1, two-pass, one wave per row
-    constexpr int V = D / 64;
-    float v[V], s = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] = y_s[half][i * 64 + lane]; s += v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s * (1.f / D);
-    float qq = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] -= mean; qq += v[i] * v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) qq += __shfl_xor(qq, o, 64);
-    const float rstd = 1.f / sqrtf(qq * (1.f / D) + p.eps);
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const int c = i * 64 + lane;
-      x1_s[half][c] = v[i] * rstd * ln_g[i] + ln_b[i];
-    }
-  }
+  if (w4i == 0)  // one wave per row
+    row_ln1<D>(y_s[half], x1_s[half], lane, p.eps, [&](int i, int) { return ln_g[i]; }, [&](int i, int) { return ln_b[i]; });
   ROW_SYNC();
   ROW_PHASE(3);
   {
     float4 a0, a1;
     gemv2_fma(W, x1_s[0] + gg * 32, x1_s[1] + gg * 32, a0, a1);
     gemv2_load(q.wk, gg, lr, W);  // W_k rows of head gg (= tid / 64), columns 4 lr ..: the absorbed-query product's operand
-    *reinterpret_cast<float4*>(part_early + (0 * G + gg) * D + lr * 4) = a0;
-    *reinterpret_cast<float4*>(part_early + (1 * G + gg) * D + lr * 4) = a1;
+    gemv2_store(part_early, gg, lr, a0, a1);
   }
   ROW_SYNC();
   ROW_PHASE(4);
-  {
-    float v = bq_v;
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_early[(trow * G + g) * D + tcol];
-    q2_s[trow][tcol] = v;
-  }
+  q2_s[trow][tcol] = sum_parts<G, D>(part_early + trow * G * D, tcol, bq_v);
   ROW_SYNC();
   ROW_PHASE(5);
   // ---- absorbed queries of both rows: q'[h][c] = scale * sum_e q2[h*32 + e] * W_k[h*32 + e][c]; thread -> (head gg, 4 channels) ----
@@ -1803,22 +1515,12 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
     const float scale = 0.17677669529663687f;  // 1 / sqrt(32)
     float4 a0, a1;
     gemv2_fma(W, q2_s[0] + gg * HD, q2_s[1] + gg * HD, a0, a1);
-    if constexpr (BX3) {  // hi / lo bf16 planes: head gg's row of 512 B, 16-byte chunk (lr >> 1) ^ gg, its half lr & 1
-      const float v0[4] = {a0.x * scale, a0.y * scale, a0.z * scale, a0.w * scale}, v1[4] = {a1.x * scale, a1.y * scale, a1.z * scale, a1.w * scale};
-      const int ob = gg * 512 + (((lr >> 1) ^ gg) << 4) + (lr & 1) * 8;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        unsigned hi[4], lo[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) split16(r ? v1[e] : v0[e], hi[e], lo[e]);
-        unsigned char* base = reinterpret_cast<unsigned char*>(qp_s[r]);
-        *reinterpret_cast<uint2*>(base + ob) = make_uint2(hi[0] | hi[1] << 16, hi[2] | hi[3] << 16);
-        *reinterpret_cast<uint2*>(base + 4096 + ob) = make_uint2(lo[0] | lo[1] << 16, lo[2] | lo[3] << 16);
-      }
+    if constexpr (BX3) {
+      store_absorbed_query_bx3<false>(qp_s[0], gg, lr * 4, a0, scale);
+      store_absorbed_query_bx3<false>(qp_s[1], gg, lr * 4, a1, scale);
     } else {
-      const int o = gg * D + ((lr ^ gg) << 2);
-      *reinterpret_cast<float4*>(qp_s[0] + o) = make_float4(a0.x * scale, a0.y * scale, a0.z * scale, a0.w * scale);
-      *reinterpret_cast<float4*>(qp_s[1] + o) = make_float4(a1.x * scale, a1.y * scale, a1.z * scale, a1.w * scale);
+      store_absorbed_query(qp_s[0], gg, lr * 4, scale4(a0, scale));
+      store_absorbed_query(qp_s[1], gg, lr * 4, scale4(a1, scale));
     }
   }
   ROW_SYNC();
@@ -1832,50 +1534,22 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
       f32x4 acc[16];
       cross_absorbed_wave_bx3<4>(mh, ml, Tb, reinterpret_cast<const unsigned char*>(qp_s[half]), stage, w4i, lane, m_run, l_run, acc);
       ROW_PHASE(12);
-      if (g == 0 && col < 8) { wm_s[half][w4i][col] = m_run; wl_s[half][w4i][col] = l_run; }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (g < 2) {  // acc[cb][reg] = ctx[head 4 g + reg][channel 16 cb + col]
-#pragma unroll
-        for (int cb = 0; cb < 16; ++cb)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) mine[(4 * g + reg) * D + 16 * cb + col] = acc[cb][reg];
-      }
+      store_wave_ml(&wm_s[half][0][0], &wl_s[half][0][0], w4i * 8 + col, g == 0 && col < 8, m_run, l_run);
+      store_wave_ctx(acc, mine, g, col);
     } else {
       f32x4 acc[4][4];
-      cross_absorbed_wave_pf<4>(mem, Tb, qp_s[half], stage, w4i, lane, m_run, l_run, acc);
+      cross_absorbed_wave<4, true>(mem, Tb, qp_s[half], stage, w4i, lane, m_run, l_run, acc);
       ROW_PHASE(12);
-      if (g == 0 && col < 8) { wm_s[half][w4i][col] = m_run; wl_s[half][w4i][col] = l_run; }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (g < 2) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg)
-            *reinterpret_cast<float4*>(mine + (4 * g + reg) * D + 64 * w + 4 * col) =
-                make_float4(acc[w][0][reg], acc[w][1][reg], acc[w][2][reg], acc[w][3][reg]);
-      }
+      store_wave_ml(&wm_s[half][0][0], &wl_s[half][0][0], w4i * 8 + col, g == 0 && col < 8, m_run, l_run);
+      store_wave_ctx(acc, mine, g, col);
     }
   }
   gemv2_load(q.wv_t, gg, lr, W);  // value projection's rows: on their way during the merge
   ROW_SYNC();
   ROW_PHASE(7);
-  for (int idx = tid; idx < 2 * 8 * (D / 4); idx += 512) {  // merge each row's four partial softmaxes (log-sum-exp combine)
+  for (int idx = tid; idx < 2 * 8 * (D / 4); idx += 512) {  // merge each row's four partial softmaxes; ctx in the queries' place
     const int row = idx / (8 * (D / 4)), rem = idx % (8 * (D / 4));
-    const int h = rem / (D / 4), c4 = (rem % (D / 4)) * 4;
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) M = fmaxf(M, wm_s[row][w][h]);
-    float L = 0.f;
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float f = wl_s[row][w][h] > 0.f ? expf(wm_s[row][w][h] - M) : 0.f;
-      L += wl_s[row][w][h] * f;
-      const float4 c = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(stage_s + (row * 4 + w) * 16384) + h * D + c4);
-      o.x += c.x * f; o.y += c.y * f; o.z += c.z * f; o.w += c.w * f;
-    }
-    const float inv = 1.f / L;
-    *reinterpret_cast<float4*>(qp_s[row] + h * D + c4) = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);  // ctx in the queries' place
+    merge_wave_softmax<4>(wm_s[row], wl_s[row], stage_s + row * 4 * 16384, qp_s[row], rem / (D / 4), (rem % (D / 4)) * 4);
   }
   ROW_SYNC();
   ROW_PHASE(8);
@@ -1885,32 +1559,23 @@ __device__ __forceinline__ void decoder_row2_absorbed_pf_body(const DecRow2P& q)
     float4 a0, a1;
     gemv2_fma(W, qp_s[0] + hoff, qp_s[1] + hoff, a0, a1);
     gemv2_load(p.wco_t, gg, lr, W);
-    *reinterpret_cast<float4*>(part_late + (0 * G + gg) * D + lr * 4) = a0;
-    *reinterpret_cast<float4*>(part_late + (1 * G + gg) * D + lr * 4) = a1;
+    gemv2_store(part_late, gg, lr, a0, a1);
   }
   ROW_SYNC();
   ROW_PHASE(9);
-  {
-    float v = bv_v;
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_late[(trow * G + g) * D + tcol];
-    a_s[trow][tcol] = v;
-  }
+  a_s[trow][tcol] = sum_parts<G, D>(part_late + trow * G * D, tcol, bv_v);
   ROW_SYNC();
   ROW_PHASE(10);
   {
     float4 a0, a1;
     gemv2_fma(W, a_s[0] + gg * 32, a_s[1] + gg * 32, a0, a1);
     ROW_SYNC();  // (every thread has read part_late's previous contents)
-    *reinterpret_cast<float4*>(part_late + (0 * G + gg) * D + lr * 4) = a0;
-    *reinterpret_cast<float4*>(part_late + (1 * G + gg) * D + lr * 4) = a1;
+    gemv2_store(part_late, gg, lr, a0, a1);
   }
   ROW_SYNC();
   ROW_PHASE(11);
   {
-    float v = bco_v + x1_s[trow][tcol];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_late[(trow * G + g) * D + tcol];
+    const float v = sum_parts<G, D>(part_late + trow * G * D, tcol, bco_v + x1_s[trow][tcol]);
     if (tvalid) p.y2[(size_t)brow * D + tcol] = v;
   }
   ROW_PHASE(20);
@@ -1937,40 +1602,28 @@ namespace d2t {
 hipError_t launch_decoder_row_absorbed(const DecRowP& r, const float* mem, long long mem_stride, const float* wk, const float* wv_t,
                                        const float* bv, hipStream_t s, const uint16_t* mem_hi, const uint16_t* mem_lo,
                                        const int* row0, const int* len) {
+  // ---- what is refused ----
   const bool ragged = row0 != nullptr;
   if (r.heads != 8 || r.D != 256 || (!ragged && r.T < 1)) return hipErrorInvalidValue;
   const bool by_sample = ragged && r.c_row_map;  // beam rows: tables per sample, reached through the row map
   if (ragged && !len) return hipErrorInvalidValue;
   if (ragged && !by_sample && (r.anc || r.rows_ptr)) return hipErrorInvalidValue;  // tables per row: greedy rows only
   if (by_sample && !r.one_row) return hipErrorInvalidValue;  // the two-row builds know neither row map nor ancestry
+  if (r.anc && (!r.one_row || r.s_Lmax > ANC_MAX)) return hipErrorInvalidValue;  // the two-row kernel reads the cache directly
   DecRow2P q{r, mem, mem_stride, wk, wv_t, bv, nullptr, nullptr, mem_hi, mem_lo, row0, len};
   static const int probe = D2T_PROBE_ENV("D2T_ROW_PROBE");  // probe builds only: skip phases (results are garbage by construction)
   q.r.probe = probe;
+  // ---- which kernel: [cross-attention on split-bf16 MFMAs][memory tables: none, per row, per sample] ----
+  using Kernel = void (*)(const DecRow2P);
+  static const Kernel one_row_kernels[2][3] = {
+      {decoder_row_absorbed_kernel<256, 0, false, 0>, decoder_row_absorbed_kernel<256, 0, false, 1>, decoder_row_absorbed_kernel<256, 0, false, 2>},
+      {decoder_row_absorbed_kernel<256, 0, true, 0>, decoder_row_absorbed_kernel<256, 0, true, 1>, decoder_row_absorbed_kernel<256, 0, true, 2>}};
+  static const Kernel two_row_kernels[2][2] = {{decoder_row2_absorbed_pf_kernel, decoder_row2_absorbed_pf_ragged_kernel},
+                                               {decoder_row2_absorbed_bx3_kernel, decoder_row2_absorbed_bx3_ragged_kernel}};
   static const bool one_row = D2T_PROBE_ENV_STR("D2T_DECODE_ONE_ROW_BLOCKS") != nullptr;  // A/B: the one-row-per-block form for every row
-  if (r.anc && (!r.one_row || r.s_Lmax > ANC_MAX)) return hipErrorInvalidValue;  // the two-row kernel reads the cache directly
-  if (ragged) {  // the ragged builds of the same two forms (no probe-build A/B variants)
-    const bool bx3 = mem_hi && mem_lo;
-    if (by_sample) {
-      if (bx3) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true, 2>), dim3(r.M), dim3(256), 0, s, q);
-      else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, false, 2>), dim3(r.M), dim3(256), 0, s, q);
-    } else if (r.one_row) {
-      if (bx3) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true, 1>), dim3(r.M), dim3(256), 0, s, q);
-      else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, false, 1>), dim3(r.M), dim3(256), 0, s, q);
-    } else if (bx3) hipLaunchKernelGGL(decoder_row2_absorbed_bx3_ragged_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
-    else hipLaunchKernelGGL(decoder_row2_absorbed_pf_ragged_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
-    return hipGetLastError();
-  }
-  if (one_row || r.one_row) {
-    if (mem_hi && mem_lo) hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0, true>), dim3(r.M), dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((decoder_row_absorbed_kernel<256, 0>), dim3(r.M), dim3(256), 0, s, q);
-    return hipGetLastError();
-  }
-#ifdef D2T_PROBES
-  static const bool no_pf = getenv("D2T_DECODE_ROW2_NO_PREFETCH") != nullptr;  // A/B: the round-3 issue order
-  if (no_pf) { hipLaunchKernelGGL(decoder_row2_absorbed_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q); return hipGetLastError(); }
-#endif
-  if (mem_hi && mem_lo) hipLaunchKernelGGL(decoder_row2_absorbed_bx3_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
-  else hipLaunchKernelGGL(decoder_row2_absorbed_pf_kernel, dim3((r.M + 1) / 2), dim3(512), 0, s, q);
+  const int bx3 = mem_hi && mem_lo;
+  if (r.one_row || (one_row && !ragged)) hipLaunchKernelGGL(one_row_kernels[bx3][by_sample ? 2 : ragged], dim3(r.M), dim3(256), 0, s, q);
+  else hipLaunchKernelGGL(two_row_kernels[bx3][ragged], dim3((r.M + 1) / 2), dim3(512), 0, s, q);
   return hipGetLastError();
 }
 
@@ -2078,32 +1731,18 @@ __global__ __launch_bounds__(256, 1) void beam_cross_kernel(const BeamCrossP p) 
 #pragma unroll
     for (int rt = 0; rt < NR; ++rt) {
       if (rt < nrt) {
-        float sv[4], mx = -INFINITY;
+        f32x4 sc;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
           const int o = (4 * g + reg) * (NR * 16) + rt * 16 + col;
-          const float sc = (part[o] + part[16 * NR * 16 + o]) + (part[2 * 16 * NR * 16 + o] + part[3 * 16 * NR * 16 + o]);
-          sv[reg] = (j0 + 4 * g + reg < T) ? sc : -INFINITY;
-          mx = fmaxf(mx, sv[reg]);
+          sc[reg] = (part[o] + part[16 * NR * 16 + o]) + (part[2 * 16 * NR * 16 + o] + part[3 * 16 * NR * 16 + o]);
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run[rt], mx);
-        const float alpha = expf(m_run[rt] - m_new);
-        float ps = 0.f;
+        float ar[4];  // the accumulators hold ctx[row 16 rt + 4g + reg]: lane 4g + reg has that row's alpha
+        online_softmax_tile(sc, j0, g, T, m_run[rt], l_run[rt], pv[rt], ar);
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          pv[rt][reg] = expf(sv[reg] - m_new);
-          ps += pv[rt][reg];
-        }
-        l_run[rt] = l_run[rt] * alpha + ps;
-        m_run[rt] = m_new;
+        for (int reg = 0; reg < 4; ++reg)
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {  // the accumulators hold ctx[row 16 rt + 4g + reg]: lane 4g + reg has that row's alpha
-          const float ar = __shfl(alpha, 4 * g + reg, 64);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[rt][e][reg] *= ar;
-        }
+          for (int e = 0; e < 4; ++e) acc[rt][e][reg] *= ar[reg];
       } else {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) pv[rt][reg] = 0.f;
@@ -2166,11 +1805,9 @@ hipError_t launch_decoder_row_beam(const DecRowP& r, const float* mem, long long
 // ---------------------------------------------------------------------------------------------------------------------
 template <int D, int HD>
 __global__ __launch_bounds__(512, 1) void decoder_row2_kernel(const DecRowP p) {
-  constexpr int NTH = 512, LPR = D / 4, G = NTH / LPR, KG = D / G;
+  constexpr int NTH = 512, G = NTH / (D / 4);
   static_assert(D / HD == 8 && NTH / 64 == 8, "one wave per head");
-  if (p.stop_at && *p.stop_at && *p.step_ptr >= *p.stop_at) return;  // block-uniform
-  decode_wave_priority();
-  TraceScope trace_(p.trace);
+  ROW_KERNEL_ENTRY(p, false);
   __shared__ __attribute__((aligned(16))) float a_s[2][D], y_s[2][D], x1_s[2][D], q2_s[2][D], part_s[2][G * D];
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int t = *p.step_ptr;
@@ -2181,82 +1818,28 @@ __global__ __launch_bounds__(512, 1) void decoder_row2_kernel(const DecRowP p) {
     valid[r] = 2 * (int)blockIdx.x + r < p.M;
     b[r] = valid[r] ? 2 * blockIdx.x + r : p.M - 1;
   }
-  // one GEMV for both rows: thread (lr, g) -> columns 4 lr .. 4 lr + 3, k in [g KG, (g + 1) KG)
-  auto gemv2 = [&](const float* in0, const float* in1, const float* __restrict__ Wt) {
-    const int lr = tid % LPR, g = tid / LPR;
-    const float* w = Wt + (size_t)(g * KG) * D + lr * 4;
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-#pragma unroll 16
-    for (int k = 0; k < KG; ++k) {
-      const float4 w4 = *reinterpret_cast<const float4*>(w + (size_t)k * D);
-      const float x0 = in0[g * KG + k], x1 = in1[g * KG + k];
-      a0.x = fmaf(x0, w4.x, a0.x); a0.y = fmaf(x0, w4.y, a0.y); a0.z = fmaf(x0, w4.z, a0.z); a0.w = fmaf(x0, w4.w, a0.w);
-      a1.x = fmaf(x1, w4.x, a1.x); a1.y = fmaf(x1, w4.y, a1.y); a1.z = fmaf(x1, w4.z, a1.z); a1.w = fmaf(x1, w4.w, a1.w);
-    }
-    *reinterpret_cast<float4*>(part_s[0] + g * D + lr * 4) = a0;
-    *reinterpret_cast<float4*>(part_s[1] + g * D + lr * 4) = a1;
-  };
   // ---- self-attention: wave = head, both rows in one loop ----
   {
-    const int head = wave;
-    const float *qh[2], *Kh[2], *Vh[2], *ck[2], *cv[2];
-    float* oh[2];
+    HeadPair h2;
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float* qkv = p.qkv + (size_t)b[r] * p.qkv_stride;
-      float* Kc = p.sk + (size_t)b[r] * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-      float* Vc = p.sv + (size_t)b[r] * p.s_batch_stride + (size_t)head * p.s_Lmax * HD;
-      ck[r] = qkv + D + head * HD;
-      cv[r] = qkv + 2 * D + head * HD;
-      if (lane < HD && valid[r]) {
-        Kc[(size_t)t * HD + lane] = ck[r][lane];
-        Vc[(size_t)t * HD + lane] = cv[r][lane];
-      }
-      qh[r] = qkv + head * HD; Kh[r] = Kc; Vh[r] = Vc; oh[r] = a_s[r] + head * HD;
-    }
-    row_attention_2h<4, HD>(qh, Kh, Vh, ck, cv, t, t + 1, oh, lane);
+    for (int r = 0; r < 2; ++r) h2.set(r, cache_append_and_heads<D, HD>(p, b[r], wave, t, lane, valid[r]), a_s[r] + wave * HD);
+    row_attention_2h<4, HD>(h2.q, h2.K, h2.V, h2.curk, h2.curv, t, t + 1, h2.out, lane);
   }
   __syncthreads();
-  gemv2(a_s[0], a_s[1], p.wo_t);
+  gemv2<D, NTH, 16>(a_s[0], a_s[1], p.wo_t, part_s[0], part_s[1], tid);
   __syncthreads();
   for (int i = tid; i < 2 * D; i += NTH) {
     const int r = i / D, c = i % D;
-    float v = p.bo[c] + p.xres[(size_t)(r ? b[1] : b[0]) * D + c];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[r][g * D + c];
-    y_s[r][c] = v;
+    y_s[r][c] = sum_parts<G, D>(part_s[r], c, p.bo[c] + p.xres[(size_t)(r ? b[1] : b[0]) * D + c]);
   }
   __syncthreads();
-  if (wave < 2) {  // LN1, two-pass, one wave per row
-    const int r = wave;
-    constexpr int V = D / 64;
-    float v[V], sm = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] = y_s[r][i * 64 + lane]; sm += v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o, 64);
-    const float mean = sm * (1.f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) { v[i] -= mean; q += v[i] * v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    const float rstd = 1.f / sqrtf(q * (1.f / D) + p.eps);
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const int c = i * 64 + lane;
-      x1_s[r][c] = v[i] * rstd * p.ln1_g[c] + p.ln1_b[c];
-    }
-  }
+  if (wave < 2) row_ln1<D>(y_s[wave], x1_s[wave], lane, p);  // one wave per row
   __syncthreads();
-  gemv2(x1_s[0], x1_s[1], p.wq_t);
+  gemv2<D, NTH, 16>(x1_s[0], x1_s[1], p.wq_t, part_s[0], part_s[1], tid);
   __syncthreads();
   for (int i = tid; i < 2 * D; i += NTH) {
     const int r = i / D, c = i % D;
-    float v = p.bq[c];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[r][g * D + c];
-    q2_s[r][c] = v;
+    q2_s[r][c] = sum_parts<G, D>(part_s[r], c, p.bq[c]);
   }
   __syncthreads();
   // ---- cross-attention over the projected memory K / V: wave = head, both rows in one loop ----
@@ -2275,13 +1858,11 @@ __global__ __launch_bounds__(512, 1) void decoder_row2_kernel(const DecRowP p) {
     row_attention_2h<8, HD>(qh, Kh, Vh, none, none, -1, p.T, oh, lane);
   }
   __syncthreads();
-  gemv2(a_s[0], a_s[1], p.wco_t);
+  gemv2<D, NTH, 16>(a_s[0], a_s[1], p.wco_t, part_s[0], part_s[1], tid);
   __syncthreads();
   for (int i = tid; i < 2 * D; i += NTH) {
     const int r = i / D, c = i % D;
-    float v = p.bco[c] + x1_s[r][c];
-#pragma unroll
-    for (int g = 0; g < G; ++g) v += part_s[r][g * D + c];
+    const float v = sum_parts<G, D>(part_s[r], c, p.bco[c] + x1_s[r][c]);
     if (r ? valid[1] : valid[0]) p.y2[(size_t)(r ? b[1] : b[0]) * D + c] = v;
   }
 }
