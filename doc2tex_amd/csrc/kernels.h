@@ -415,7 +415,7 @@ hipError_t launch_bilstm_train_bwd(const float* dout, const float* sv_gates, con
 // hprev[d][b*T + t][H] = h of direction d at the step processed before t (zero at its first step), from out [B*T][2H]
 hipError_t launch_bilstm_hprev(const float* out, float* hprev_fwd, float* hprev_rev, int B, int T, int H, hipStream_t s);
 
-// ---- training step (train_kernels.hip) --------------------------------------
+// ---- training step (train_kernels.hip, train_wgrad.hip, train_attn.hip) --------------------------------------
 // Weight gradient ("TN" GEMM, optional filter taps): part[z][tap][m][n] = sum_{p in chunk z} a[p][m] * x[src(p,tap)][n]
 struct WgradP {
   const float* a;   // [P][lda]: upstream gradient rows (dz of a convolution / dy of a Linear)
@@ -428,15 +428,21 @@ struct WgradP {
   int S, chunk;     // split over row chunks of `chunk` rows
   int bf16x3;       // 128 x 128 tiles only: split-bf16 arithmetic (three bf16 MFMAs per product)
   // both set: the operands as split-bf16 records ([row][32 x hi | 32 x lo] per 32-column group, conv_common.h) of a / b --
-  // geom convolutions with wgrad_rec_shape(M, N) >= 0 and chunk % 16 == 0 in bf16x3 mode; `zero`: 256 zero bytes
+  // geom convolutions with a wgrad_rec_tile(M, N) and chunk % 16 == 0 in bf16x3 mode; `zero`: 256 zero bytes
   const uint16_t* a_rec = nullptr;
   const uint16_t* b_rec = nullptr;
   const void* zero = nullptr;
 };
 hipError_t launch_wgrad(const WgradP& p, hipStream_t s);
-// record kernel's block tile: 0 = 128 x 128 (three blocks per CU), 1 = 256 x 128 (two), 2 = 256 x 256 (one), 3 = 128 x 64 (N = 64),
-// 4 = 64 x 32 (M = 64, N = 32); -1 = not served
-int wgrad_rec_shape(int M, int N);
+// a block tile of the record kernel: 256 x 256 (one block per CU), 256 x 128 (two), 128 x 128 (three), 128 x 64 (N = 64),
+// 64 x 32 (M = 64, N = 32)
+struct WgradRecTile {
+  int bm, bn, threads;
+  int slots;  // blocks of this tile the device holds at once
+  void (*kernel)(const WgradP);
+};
+// the tile launch_wgrad takes for record operands of M x N channels; nullptr = not served
+const WgradRecTile* wgrad_rec_tile(int M, int N);
 hipError_t launch_wgrad_reduce(const float* part, float* dst, int S, int taps, int M, int N, int layout, int accumulate,
                                hipStream_t s);
 enum { CR_SUM = 0, CR_SUM_SQ = 1, CR_BN_BWD = 2, CR_LN_BWD = 3 };

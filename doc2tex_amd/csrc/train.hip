@@ -8,7 +8,7 @@
 //
 // Supported stack: HybridViT (ResNet backbone + ViTEncoderV3) or ResNet+None encoders with the TFM head; dropout 0.
 // All arithmetic fp32: GEMMs and convolutions (forward and data gradients) on the fp32-MFMA implicit-GEMM kernel
-// (conv_mfma.hip), weight gradients on the fp32-MFMA TN kernel (train_kernels.hip).  The network is recorded as a
+// (conv_mfma.hip), weight gradients on the fp32-MFMA TN kernel (train_wgrad.hip).  The network is recorded as a
 // tape of nodes over row-major [rows][cols] tensors (NHWC maps are [B*H*W][C]); the backward walks it in reverse and
 // accumulates into tensor gradients, so residual fan-out needs no special cases.
 #include "ctx.h"
@@ -219,15 +219,26 @@ struct Tr {  // builder / runner bound to one context and stream
     p->split_tail = 1;
     return D2T_OK;
   }
-  // dst[c] (+)= column sums of a[R][C]
-  int colsum(const float* a, long long R, int C, float* dst) {
-    const int chunks = colreduce_chunks(R, C);
-    RC(ensure_part((size_t)chunks * 2 * C));
-    ColRedP p{};
-    p.a = a; p.part = st->part; p.R = R; p.C = C; p.mode = CR_SUM;
+  // the column reduction p describes (a, y, z, mean, rstd, R, C, mode) into per-chunk partials in st->part; *chunks: how many
+  int colreduce_part(ColRedP p, int* chunks) {
+    *chunks = colreduce_chunks(p.R, p.C);
+    RC(ensure_part((size_t)*chunks * 2 * p.C));
+    p.part = st->part;
     TCHK(launch_colreduce(p, s));
-    TCHK(launch_colreduce_final(st->part, chunks, C, dst, nullptr, 0, s));
     return D2T_OK;
+  }
+  // ... and its two sums per column into out0[C], out1[C] (out1 nullable)
+  int colreduce2(const ColRedP& p, float* out0, float* out1) {
+    int chunks;
+    RC(colreduce_part(p, &chunks));
+    TCHK(launch_colreduce_final(st->part, chunks, p.C, out0, out1, 0, s));
+    return D2T_OK;
+  }
+  // dst[c] = column sums of a[R][C]
+  int colsum(const float* a, long long R, int C, float* dst) {
+    ColRedP p{};
+    p.a = a; p.R = R; p.C = C; p.mode = CR_SUM;
+    return colreduce2(p, dst, nullptr);
   }
   // dW[M][N](taps) = a^T (x) b  with the split-K two-pass reduction
   int wgrad(const float* a, int lda, const float* b, int ldb, long long P, int M, int N, int taps, const Node* geom,
@@ -235,16 +246,15 @@ struct Tr {  // builder / runner bound to one context and stream
             const uint16_t* b_rec = nullptr) {
     // both operands exist as split-bf16 records (a convolution between BatchNorm layers): the LDS-DMA kernel
     static const bool rec_off = D2T_PROBE_ENV_STR("D2T_WGRAD_REC") && D2T_PROBE_ENV("D2T_WGRAD_REC") == 0;
-    const int shape = !rec_off && a_rec && b_rec && geom && c->conv_bf16x3 && c->zero_page && lda == M && ldb == N ? wgrad_rec_shape(M, N) : -1;
-    const bool rec = shape >= 0;
-    static const int TM[5] = {128, 256, 256, 128, 64}, TN[5] = {128, 128, 256, 64, 32}, SLOTS[5] = {768, 512, 256, 1024, 2048};
+    const WgradRecTile* rec =
+        !rec_off && a_rec && b_rec && geom && c->conv_bf16x3 && c->zero_page && lda == M && ldb == N ? wgrad_rec_tile(M, N) : nullptr;
     const int tile = (M <= 64 || N <= 64) ? 64 : 128;
-    const long long tiles = rec ? (long long)(M / TM[shape]) * (N / TN[shape]) * taps
+    const long long tiles = rec ? (long long)(M / rec->bm) * (N / rec->bn) * taps
                                 : (long long)((M + tile - 1) / tile) * ((N + tile - 1) / tile) * taps;
     // split the rows into S chunks so that tiles * S blocks fill whole rounds of the block slots (two 64 KB-LDS blocks per
     // CU on 256 CUs; the record kernel: one to eight per CU by tile shape): among the S that give >= ~2 rounds pick the
     // one wasting least of its last round
-    const long long slots = rec ? SLOTS[shape] : 512;
+    const long long slots = rec ? rec->slots : 512;
     const long long smax = std::max<long long>(1, (P + 511) / 512);
     long long S = 1;
     double best = -1.0;
@@ -280,6 +290,15 @@ struct Tr {  // builder / runner bound to one context and stream
     if (!x.grad) { x.grad = g; return D2T_OK; }
     TCHK(launch_ew(x.grad, g, x.grad, (size_t)x.rows * x.cols, EW_ADD, s));
     return D2T_OK;
+  }
+  // gradient of tensor `id` from one launch: a fresh dx of the tensor's n elements, launch(dx, n) fills it, then add_grad
+  template <class F>
+  int grad_to(int id, F launch) {
+    const size_t n = (size_t)st->t[id].rows * st->t[id].cols;
+    float* dx;
+    RC(alloc(&dx, n));
+    TCHK(launch(dx, n));
+    return add_grad(id, dx);
   }
   int own_grad(int id) {  // make sure tensor `id` has a gradient buffer (contents unspecified)
     TT& x = st->t[id];
@@ -322,7 +341,7 @@ struct Tr {  // builder / runner bound to one context and stream
     if (bnkey.empty()) {
       RC(new_tensor(P, Cout, out, x.B, OH, OW, n.z));
     } else {
-      RC(bn_forward(n, P, Cout, res));
+      RC(bn_forward(n, P, Cout));
       RC(new_tensor(P, Cout, out, x.B, OH, OW));
       const float *g, *b;
       RC(raw(bnkey + ".weight", &g, Cout));
@@ -336,14 +355,13 @@ struct Tr {  // builder / runner bound to one context and stream
     st->nodes.push_back(n);
     return D2T_OK;
   }
-  int bn_forward(Node& n, long long P, int C, int /*res*/) {
+  int bn_forward(Node& n, long long P, int C) {
     RC(alloc(&n.mean, C));
     RC(alloc(&n.rstd, C));
-    const int chunks = colreduce_chunks(P, C);
-    RC(ensure_part((size_t)chunks * 2 * C));
     ColRedP p{};
-    p.a = n.z; p.part = st->part; p.R = P; p.C = C; p.mode = CR_SUM_SQ;
-    TCHK(launch_colreduce(p, s));
+    p.a = n.z; p.R = P; p.C = C; p.mode = CR_SUM_SQ;
+    int chunks;
+    RC(colreduce_part(p, &chunks));
     const RawW *rm, *rv;
     RC(need(c, n.bnkey + ".running_mean", &rm));
     RC(need(c, n.bnkey + ".running_var", &rv));
@@ -360,7 +378,7 @@ struct Tr {  // builder / runner bound to one context and stream
     RC(raw(wkey + ".weight", &w, (size_t)Cout * 9 * Cin));
     RC(alloc(&n.z, (size_t)P * Cout));
     TCHK(launch_stem_raw(img, w, n.z, B, Cin, H, W, Cout, s));
-    RC(bn_forward(n, P, Cout, -1));
+    RC(bn_forward(n, P, Cout));
     RC(new_tensor(P, Cout, out, B, H, W));
     const float *g, *b;
     RC(raw(bnkey + ".weight", &g, Cout));
@@ -682,7 +700,7 @@ struct Tr {  // builder / runner bound to one context and stream
     const d2t_config& g = c->cfg;
     const TT f = st->t[feat];
     const int D = g.vit_dim, gh = (f.H + g.patch_h - 1) / g.patch_h, gw = (f.W + g.patch_w - 1) / g.patch_w, n = gh * gw;
-    // (memories beyond about 600 tokens: the training attention kernels read K / V from global memory, train_kernels.hip GKV)
+    // (memories beyond about 600 tokens: the training attention kernels read K / V from global memory, train_attn.hip GKV)
     if (n + 1 > 4096) return fail(c, D2T_EINVAL, "training step: memory length %d > 4096 unsupported", n + 1);
     int patch;
     // zero padding right / bottom = out-of-image taps of the strided convolution
@@ -1082,16 +1100,10 @@ struct Tr {  // builder / runner bound to one context and stream
     float *dg, *db;
     RC(grad_buf(n.gkey + ".weight", &dg));
     RC(grad_buf(n.gkey + ".bias", &db));
-    const int chunks = colreduce_chunks(x.rows, x.cols);
-    RC(ensure_part((size_t)chunks * 2 * x.cols));
     ColRedP p{};
-    p.a = y.grad; p.z = x.p; p.mean = n.mean; p.rstd = n.rstd; p.part = st->part; p.R = x.rows; p.C = x.cols; p.mode = CR_LN_BWD;
-    TCHK(launch_colreduce(p, s));
-    TCHK(launch_colreduce_final(st->part, chunks, x.cols, db, dg, 0, s));
-    float* dx;
-    RC(alloc(&dx, (size_t)x.rows * x.cols));
-    TCHK(launch_ln_bwd(y.grad, x.p, n.mean, n.rstd, g, nullptr, dx, (int)x.rows, x.cols, s));
-    return add_grad(n.in, dx);
+    p.a = y.grad; p.z = x.p; p.mean = n.mean; p.rstd = n.rstd; p.R = x.rows; p.C = x.cols; p.mode = CR_LN_BWD;
+    RC(colreduce2(p, db, dg));
+    return grad_to(n.in, [&](float* dx, size_t) { return launch_ln_bwd(y.grad, x.p, n.mean, n.rstd, g, nullptr, dx, (int)x.rows, x.cols, s); });
   }
   int bwd_attn(const Node& n) {
     RC(own_grad(n.in));
@@ -1121,13 +1133,10 @@ struct Tr {  // builder / runner bound to one context and stream
       float *dgam, *dbet, *s0, *s1, *dzb, *gres = nullptr;
       RC(grad_buf(n.bnkey + ".weight", &dgam));
       RC(grad_buf(n.bnkey + ".bias", &dbet));
-      const int chunks = colreduce_chunks(P, Cout);
-      RC(ensure_part((size_t)chunks * 2 * Cout));
       ColRedP p{};
-      p.a = y.grad; p.y = n.relu ? y.p : nullptr; p.z = n.z; p.mean = n.mean; p.rstd = n.rstd; p.part = st->part;
+      p.a = y.grad; p.y = n.relu ? y.p : nullptr; p.z = n.z; p.mean = n.mean; p.rstd = n.rstd;
       p.R = P; p.C = Cout; p.mode = CR_BN_BWD;
-      TCHK(launch_colreduce(p, s));
-      TCHK(launch_colreduce_final(st->part, chunks, Cout, dbet, dgam, 0, s));
+      RC(colreduce2(p, dbet, dgam));
       s0 = dbet; s1 = dgam;
       RC(alloc(&dzb, (size_t)P * Cout));
       if (n.in2 >= 0) RC(alloc(&gres, (size_t)P * Cout));
@@ -1185,10 +1194,9 @@ struct Tr {  // builder / runner bound to one context and stream
   }
   int bwd_pool(const Node& n) {
     const TT& x = st->t[n.in];
-    float* dx;
-    RC(alloc(&dx, (size_t)x.rows * x.cols));
-    TCHK(launch_maxpool_bwd(x.p, st->t[n.out].grad, dx, x.B, x.H, x.W, x.cols, n.SH, n.SW, n.PH, n.PW, s, n.KW));
-    return add_grad(n.in, dx);
+    return grad_to(n.in, [&](float* dx, size_t) {
+      return launch_maxpool_bwd(x.p, st->t[n.out].grad, dx, x.B, x.H, x.W, x.cols, n.SH, n.SW, n.PH, n.PW, s, n.KW);
+    });
   }
   int bwd_tokens(const Node& n) {
     const TT& y = st->t[n.out];
@@ -1234,14 +1242,9 @@ struct Tr {  // builder / runner bound to one context and stream
         case N_TOKENS: RC(bwd_tokens(n)); break;
         case N_ADDCONST: RC(add_grad(n.in, st->t[n.out].grad)); break;
         case N_LSTM: RC(bwd_lstm(n)); break;
-        case N_DROPOUT: {
-          const TT& x = st->t[n.in];
-          float* dx;
-          RC(alloc(&dx, (size_t)x.rows * x.cols));
-          TCHK(launch_apply_mask(st->t[n.out].grad, n.mask, n.mscale, dx, (size_t)x.rows * x.cols, s));
-          RC(add_grad(n.in, dx));
+        case N_DROPOUT:
+          RC(grad_to(n.in, [&](float* dx, size_t k) { return launch_apply_mask(st->t[n.out].grad, n.mask, n.mscale, dx, k, s); }));
           break;
-        }
         case N_ADD: {  // both operands receive the gradient; the second gets its own copy unless it only accumulates
           float* g = st->t[n.out].grad;
           RC(add_grad(n.in, g));
@@ -1256,22 +1259,15 @@ struct Tr {  // builder / runner bound to one context and stream
           break;
         }
         case N_BILSTM: RC(bwd_bilstm(n)); break;
-        case N_MEANH: {
-          const TT& x = st->t[n.in];
-          float* dx;
-          RC(alloc(&dx, (size_t)x.rows * x.cols));
-          TCHK(launch_mean_h_bwd(st->t[n.out].grad, dx, x.B, x.H, x.W, x.cols, s));
-          RC(add_grad(n.in, dx));
+        case N_MEANH:
+          RC(grad_to(n.in, [&](float* dx, size_t) {
+            const TT& x = st->t[n.in];
+            return launch_mean_h_bwd(st->t[n.out].grad, dx, x.B, x.H, x.W, x.cols, s);
+          }));
           break;
-        }
-        case N_RELU: {
-          const TT& x = st->t[n.in];
-          float* dx;
-          RC(alloc(&dx, (size_t)x.rows * x.cols));
-          TCHK(launch_ew(st->t[n.out].grad, st->t[n.out].p, dx, (size_t)x.rows * x.cols, EW_RELU_BWD, s));
-          RC(add_grad(n.in, dx));
+        case N_RELU:
+          RC(grad_to(n.in, [&](float* dx, size_t k) { return launch_ew(st->t[n.out].grad, st->t[n.out].p, dx, k, EW_RELU_BWD, s); }));
           break;
-        }
         case N_BCAST: {  // out = x + y[b]: dx = dout; dy[b][c] = sum over the image's positions
           const TT& x = st->t[n.in];
           const TT& o = st->t[n.out];
@@ -1310,14 +1306,9 @@ struct Tr {  // builder / runner bound to one context and stream
           TCHK(launch_sum_small(sdl, B, dbg, s));
           break;
         }
-        case N_GELU: {
-          const TT& x = st->t[n.in];
-          float* dx;
-          RC(alloc(&dx, (size_t)x.rows * x.cols));
-          TCHK(launch_ew(st->t[n.out].grad, x.p, dx, (size_t)x.rows * x.cols, EW_GELU_BWD, s));
-          RC(add_grad(n.in, dx));
+        case N_GELU:
+          RC(grad_to(n.in, [&](float* dx, size_t k) { return launch_ew(st->t[n.out].grad, st->t[n.in].p, dx, k, EW_GELU_BWD, s); }));
           break;
-        }
         case N_EMBED: {
           float* dE;
           RC(grad_buf(n.wkey, &dE));

@@ -1,14 +1,12 @@
 // Kernels of the training step (train.hip): everything module.train() + loss.backward() needs beyond the
-// forward GEMM/convolution kernel, all fp32.
+// forward GEMM/convolution kernel, the weight gradients (train_wgrad.hip) and softmax attention (train_attn.hip), all fp32.
 //
-//   wgrad_kernel        weight gradients of Conv2d / Linear: the "TN" GEMM  dW[co][tap][ci] = sum_p dz[p][co] * x[p+tap][ci]
-//                       on the fp32 MFMA, split over pixel chunks (deterministic two-pass reduction)
 //   colreduce_kernel    per-channel sums over rows: BatchNorm batch statistics, BatchNorm / LayerNorm parameter
 //                       gradients, bias gradients
 //   bn_*                BatchNorm2d in training mode (batch statistics, running-statistics update, backward)
 //   ln_*                LayerNorm forward with saved statistics, backward
-//   attn_*              softmax attention forward (saving the probabilities) and backward, causal / key-padding masks
-//   maxpool_bwd, relu/gelu backward, embedding backward, small data-movement helpers
+//   ce_*                fused cross-entropy, plain and smoothed / class-weighted
+//   maxpool_bwd, relu/gelu backward, embedding, dropout masks, GlobalContext, BiLSTM, small data-movement helpers
 //
 // Reference semantics: torch autograd of feature_extractor/resnet.py:205-245, seq_modeling/vit/vision_transformer.py:26-122,
 // prediction_head/tfm.py:103-118 as driven by engine/training.py:76-164.
@@ -18,588 +16,14 @@
 
 #include "conv_common.h"
 #include "kernels.h"
+#include "train_common.h"
 
 namespace d2t {
 
 namespace {
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 constexpr int EW_THREADS = 256;
 inline int ew_grid(size_t n4) { return (int)std::min<size_t>((n4 + EW_THREADS - 1) / EW_THREADS, 65535u * 16u); }
 }  // namespace
-
-// ---------------------------------------------------------------------------
-// wgrad: out[z][tap][m][n] = sum_{p in chunk z} A[p][m] * X[src(p, tap)][n]
-// Block tile BM x BN, 4 waves (2x2), K-step = 32 rows; both operand tiles are stored [k][col] in LDS exactly as
-// they lie in memory (rows = pixels, contiguous channels), and v_mfma_f32_32x32x2_f32 wants A[i][k] / B[k][j] with
-// i, j = lane & 31: consecutive lanes read consecutive floats of one LDS row -> conflict-free ds_read_b32.
-// ---------------------------------------------------------------------------
-template <int BM, int BN>
-__global__ __launch_bounds__(256) void wgrad_kernel(const WgradP p) {
-  constexpr int BK = 32;
-  constexpr int WTM = BM / 2, WTN = BN / 2, MI = WTM / 32, NJ = WTN / 32;
-  constexpr int AV = BM / 4, BV = BN / 4;               // float4 per tile row
-  constexpr int ALD = (BK * AV) / 256, BLD = (BK * BV) / 256;  // float4 loads per thread per stage
-  static_assert(ALD >= 1 && BLD >= 1, "tile too small");
-  __shared__ __attribute__((aligned(16))) float As[2][BK][BM];
-  __shared__ __attribute__((aligned(16))) float Bs[2][BK][BN];
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int m0 = (blockIdx.x / tiles_n) * BM, n0 = (blockIdx.x % tiles_n) * BN;
-  const int tap = blockIdx.y, kh = tap / p.KW, kw = tap % p.KW;
-  const int z = blockIdx.z;
-  const long long r_begin = (long long)z * p.chunk;
-  const long long r_end = r_begin + p.chunk < p.P ? r_begin + p.chunk : p.P;
-  const int ohow = p.OH * p.OW;
-
-  float4 ra[ALD], rb[BLD];
-  auto fetch = [&](long long r0) {
-#pragma unroll
-    for (int i = 0; i < ALD; ++i) {
-      const int idx = tid + i * 256, row = idx / AV, c4 = (idx % AV) * 4;
-      const long long r = r0 + row;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < r_end && m0 + c4 < p.M) v = *reinterpret_cast<const float4*>(p.a + r * p.lda + m0 + c4);
-      ra[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < BLD; ++i) {
-      const int idx = tid + i * 256, row = idx / BV, c4 = (idx % BV) * 4;
-      const long long r = r0 + row;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < r_end && n0 + c4 < p.N) {
-        long long src = r;
-        bool ok = true;
-        if (p.geom) {
-          const int b = (int)(r / ohow), rem = (int)(r - (long long)b * ohow);
-          const int oh = rem / p.OW, ow = rem - oh * p.OW;
-          const int ih = oh * p.SH - p.PH + kh, iw = ow * p.SW - p.PW + kw;
-          ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-          src = ((long long)b * p.H + ih) * p.W + iw;
-        }
-        if (ok) v = *reinterpret_cast<const float4*>(p.b + src * p.ldb + n0 + c4);
-      }
-      rb[i] = v;
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < ALD; ++i) {
-      const int idx = tid + i * 256, row = idx / AV, c4 = (idx % AV) * 4;
-      *reinterpret_cast<float4*>(&As[buf][row][c4]) = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < BLD; ++i) {
-      const int idx = tid + i * 256, row = idx / BV, c4 = (idx % BV) * 4;
-      *reinterpret_cast<float4*>(&Bs[buf][row][c4]) = rb[i];
-    }
-  };
-
-  const int wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
-  f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  const int steps = (int)((r_end - r_begin + BK - 1) / BK);
-  if (steps > 0) {
-    fetch(r_begin);
-    stash(0);
-  }
-  __syncthreads();
-  for (int st = 0; st < steps; ++st) {
-    const int cur = st & 1;
-    if (st + 1 < steps) fetch(r_begin + (long long)(st + 1) * BK);
-#pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
-      float fa[MI], fb[NJ];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) fa[i] = As[cur][2 * kk + h][wm * WTM + i * 32 + r];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) fb[j] = Bs[cur][2 * kk + h][wn * WTN + j * 32 + r];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    if (st + 1 < steps) stash(cur ^ 1);
-    __syncthreads();
-  }
-  float* out = p.part + ((size_t)z * p.taps + tap) * p.M * p.N;
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int n = n0 + wn * WTN + j * 32 + r;
-      if (n >= p.N) continue;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int m = m0 + wm * WTM + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        if (m < p.M) out[(size_t)m * p.N + n] = acc[i][j][reg];
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Split-bf16 weight gradient (conv_precision = bf16x3): the same TN GEMM on v_mfma_f32_32x32x16_bf16 with
-// dz = hi + lo, x = hi + lo and three MFMAs per product.  Both operand tiles stay pixel-major in LDS (rows = pixels,
-// exactly as they are loaded and split); the MFMA wants, per lane, eight consecutive K (= pixel) values of ONE column,
-// which is what gfx950's transposing LDS read delivers: ds_read_b64_tr_b16 hands lane i of a 16-lane group column i of
-// a 4-row x 16-column block.  Two of them per fragment.  LDS rows are 320 B (256 B of data + 64 B pad): a 32-lane
-// half reads 4 rows x 64 B, and a row stride of 64 (mod 256) bytes makes those 256 bytes hit all 64 banks once.
-// Block tile 128 x 128, 4 waves (wave tile 64 x 64), K-step = 16 pixels, double-buffered, 40 KB of LDS.
-// ---------------------------------------------------------------------------
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s4_t __attribute__((ext_vector_type(4)));
-typedef short s8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s4_t* lds_s4_ptr;
-
-__device__ __forceinline__ void split4_bf16(const float4 v, uint2& hi, uint2& lo) {
-  const unsigned x0 = __float_as_uint(v.x), x1 = __float_as_uint(v.y), x2 = __float_as_uint(v.z), x3 = __float_as_uint(v.w);
-  hi.x = (x0 >> 16) | (x1 & 0xFFFF0000u);
-  hi.y = (x2 >> 16) | (x3 & 0xFFFF0000u);
-  const __bf16 l0 = (__bf16)(v.x - __uint_as_float(x0 & 0xFFFF0000u)), l1 = (__bf16)(v.y - __uint_as_float(x1 & 0xFFFF0000u));
-  const __bf16 l2 = (__bf16)(v.z - __uint_as_float(x2 & 0xFFFF0000u)), l3 = (__bf16)(v.w - __uint_as_float(x3 & 0xFFFF0000u));
-  lo.x = (unsigned)*reinterpret_cast<const unsigned short*>(&l0) | ((unsigned)*reinterpret_cast<const unsigned short*>(&l1) << 16);
-  lo.y = (unsigned)*reinterpret_cast<const unsigned short*>(&l2) | ((unsigned)*reinterpret_cast<const unsigned short*>(&l3) << 16);
-}
-
-__global__ __launch_bounds__(256) void wgrad_bf16x3_kernel(const WgradP p) {
-  constexpr int BM = 128, BN = 128, BK = 16, LDR = 160;  // LDR: uint16 per LDS row (320 B)
-  constexpr int PLANE = BK * LDR;                         // uint16 per plane per stage
-  __shared__ __attribute__((aligned(16))) unsigned short sm[2][4][PLANE];  // [stage][A_hi, A_lo, B_hi, B_lo]
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int m0 = (blockIdx.x / tiles_n) * BM, n0 = (blockIdx.x % tiles_n) * BN;
-  const int tap = blockIdx.y, kh = tap / p.KW, kw = tap % p.KW;
-  const long long r_begin = (long long)blockIdx.z * p.chunk;
-  const long long r_end = r_begin + p.chunk < p.P ? r_begin + p.chunk : p.P;
-  const int ohow = p.OH * p.OW;
-  // staging: 16 rows x 32 float4 per operand = 512 float4 -> two per thread
-  float4 ra[2], rb[2];
-  auto fetch = [&](long long r0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = tid + i * 256, row = idx >> 5, c4 = (idx & 31) * 4;
-      const long long r = r0 + row;
-      float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
-      if (r < r_end) {
-        if (m0 + c4 < p.M) va = *reinterpret_cast<const float4*>(p.a + r * p.lda + m0 + c4);
-        if (n0 + c4 < p.N) {
-          long long src = r;
-          bool ok = true;
-          if (p.geom) {
-            const int b = (int)(r / ohow), rem = (int)(r - (long long)b * ohow);
-            const int oh = rem / p.OW, ow = rem - oh * p.OW;
-            const int ih = oh * p.SH - p.PH + kh, iw = ow * p.SW - p.PW + kw;
-            ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-            src = ((long long)b * p.H + ih) * p.W + iw;
-          }
-          if (ok) vb = *reinterpret_cast<const float4*>(p.b + src * p.ldb + n0 + c4);
-        }
-      }
-      ra[i] = va; rb[i] = vb;
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int idx = tid + i * 256, row = idx >> 5, c4 = (idx & 31) * 4;
-      uint2 hi, lo;
-      split4_bf16(ra[i], hi, lo);
-      *reinterpret_cast<uint2*>(&sm[buf][0][row * LDR + c4]) = hi;
-      *reinterpret_cast<uint2*>(&sm[buf][1][row * LDR + c4]) = lo;
-      split4_bf16(rb[i], hi, lo);
-      *reinterpret_cast<uint2*>(&sm[buf][2][row * LDR + c4]) = hi;
-      *reinterpret_cast<uint2*>(&sm[buf][3][row * LDR + c4]) = lo;
-    }
-  };
-  const int wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
-  // transposing read: group g = lane / 16 covers columns 16 (g & 1) .. +15 of a 32-column fragment and K rows 8 (g >> 1) .. +7
-  const int g = lane >> 4, l16 = lane & 15;
-  const int tr_off = ((8 * (g >> 1) + (l16 >> 2)) * LDR + 16 * (g & 1) + 4 * (l16 & 3));  // uint16 units, rows +0..3
-  auto frag = [&](const unsigned short* plane, int col0) -> bf16x8_t {
-    const unsigned short* q = plane + tr_off + col0;
-    const s4_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(q));
-    const s4_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(q + 4 * LDR));
-    s8_t v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    return __builtin_bit_cast(bf16x8_t, v);
-  };
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const int steps = (int)((r_end - r_begin + BK - 1) / BK);
-  if (steps > 0) { fetch(r_begin); stash(0); }
-  __syncthreads();
-  for (int st = 0; st < steps; ++st) {
-    const int cur = st & 1;
-    if (st + 1 < steps) fetch(r_begin + (long long)(st + 1) * BK);
-    bf16x8_t ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      ah[i] = frag(sm[cur][0], wm * 64 + i * 32);
-      al[i] = frag(sm[cur][1], wm * 64 + i * 32);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      bh[j] = frag(sm[cur][2], wn * 64 + j * 32);
-      bl[j] = frag(sm[cur][3], wn * 64 + j * 32);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-      }
-    if (st + 1 < steps) stash(cur ^ 1);
-    __syncthreads();
-  }
-  float* out = p.part + ((size_t)blockIdx.z * p.taps + tap) * p.M * p.N;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + r;
-      if (n >= p.N) continue;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int m = m0 + wm * 64 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        if (m < p.M) out[(size_t)m * p.N + n] = acc[i][j][reg];
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Split-bf16 weight gradient on operand RECORDS (the convolution layers whose dz and input already exist as
-// [pixel][32 x hi | 32 x lo] records: the BatchNorm kernels write them for the forward / data-gradient convolutions).
-// Same products as wgrad_bf16x3_kernel -- lo*hi, hi*lo, hi*hi into one fp32 accumulator -- but nothing is split or staged
-// through registers: a K-step's 16 pixel rows of both operands travel global -> LDS by LDS-DMA (16 bytes per lane), three
-// stages deep with a counted vmcnt wait and ONE raw barrier per step (the scheme of conv_bf16x3p.hip), and three blocks
-// share a CU so that one block's barrier is covered by the others' MFMAs.
-//   LDS stage = A [16 rows][512 B] | B [16 rows][512 B]; a row = the tile's four records of one pixel = 32 chunks of
-//   16 bytes (chunk 8 g + 0..3: hi of group g, 8 g + 4..7: lo).  Row stride 512 B puts every row on the same banks, so
-//   chunk c of row r is stored at position c ^ ((r & 3) << 2): the four rows of a transposing read (ds_read_b64_tr_b16:
-//   4 rows x 64 B per 32 lanes) then start 64 B apart modulo 256 B and cover the 64 banks once.  The LDS-DMA writes lane
-//   l of a wave at base + 16 l, so the swizzle is applied on the SOURCE side: the lane fetches the chunk that belongs at
-//   its position.
-// ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-template <int N>
-__device__ __forceinline__ void wg_wait_vm() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
-
-// chunk swizzle of an LDS row of ROWB bytes: the four consecutive rows of a transposing read must start in four different
-// 64-byte slots modulo 256 bytes.  Rows of 256 bytes or more all start in the same slot: XOR the row's low two bits into
-// bits 2-3 of the chunk index; 128-byte rows alternate between two slots: flip bit 2 (hi <-> lo half) on rows 2, 3 mod 4.
-template <int ROWB>
-__device__ __forceinline__ int wg_swz(int row) {
-  static_assert(ROWB >= 128, "a row holds at least one record");
-  return ROWB >= 256 ? (row & 3) << 2 : ((row >> 1) & 1) << 2;
-}
-
-template <int MI, int NJ, int WM, int WN, int ABL = 0>
-// (ABL: timing probes -- 1 no MFMAs, 2 no fragment reads, 3 no LDS-DMA, 4 plain ds_read_b64, 5 the step's LDS-DMA issued
-// in one burst behind the barrier)
-// wave tile (32 MI) x (32 NJ), WM x WN waves.  <4,2,2,4> 256 x 256 with 512 threads, one block per CU (a third less
-// L2 -> LDS traffic per MFMA than 256 x 128); <4,2,2,2> 256 x 128, two; <2,2,2,2> 128 x 128, three; and for the narrow
-// layers at the front of the network <2,2,2,1> 128 x 64 (two waves) and <2,1,1,1> 64 x 32 (one wave)
-// (second launch bound = waves per SIMD the register budget must allow: 3 for the 128 x 128 tile, 2 otherwise)
-__global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 && MI == 2 ? 3 : 2)
-void wgrad_rec_kernel(const WgradP p) {
-  constexpr int BK = 16, NS = 3, BM = 32 * MI * WM, BN = 32 * NJ * WN, NT = 64 * WM * WN;
-  constexpr int AROWB = BM * 4, BROWB = BN * 4;      // bytes per LDS row: the tile's records of one pixel
-  constexpr int AOPB = BK * AROWB, BOPB = BK * BROWB, STAGE = AOPB + BOPB;
-  constexpr int ACH = AROWB / 16, BCH = BROWB / 16;  // 16-byte chunks per row
-  constexpr int ARPI = NT / ACH, ANI = BK / ARPI;    // rows per block-wide DMA instruction, instructions per step
-  constexpr int BRPI = NT / BCH, BNI = BK / BRPI;
-  constexpr int PIECES = ANI + BNI, IBYTES = NT * 16;
-  static_assert(ARPI % 4 == 0 && BRPI % 4 == 0, "the source-side swizzle needs (row + k RPI) & 3 == row & 3");
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[NS * STAGE];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tiles_n = p.N / BN;
-  const int m0 = (blockIdx.x / tiles_n) * BM, n0 = (blockIdx.x % tiles_n) * BN;
-  const int tap = blockIdx.y, kh = tap / p.KW, kw = tap % p.KW;
-  const long long r_begin = (long long)blockIdx.z * p.chunk;
-  const long long r_end = r_begin + p.chunk < p.P ? r_begin + p.chunk : p.P;
-  const int KT = (int)((r_end - r_begin + BK - 1) / BK);
-  const unsigned char* zero = reinterpret_cast<const unsigned char*>(p.zero) + (lane & 15) * 16;
-
-  // ---- LDS-DMA source side.  A: rows arow + ARPI i (i < ANI) of every stage, chunk position acpos; B: rows brow + BRPI i ----
-  const int arow = tid / ACH, acpos = tid % ACH, brow = tid / BCH, bcpos = tid % BCH;
-  const int acsrc = acpos ^ wg_swz<AROWB>(arow), bcsrc = bcpos ^ wg_swz<BROWB>(brow);
-  const size_t arow_b = (size_t)p.M * 4, brow_b = (size_t)p.N * 4;  // bytes per pixel row of the record arrays
-  const unsigned char* a_src = reinterpret_cast<const unsigned char*>(p.a_rec) + (size_t)(r_begin + arow) * arow_b +
-                               (size_t)(m0 / 32 + (acsrc >> 3)) * 128 + (acsrc & 7) * 16;
-  const unsigned char* b_base = reinterpret_cast<const unsigned char*>(p.b_rec) + (size_t)(n0 / 32 + (bcsrc >> 3)) * 128 + (bcsrc & 7) * 16;
-  long long rr = r_begin;  // first pixel row of the step about to be issued
-  int pb[BNI], poh[BNI], pow_[BNI];
-#pragma unroll
-  for (int i = 0; i < BNI; ++i) {
-    const long long r = r_begin + brow + BRPI * i;
-    const int ohow = p.OH * p.OW;
-    pb[i] = (int)(r / ohow);
-    const int rem = (int)(r - (long long)pb[i] * ohow);
-    poh[i] = rem / p.OW;
-    pow_[i] = rem - poh[i] * p.OW;
-  }
-  long long rrb = r_begin;
-  // one LDS-DMA instruction of the stage: pieces 0 .. ANI-1 = the A rows, ANI .. ANI+BNI-1 = the B rows
-  auto issue_piece = [&](int stage, int k) {
-    unsigned char* sa = smem + stage * STAGE + wave * 1024;  // wave-uniform bases; the hardware adds 16 * lane
-    if (k < ANI) {
-      const bool live = rr + arow + ARPI * k < r_end;
-      const unsigned char* as = live ? a_src + (size_t)(ARPI * k) * arow_b : zero;
-      __builtin_amdgcn_global_load_lds(as, (lds_void_ptr)(sa + k * IBYTES), 16, 0, 0);
-      if (k == ANI - 1) { a_src += (size_t)BK * arow_b; rr += BK; }
-    } else {
-      const int i = k - ANI;
-      const bool live = rrb + brow + BRPI * i < r_end;
-      const int ih = poh[i] * p.SH - p.PH + kh, iw = pow_[i] * p.SW - p.PW + kw;
-      const bool ok = live && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-      const unsigned char* bs = ok ? b_base + ((size_t)((long long)pb[i] * p.H + ih) * p.W + iw) * brow_b : zero;
-      __builtin_amdgcn_global_load_lds(bs, (lds_void_ptr)(sa + AOPB + i * IBYTES), 16, 0, 0);
-      pow_[i] += BK;  // advance to the same piece of the next step
-      while (pow_[i] >= p.OW) {
-        pow_[i] -= p.OW;
-        if (++poh[i] == p.OH) { poh[i] = 0; ++pb[i]; }
-      }
-      if (i == BNI - 1) rrb += BK;
-    }
-  };
-  auto issue = [&](int stage) {
-#pragma unroll
-    for (int k = 0; k < PIECES; ++k) issue_piece(stage, k);
-  };
-
-  // ---- fragment side ----
-  const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
-  const int g16 = lane >> 4, l16 = lane & 15;
-  // (the second transposing read of a fragment is four rows further down: same swizzle term)
-  const int frow = 8 * (g16 >> 1) + (l16 >> 2), fsub = (g16 & 1) * 2 + ((l16 & 3) >> 1);
-  const int fxa = wg_swz<AROWB>(frow), fxb = wg_swz<BROWB>(frow);
-  int offa[MI][2], offb[NJ][2];  // [fragment][hi, lo]
-#pragma unroll
-  for (int part = 0; part < 2; ++part) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-      offa[i][part] = frow * AROWB + (l16 & 1) * 8 + (((((wm * MI + i) << 3) | (part << 2) | fsub) ^ fxa) << 4);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-      offb[j][part] = AOPB + frow * BROWB + (l16 & 1) * 8 + (((((wn * NJ + j) << 3) | (part << 2) | fsub) ^ fxb) << 4);
-  }
-  auto frag = [&](const unsigned char* q, int rowb) -> bf16x8_t {
-    if (ABL == 4) {
-      const s4_t a4 = *reinterpret_cast<const s4_t*>(q), b4 = *reinterpret_cast<const s4_t*>(q + 4 * rowb);
-      s8_t v = {a4[0], a4[1], a4[2], a4[3], b4[0], b4[1], b4[2], b4[3]};
-      return __builtin_bit_cast(bf16x8_t, v);
-    }
-    const s4_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(q));
-    const s4_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(q + 4 * rowb));
-    s8_t v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    return __builtin_bit_cast(bf16x8_t, v);
-  };
-  f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  if (KT > 0) issue(0);
-  if (KT > 1) issue(1);
-  int cur = 0, nxt2 = 2;
-  constexpr bool burst = ABL == 3 || ABL == 5;
-  bf16x8_t ah[MI], al[MI], bh[NJ], bl[NJ];
-  for (int kt = 0; kt < KT; ++kt) {
-    if (kt + 1 < KT) wg_wait_vm<PIECES>(); else wg_wait_vm<0>();  // this wave's pieces of step kt have landed
-    __builtin_amdgcn_s_barrier();  // ... and everybody else's; nobody reads stage kt-1 any more
-    if (burst && kt + 2 < KT && (ABL != 3 || kt + 2 < 3)) issue(nxt2);
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned char* st = smem + cur * STAGE;
-    if (ABL != 2 || kt == 0) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        bh[j] = frag(st + offb[j][0], BROWB);
-        bl[j] = frag(st + offb[j][1], BROWB);
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        ah[i] = frag(st + offa[i][0], AROWB);
-        al[i] = frag(st + offa[i][1], AROWB);
-      }
-    }
-    if (ABL == 1) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) asm volatile("" ::"v"(ah[i]), "v"(al[i]));
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) asm volatile("" ::"v"(bh[j]), "v"(bl[j]));
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        if (ABL != 1 || kt == 0) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-        // the LDS-DMA of step kt+2: one instruction behind each (i, j) group of MFMAs, the last PIECES groups of the step.
-        // (In one burst behind the barrier the waves of a block queue up in the vector-memory path together and the
-        // MFMAs wait behind them: 951 us on the dominant layer against 833 us this way; all at once after the first /
-        // second row of groups: 867 / 847 us.)
-        // The narrow tiles have more pieces than groups: PPG pieces behind each group from the first on.
-        if (!burst && kt + 2 < KT) {
-          constexpr int GROUPS = MI * NJ, PPG = (PIECES + GROUPS - 1) / GROUPS;
-          constexpr int first = PPG == 1 ? GROUPS - PIECES : 0;
-          const int g = i * NJ + j - first;
-          if (g >= 0) {
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < PPG; ++q)
-              if (g * PPG + q < PIECES) issue_piece(nxt2, g * PPG + q);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the fragment reads have returned before the next barrier (WAR on the stage)
-    cur = cur == 2 ? 0 : cur + 1;
-    nxt2 = nxt2 == 2 ? 0 : nxt2 + 1;
-  }
-  float* out = p.part + ((size_t)blockIdx.z * p.taps + tap) * p.M * p.N;
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int n = n0 + wn * 32 * NJ + j * 32 + r;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int m = m0 + wm * 32 * MI + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        out[(size_t)m * p.N + n] = acc[i][j][reg];
-      }
-    }
-}
-
-// block tile of the record kernel: 0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256 (D2T_WGRAD_WIDE caps these three),
-// 3 = 128 x 64 (Cin = 64), 4 = 64 x 32 (conv0_2: 32 -> 64 channels); -1: the channel counts fit none of them
-int wgrad_rec_shape(int M, int N) {
-  static const int mode = D2T_PROBE_ENV_STR("D2T_WGRAD_WIDE") ? D2T_PROBE_ENV("D2T_WGRAD_WIDE") : 2;
-  static const bool narrow = !(D2T_PROBE_ENV_STR("D2T_WGRAD_NARROW") && D2T_PROBE_ENV("D2T_WGRAD_NARROW") == 0);
-  if (M % 128 == 0 && N % 128 == 0) {
-    if (mode >= 2 && M % 256 == 0 && N % 256 == 0) return 2;
-    if (mode >= 1 && M % 256 == 0) return 1;
-    return 0;
-  }
-  if (narrow && M % 128 == 0 && N == 64) return 3;
-  if (narrow && M == 64 && N == 32) return 4;
-  return -1;
-}
-hipError_t launch_wgrad(const WgradP& p, hipStream_t s) {
-  if (p.M <= 0 || p.N <= 0 || p.P <= 0) return hipSuccess;
-  if (p.M % 4 || p.N % 4 || p.lda % 4 || p.ldb % 4 || p.S < 1 || p.chunk < 1 || p.taps < 1) return hipErrorInvalidValue;
-  if (p.a_rec) {  // record operands: see wgrad_rec_ok
-    if (!p.b_rec || !p.zero || !p.geom || !p.bf16x3 || wgrad_rec_shape(p.M, p.N) < 0 || p.chunk % 16) return hipErrorInvalidValue;
-    static const int abl = D2T_PROBE_ENV("D2T_WGRAD_ABL");
-    const int shape = wgrad_rec_shape(p.M, p.N);
-    if (shape == 2) {
-      dim3 grid((p.M / 256) * (p.N / 256), p.taps, p.S);
-      hipLaunchKernelGGL((wgrad_rec_kernel<4, 2, 2, 4, 0>), grid, dim3(512), 0, s, p);
-    } else if (shape == 1) {
-      dim3 grid((p.M / 256) * (p.N / 128), p.taps, p.S);
-      if (abl == 1) hipLaunchKernelGGL((wgrad_rec_kernel<4, 2, 2, 2, 1>), grid, dim3(256), 0, s, p);
-      else if (abl == 2) hipLaunchKernelGGL((wgrad_rec_kernel<4, 2, 2, 2, 2>), grid, dim3(256), 0, s, p);
-      else if (abl == 3) hipLaunchKernelGGL((wgrad_rec_kernel<4, 2, 2, 2, 3>), grid, dim3(256), 0, s, p);
-      else if (abl == 4) hipLaunchKernelGGL((wgrad_rec_kernel<4, 2, 2, 2, 4>), grid, dim3(256), 0, s, p);
-      else if (abl == 5) hipLaunchKernelGGL((wgrad_rec_kernel<4, 2, 2, 2, 5>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((wgrad_rec_kernel<4, 2, 2, 2, 0>), grid, dim3(256), 0, s, p);
-    } else if (shape == 0) {
-      dim3 grid((p.M / 128) * (p.N / 128), p.taps, p.S);
-      hipLaunchKernelGGL((wgrad_rec_kernel<2, 2, 2, 2, 0>), grid, dim3(256), 0, s, p);
-    } else if (shape == 3) {
-      dim3 grid((p.M / 128) * (p.N / 64), p.taps, p.S);
-      hipLaunchKernelGGL((wgrad_rec_kernel<2, 2, 2, 1, 0>), grid, dim3(128), 0, s, p);
-    } else if (shape == 4) {
-      dim3 grid((p.M / 64) * (p.N / 32), p.taps, p.S);
-      hipLaunchKernelGGL((wgrad_rec_kernel<2, 1, 1, 1, 0>), grid, dim3(64), 0, s, p);
-    } else {
-      return hipErrorInvalidValue;
-    }
-  } else if (p.M <= 64 || p.N <= 64) {
-    dim3 grid(((p.M + 63) / 64) * ((p.N + 63) / 64), p.taps, p.S);
-    hipLaunchKernelGGL((wgrad_kernel<64, 64>), grid, dim3(256), 0, s, p);
-  } else {
-    dim3 grid(((p.M + 127) / 128) * ((p.N + 127) / 128), p.taps, p.S);
-    if (p.bf16x3) hipLaunchKernelGGL(wgrad_bf16x3_kernel, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((wgrad_kernel<128, 128>), grid, dim3(256), 0, s, p);
-  }
-  return hipGetLastError();
-}
-
-// dst = (accumulate ? dst : 0) + sum_z part[z][tap][m][n];  layout 0: dst[m][n] (taps == 1);  layout 1: OIHW dst[m][n][tap]
-__global__ void wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dst, int S, int taps, int M, int N,
-                                    int layout, int accumulate) {
-  const size_t total = (size_t)taps * M * N;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    float v = 0.f;
-#pragma unroll 8
-    for (int z = 0; z < S; ++z) v += part[(size_t)z * total + i];
-    const int n = (int)(i % N), m = (int)((i / N) % M), tap = (int)(i / ((size_t)M * N));
-    const size_t o = layout == 1 ? ((size_t)m * N + n) * taps + tap : (size_t)m * N + n;
-    dst[o] = accumulate ? dst[o] + v : v;
-  }
-}
-// few outputs, many partials (the stem's 288 filter taps over ~2000 pixel chunks, conv0_2's 18432 over 227): one block per output, its 256 threads
-// take every 256th partial and a fixed-order tree adds them (a thread per output would walk the partials serially)
-__global__ __launch_bounds__(256) void wgrad_reduce_small_kernel(const float* __restrict__ part, float* __restrict__ dst, int S,
-                                                                 int taps, int M, int N, int layout, int accumulate) {
-  __shared__ float red[256];
-  const size_t total = (size_t)taps * M * N, i = blockIdx.x;
-  float v = 0.f;
-  for (int z = threadIdx.x; z < S; z += 256) v += part[(size_t)z * total + i];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const int n = (int)(i % N), m = (int)((i / N) % M), tap = (int)(i / ((size_t)M * N));
-    const size_t o = layout == 1 ? ((size_t)m * N + n) * taps + tap : (size_t)m * N + n;
-    dst[o] = accumulate ? dst[o] + red[0] : red[0];
-  }
-}
-hipError_t launch_wgrad_reduce(const float* part, float* dst, int S, int taps, int M, int N, int layout, int accumulate,
-                               hipStream_t s) {
-  const size_t total = (size_t)taps * M * N;
-  if ((total <= 4096 && S >= 256) || (total <= 65536 && S >= 128)) {
-    hipLaunchKernelGGL(wgrad_reduce_small_kernel, dim3((unsigned)total), dim3(256), 0, s, part, dst, S, taps, M, N, layout,
-                       accumulate);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, part,
-                     dst, S, taps, M, N, layout, accumulate);
-  return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------
 // Column reductions over the rows of row-major [R][C] matrices -> part[chunk][2][C]
@@ -1221,350 +645,6 @@ hipError_t launch_ln_bwd(const float* dy, const float* x, const float* mean, con
 }
 
 // ---------------------------------------------------------------------------
-// Attention with saved probabilities.  q/k/v/o are addressed as  base + (b*L + i)*ld + head*HD ; one block per
-// (batch, head); K and V of the head live in LDS.  mask: causal (key j <= query i) and/or key padding
-// (keytok[b][j] == pad_id masked) -- nn.MultiheadAttention's additive -inf masks (tfm.py:74-91).
-// probs [B][heads][Lq][Lk] is written for the backward pass.
-// ---------------------------------------------------------------------------
-// GKV (memories too long for a head's K and V to sit in LDS: crops beyond about 600 tokens, the shipped max_dimension [800, 800]
-// gives 2526): the same loops read K / V rows from global memory (L2) -- slow, and the same sums in the same order.
-template <int HD, bool GKV = false>
-__global__ __launch_bounds__(1024) void attn_train_fwd_kernel(const AttnTrainP p) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int b = blockIdx.x / p.heads, hh = blockIdx.x % p.heads;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, NT = blockDim.x, NW = NT >> 6;
-  const float* Ks;  // key j, channel c at Ks[j * KLD + c]
-  const float* Vs;
-  float* Ps;        // [waves][Lk]
-  int KLD, VLD;
-  if (GKV) {
-    Ks = p.k + (size_t)b * p.Lk * p.ldk + hh * HD; KLD = p.ldk;
-    Vs = p.v + (size_t)b * p.Lk * p.ldv + hh * HD; VLD = p.ldv;
-    Ps = sm;
-  } else {
-    float* ks = sm;                              // [Lk][HD+1]
-    float* vs = ks + (size_t)p.Lk * (HD + 1);    // [Lk][HD]
-    Ps = vs + (size_t)p.Lk * HD;
-    for (int i = tid; i < p.Lk * HD; i += NT) {
-      const int j = i / HD, c = i % HD;
-      ks[j * (HD + 1) + c] = p.k[((size_t)b * p.Lk + j) * p.ldk + hh * HD + c];
-      vs[j * HD + c] = p.v[((size_t)b * p.Lk + j) * p.ldv + hh * HD + c];
-    }
-    __syncthreads();
-    Ks = ks; KLD = HD + 1;
-    Vs = vs; VLD = HD;
-  }
-  const float scale = rsqrtf((float)HD);
-  float* P = Ps + (size_t)wave * p.Lk;
-  for (int i = wave; i < p.Lq; i += NW) {
-    const float* qp = p.q + ((size_t)b * p.Lq + i) * p.ldq + hh * HD;
-    float q[HD];
-#pragma unroll
-    for (int c = 0; c < HD; ++c) q[c] = qp[c];
-    float mx = -INFINITY;
-    for (int j = lane; j < p.Lk; j += 64) {
-      bool ok = !(p.causal && j > i);
-      if (ok && p.keytok) ok = p.keytok[(size_t)b * p.Lk + j] != p.pad_id;
-      float a = -INFINITY;
-      if (ok) {
-        a = 0.f;
-#pragma unroll
-        for (int c = 0; c < HD; ++c) a = fmaf(q[c], Ks[(size_t)j * KLD + c], a);
-        a *= scale;
-      }
-      P[j] = a;
-      mx = fmaxf(mx, a);
-    }
-    mx = wmax(mx);
-    float sum = 0.f;
-    for (int j = lane; j < p.Lk; j += 64) {
-      const float e = P[j] == -INFINITY ? 0.f : expf(P[j] - mx);
-      P[j] = e;
-      sum += e;
-    }
-    sum = wsum(sum);
-    const float inv = 1.f / sum;
-    float* prow = p.probs + (((size_t)b * p.heads + hh) * p.Lq + i) * p.Lk;
-    const uint8_t* mrow = p.dropmask ? p.dropmask + (((size_t)b * p.heads + hh) * p.Lq + i) * p.Lk : nullptr;
-    for (int j = lane; j < p.Lk; j += 64) {
-      const float w = P[j] * inv;
-      prow[j] = w;                                            // saved: the softmax itself
-      P[j] = mrow ? w * (mrow[j] ? p.dropscale : 0.f) : w;    // used: after dropout (nn.MultiheadAttention dropout)
-    }
-    // o[c] = sum_j P[j] * V[j][c]: lane -> (c = lane % HD, key phase = lane / HD)
-    constexpr int PH = 64 / HD;
-    const int c = lane % HD, ph = lane / HD;
-    float o = 0.f;
-#pragma unroll 8
-    for (int j = ph; j < p.Lk; j += PH) o = fmaf(P[j], Vs[(size_t)j * VLD + c], o);
-    if (PH == 2) o += __shfl_xor(o, 32, 64);
-    if (lane < HD) p.o[((size_t)b * p.Lq + i) * p.ldo + hh * HD + c] = o;
-  }
-}
-static hipError_t attn_lds(const void* fn, size_t lds) {
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-// One block per (batch, head) leaves a CU with a single block; sixteen waves in it (four per SIMD) hide the latency of the
-// per-query loops that four could not (forward 382 -> ~130 us, backward 656 -> ~250 us at B = 32, 261 tokens).  Fewer when
-// the per-wave LDS rows do not fit.
-static int attn_waves(size_t base_bytes, int Lk) {
-  for (int nw = 16; nw > 4; nw -= 4)
-    if (base_bytes + (size_t)nw * Lk * 4 <= 160 * 1024) return nw;
-  return 4;
-}
-// waves of the global-K/V forms: as many per-wave rows of Lk floats as fit (a multiple of four, at most sixteen)
-static int attn_waves_gkv(int Lk) {
-  int nw = (int)((size_t)160 * 1024 / ((size_t)Lk * 4)) & ~3;
-  return nw > 16 ? 16 : nw;
-}
-hipError_t launch_attn_train_fwd(const AttnTrainP& p, hipStream_t s) {
-  const size_t base = ((size_t)p.Lk * (p.hd + 1) + (size_t)p.Lk * p.hd) * 4;
-  hipError_t e;
-  if (base + (size_t)4 * p.Lk * 4 > 160 * 1024) {  // K and V of a head do not fit in LDS beside four score rows
-    const int nwg = attn_waves_gkv(p.Lk);
-    if (nwg < 4 || (p.hd != 32 && p.hd != 64)) return hipErrorInvalidValue;
-    const size_t ldsg = (size_t)nwg * p.Lk * 4;
-    if (p.hd == 32) {
-      if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_fwd_kernel<32, true>), ldsg)) != hipSuccess) return e;
-      hipLaunchKernelGGL((attn_train_fwd_kernel<32, true>), dim3(p.B * p.heads), dim3(nwg * 64), ldsg, s, p);
-    } else {
-      if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_fwd_kernel<64, true>), ldsg)) != hipSuccess) return e;
-      hipLaunchKernelGGL((attn_train_fwd_kernel<64, true>), dim3(p.B * p.heads), dim3(nwg * 64), ldsg, s, p);
-    }
-    return hipGetLastError();
-  }
-  const int nw = attn_waves(base, p.Lk);
-  const size_t lds = base + (size_t)nw * p.Lk * 4;
-  if (p.hd == 32) {
-    if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_fwd_kernel<32>), lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(attn_train_fwd_kernel<32>, dim3(p.B * p.heads), dim3(nw * 64), lds, s, p);
-  } else if (p.hd == 64) {
-    if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_fwd_kernel<64>), lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(attn_train_fwd_kernel<64>, dim3(p.B * p.heads), dim3(nw * 64), lds, s, p);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-// Backward: dV = P^T dO;  dP = dO V^T;  dS = P * (dP - rowsum(dP * P));  dQ = scale * dS K;  dK = scale * dS^T Q.
-// One block per (batch, head); dS overwrites the saved probabilities in place (phase 2), phases separated by
-// block barriers.  p.o carries dO; p.dq / p.dk / p.dv use the q / k / v strides.
-// (GKV: K / V rows from global memory, as in the forward kernel; any multiple of 64 threads)
-template <int HD, bool GKV = false>
-__global__ __launch_bounds__(1024) void attn_train_bwd_kernel(const AttnTrainP p) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int b = blockIdx.x / p.heads, hh = blockIdx.x % p.heads;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, NT = blockDim.x, NW = NT >> 6;
-  const float* Ks;  // key j, channel c at Ks[j * KLD + c]
-  const float* Vs;
-  float* Ds;        // [waves][Lk]: the dS row a wave is working on
-  int KLD, VLD;
-  if (GKV) {
-    Ks = p.k + (size_t)b * p.Lk * p.ldk + hh * HD; KLD = p.ldk;
-    Vs = p.v + (size_t)b * p.Lk * p.ldv + hh * HD; VLD = p.ldv;
-    Ds = sm;
-  } else {
-    float* ks = sm;                            // [Lk][HD+1]
-    float* vs = ks + (size_t)p.Lk * (HD + 1);  // [Lk][HD+1]
-    Ds = vs + (size_t)p.Lk * (HD + 1);
-    for (int i = tid; i < p.Lk * HD; i += NT) {
-      const int j = i / HD, c = i % HD;
-      ks[j * (HD + 1) + c] = p.k[((size_t)b * p.Lk + j) * p.ldk + hh * HD + c];
-      vs[j * (HD + 1) + c] = p.v[((size_t)b * p.Lk + j) * p.ldv + hh * HD + c];
-    }
-    Ks = ks; KLD = HD + 1;
-    Vs = vs; VLD = HD + 1;
-  }
-  float* probs = p.probs + ((size_t)b * p.heads + hh) * p.Lq * p.Lk;
-  constexpr int PH = 64 / HD;
-  const int c = lane % HD, ph = lane / HD;
-  const uint8_t* dmask = p.dropmask ? p.dropmask + ((size_t)b * p.heads + hh) * p.Lq * p.Lk : nullptr;
-  // phase 1: dV[j][c] = sum_i (P o D)[i][j] * dO[i][c]   (wave per key; D = dropout keep mask * scale)
-  for (int j = wave; j < p.Lk; j += NW) {
-    float a = 0.f;
-#pragma unroll 8
-    for (int i = ph; i < p.Lq; i += PH) {
-      float w = probs[(size_t)i * p.Lk + j];
-      if (dmask) w *= dmask[(size_t)i * p.Lk + j] ? p.dropscale : 0.f;
-      a = fmaf(w, p.o[((size_t)b * p.Lq + i) * p.ldo + hh * HD + c], a);
-    }
-    if (PH == 2) a += __shfl_xor(a, 32, 64);
-    if (lane < HD) p.dv[((size_t)b * p.Lk + j) * p.ldv + hh * HD + c] = a;
-  }
-  __syncthreads();
-  const float scale = rsqrtf((float)HD);
-  // phase 2: per query row: dS, dQ (wave per query)
-  for (int i = wave; i < p.Lq; i += NW) {
-    const float* dop = p.o + ((size_t)b * p.Lq + i) * p.ldo + hh * HD;
-    float d_o[HD];
-#pragma unroll
-    for (int cc = 0; cc < HD; ++cc) d_o[cc] = dop[cc];
-    float* prow = probs + (size_t)i * p.Lk;
-    const uint8_t* mrow = dmask ? dmask + (size_t)i * p.Lk : nullptr;
-    float dsum = 0.f;
-    for (int j = lane; j < p.Lk; j += 64) {
-      float dp = 0.f;
-#pragma unroll
-      for (int cc = 0; cc < HD; ++cc) dp = fmaf(d_o[cc], Vs[(size_t)j * VLD + cc], dp);
-      if (mrow) dp *= mrow[j] ? p.dropscale : 0.f;
-      dsum = fmaf(dp, prow[j], dsum);
-    }
-    dsum = wsum(dsum);
-    for (int j = lane; j < p.Lk; j += 64) {
-      float dp = 0.f;
-#pragma unroll
-      for (int cc = 0; cc < HD; ++cc) dp = fmaf(d_o[cc], Vs[(size_t)j * VLD + cc], dp);
-      if (mrow) dp *= mrow[j] ? p.dropscale : 0.f;
-      const float ds = prow[j] * (dp - dsum);
-      prow[j] = ds;  // read again by phase 3 (after the block barrier)
-      Ds[wave * p.Lk + j] = ds;
-    }
-    float a = 0.f;
-#pragma unroll 8
-    for (int j = ph; j < p.Lk; j += PH) a = fmaf(Ds[wave * p.Lk + j], Ks[(size_t)j * KLD + c], a);
-    if (PH == 2) a += __shfl_xor(a, 32, 64);
-    if (lane < HD) p.dq[((size_t)b * p.Lq + i) * p.ldq + hh * HD + c] = a * scale;
-  }
-  __syncthreads();
-  // phase 3: dK[j][c] = scale * sum_i dS[i][j] * Q[i][c]   (wave per key)
-  for (int j = wave; j < p.Lk; j += NW) {
-    float a = 0.f;
-#pragma unroll 8
-    for (int i = ph; i < p.Lq; i += PH) a = fmaf(probs[(size_t)i * p.Lk + j], p.q[((size_t)b * p.Lq + i) * p.ldq + hh * HD + c], a);
-    if (PH == 2) a += __shfl_xor(a, 32, 64);
-    if (lane < HD) p.dk[((size_t)b * p.Lk + j) * p.ldk + hh * HD + c] = a * scale;
-  }
-}
-// Same mathematics with coalesced accesses: dO and Q of the head are staged in LDS too, and the two column-wise
-// reductions (dV over queries with P, dK over queries with dS) run with lane = key (consecutive lanes read consecutive
-// probabilities of one query row) and wave = group of HD/4 channels.  Needs (2*Lk*(HD+1) + 2*Lq*HD + 4*Lk) floats of LDS.
-template <int HD>
-__global__ __launch_bounds__(1024) void attn_train_bwd_fast_kernel(const AttnTrainP p) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* Ks = sm;                             // [Lk][HD+1]
-  float* Vs = Ks + (size_t)p.Lk * (HD + 1);   // [Lk][HD+1]
-  float* dOs = Vs + (size_t)p.Lk * (HD + 1);  // [Lq][HD]
-  float* Qs = dOs + (size_t)p.Lq * HD;        // [Lq][HD]
-  float* Ds = Qs + (size_t)p.Lq * HD;         // [waves][Lk]
-  const int b = blockIdx.x / p.heads, hh = blockIdx.x % p.heads;
-  // a multiple of four waves: wave & 3 = channel group of the column reductions, wave >> 2 = which 64-key blocks it takes
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, NT = blockDim.x, NW = NT >> 6;
-  const int cgrp = wave & 3, kgrp = wave >> 2, nkg = NW >> 2;
-  for (int i = tid; i < p.Lk * HD; i += NT) {
-    const int j = i / HD, c = i % HD;
-    Ks[j * (HD + 1) + c] = p.k[((size_t)b * p.Lk + j) * p.ldk + hh * HD + c];
-    Vs[j * (HD + 1) + c] = p.v[((size_t)b * p.Lk + j) * p.ldv + hh * HD + c];
-  }
-  for (int i = tid; i < p.Lq * HD; i += NT) {
-    const int r = i / HD, c = i % HD;
-    dOs[i] = p.o[((size_t)b * p.Lq + r) * p.ldo + hh * HD + c];
-    Qs[i] = p.q[((size_t)b * p.Lq + r) * p.ldq + hh * HD + c];
-  }
-  __syncthreads();
-  float* probs = p.probs + ((size_t)b * p.heads + hh) * p.Lq * p.Lk;
-  constexpr int CG = HD / 4;  // channels per wave
-  // column reduction out[j][c] = alpha * sum_i M[i][j] * R[i][c]
-  const uint8_t* dmask = p.dropmask ? p.dropmask + ((size_t)b * p.heads + hh) * p.Lq * p.Lk : nullptr;
-  auto colred = [&](const float* R, float* out, int ld, float alpha, const uint8_t* dm) {
-    for (int j0 = kgrp * 64; j0 < p.Lk; j0 += 64 * nkg) {
-      const int j = j0 + lane;
-      float acc[CG];
-#pragma unroll
-      for (int c = 0; c < CG; ++c) acc[c] = 0.f;
-      if (j < p.Lk) {
-#pragma unroll 8
-        for (int i = 0; i < p.Lq; ++i) {
-          float m = probs[(size_t)i * p.Lk + j];
-          if (dm) m *= dm[(size_t)i * p.Lk + j] ? p.dropscale : 0.f;
-          const float* r = R + i * HD + cgrp * CG;
-#pragma unroll
-          for (int c = 0; c < CG; ++c) acc[c] = fmaf(m, r[c], acc[c]);
-        }
-        float* o = out + ((size_t)b * p.Lk + j) * ld + hh * HD + cgrp * CG;
-#pragma unroll
-        for (int c = 0; c < CG; ++c) o[c] = acc[c] * alpha;
-      }
-    }
-  };
-  if (!(p.probe & 1)) colred(dOs, p.dv, p.ldv, 1.f, dmask);  // phase 1: dV = (P o D)^T dO
-  __syncthreads();
-  const float scale = rsqrtf((float)HD);
-  constexpr int PH = 64 / HD;
-  const int c = lane % HD, ph = lane / HD;
-  for (int i = wave; i < p.Lq && !(p.probe & 2); i += NW) {  // phase 2: dS (in place) and dQ, one wave per query row
-    const float* d_o = dOs + i * HD;
-    float* prow = probs + (size_t)i * p.Lk;
-    float dsum = 0.f;
-    for (int j = lane; j < p.Lk; j += 64) {
-      float dp = 0.f;
-#pragma unroll
-      for (int cc = 0; cc < HD; ++cc) dp = fmaf(d_o[cc], Vs[j * (HD + 1) + cc], dp);
-      if (dmask) dp *= dmask[(size_t)i * p.Lk + j] ? p.dropscale : 0.f;
-      Ds[wave * p.Lk + j] = dp;
-      dsum = fmaf(dp, prow[j], dsum);
-    }
-    dsum = wsum(dsum);
-    for (int j = lane; j < p.Lk; j += 64) {
-      const float ds = prow[j] * (Ds[wave * p.Lk + j] - dsum);
-      prow[j] = ds;
-      Ds[wave * p.Lk + j] = ds;
-    }
-    float a = 0.f;
-#pragma unroll 8
-    for (int j = ph; j < p.Lk; j += PH) a = fmaf(Ds[wave * p.Lk + j], Ks[j * (HD + 1) + c], a);
-    if (PH == 2) a += __shfl_xor(a, 32, 64);
-    if (lane < HD) p.dq[((size_t)b * p.Lq + i) * p.ldq + hh * HD + c] = a * scale;
-  }
-  __syncthreads();
-  if (!(p.probe & 4)) colred(Qs, p.dk, p.ldk, scale, nullptr);  // phase 3: dK = scale * dS^T Q
-}
-
-hipError_t launch_attn_train_bwd(const AttnTrainP& p_in, hipStream_t s) {
-  AttnTrainP p = p_in;
-  static const int probe = D2T_PROBE_ENV("D2T_ATTN_BWD_PROBE");  // timing probe: skip phases (bit mask)
-  p.probe = probe;
-  const size_t lds = ((size_t)2 * p.Lk * (p.hd + 1) + 4 * (size_t)p.Lk) * 4;
-  const size_t base_fast = ((size_t)2 * p.Lk * (p.hd + 1) + (size_t)2 * p.Lq * p.hd) * 4;
-  const int nw = attn_waves(base_fast, p.Lk);
-  const size_t lds_fast = base_fast + (size_t)nw * p.Lk * 4;
-  hipError_t e;
-  if (lds_fast <= 160 * 1024 && (p.hd == 32 || p.hd == 64)) {
-    if (p.hd == 32) {
-      if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_bwd_fast_kernel<32>), lds_fast)) != hipSuccess) return e;
-      hipLaunchKernelGGL(attn_train_bwd_fast_kernel<32>, dim3(p.B * p.heads), dim3(nw * 64), lds_fast, s, p);
-    } else {
-      if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_bwd_fast_kernel<64>), lds_fast)) != hipSuccess) return e;
-      hipLaunchKernelGGL(attn_train_bwd_fast_kernel<64>, dim3(p.B * p.heads), dim3(nw * 64), lds_fast, s, p);
-    }
-    return hipGetLastError();
-  }
-  if (p.hd != 32 && p.hd != 64) return hipErrorInvalidValue;
-  if (lds > 160 * 1024) {  // K and V of a head do not fit in LDS: rows from global memory
-    const int nwg = attn_waves_gkv(p.Lk);
-    if (nwg < 4) return hipErrorInvalidValue;
-    const size_t ldsg = (size_t)nwg * p.Lk * 4;
-    if (p.hd == 32) {
-      if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_bwd_kernel<32, true>), ldsg)) != hipSuccess) return e;
-      hipLaunchKernelGGL((attn_train_bwd_kernel<32, true>), dim3(p.B * p.heads), dim3(nwg * 64), ldsg, s, p);
-    } else {
-      if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_bwd_kernel<64, true>), ldsg)) != hipSuccess) return e;
-      hipLaunchKernelGGL((attn_train_bwd_kernel<64, true>), dim3(p.B * p.heads), dim3(nwg * 64), ldsg, s, p);
-    }
-    return hipGetLastError();
-  }
-  if (p.hd == 32) {
-    if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_bwd_kernel<32>), lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(attn_train_bwd_kernel<32>, dim3(p.B * p.heads), dim3(256), lds, s, p);
-  } else {
-    if ((e = attn_lds(reinterpret_cast<const void*>(attn_train_bwd_kernel<64>), lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(attn_train_bwd_kernel<64>, dim3(p.B * p.heads), dim3(256), lds, s, p);
-  }
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
 // Embedding: x[r][:] = E[tok[r]][:] * scale + pe[r % L][:];  backward (deterministic, block per vocabulary row):
 // dE[v][:] = scale * sum_{r: tok[r] == v} dx[r][:], zero for the padding row (nn.Embedding padding_idx).
 // ---------------------------------------------------------------------------
@@ -1790,9 +870,9 @@ hipError_t launch_sum_rows_strided(const float* x, float* out, int B, long long 
   return hipGetLastError();
 }
 
-// Stem convolution (Cin = 1 or 3, 3x3, pad 1) in training mode: raw weights, no bias / BN (z = conv(x)); and its
-// weight gradient dW[co][ci][kh][kw] = sum_p dz[p][co] * x[ci][p + tap]  (block per (co-group), deterministic).
-// The image is NCHW planar; a "tap" below is (ci * 3 + kh) * 3 + kw, the OIHW order of the raw weights.
+// Stem convolution (Cin = 1 or 3, 3x3, pad 1) in training mode: raw weights, no bias / BN (z = conv(x)).  Its weight
+// gradient is stem_wgrad_kernel in train_wgrad.hip.  The image is NCHW planar; a "tap" below is (ci * 3 + kh) * 3 + kw, the
+// OIHW order of the raw weights.
 template <int CIN>
 __global__ __launch_bounds__(256) void stem_raw_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                        float* __restrict__ z, int B, int H, int W, int Cout) {
@@ -1831,56 +911,6 @@ hipError_t launch_stem_raw(const float* img, const float* w, float* z, int B, in
   if (Cin == 1) hipLaunchKernelGGL(stem_raw_kernel<1>, grid, dim3(256), 0, s, img, w, z, B, H, W, Cout);
   else if (Cin == 3) hipLaunchKernelGGL(stem_raw_kernel<3>, grid, dim3(256), 0, s, img, w, z, B, H, W, Cout);
   else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-// part[chunk][tap][co]: chunked over pixels; reduced by launch_wgrad_reduce with M = Cout, N = 1 ... (taps = 9 * CIN)
-template <int CO, int CIN>  // output channels: 32 (ResNet conv0_1) or 64 (VGG's first convolution); image channels 1 or 3
-__global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ img, const float* __restrict__ dz,
-                                                         float* __restrict__ part, int B, int H, int W, int chunk) {
-  // thread -> (co = tid % CO, pixel lane = tid / CO)
-  constexpr int NPL = 256 / CO, K = 9 * CIN;
-  __shared__ float red[NPL][K][CO];
-  const int co = threadIdx.x % CO, pl = threadIdx.x / CO;
-  const long long P = (long long)B * H * W;
-  const long long r0 = (long long)blockIdx.x * chunk, r1 = r0 + chunk < P ? r0 + chunk : P;
-  float acc[K];
-#pragma unroll
-  for (int t = 0; t < K; ++t) acc[t] = 0.f;
-  for (long long r = r0 + pl; r < r1; r += NPL) {
-    const int x = (int)(r % W), y = (int)((r / W) % H);
-    const long long b = r / ((long long)W * H);
-    const float g = dz[(size_t)r * CO + co];
-#pragma unroll
-    for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          const int ih = y + kh - 1, iw = x + kw - 1;
-          if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W)
-            acc[(ci * 3 + kh) * 3 + kw] = fmaf(g, img[(((size_t)b * CIN + ci) * H + ih) * W + iw], acc[(ci * 3 + kh) * 3 + kw]);
-        }
-  }
-#pragma unroll
-  for (int t = 0; t < K; ++t) red[pl][t][co] = acc[t];
-  __syncthreads();
-  for (int i = threadIdx.x; i < K * CO; i += 256) {
-    const int t = i / CO, c = i % CO;
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) v += red[k][t][c];
-    part[((size_t)blockIdx.x * K + t) * CO + c] = v;  // [chunk][tap][co] == wgrad partial layout with M = Cout, N = 1
-  }
-}
-hipError_t launch_stem_wgrad(const float* img, const float* dz, float* part, int B, int Cin, int H, int W, int Cout, int chunk,
-                             int nchunks, hipStream_t s) {
-#define D2T_STEM_WGRAD(CO, CI) hipLaunchKernelGGL((stem_wgrad_kernel<CO, CI>), dim3(nchunks), dim3(256), 0, s, img, dz, part, B, H, W, chunk)
-  if (Cout == 32 && Cin == 1) D2T_STEM_WGRAD(32, 1);
-  else if (Cout == 64 && Cin == 1) D2T_STEM_WGRAD(64, 1);
-  else if (Cout == 32 && Cin == 3) D2T_STEM_WGRAD(32, 3);
-  else if (Cout == 64 && Cin == 3) D2T_STEM_WGRAD(64, 3);
-  else return hipErrorInvalidValue;
-#undef D2T_STEM_WGRAD
   return hipGetLastError();
 }
 

@@ -629,7 +629,7 @@ def test_training_step_under_autocast_and_grad_scaler(cases):
 def test_training_step_over_a_memory_beyond_512_tokens(manifests, cname):
     """The shipped training configuration allows crops up to 800 x 800 (config/train.yaml:3: 2526 memory tokens).  Beyond about 600
     tokens a head's K and V no longer fit in LDS beside the score rows: the training attention kernels then read K / V rows from
-    global memory (train_kernels.hip GKV: the same sums in the same order, slower), and the LSTM head's backward keeps its six
+    global memory (train_attn.hip GKV: the same sums in the same order, slower), and the LSTM head's backward keeps its six
     alignment rows at 4096 entries.  A 192 x 768 crop (583 tokens) through the whole step -- loss, logits and every gradient
     against the oracle's autograd -- on the HybridViT + TFM stack (ViT self-attention and decoder cross-attention over 583 keys)
     and on HybridViT + Attnv2 (582 keys in the LSTM head)."""

@@ -222,6 +222,13 @@ def test_layernorm_backward(rows, D, eps):
     (3, 25, 25, 8, 32, 1, True),     # decoder self-attention: causal + PAD key-padding mask
     (3, 25, 70, 8, 32, 0, False),    # decoder cross-attention over the memory
     (2, 23, 23, 8, 64, 1, True),     # d_model 512 (config C1): head_dim 64
+    # (all of the above: K and V in LDS forward, the coalesced "fast" backward.  Below, the smallest shapes that reach the
+    # other launcher branches -- 160 KB of LDS decide them, see launch_attn_train_fwd / launch_attn_train_bwd)
+    (1, 320, 320, 2, 32, 1, True),   # forward LDS; backward: dO and Q no longer fit beside K and V -> the plain LDS kernel
+    (1, 8, 580, 2, 32, 0, False),    # forward LDS; backward plain LDS kernel, wide cross-attention (four waves)
+    (1, 160, 160, 2, 64, 0, False),  # forward LDS; backward plain LDS kernel at head_dim 64
+    (1, 8, 600, 2, 32, 0, False),    # K and V of a head do not fit in LDS: forward and backward read them from global memory
+    (1, 8, 320, 2, 64, 0, False),    # ... the same at head_dim 64
 ])
 def test_attention_backward(nb, Lq, Lk, heads, hd, causal, pad):
     lib = _lib.require_device()

@@ -3,7 +3,7 @@
 // what a device run cannot show safely: no access outside the buffers for any V, row base alignment and mode; every loss and
 // gradient element written; ignored rows exactly 0; values against a double-precision evaluation of the formulas.  No GPU.
 // threadIdx / blockIdx, float4, __shfl_xor, wsum and wmax below are HOST stand-ins written for this program, not the device
-// ones: they must be kept in step with train_kernels.hip by hand (same xor-butterfly order, so the sums round alike).
+// ones: they must be kept in step with csrc/train_common.h by hand (same xor-butterfly order, so the sums round alike).
 //   cd tools/probe && sed -n '/\[ce_smooth: begin\]/,/\[ce_smooth: end\]/p' ../../doc2tex_amd/csrc/train_kernels.hip > ce_smooth.inc
 //   g++ -std=c++20 -O1 -g -fsanitize=address,undefined -fno-sanitize=alignment -pthread ce_smooth_host.cpp -o ce_smooth_host
 //   ./ce_smooth_host        (lines only for cases beyond 1e-6 of the tensor's maximum: expected for V <= 3 alone)
