@@ -11,7 +11,7 @@ constexpr int GRP_MAXB = 64, GRP_WORDS = 2 * GRP_MAXB + 2;
 // Longest encoder memory a decode can attend over: 4096 tokens (the shipped max_dimension [800, 800] gives 2526).  The TFM row
 // kernels walk the keys with a running softmax -- the absorbed form (d_model 256) in 16-key tiles, the projected-K/V form
 // (d_model 512) in groups per lane -- and the LSTM-attention decode kernel keeps two alignment rows of that length in LDS
-// (recurrent.hip AD_MAXT).
+// (recurrent_common.h AD_MAXT).
 inline int memory_cap(const d2t_ctx*) { return 4096; }
 
 inline hipError_t linear_big(d2t_ctx* c, hipStream_t s, const float* x, const LinW& w, const float* res, float* y, int M,

@@ -415,7 +415,7 @@ hipError_t launch_bilstm_train_bwd(const float* dout, const float* sv_gates, con
 // hprev[d][b*T + t][H] = h of direction d at the step processed before t (zero at its first step), from out [B*T][2H]
 hipError_t launch_bilstm_hprev(const float* out, float* hprev_fwd, float* hprev_rev, int B, int T, int H, hipStream_t s);
 
-// ---- training step (train_kernels.hip, train_wgrad.hip, train_attn.hip) --------------------------------------
+// ---- training step (train_kernels.hip, train_wgrad.hip, train_attn.hip; the recurrent paths above: train_recurrent.hip) ----
 // Weight gradient ("TN" GEMM, optional filter taps): part[z][tap][m][n] = sum_{p in chunk z} a[p][m] * x[src(p,tap)][n]
 struct WgradP {
   const float* a;   // [P][lda]: upstream gradient rows (dz of a convolution / dy of a Linear)

@@ -224,6 +224,62 @@ hipError_t launch_maxpool(const float* x, float* y, int B, int H, int W, int C, 
   return hipGetLastError();
 }
 
+// any window and stride (the VGG extractor's pools), same layout and padding rule
+__global__ __launch_bounds__(256) void maxpool_k_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H,
+                                                        int W, int C, int OH, int OW, int KH, int KW, int SH, int SW,
+                                                        int PH, int PW) {
+  const int cq = C >> 2;
+  const long long total = (long long)B * OH * OW * cq;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int c4 = (int)(idx % cq);
+    const long long pix = idx / cq;
+    const int ow = (int)(pix % OW);
+    const int oh = (int)((pix / OW) % OH);
+    const long long b = pix / ((long long)OW * OH);
+    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    for (int kh = 0; kh < KH; ++kh)
+      for (int kw = 0; kw < KW; ++kw) {
+        const int ih = oh * SH - PH + kh, iw = ow * SW - PW + kw;
+        if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
+          const float4 v = *reinterpret_cast<const float4*>(x + ((b * H + ih) * W + iw) * C + c4 * 4);
+          m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+        }
+      }
+    *reinterpret_cast<float4*>(y + pix * C + c4 * 4) = m;
+  }
+}
+
+hipError_t launch_maxpool_k(const float* x, float* y, int B, int H, int W, int C, int KH, int KW, int SH, int SW,
+                            int PH, int PW, hipStream_t s) {
+  if (C % 4) return hipErrorInvalidValue;
+  const int OH = (H + 2 * PH - KH) / SH + 1, OW = (W + 2 * PW - KW) / SW + 1;
+  const long long total = (long long)B * OH * OW * (C / 4);
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  hipLaunchKernelGGL(maxpool_k_kernel, dim3(blocks), dim3(256), 0, s, x, y, B, H, W, C, OH, OW, KH, KW, SH, SW, PH, PW);
+  return hipGetLastError();
+}
+
+__global__ void mean_h_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C) {
+  const long long total = (long long)B * W * C;
+  const float inv = 1.f / (float)H;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(idx % C);
+    const int w = (int)((idx / C) % W);
+    const long long b = idx / ((long long)C * W);
+    float s = 0.f;
+    for (int h = 0; h < H; ++h) s += x[((b * H + h) * W + w) * C + c];
+    y[idx] = s * inv;
+  }
+}
+hipError_t launch_mean_h(const float* x, float* y, int B, int H, int W, int C, hipStream_t s) {
+  const long long total = (long long)B * W * C;
+  hipLaunchKernelGGL(mean_h_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)),
+                     dim3(256), 0, s, x, y, B, H, W, C);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // LayerNorm over the last dim, one wave per row, row in registers
 // (vision_transformer.py:119-122 eps 1e-6; nn.TransformerDecoderLayer norms eps 1e-5).
@@ -622,6 +678,23 @@ hipError_t launch_repack_ohwi(const float* w_ohwi, float* w_out, int Cout, int K
   const long long total = (long long)Cout * KH * KW * Cin;
   hipLaunchKernelGGL(repack_ohwi_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)),
                      dim3(256), 0, s, w_ohwi, w_out, Cout, KH, KW, Cin);
+  return hipGetLastError();
+}
+
+__global__ void transpose_into_kernel(const float* __restrict__ src, int rows, int cols, float* __restrict__ dst,
+                                      int ld, int row_off) {
+  const long long total = (long long)rows * cols;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i / rows), r = (int)(i % rows);
+    dst[(size_t)(row_off + c) * ld + r] = src[(size_t)r * cols + c];
+  }
+}
+hipError_t launch_transpose_into(const float* src, int rows, int cols, float* dst, int ld, int row_off,
+                                 hipStream_t s) {
+  const long long total = (long long)rows * cols;
+  hipLaunchKernelGGL(transpose_into_kernel, dim3((unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048)),
+                     dim3(256), 0, s, src, rows, cols, dst, ld, row_off);
   return hipGetLastError();
 }
 

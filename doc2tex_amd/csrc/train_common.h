@@ -1,4 +1,5 @@
-// Wave-wide reductions shared by the training kernels (train_kernels.hip, train_attn.hip).
+// Wave-wide reductions shared by the training kernels (train_kernels.hip, train_attn.hip, train_recurrent.hip) and the
+// recurrent kernels (recurrent_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,12 +1,13 @@
 // Kernels of the training step (train.hip): everything module.train() + loss.backward() needs beyond the
-// forward GEMM/convolution kernel, the weight gradients (train_wgrad.hip) and softmax attention (train_attn.hip), all fp32.
+// forward GEMM/convolution kernel, the weight gradients (train_wgrad.hip), softmax attention (train_attn.hip) and the
+// recurrent paths (train_recurrent.hip), all fp32.
 //
 //   colreduce_kernel    per-channel sums over rows: BatchNorm batch statistics, BatchNorm / LayerNorm parameter
 //                       gradients, bias gradients
 //   bn_*                BatchNorm2d in training mode (batch statistics, running-statistics update, backward)
 //   ln_*                LayerNorm forward with saved statistics, backward
 //   ce_*                fused cross-entropy, plain and smoothed / class-weighted
-//   maxpool_bwd, relu/gelu backward, embedding, dropout masks, GlobalContext, BiLSTM, small data-movement helpers
+//   maxpool_bwd, relu/gelu backward, embedding, dropout masks, GlobalContext, small data-movement helpers
 //
 // Reference semantics: torch autograd of feature_extractor/resnet.py:205-245, seq_modeling/vit/vision_transformer.py:26-122,
 // prediction_head/tfm.py:103-118 as driven by engine/training.py:76-164.
@@ -1108,145 +1109,6 @@ __global__ void mean_h_bwd_kernel(const float* __restrict__ dy, float* __restric
 hipError_t launch_mean_h_bwd(const float* dy, float* dx, int B, int H, int W, int C, hipStream_t s) {
   const size_t total = (size_t)B * H * W * C;
   hipLaunchKernelGGL(mean_h_bwd_kernel, dim3(ew_grid((total + 3) / 4)), dim3(EW_THREADS), 0, s, dy, dx, total, H, W, C, 1.f / H);
-  return hipGetLastError();
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-constexpr int BL_RB = 4;  // batch rows per block, as the inference kernel (recurrent.hip)
-
-// grid (2 directions, ceil(B / 4)); 1024 threads = the 4H gate rows (H = 256); the same arithmetic as bilstm_kernel
-__global__ __launch_bounds__(1024) void bilstm_train_fwd_kernel(const float* __restrict__ g, const float* __restrict__ whh_t,
-                                                                float* __restrict__ out, float* __restrict__ sv_gates,
-                                                                float* __restrict__ sv_c, int B, int T, int H) {
-  __shared__ float h_s[BL_RB][256], c_s[BL_RB][256], gate_s[BL_RB][1024];
-  const int dir = blockIdx.x, b0 = blockIdx.y * BL_RB, r = threadIdx.x;
-  const int G4 = 4 * H;
-  const float* Wt = whh_t + (size_t)dir * H * G4;
-  for (int i = r; i < BL_RB * H; i += 1024) { (&h_s[0][0])[i] = 0.f; (&c_s[0][0])[i] = 0.f; }
-  __syncthreads();
-  for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
-    float acc[BL_RB];
-#pragma unroll
-    for (int b = 0; b < BL_RB; ++b) acc[b] = (b0 + b < B) ? g[((size_t)(b0 + b) * T + t) * (2 * G4) + dir * G4 + r] : 0.f;
-#pragma unroll 8
-    for (int k = 0; k < H; ++k) {
-      const float w = Wt[(size_t)k * G4 + r];
-#pragma unroll
-      for (int b = 0; b < BL_RB; ++b) acc[b] = fmaf(h_s[b][k], w, acc[b]);
-    }
-#pragma unroll
-    for (int b = 0; b < BL_RB; ++b) gate_s[b][r] = acc[b];
-    __syncthreads();
-    {
-      const int b = r >> 8, j = r & 255;
-      if (b0 + b < B) {
-        const float ig = sigm(gate_s[b][j]), fg = sigm(gate_s[b][H + j]);
-        const float gg = tanhf(gate_s[b][2 * H + j]), og = sigm(gate_s[b][3 * H + j]);
-        const float cc = fg * c_s[b][j] + ig * gg;
-        const float hh = og * tanhf(cc);
-        c_s[b][j] = cc;
-        h_s[b][j] = hh;
-        const size_t row = (size_t)(b0 + b) * T + t;
-        out[row * (2 * H) + dir * H + j] = hh;
-        float* sg = sv_gates + row * (2 * G4) + dir * G4;
-        sg[j] = ig; sg[H + j] = fg; sg[2 * H + j] = gg; sg[3 * H + j] = og;
-        sv_c[row * (2 * H) + dir * H + j] = cc;
-      }
-    }
-    __syncthreads();
-  }
-}
-hipError_t launch_bilstm_train_fwd(const float* gates, const float* whh_t, float* out, float* sv_gates, float* sv_c, int B, int T,
-                                   int H, hipStream_t s) {
-  if (H != 256 || B < 1 || T < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(bilstm_train_fwd_kernel, dim3(2, (B + BL_RB - 1) / BL_RB), dim3(1024), 0, s, gates, whh_t, out, sv_gates, sv_c,
-                     B, T, H);
-  return hipGetLastError();
-}
-
-// Backward through time, same grid.  Per step (reverse processing order): phase 1, thread = (row, hidden unit): the cell's
-// gradients and the pre-activation gate gradients (kept in LDS and written out); phase 2, thread = (quarter of the 4H gate
-// rows, hidden unit k): dh_prev[b][k] = sum_r dgate[b][r] W_hh[r][k] for the block's four rows, each weight read once.
-__global__ __launch_bounds__(1024) void bilstm_train_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ sv_gates,
-                                                                const float* __restrict__ sv_c, const float* __restrict__ whh_fwd,
-                                                                const float* __restrict__ whh_rev, float* __restrict__ dgates,
-                                                                int B, int T, int H) {
-  __shared__ float dh_s[BL_RB][256], dc_s[BL_RB][256], dg_s[BL_RB][1024], part_s[4][BL_RB][256];
-  const int dir = blockIdx.x, b0 = blockIdx.y * BL_RB, tid = threadIdx.x;
-  const int G4 = 4 * H;
-  const float* W = dir == 0 ? whh_fwd : whh_rev;  // [4H][H]
-  for (int i = tid; i < BL_RB * H; i += 1024) { (&dh_s[0][0])[i] = 0.f; (&dc_s[0][0])[i] = 0.f; }
-  __syncthreads();
-  for (int step = T - 1; step >= 0; --step) {
-    const int t = dir == 0 ? step : T - 1 - step;
-    const int tp = dir == 0 ? t - 1 : t + 1;  // the step processed before t (none when step == 0)
-    {
-      const int b = tid >> 8, j = tid & 255;
-      float di = 0.f, df = 0.f, dgg = 0.f, dop = 0.f;
-      if (b0 + b < B) {
-        const size_t row = (size_t)(b0 + b) * T + t;
-        const float* sg = sv_gates + row * (2 * G4) + dir * G4;
-        const float ig = sg[j], fg = sg[H + j], gg = sg[2 * H + j], og = sg[3 * H + j];
-        const float cc = sv_c[row * (2 * H) + dir * H + j];
-        const float cp = step > 0 ? sv_c[((size_t)(b0 + b) * T + tp) * (2 * H) + dir * H + j] : 0.f;
-        const float dh = dout[row * (2 * H) + dir * H + j] + dh_s[b][j];
-        const float tc = tanhf(cc);
-        const float dc = dc_s[b][j] + dh * og * (1.f - tc * tc);
-        di = dc * gg * ig * (1.f - ig);
-        df = dc * cp * fg * (1.f - fg);
-        dgg = dc * ig * (1.f - gg * gg);
-        dop = dh * tc * og * (1.f - og);
-        dc_s[b][j] = dc * fg;
-        float* o = dgates + row * (2 * G4) + dir * G4;
-        o[j] = di; o[H + j] = df; o[2 * H + j] = dgg; o[3 * H + j] = dop;
-      }
-      dg_s[b][j] = di; dg_s[b][H + j] = df; dg_s[b][2 * H + j] = dgg; dg_s[b][3 * H + j] = dop;
-    }
-    __syncthreads();
-    {
-      const int q = tid >> 8, k = tid & 255;
-      float acc[BL_RB];
-#pragma unroll
-      for (int b = 0; b < BL_RB; ++b) acc[b] = 0.f;
-      const int r0 = q * 256;
-#pragma unroll 8
-      for (int r = r0; r < r0 + 256; ++r) {
-        const float w = W[(size_t)r * H + k];
-#pragma unroll
-        for (int b = 0; b < BL_RB; ++b) acc[b] = fmaf(dg_s[b][r], w, acc[b]);
-      }
-#pragma unroll
-      for (int b = 0; b < BL_RB; ++b) part_s[q][b][k] = acc[b];
-    }
-    __syncthreads();
-    {
-      const int b = tid >> 8, k = tid & 255;
-      dh_s[b][k] = (part_s[0][b][k] + part_s[1][b][k]) + (part_s[2][b][k] + part_s[3][b][k]);
-    }
-    __syncthreads();
-  }
-}
-hipError_t launch_bilstm_train_bwd(const float* dout, const float* sv_gates, const float* sv_c, const float* whh_fwd,
-                                   const float* whh_rev, float* dgates, int B, int T, int H, hipStream_t s) {
-  if (H != 256 || B < 1 || T < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(bilstm_train_bwd_kernel, dim3(2, (B + BL_RB - 1) / BL_RB), dim3(1024), 0, s, dout, sv_gates, sv_c, whh_fwd,
-                     whh_rev, dgates, B, T, H);
-  return hipGetLastError();
-}
-__global__ void bilstm_hprev_kernel(const float* __restrict__ out, float* __restrict__ hf, float* __restrict__ hr, int B, int T,
-                                    int H) {
-  const size_t total = (size_t)B * T * H;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int j = (int)(i % H), t = (int)((i / H) % T);
-    const size_t b = i / ((size_t)H * T);
-    hf[i] = t > 0 ? out[((b * T + t - 1) * 2) * H + j] : 0.f;
-    hr[i] = t + 1 < T ? out[((b * T + t + 1) * 2 + 1) * H + j] : 0.f;
-  }
-}
-hipError_t launch_bilstm_hprev(const float* out, float* hprev_fwd, float* hprev_rev, int B, int T, int H, hipStream_t s) {
-  const size_t total = (size_t)B * T * H;
-  hipLaunchKernelGGL(bilstm_hprev_kernel, dim3(ew_grid((total + 3) / 4)), dim3(EW_THREADS), 0, s, out, hprev_fwd, hprev_rev, B, T, H);
   return hipGetLastError();
 }
 

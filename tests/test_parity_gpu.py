@@ -120,6 +120,21 @@ def test_two_row_decode_blocks_do_not_couple_their_rows(cases):
     assert torch.equal(l_all, swapped[1].flip(0))
 
 
+def test_bilstm_blocks_do_not_couple_their_rows():
+    """The BiLSTM recurrence (VGG + BiLSTM stacks: C0 / B0) steps four rows per block (recurrent.hip bilstm_fwd_kernel): a
+    row's logits must not depend on which rows share its block, nor on the last block being ragged (five rows: 4 + 1)."""
+    L = 10
+    cfg, m = engine_model("C0", L)
+    img = synth.synth_images(5, 32, 100, seed=79).cuda()
+    text = torch.zeros(5, L + 1, dtype=torch.long, device="cuda")
+    with torch.no_grad():
+        p_all, l_all, _ = m(img, text, is_train=False)
+        parts = [m(img[i:i + n], text[i:i + n], is_train=False) for i, n in ((0, 1), (1, 3), (4, 1))]
+        swapped = m(img.flip(0), text, is_train=False)
+    assert torch.equal(p_all, torch.cat([q[0] for q in parts])) and torch.equal(l_all, torch.cat([q[1] for q in parts]))
+    assert torch.equal(l_all, swapped[1].flip(0))
+
+
 def test_determinism_and_weight_reload(cases):
     c = _case(cases, "greedy", "t2_greedy")
     cfg, m = engine_model(c["config"], c["max_seq_len"], c["wseed"], 0.0)
@@ -667,6 +682,8 @@ def test_fp32_convolutions_keep_parity(cases, name):
     ("T2", 48, 64, 1, "fp32"), ("T2", 45, 63, 3, "bf16x3"), ("T2", 35, 61, 2, "fp32"), ("T2", 47, 61, 5, "bf16x3"),
     ("T1", 32, 64, 1, "bf16x3"), ("T1", 45, 99, 3, "fp32"), ("T1", 63, 130, 2, "bf16x3"),
     ("TS0", 48, 64, 3, "bf16x3"), ("T2G", 41, 59, 2, "bf16x3"),
+    # VGG + BiLSTM (24 memory tokens): batches that are no multiple of the four rows a BiLSTM block takes
+    ("C0", 32, 100, 5, "fp32"), ("B0", 32, 100, 3, "bf16x3"),
 ])
 def test_odd_crop_shapes_and_batch_sizes(manifests, cname, H, W, B, precision):
     """Ragged geometry: odd heights / widths (every pool and strided conv floors differently), batch sizes that are not
