@@ -40,6 +40,24 @@ class D2TPrepPlan(C.Structure):  # include/d2t_prep.h d2t_prep_plan
                                          "min_branch", "status")]
 
 
+class D2TOpAttnDecodeArgs(C.Structure):  # include/d2t.h d2t_op_attn_decode_args
+    _fields_ = [(n, C.c_void_p) for n in (
+        "mem", "kp", "wq_t", "bq", "wloc", "bloc", "wscore", "wx_t", "bx", "wg_t", "bg", "wih_t", "bih", "wic_t", "bic", "emb",
+        "tokgate", "probs", "tokens", "end_step", "st_h_in", "st_c_in", "st_mem_in", "st_h_out", "st_c_out", "st_mem_out",
+        "tok_in", "row_sample", "teacher", "use_teacher", "out_dropmask", "sv_tok", "sv_hprev", "sv_cprev", "sv_hafter",
+        "sv_cafter", "sv_gates", "sv_alpha", "sv_hq", "sv_x", "exit_state", "steps_dev")] + \
+        [("bscore", C.c_float), ("out_dropscale", C.c_float)] + \
+        [(n, C.c_int32) for n in ("B", "T", "S", "V", "taps", "key_off", "init_mode", "coverage", "end_token", "step_mode",
+                                  "first", "samples")]
+
+
+class D2TOpAttnLstmBwdArgs(C.Structure):  # include/d2t.h d2t_op_attn_lstm_bwd_args
+    _fields_ = [(n, C.c_void_p) for n in (
+        "dlogits", "mem", "kp", "wg_t", "wih_raw", "whh_raw", "wq_raw", "wloc", "bloc", "wscore", "sv_cprev", "sv_cafter",
+        "sv_gates", "sv_alpha", "sv_hq", "dhl", "dmem", "dkp", "dgates", "dhq", "demb", "dh0", "dc0", "dwloc", "dbloc", "dwscore",
+        "dbscore")] + [(n, C.c_int32) for n in ("B", "T", "S", "V", "taps", "key_off", "coverage")]
+
+
 PREP_DEMO, PREP_API = 0, 1
 NORM_ALB, NORM_RAW = 0, 1
 PREP_OK, PREP_UNBOUND_LOCAL, PREP_FALLBACK = 0, 1, 2
@@ -142,6 +160,15 @@ SIGNATURES = {
     "d2t_op_train_layernorm": (_I, [_P] * 8 + [_I, _I, C.c_float, _P]),
     "d2t_op_train_attention": (_I, [_P] * 7 + [_I] * 6 + [_P]),
     "d2t_op_train_maxpool": (_I, [_P] * 4 + [_I] * 8 + [_P]),
+    # the recurrent kernels one at a time (test infrastructure)
+    "d2t_op_bilstm": (_I, [_P] * 5 + [_I] * 3 + [_P]),
+    "d2t_op_bilstm_hprev": (_I, [_P] * 3 + [_I] * 3 + [_P]),
+    "d2t_op_bilstm_bwd": (_I, [_P] * 6 + [_I] * 3 + [_P]),
+    "d2t_op_attn_decode": (_I, [C.POINTER(D2TOpAttnDecodeArgs), _P]),
+    "d2t_op_attn_decode_finalize": (_I, [_P, _P] + [_I] * 4 + [_P] * 4),
+    "d2t_op_attn_alpha_gather": (_I, [_P] * 4 + [_I] * 4 + [_P]),
+    "d2t_op_attn_lstm_bwd": (_I, [C.POINTER(D2TOpAttnLstmBwdArgs), _P]),
+    "d2t_op_loc_unfold_bwd": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I] + [_P] * 5),
 }
 # include/d2t_prep.h
 SIGNATURES_PREP = {

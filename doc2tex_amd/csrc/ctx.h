@@ -234,6 +234,8 @@ int fail(d2t_ctx* c, int code, const char* fmt, ...) {
   if (c) c->err = buf;
   return code;
 }
+// a launcher's status as a return code of the context-free d2t_op_* entries: a refusal is D2T_EINVAL
+[[maybe_unused]] int op_status(hipError_t e) { return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP; }
 #define HIPCHK(c, expr)                                                                        \
   do {                                                                                         \
     hipError_t e_ = (expr);                                                                    \

@@ -183,7 +183,7 @@ int d2t_op_skinny(const float* x, const float* w, const float* bias, const float
   p.step_ptr = step; p.out_step_stride = out_step_stride;
   p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_out = ln_out;
   const hipError_t e = launch_skinny(p, s);
-  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+  return op_status(e);
 }
 
 namespace {
@@ -443,7 +443,7 @@ int d2t_op_beam_topk(const float* logits, const float* scores, const int32_t* se
       return D2T_EINVAL;
   }
   const hipError_t e = launch_beam_topk_batch(logits, scores, seg, N, V, kmax, topv, topi, s);
-  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+  return op_status(e);
 }
 
 int d2t_op_beam_advance(int32_t init, int64_t go_token, int32_t* ctrl, int64_t* tok, float* scores, int32_t* map, int32_t* prev,
@@ -482,7 +482,7 @@ int d2t_op_beam_advance(int32_t init, int64_t go_token, int32_t* ctrl, int64_t* 
     }
   }
   const hipError_t e = launch_beam_dev_advance(b, s);
-  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+  return op_status(e);
 }
 
 int d2t_op_beam_ancestry(const int32_t* anc_old, int32_t* anc_new, const int32_t* prev, int32_t rows, int32_t stride,
@@ -495,7 +495,7 @@ int d2t_op_beam_ancestry(const int32_t* anc_old, int32_t* anc_new, const int32_t
   if (t[0] < 0 || t[0] > stride) return D2T_EINVAL;  // positions 0 .. t - 1 of a row are written
   for (int v : pv) if (v < 0 || v >= rows) return D2T_EINVAL;
   const hipError_t e = launch_beam_ancestry(anc_old, anc_new, prev, rows, stride, step_in, step_out, s, rows_ptr, stop);
-  return e == hipSuccess ? D2T_OK : e == hipErrorInvalidValue ? D2T_EINVAL : D2T_EHIP;
+  return op_status(e);
 }
 
 int d2t_op_cache_gather(const float* src, float* dst, const int32_t* prev, int32_t slabs, int32_t cap, int32_t M, int32_t heads,
@@ -508,6 +508,111 @@ int d2t_op_cache_gather(const float* src, float* dst, const int32_t* prev, int32
   if (!fetch_ints(s, prev, M, &pv)) return D2T_EHIP;
   for (int v : pv) if (v < 0 || v >= cap) return D2T_EINVAL;
   return launch_cache_gather(src, dst, prev, slabs, cap, M, heads, Lmax, hd, rows, s) == hipSuccess ? D2T_OK : D2T_EHIP;
+}
+
+// ---------------------------------------------------------------------------
+// recurrent kernels one at a time (test infrastructure; see include/d2t.h): the launchers of recurrent.hip on caller
+// tensors in the kernels' own layouts, behind the same checks.  Asynchronous unless an integer table has to be read back.
+// ---------------------------------------------------------------------------
+namespace {
+// n 64-bit token ids of device memory, each in [0, V)?  (the stream's earlier work has finished)  0 / D2T_EINVAL / D2T_EHIP
+int tokens_in_range(hipStream_t s, const int64_t* dev, size_t n, int V) {
+  std::vector<int64_t> h(n);
+  if (hipStreamSynchronize(s) != hipSuccess) return D2T_EHIP;
+  if (n && hipMemcpy(h.data(), dev, n * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return D2T_EHIP;
+  for (int64_t v : h) if (v < 0 || v >= V) return D2T_EINVAL;
+  return D2T_OK;
+}
+}  // namespace
+
+int d2t_op_bilstm(const float* g, const float* whh_t, float* out, float* sv_gates, float* sv_c, int32_t B, int32_t T,
+                  int32_t H, d2t_stream stream) {
+  if (!g || !whh_t || !out || (sv_gates == nullptr) != (sv_c == nullptr)) return D2T_EINVAL;
+  if (H != 256 || B < 1 || B > 65535 * 4 || T < 1) return D2T_EINVAL;  // grid.y blocks of four rows
+  hipStream_t s = (hipStream_t)stream;
+  return op_status(sv_gates ? launch_bilstm_train_fwd(g, whh_t, out, sv_gates, sv_c, B, T, H, s) : launch_bilstm(g, whh_t, out, B, T, H, s));
+}
+
+int d2t_op_bilstm_hprev(const float* out, float* hprev_fwd, float* hprev_rev, int32_t B, int32_t T, int32_t H,
+                        d2t_stream stream) {
+  if (!out || !hprev_fwd || !hprev_rev || B < 1 || T < 1 || H < 1) return D2T_EINVAL;
+  return op_status(launch_bilstm_hprev(out, hprev_fwd, hprev_rev, B, T, H, (hipStream_t)stream));
+}
+
+int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream) {
+  if (!a || !a->mem || !a->kp || !a->wq_t || !a->bq || !a->wloc || !a->bloc || !a->wscore || !a->wx_t || !a->bx || !a->wg_t ||
+      !a->bg || !a->probs || !a->tokens || !a->end_step)
+    return D2T_EINVAL;
+  if (a->B < 1 || a->B > 65535 || a->S < 1 || a->V < 1 || a->V > D2T_ATTN_MAX_CLASSES || a->taps < 1 || a->taps > 11 ||
+      a->key_off < 0 || a->key_off > 1 || a->init_mode < 0 || a->init_mode > 2 || a->T - a->key_off < 1 ||
+      a->T - a->key_off > 4096 || a->end_token < 0 || a->end_token >= a->V)
+    return D2T_EINVAL;
+  if ((a->emb == nullptr) == (a->tokgate == nullptr)) return D2T_EINVAL;
+  if (a->init_mode != 0 && (!a->wih_t || !a->bih || !a->wic_t || !a->bic)) return D2T_EINVAL;
+  if ((a->sv_hprev == nullptr) != (a->sv_cprev == nullptr)) return D2T_EINVAL;
+  if ((a->sv_gates == nullptr) != (a->sv_hafter == nullptr) || (a->sv_gates == nullptr) != (a->sv_cafter == nullptr)) return D2T_EINVAL;
+  if ((a->use_teacher || a->sv_tok) && !a->teacher) return D2T_EINVAL;
+  if (a->exit_state && (!a->steps_dev || a->step_mode || a->teacher)) return D2T_EINVAL;
+  if (!a->exit_state && a->steps_dev) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (a->step_mode) {
+    if (a->S != 1 || a->teacher || a->samples < 1 || !a->st_h_out || !a->st_c_out || !a->st_mem_out) return D2T_EINVAL;
+    if (!a->first && (!a->st_h_in || !a->st_c_in || !a->st_mem_in || !a->tok_in)) return D2T_EINVAL;
+    if (a->row_sample) {
+      std::vector<int> h;
+      if (!fetch_ints(s, a->row_sample, a->B, &h)) return D2T_EHIP;
+      for (int v : h) if (v < 0 || v >= a->samples) return D2T_EINVAL;
+    }
+    if (!a->first)
+      if (int rc = tokens_in_range(s, a->tok_in, a->B, a->V)) return rc;
+  } else if (a->samples != a->B || a->row_sample || a->tok_in) {
+    return D2T_EINVAL;
+  }
+  if (a->teacher)
+    if (int rc = tokens_in_range(s, a->teacher, (size_t)a->B * a->S, a->V)) return rc;
+  AttnDecP p{};
+  p.mem = a->mem; p.T = a->T; p.D = 256; p.key_off = a->key_off; p.init_mode = a->init_mode;
+  p.kp = a->kp; p.wq_t = a->wq_t; p.bq = a->bq; p.wloc = a->wloc; p.bloc = a->bloc; p.taps = a->taps;
+  p.wscore = a->wscore; p.bscore = a->bscore; p.wx_t = a->wx_t; p.bx = a->bx; p.wg_t = a->wg_t; p.bg = a->bg;
+  p.wih_t = a->wih_t; p.bih = a->bih; p.wic_t = a->wic_t; p.bic = a->bic; p.emb = a->emb; p.tokgate = a->tokgate;
+  p.probs = a->probs; p.tokens = a->tokens; p.end_step = a->end_step;
+  p.B = a->B; p.S = a->S; p.V = a->V; p.H = 256; p.E = 256; p.coverage = a->coverage != 0; p.end_token = a->end_token;
+  p.step_mode = a->step_mode != 0; p.first = a->first != 0;
+  p.st_h_in = a->st_h_in; p.st_c_in = a->st_c_in; p.st_mem_in = a->st_mem_in;
+  p.st_h_out = a->st_h_out; p.st_c_out = a->st_c_out; p.st_mem_out = a->st_mem_out;
+  p.tok_in = a->tok_in; p.row_sample = a->row_sample;
+  p.teacher = a->teacher; p.use_teacher = a->use_teacher; p.out_dropmask = a->out_dropmask; p.out_dropscale = a->out_dropscale;
+  p.sv_tok = a->sv_tok; p.sv_hprev = a->sv_hprev; p.sv_cprev = a->sv_cprev; p.sv_hafter = a->sv_hafter; p.sv_cafter = a->sv_cafter;
+  p.sv_gates = a->sv_gates; p.sv_alpha = a->sv_alpha; p.sv_hq = a->sv_hq; p.sv_x = a->sv_x;
+  p.exit_state = reinterpret_cast<unsigned long long*>(a->exit_state);
+  hipError_t e = hipMemsetAsync(a->end_step, 0xFF, (size_t)a->B * 4, s);  // -1 = never emitted the end token
+  if (e == hipSuccess && a->exit_state) e = hipMemsetAsync(a->exit_state, 0, 8, s);
+  if (e == hipSuccess) e = launch_attn_decode(p, s);
+  if (e == hipSuccess && a->exit_state)
+    e = launch_attn_decode_finalize(p.exit_state, a->steps_dev, a->B, a->S, a->V, a->T - a->key_off, a->tokens, a->probs,
+                                    a->sv_alpha, s);
+  return op_status(e);
+}
+
+int d2t_op_attn_decode_finalize(const uint64_t* exit_state, int32_t* steps_dev, int32_t B, int32_t S, int32_t V, int32_t Tk,
+                                int64_t* tokens, float* probs, float* alpha, d2t_stream stream) {
+  if (!exit_state || !steps_dev || !tokens || !probs || B < 1 || S < 1 || V < 1 || Tk < 1) return D2T_EINVAL;
+  return op_status(launch_attn_decode_finalize(reinterpret_cast<const unsigned long long*>(exit_state), steps_dev, B, S, V, Tk,
+                                               tokens, probs, alpha, (hipStream_t)stream));
+}
+
+int d2t_op_attn_alpha_gather(const float* hist, const int32_t* path, const int32_t* len, float* out, int32_t N, int32_t S,
+                             int32_t cap, int32_t Tk, d2t_stream stream) {
+  if (!hist || !path || !len || !out || N < 1 || S < 1 || cap < 1 || Tk < 1) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> l, pt;
+  if (!fetch_ints(s, len, N, &l) || !fetch_ints(s, path, (size_t)N * S, &pt)) return D2T_EHIP;
+  for (int i = 0; i < N; ++i) {
+    if (l[i] < 0 || l[i] > S) return D2T_EINVAL;
+    for (int j = 0; j < l[i]; ++j)
+      if (pt[(size_t)i * S + j] < 0 || pt[(size_t)i * S + j] >= cap) return D2T_EINVAL;
+  }
+  return op_status(launch_attn_alpha_gather(hist, path, len, out, N, S, cap, Tk, s));
 }
 
 }  // extern "C"

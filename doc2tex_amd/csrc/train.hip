@@ -1812,4 +1812,47 @@ int d2t_op_train_maxpool(const float* x, const float* dy, float* y, float* dx, i
   return o.finish(run());
 }
 
+// The recurrent backward kernels one at a time (include/d2t.h): train_recurrent.hip's launchers on caller tensors in the
+// kernels' own layouts, asynchronous on the stream.
+int d2t_op_bilstm_bwd(const float* dout, const float* sv_gates, const float* sv_c, const float* whh_fwd, const float* whh_rev,
+                      float* dgates, int32_t B, int32_t T, int32_t H, d2t_stream stream) {
+  if (!dout || !sv_gates || !sv_c || !whh_fwd || !whh_rev || !dgates) return D2T_EINVAL;
+  if (H != 256 || B < 1 || B > 65535 * 4 || T < 1) return D2T_EINVAL;  // grid.y blocks of four rows
+  return op_status(launch_bilstm_train_bwd(dout, sv_gates, sv_c, whh_fwd, whh_rev, dgates, B, T, H, (hipStream_t)stream));
+}
+
+int d2t_op_attn_lstm_bwd(const d2t_op_attn_lstm_bwd_args* a, d2t_stream stream) {
+  if (!a || !a->dlogits || !a->mem || !a->kp || !a->wih_raw || !a->whh_raw || !a->wq_raw || !a->wloc || !a->bloc || !a->wscore ||
+      !a->sv_cprev || !a->sv_cafter || !a->sv_gates || !a->sv_alpha || !a->sv_hq || !a->dmem || !a->dkp || !a->dgates || !a->dhq ||
+      !a->dh0 || !a->dc0 || !a->dwloc || !a->dbloc || !a->dwscore || !a->dbscore)
+    return D2T_EINVAL;
+  if (!a->dhl && (!a->wg_t || a->V > 1024)) return D2T_EINVAL;  // the in-kernel generator product stages 1024 classes
+  if (a->B < 1 || a->B > 65535 || a->S < 1 || a->V < 1 || a->V > D2T_ATTN_MAX_CLASSES || a->taps < 1 || a->taps > 11 ||
+      a->key_off < 0 || a->key_off > 1 || a->T - a->key_off < 1 || a->T - a->key_off > 4096)
+    return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  AttnTrainBwdP p{};
+  p.dlogits = a->dlogits; p.mem = a->mem; p.T = a->T; p.D = 256; p.key_off = a->key_off; p.kp = a->kp;
+  p.wg_t = a->wg_t; p.wih_raw = a->wih_raw; p.whh_raw = a->whh_raw; p.wq_raw = a->wq_raw;
+  p.wloc = a->wloc; p.bloc = a->bloc; p.wscore = a->wscore; p.taps = a->taps;
+  p.sv_cprev = a->sv_cprev; p.sv_cafter = a->sv_cafter; p.sv_gates = a->sv_gates; p.sv_alpha = a->sv_alpha; p.sv_hq = a->sv_hq;
+  p.dmem = a->dmem; p.dkp = a->dkp; p.dgates = a->dgates; p.dhq = a->dhq; p.demb = a->demb; p.dhl = a->dhl;
+  p.dh0 = a->dh0; p.dc0 = a->dc0; p.dwloc = a->dwloc; p.dbloc = a->dbloc; p.dwscore = a->dwscore; p.dbscore = a->dbscore;
+  p.B = a->B; p.S = a->S; p.V = a->V; p.H = 256; p.E = 256; p.coverage = a->coverage != 0;
+  const size_t n = (size_t)a->B * a->T * 256 * sizeof(float);
+  hipError_t e = hipMemsetAsync(a->dmem, 0, n, s);
+  if (e == hipSuccess) e = hipMemsetAsync(a->dkp, 0, n, s);
+  if (e == hipSuccess) e = launch_attn_train_lstm_bwd(p, s);
+  return op_status(e);
+}
+
+int d2t_op_loc_unfold_bwd(const float* dwloc, const float* dbloc, int32_t B, const float* conv_w, const float* conv_b,
+                          const float* proj_w, int32_t H, int32_t kd, int32_t taps, float* d_conv_w, float* d_conv_b,
+                          float* d_proj_w, float* d_proj_b, d2t_stream stream) {
+  if (!dwloc || !dbloc || !conv_w || !conv_b || !proj_w || !d_conv_w || !d_conv_b || !d_proj_w || !d_proj_b) return D2T_EINVAL;
+  if (B < 1 || H < 1 || kd < 1 || taps < 1 || (long long)H * (taps + 1) * 4 > 64 * 1024) return D2T_EINVAL;  // one block's LDS
+  return op_status(launch_loc_unfold_bwd(dwloc, dbloc, B, conv_w, conv_b, proj_w, H, kd, taps, d_conv_w, d_conv_b, d_proj_w,
+                                             d_proj_b, (hipStream_t)stream));
+}
+
 }  // extern "C"

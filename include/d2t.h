@@ -581,6 +581,60 @@ int d2t_op_beam_ancestry(const int32_t* anc_old, int32_t* anc_new, const int32_t
 int d2t_op_cache_gather(const float* src, float* dst, const int32_t* prev, int32_t slabs, int32_t cap, int32_t M, int32_t heads,
                         int32_t Lmax, int32_t hd, int32_t rows, d2t_stream stream);
 
+/* ---- the recurrent kernels, one at a time ------------------------------------------------------------------------
+ * TEST INFRASTRUCTURE (tests/test_recurrent_ops_gpu.py): the BiLSTM recurrence, the LSTM-attention decoder loop and their
+ * small helpers (csrc/recurrent.hip), behind the same rules as the decode-step entries above -- no context, device
+ * pointers, every size and every device-side integer table checked before anything is launched (D2T_EINVAL otherwise).
+ * Unlike those entries the tensors are in the KERNELS' OWN layouts (transposed weights, the folded location filter, gates
+ * [B*T][8H]): what the engine hands its launchers.  H = D = E = 256.  The backward kernels' entries are further down, next
+ * to the d2t_op_train_* entries. */
+/* One bidirectional LSTM layer from its input projection: g [B*T][2*4H] (forward | reverse gates i, f, g, o, biases
+ * included), whh_t [2][H][4H] (W_hh^T per direction); out [B][T][2H] = [h_fwd | h_rev].  sv_gates [B*T][2*4H] and sv_c
+ * [B*T][2H] (both or neither): the training forward, which keeps the gates AFTER their nonlinearities and the cell state. */
+int d2t_op_bilstm(const float* g, const float* whh_t, float* out, float* sv_gates, float* sv_c, int32_t B, int32_t T,
+                  int32_t H, d2t_stream stream);
+/* The h_prev operands of the W_hh gradient GEMMs: hprev_fwd[b][t] = out[b][t-1][:H], hprev_rev[b][t] = out[b][t+1][H:]
+ * (zeros at the ends); out [B][T][2H], both results [B*T][H]. */
+int d2t_op_bilstm_hprev(const float* out, float* hprev_fwd, float* hprev_rev, int32_t B, int32_t T, int32_t H,
+                        d2t_stream stream);
+/* The LSTM-attention decoder loop (launch_attn_decode; struct AttnDecP of csrc/kernels.h, whose field names these are).
+ * Required: mem [samples][T][256], kp [samples][T][256], wq_t [256][256], bq, wloc [256][taps], bloc, wscore, wx_t [768][1024],
+ * bx [1024], wg_t [256][V], bg [V], probs [B][S][V], tokens [B][S], end_step [B] (set to -1 by the entry first, as the engine
+ * does); exactly one of emb [V][256] / tokgate [V][1024]; wih_t / bih / wic_t / bic when init_mode != 0.
+ * samples = B outside step mode.  Step mode (S = 1): st_*_out required, st_*_in and tok_in [B] unless first; row_sample
+ * (optional) [B] < samples.  teacher [B][S] < V (not in step mode) with use_teacher [S], sv_tok; out_dropmask [B][S][V];
+ * the sv_* buffers are optional (hprev + cprev together; gates + hafter + cafter together).
+ * exit_state (needs steps_dev; neither step mode nor teacher): the early-exit build -- the word is zeroed, the loop runs, and
+ * the finalize kernel follows on the stream, as the engine's greedy is_test path. */
+typedef struct d2t_op_attn_decode_args {
+  const float *mem, *kp, *wq_t, *bq, *wloc, *bloc, *wscore, *wx_t, *bx, *wg_t, *bg, *wih_t, *bih, *wic_t, *bic, *emb, *tokgate;
+  float* probs;
+  int64_t* tokens;
+  int32_t* end_step;
+  const float *st_h_in, *st_c_in, *st_mem_in;
+  float *st_h_out, *st_c_out, *st_mem_out;
+  const int64_t* tok_in;
+  const int32_t* row_sample;
+  const int64_t* teacher;
+  const uint8_t *use_teacher, *out_dropmask;
+  int64_t* sv_tok;
+  float *sv_hprev, *sv_cprev, *sv_hafter, *sv_cafter, *sv_gates, *sv_alpha, *sv_hq, *sv_x;
+  uint64_t* exit_state;
+  int32_t* steps_dev;
+  float bscore, out_dropscale;
+  int32_t B, T, S, V, taps, key_off, init_mode, coverage, end_token, step_mode, first, samples;
+} d2t_op_attn_decode_args;
+int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream);
+/* The finalize kernel alone on a caller-given exit word {rows ended : high 32 bits, largest end step : low 32 bits}:
+ * *steps_dev = largest end step + 1 if all B rows ended and that is below S, else S; tokens [B][S], probs [B][S][V] and
+ * alpha [B][S][Tk] (optional) zeroed for the steps [steps, S) of every row. */
+int d2t_op_attn_decode_finalize(const uint64_t* exit_state, int32_t* steps_dev, int32_t B, int32_t S, int32_t V, int32_t Tk,
+                                int64_t* tokens, float* probs, float* alpha, d2t_stream stream);
+/* out [N][S][Tk] = hist[j][path[i*S + j]][:] for j < len[i], zeros for len[i] <= j < S; hist [S][cap][Tk], path [N][S]
+ * (values < cap where j < len[i]), len [N] in [0, S].  out must be 16-byte aligned. */
+int d2t_op_attn_alpha_gather(const float* hist, const int32_t* path, const int32_t* len, float* out, int32_t N, int32_t S,
+                             int32_t cap, int32_t Tk, d2t_stream stream);
+
 /* ---- fused cross-entropy ------------------------------------------------------------------------------------------
  * The criterion of the reference's training step -- nn.CrossEntropyLoss(ignore_index = PAD, reduction = 'none') on
  * preds.view(-1, V) / target.view(-1) (engine/training.py:50-53, 83, 90; modules/loss/builder.py:18-24) -- as one kernel
@@ -638,6 +692,29 @@ int d2t_op_train_attention(const float* q, const float* kv, const int64_t* keyto
                            d2t_stream stream);
 int d2t_op_train_maxpool(const float* x, const float* dy, float* y, float* dx, int32_t B, int32_t H, int32_t W, int32_t C,
                          int32_t SH, int32_t SW, int32_t PH, int32_t PW, d2t_stream stream);
+/* The backward kernels of the recurrent paths one at a time (csrc/train_recurrent.hip; test infrastructure with the rules of
+ * d2t_op_bilstm above: kernel layouts, asynchronous on the stream, H = D = E = 256).
+ * BiLSTM through time: dout [B][T][2H]; sv_gates / sv_c as d2t_op_bilstm saved them; whh_fwd / whh_rev [4H][H] as stored;
+ * dgates [B*T][2*4H] = the gradient of the pre-activation gates. */
+int d2t_op_bilstm_bwd(const float* dout, const float* sv_gates, const float* sv_c, const float* whh_fwd, const float* whh_rev,
+                      float* dgates, int32_t B, int32_t T, int32_t H, d2t_stream stream);
+/* Backward of the teacher-forced LSTM-attention loop (launch_attn_train_lstm_bwd; struct AttnTrainBwdP of csrc/kernels.h).
+ * dlogits [B][S][V]; mem / kp [B][T][256]; wg_t [256][V]; wih_raw [1024][512], whh_raw [1024][256], wq_raw [256][256] as stored;
+ * the sv_* of the forward.  dmem / dkp [B][T][256] are zeroed by the entry, then accumulated into.  Per-(row, step) factors:
+ * dgates [B][S][1024], dhq [B][S][256], demb [B][S][256] (optional); dh0 / dc0 [B][256]; per-row partials dwloc [B][256][taps],
+ * dbloc / dwscore [B][256], dbscore [B].  dhl (optional) [B][S][256] = dlogits . generator.weight; required when V > 1024. */
+typedef struct d2t_op_attn_lstm_bwd_args {
+  const float *dlogits, *mem, *kp, *wg_t, *wih_raw, *whh_raw, *wq_raw, *wloc, *bloc, *wscore;
+  const float *sv_cprev, *sv_cafter, *sv_gates, *sv_alpha, *sv_hq, *dhl;
+  float *dmem, *dkp, *dgates, *dhq, *demb, *dh0, *dc0, *dwloc, *dbloc, *dwscore, *dbscore;
+  int32_t B, T, S, V, taps, key_off, coverage;
+} d2t_op_attn_lstm_bwd_args;
+int d2t_op_attn_lstm_bwd(const d2t_op_attn_lstm_bwd_args* a, d2t_stream stream);
+/* Gradients of loc_conv.weight [kd][taps], loc_conv.bias [kd], loc_proj.weight [H][kd], loc_proj.bias [H] from the per-row
+ * partials of the folded filter, dwloc [B][H][taps] and dbloc [B][H]. */
+int d2t_op_loc_unfold_bwd(const float* dwloc, const float* dbloc, int32_t B, const float* conv_w, const float* conv_b,
+                          const float* proj_w, int32_t H, int32_t kd, int32_t taps, float* d_conv_w, float* d_conv_b,
+                          float* d_proj_w, float* d_proj_b, d2t_stream stream);
 
 #ifdef __cplusplus
 }
