@@ -1,4 +1,4 @@
-// Shared between the engine*.hip files (inference) and train.hip (training step): the context struct, packed-weight
+// Shared between the engine*.hip files (inference) and the train*.hip files (training step): the context struct, packed-weight
 // records and small host helpers.  Internal to libd2t; the public surface is include/d2t.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,7 +18,7 @@
 
 using namespace d2t;
 
-struct d2t_train_state;  // train.hip
+struct d2t_train_state;  // train_tape.h
 
 namespace {
 
@@ -220,7 +220,7 @@ struct d2t_ctx {
   unsigned long long* dtrace = nullptr;
   int dtrace_next = 0;
   static constexpr int DTRACE_SLOTS = 8192;
-  d2t_train_state* train = nullptr;  // lazily created by d2t_train_* (train.hip)
+  d2t_train_state* train = nullptr;  // lazily created by d2t_train_* (train_abi.hip, train_models.hip)
 };
 
 namespace {
