@@ -25,6 +25,11 @@ namespace {
 constexpr int TOK_PAD = 0, TOK_GO = 1, TOK_END = 2;  // converter/tfm_converter.py:8
 const int RESNET_LAYERS[4] = {1, 2, 5, 3};           // feature_extractor/resnet.py:262
 
+}  // namespace
+
+// The records of the context.  They are members of d2t_ctx and parameters of functions that cross the engine's files
+// (engine_impl.h), so their names have linkage; hidden: nothing of them belongs to the library's surface.
+#pragma GCC visibility push(hidden)
 struct RawW {
   float* p = nullptr;
   std::vector<int64_t> shape;
@@ -94,8 +99,7 @@ struct Act {
   size_t numel() const { return (size_t)B * H * W * C; }
   uint16_t* planes() const { return reinterpret_cast<uint16_t*>(p); }
 };
-
-}  // namespace
+#pragma GCC visibility pop
 
 struct d2t_ctx {
   d2t_config cfg;
@@ -244,6 +248,16 @@ int fail(d2t_ctx* c, int code, const char* fmt, ...) {
 
 int dev_alloc(d2t_ctx* c, void** p, size_t bytes) {
   if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return fail(c, D2T_ENOMEM, "hipMalloc(%zu) failed", bytes);
+  return D2T_OK;
+}
+// `count` elements that the context owns (c->owned: freed on destroy / re-finalize).  The buffer is recorded as soon as it
+// exists, so nothing leaks when a later allocation of the same packing step fails.
+template <typename T>
+int owned_alloc(d2t_ctx* c, T** p, size_t count) {
+  void* q;
+  if (int rc = dev_alloc(c, &q, count * sizeof(T))) return rc;
+  c->owned.push_back(q);
+  *p = static_cast<T*>(q);
   return D2T_OK;
 }
 // grow-only buffer; growing synchronises the device (never during graph capture)

@@ -1,6 +1,17 @@
-// Shared between the engine*.hip files: constants and small host helpers that more than one of them needs.  Internal to libd2t.
+// Shared between the engine*.hip files: constants and small host helpers that more than one of them needs, and the functions
+// of engine_weights.hip that engine.hip calls.  Internal to libd2t.
 #pragma once
 #include "ctx.h"
+
+// (hidden: these functions cross two files, but none of their symbols belongs to the library's surface)
+#pragma GCC visibility push(hidden)
+namespace eng {
+// engine_weights.hip: the fp16 hi / lo planes of a packed convolution weight, made on the first launch that needs them
+int f16_planes(d2t_ctx* c, ConvW& w, hipStream_t s);
+// engine_weights.hip: frees every packed buffer and leaves the context unfinalized (re-finalize, destroy)
+void free_packed(d2t_ctx* c);
+}  // namespace eng
+#pragma GCC visibility pop
 
 namespace {
 
