@@ -209,11 +209,20 @@ struct d2t_ctx {
   // pinned host copy.  Its own buffer: a greedy slot's tables may belong to a decode still in flight on another chain.  The
   // search synchronises before it returns, so both are idle between calls
   int* brg_tab = nullptr; int* brg_host = nullptr; int brg_cap = 0;
-  // ragged decode groups (rtab != nullptr): B is the row total, T is 0 and the batch layout is NOT part of the key -- the loop
-  // reads lengths and offsets from the tables at rtab; aux = the slot's bf16-plane offset (a function of the slot's capacity)
-  // ragged beam search: B = N * beam, T = 0, variant = the uniform beam loop's with bit 62 set, rtab = the beam tables
-  struct GraphKey { int B, T, steps; const void* tok; const void* logits; const void* ckv; const void* dws; const void* skv; const void* dstate; long long variant;
-                    const void* rtab; long long aux; };
+  // What a captured decode loop depends on (zeroed as a whole, then filled; compared with memcmp).  B rows (beam: N * beam)
+  // over T memory tokens, `steps` steps per graph, the engine buffers it touches, and per loop kind:
+  //   greedy (one step replayed under the host's poll, or the whole loop): dev_exit, rows_per_batch
+  //   device-side beam loop: N, beam
+  // ragged (greedy group or beam search): T and rows_per_batch are 0 and the layout is NOT part of the key -- the loop reads
+  // lengths and offsets from the tables at rtab (rg_cap rows each; 0 for the beam tables) and the bf16 planes plane_elems
+  // floats behind the slot's start (a function of the slot's capacity)
+  enum LoopKind : int { LOOP_GREEDY_STEP = 0, LOOP_GREEDY_WHOLE = 1, LOOP_BEAM_DEV = 2 };
+  struct GraphKey {
+    int B, T, steps;
+    const void *tok, *logits, *ckv, *dws, *skv, *dstate, *rtab;
+    int loop, dev_exit, rows_per_batch, ragged, rg_cap, N, beam;
+    long long plane_elems;
+  };
   struct GraphEnt { GraphKey key; hipGraphExec_t exec; };
   std::vector<GraphEnt> graphs;  // small cache of captured decode steps (most recent last)
   // kernel timing log (d2t_profile_*)

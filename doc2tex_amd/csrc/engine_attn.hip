@@ -1,6 +1,7 @@
 // libd2t engine, LSTM-attention heads: the greedy decode (synchronous and pipelined) and the beam search of the C-ABI.
 // Host code only: the kernels are recurrent.hip's.
 #include "engine_impl.h"
+#include "carve.h"
 
 extern "C" {
 
@@ -18,6 +19,23 @@ AttnDecP attn_dec_params(const d2t_ctx* c, const float* memory, int T, const flo
   p.wih_t = c->attn.wih_t; p.bih = c->attn.bih; p.wic_t = c->attn.wic_t; p.bic = c->attn.bic;
   p.emb = c->attn.emb; p.tokgate = c->attn.tokgate;
   p.V = g.vocab; p.H = g.attn_hidden; p.E = g.attn_hidden; p.coverage = g.attn_coverage; p.end_token = 1;  // attn_converter.py:8
+  return p;
+}
+// The step pack of the beam search (one host -> device copy per step), its size padded to 16 bytes:
+// tok i64 [cap] | scores [cap] | map [cap] | idx_h [cap] | idx_m [cap] | seg [N][3].  One layout for the device buffer and
+// its pinned host mirror.
+struct AttnBeamPack { char* base; size_t bytes; int64_t* tok; float* scores; int *map, *idx_h, *idx_m, *seg; };
+static AttnBeamPack attn_beam_pack(Carver& cv, int N, int cap) {
+  AttnBeamPack p;
+  cv.align(8);
+  const size_t at0 = cv.total();
+  p.base = cv.here();
+  p.tok = cv.take<int64_t>(cap);
+  p.scores = cv.take<float>(cap);
+  p.map = cv.take<int>(cap); p.idx_h = cv.take<int>(cap); p.idx_m = cv.take<int>(cap);
+  p.seg = cv.take<int>(3 * (size_t)N);
+  p.bytes = (cv.total() - at0 + 15) & ~(size_t)15;
+  cv.at = at0 + p.bytes;
   return p;
 }
 // What every greedy call of the LSTM-attention heads refuses, before anything is enqueued.
@@ -170,40 +188,39 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
   // workspace: logits [cap][V] | topv [cap] | topi [cap] (one device -> host copy per step) | h_in c_in h_out c_out [cap][H]
   //            | mem_in mem_out [cap][Tk] | end_step [cap] | dummy tokens i64 [cap] | step pack (one host -> device copy per
   //            step): tok i64 [cap] | scores [cap] | map [cap] | idx_h [cap] | idx_m [cap] | seg [N][3]
-  const size_t nf = (size_t)cap * V + 2 * (size_t)cap + 4 * (size_t)cap * Hh + 2 * (size_t)cap * Tk + cap;
-  const size_t pack_off = ((nf * 4 + 15) & ~(size_t)15) + (size_t)cap * 8;
-  const size_t pack_bytes = ((size_t)cap * (8 + 4 * 4) + (size_t)N * 12 + 15) & ~(size_t)15;
-  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, pack_off + pack_bytes + 64))) return rc;
-  float* d_logits = c->beam_ws;
-  float* d_topv = d_logits + (size_t)cap * V;
-  int* d_topi = reinterpret_cast<int*>(d_topv + cap);
-  float* st[6];
-  st[0] = reinterpret_cast<float*>(d_topi + cap);  // h_in
-  st[1] = st[0] + (size_t)cap * Hh;               // c_in
-  st[2] = st[1] + (size_t)cap * Hh;               // h_out
-  st[3] = st[2] + (size_t)cap * Hh;               // c_out
-  st[4] = st[3] + (size_t)cap * Hh;               // mem_in
-  st[5] = st[4] + (size_t)cap * Tk;               // mem_out
-  int* d_end = reinterpret_cast<int*>(st[5] + (size_t)cap * Tk);
-  char* d_pack = reinterpret_cast<char*>(c->beam_ws) + pack_off;
-  int64_t* d_dummy = reinterpret_cast<int64_t*>(d_pack) - cap;
-  int64_t* d_tok = reinterpret_cast<int64_t*>(d_pack);
-  float* d_scores = reinterpret_cast<float*>(d_tok + cap);
-  int* d_map = reinterpret_cast<int*>(d_scores + cap);
-  int* d_idxh = d_map + cap;
-  int* d_idxm = d_idxh + cap;
-  int* d_seg = d_idxm + cap;
+  float *d_logits, *d_topv, *st[6];  // st: h_in c_in h_out c_out mem_in mem_out
+  int *d_topi, *d_end;
+  int64_t* d_dummy;
+  AttnBeamPack dp, hpk;  // the step pack on the device and in the pinned mirror
+  auto ws_carve = [&](Carver cv) {
+    d_logits = cv.take<float>((size_t)cap * V);
+    d_topv = cv.take<float>(cap);
+    d_topi = cv.take<int>(cap);
+    for (int i = 0; i < 6; ++i) st[i] = cv.take<float>((size_t)cap * (i < 4 ? Hh : Tk));
+    d_end = cv.take<int>(cap);
+    d_dummy = cv.take<int64_t>(cap, 16);
+    dp = attn_beam_pack(cv, N, cap);
+    return cv.total() + 64;
+  };
+  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, ws_carve(Carver())))) return rc;
+  ws_carve(Carver(c->beam_ws));
   // pinned host mirror: the step pack | topv [cap] | topi [cap]
-  if ((rc = ensure_host_beam(c, pack_bytes + 2 * (size_t)cap * 4))) return rc;
-  char* hp = c->h_beam;
-  int64_t* h_tok = reinterpret_cast<int64_t*>(hp);
-  float* h_scores = reinterpret_cast<float*>(h_tok + cap);
-  int* h_map = reinterpret_cast<int*>(h_scores + cap);
-  int* h_idxh = h_map + cap;
-  int* h_idxm = h_idxh + cap;
-  int* h_seg = h_idxm + cap;
-  float* h_topv = reinterpret_cast<float*>(hp + pack_bytes);
-  int* h_topi = reinterpret_cast<int*>(h_topv + cap);
+  float* h_topv;
+  int* h_topi;
+  auto mirror_carve = [&](Carver cv) {
+    hpk = attn_beam_pack(cv, N, cap);
+    h_topv = cv.take<float>(cap);
+    h_topi = cv.take<int>(cap);
+    return cv.total();
+  };
+  if ((rc = ensure_host_beam(c, mirror_carve(Carver())))) return rc;
+  mirror_carve(Carver(c->h_beam));
+  char *const d_pack = dp.base, *const hp = hpk.base;
+  const size_t pack_bytes = dp.bytes;
+  int64_t *const d_tok = dp.tok, *const h_tok = hpk.tok;
+  float *const d_scores = dp.scores, *const h_scores = hpk.scores;
+  int *const d_map = dp.map, *const d_idxh = dp.idx_h, *const d_idxm = dp.idx_m, *const d_seg = dp.seg;
+  int *const h_map = hpk.map, *const h_idxh = hpk.idx_h, *const h_idxm = hpk.idx_m, *const h_seg = hpk.seg;
   HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, N * T, ACT_NONE));
   AttnDecP p = attn_dec_params(c, memory, T, kp);
   p.probs = d_logits; p.tokens = d_dummy; p.end_step = d_end;
