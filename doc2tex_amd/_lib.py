@@ -104,6 +104,9 @@ SIGNATURES = {
     "d2t_decode_attn_beam_batch": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_decode_attn_beam_batch_alpha": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P,
                                                _P]),
+    "d2t_decode_attn_beam_batch_ragged": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(C.c_int64), C.POINTER(_I),
+                                               C.POINTER(C.c_float), _P, _P]),
+    "d2t_decode_attn_supports_ragged_beam": (_I, [_P]),
     "d2t_decode_attn_beam": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_set_conv_precision": (_I, [_P, _I]),
     "d2t_set_mixed_units": (_I, [_P, _I]),
@@ -165,6 +168,7 @@ SIGNATURES = {
     "d2t_op_bilstm_hprev": (_I, [_P] * 3 + [_I] * 3 + [_P]),
     "d2t_op_bilstm_bwd": (_I, [_P] * 6 + [_I] * 3 + [_P]),
     "d2t_op_attn_decode": (_I, [C.POINTER(D2TOpAttnDecodeArgs), _P]),
+    "d2t_op_attn_decode_ragged": (_I, [C.POINTER(D2TOpAttnDecodeArgs), _P, _P, _I, _P]),
     "d2t_op_attn_decode_finalize": (_I, [_P, _P] + [_I] * 4 + [_P] * 4),
     "d2t_op_attn_alpha_gather": (_I, [_P] * 4 + [_I] * 4 + [_P]),
     "d2t_op_attn_lstm_bwd": (_I, [C.POINTER(D2TOpAttnLstmBwdArgs), _P]),

@@ -273,20 +273,34 @@ class Model(nn.Module):
     def _beam_search_mixed(self, inputs, beam, return_attn=False):
         """beam_search_batch for a list of image tensors [n_i, C, H_i, W_i] (crops of different sizes, e.g. the buckets of
         Preprocessor.batch): every tensor is encoded on its own, the memories are packed and ONE search advances the
-        hypotheses of all samples (Engine.decode_beam_batch_ragged).  Returns the flat list of results in input order, each
-        identical to the single-tensor call on its tensor.  Where the engine has no ragged beam search (d_model 512,
-        beam_shared_tile, the LSTM-attention heads) the tensors are searched one after the other by that call."""
+        hypotheses of all samples (TFM head: Engine.decode_beam_batch_ragged; Attn / Attnv2: Engine.decode_attn_beam_batch_ragged,
+        whose host-side loop then pays its batch_max_length + 1 round trips once instead of once per tensor).  Returns the flat
+        list of results in input order, each identical to the single-tensor call on its tensor; with return_attn (LSTM-attention
+        heads) every sample's map is cut to its own [len, Tk_i].  Where the engine has no ragged beam search (d_model 512,
+        beam_shared_tile, the 'loc_aware' cell) the tensors are searched one after the other by that call -- and so is a
+        return_attn list whose alignment history, at the longest memory's stride, would exceed _lib.ATTN_MAP_BUDGET bytes."""
         if len(inputs) == 0:
             return []
         eng = self.engine()
-        if self.stages["Pred"] != "TFM" or return_attn or not eng.supports_ragged_beam():
-            out = []
-            for x in inputs:
-                out += self.beam_search_batch(x, beam, return_attn)
-            return out
+        tfm = self.stages["Pred"] == "TFM"
+        if (return_attn and tfm) or not (eng.supports_ragged_beam() if tfm else eng.supports_ragged_attn_beam()):
+            return self._beam_search_each(inputs, beam, return_attn)
         from .engine import pack_memories
         packed, lengths = pack_memories([self.forward_encoder(x)[0] for x in inputs])
-        return eng.decode_beam_batch_ragged(packed, lengths, beam)
+        if tfm:
+            return eng.decode_beam_batch_ragged(packed, lengths, beam)
+        if return_attn:
+            from . import _lib
+            if len(lengths) * eng.attn_map_bytes(max(lengths), beam) > _lib.ATTN_MAP_BUDGET:
+                del packed
+                return self._beam_search_each(inputs, beam, return_attn)  # (which splits each tensor's batch as it needs)
+        return eng.decode_attn_beam_batch_ragged(packed, lengths, beam, return_alpha=return_attn)
+
+    def _beam_search_each(self, inputs, beam, return_attn):
+        out = []
+        for x in inputs:
+            out += self.beam_search_batch(x, beam, return_attn)
+        return out
 
     def _group_decode(self, eng, memory, start, is_test=False):
         """pipelined + decode_group > 1: collect the encoder memories of consecutive calls, launch one decode per group.

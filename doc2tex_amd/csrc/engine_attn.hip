@@ -103,56 +103,10 @@ int attn_greedy_impl(d2t_ctx* c, const float* memory, int B, int T, int is_test,
   if (steps_out) *steps_out = steps;
   return D2T_OK;
 }
-}  // namespace
 
-int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
-                           float* probs, int32_t* steps_out, d2t_stream stream) {
-  return d2t_decode_attn_greedy_alpha(c, memory, B, T, is_test, tokens, probs, nullptr, steps_out, stream);
-}
-
-int d2t_decode_attn_greedy_alpha(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
-                                 float* probs, float* alpha, int32_t* steps_out, d2t_stream stream) {
-  DevGuard dg_(c);
-  if (!steps_out) return fail(c, D2T_EINVAL, "bad argument");
-  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
-  return attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, steps_out, (hipStream_t)stream, false);
-}
-
-int d2t_decode_attn_greedy_submit(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
-                                  float* probs, float* alpha, d2t_stream stream, int64_t* ticket_out) {
-  DevGuard dg_(c);
-  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
-  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
-  if (int rc = check_dev_ptr(c, probs, "probs")) return rc;
-  const int rc = attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, nullptr, (hipStream_t)stream, true);
-  if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
-  return rc;
-}
-
-int d2t_decode_attn_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out, int32_t* len_out,
-                         float* score_out, d2t_stream stream) {
-  DevGuard dg_(c);
-  // Attention.forward_beam (prediction_head/seq2seq.py:83-222) / AttentionV2.forward_beam (seq2seq_v2.py:12-174) for
-  // one sample: the batched search with N = 1.
-  return d2t_decode_attn_beam_batch(c, memory, 1, T, beam_size, seq_out, len_out, score_out, stream);
-}
-
-int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
-                               int32_t* len_out, float* score_out, d2t_stream stream) {
-  return d2t_decode_attn_beam_batch_alpha(c, memory, N, T, beam_size, seq_out, len_out, score_out, nullptr, stream);
-}
-
-int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
-                                     int32_t* len_out, float* score_out, float* alpha_out, d2t_stream stream) {
-  DevGuard dg_(c);
-  // Attention / AttentionV2.forward_beam for N samples in one step loop: rows = live hypotheses of all samples, each
-  // attending over its own sample's keys (row map).  The attention cell + LSTMCell + generator of every live hypothesis run
-  // as ONE launch per step (the greedy kernel in step mode, one block per hypothesis), log_softmax + top-k per sample
-  // segment on the device, the reference's bookkeeping per sample on the host -- including its quirks: step 0 ranks row 0
-  // only; the LSTM state follows prev_word_inds[incomplete] but the coverage memory only `incomplete`; if the last executed
-  // step completed nothing the first live sequence is returned; otherwise the best score/len sequence with the MAXIMUM raw
-  // score.
-  if (!c || !memory || !seq_out || !len_out || !score_out || N < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
+constexpr int ATTN_BEAM_MAX_N = 1024;  // samples of one ragged search (as the TFM head's ragged search)
+// What every beam search of the LSTM-attention heads refuses, behind the entry's own argument check.
+int attn_beam_check(d2t_ctx* c, int beam_size) {
   if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
   const d2t_config& g = c->cfg;
   if (g.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "context was not created with the Attn decoder");
@@ -160,11 +114,32 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
     return fail(c, D2T_ESTATE, "LSTM beam search is implemented for the coverage and Bahdanau cells (the reference's 'loc_aware' beam "
                 "hands the previous beam's un-reordered alignment to the next step, seq2seq.py:207)");
   if (beam_size < 1 || beam_size > 16) return fail(c, D2T_EINVAL, "beam_size must be in [1,16]");
+  return D2T_OK;
+}
+
+// Attention / AttentionV2.forward_beam for N samples in one step loop: rows = live hypotheses of all samples, each
+// attending over its own sample's keys (row map).  The attention cell + LSTMCell + generator of every live hypothesis run
+// as ONE launch per step (the greedy kernel in step mode, one block per hypothesis), log_softmax + top-k per sample
+// segment on the device, the reference's bookkeeping per sample on the host -- including its quirks: step 0 ranks row 0
+// only; the LSTM state follows prev_word_inds[incomplete] but the coverage memory only `incomplete`; if the last executed
+// step completed nothing the first live sequence is returned; otherwise the best score/len sequence with the MAXIMUM raw
+// score.
+// Uniform (Ts == nullptr): memory [N][T][H].  Ragged (Ts = host [N], T unused): memory is packed, sample i's Ts[i] rows
+// behind sample i-1's; ONE key projection over all packed rows (linear_any computes a row from that row alone, so each
+// sample's projection is its uniform call's bit for bit), the per-sample tables [row0 | T] uploaded once in front of the
+// loop, and the coverage memory, the alignment history and alpha_out [N][S][st_ld] on the row stride st_ld = the largest Tk.
+// The bookkeeping below does not know which of the two it serves.  The caller has checked the lengths.
+int attn_beam_impl(d2t_ctx* c, const float* memory, int N, int T, const int32_t* Ts, int beam_size, int64_t* seq_out,
+                   int32_t* len_out, float* score_out, float* alpha_out, hipStream_t s) {
+  const d2t_config& g = c->cfg;
   const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab, cap = N * beam_size;
   const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
-  const int Tk = T - key_off;
-  if (Tk < 1 || Tk > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
-  hipStream_t s = (hipStream_t)stream;
+  size_t mem_rows = (size_t)N * T;
+  if (Ts) {
+    mem_rows = 0; T = 0;
+    for (int i = 0; i < N; ++i) { mem_rows += (size_t)Ts[i]; T = std::max(T, (int)Ts[i]); }
+  }
+  const int Tk = T - key_off;  // ragged: the largest, = st_ld
   int rc;
   // alignment maps (viz_attn): every step's launch writes its rows' alignments into its own slice of a history
   // [S][cap][Tk], kept apart from the workspace below; the chosen paths [N][S] and lengths [N] follow it
@@ -183,13 +158,14 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
   // asynchronous greedy decode (d2t_decode_attn_greedy_submit), which may still read it
   d2t_ctx::Chain& ch = c->chains[0];
   if (c->ev_done_valid[0]) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done[0], 0));
-  if ((rc = ensure(c, &ch.dws, &ch.dws_cap, ((size_t)N * T * Hh + 16) * 4))) return rc;
+  if ((rc = ensure(c, &ch.dws, &ch.dws_cap, (mem_rows * Hh + 16) * 4))) return rc;
   float* kp = ch.dws;
   // workspace: logits [cap][V] | topv [cap] | topi [cap] (one device -> host copy per step) | h_in c_in h_out c_out [cap][H]
   //            | mem_in mem_out [cap][Tk] | end_step [cap] | dummy tokens i64 [cap] | step pack (one host -> device copy per
   //            step): tok i64 [cap] | scores [cap] | map [cap] | idx_h [cap] | idx_m [cap] | seg [N][3]
+  //            | ragged: the per-sample tables row0 [N] | T [N]
   float *d_logits, *d_topv, *st[6];  // st: h_in c_in h_out c_out mem_in mem_out
-  int *d_topi, *d_end;
+  int *d_topi, *d_end, *d_tab;
   int64_t* d_dummy;
   AttnBeamPack dp, hpk;  // the step pack on the device and in the pinned mirror
   auto ws_carve = [&](Carver cv) {
@@ -200,17 +176,19 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
     d_end = cv.take<int>(cap);
     d_dummy = cv.take<int64_t>(cap, 16);
     dp = attn_beam_pack(cv, N, cap);
+    d_tab = cv.take<int>(Ts ? 2 * (size_t)N : 0);
     return cv.total() + 64;
   };
   if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, ws_carve(Carver())))) return rc;
   ws_carve(Carver(c->beam_ws));
-  // pinned host mirror: the step pack | topv [cap] | topi [cap]
+  // pinned host mirror: the step pack | topv [cap] | topi [cap] | ragged: the tables
   float* h_topv;
-  int* h_topi;
+  int *h_topi, *h_tab;
   auto mirror_carve = [&](Carver cv) {
     hpk = attn_beam_pack(cv, N, cap);
     h_topv = cv.take<float>(cap);
     h_topi = cv.take<int>(cap);
+    h_tab = cv.take<int>(Ts ? 2 * (size_t)N : 0);
     return cv.total();
   };
   if ((rc = ensure_host_beam(c, mirror_carve(Carver())))) return rc;
@@ -221,7 +199,7 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
   float *const d_scores = dp.scores, *const h_scores = hpk.scores;
   int *const d_map = dp.map, *const d_idxh = dp.idx_h, *const d_idxm = dp.idx_m, *const d_seg = dp.seg;
   int *const h_map = hpk.map, *const h_idxh = hpk.idx_h, *const h_idxm = hpk.idx_m, *const h_seg = hpk.seg;
-  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, N * T, ACT_NONE));
+  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, (int)mem_rows, ACT_NONE));
   AttnDecP p = attn_dec_params(c, memory, T, kp);
   p.probs = d_logits; p.tokens = d_dummy; p.end_step = d_end;
   p.S = 1; p.coverage = 1;
@@ -229,6 +207,11 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
   p.st_h_in = st[0]; p.st_c_in = st[1]; p.st_mem_in = st[4];
   p.st_h_out = st[2]; p.st_c_out = st[3]; p.st_mem_out = st[5];
   p.tok_in = d_tok; p.row_sample = d_map;
+  if (Ts) {  // (the previous search has synchronised: the mirror is idle)
+    d2t_ragged_beam_tables(N, Ts, h_tab, h_tab + N);
+    HIPCHK(c, hipMemcpyAsync(d_tab, h_tab, 2 * (size_t)N * 4, hipMemcpyHostToDevice, s));
+    p.smp_row0 = d_tab; p.smp_T = d_tab + N; p.st_ld = Tk;
+  }
 
   struct Smp {
     std::vector<std::vector<int64_t>> seqs, complete;
@@ -348,6 +331,79 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
     HIPCHK(c, hipStreamSynchronize(s));  // h_path is pageable and local
   }
   return D2T_OK;
+}
+}  // namespace
+
+int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                           float* probs, int32_t* steps_out, d2t_stream stream) {
+  return d2t_decode_attn_greedy_alpha(c, memory, B, T, is_test, tokens, probs, nullptr, steps_out, stream);
+}
+
+int d2t_decode_attn_greedy_alpha(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                                 float* probs, float* alpha, int32_t* steps_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  if (!steps_out) return fail(c, D2T_EINVAL, "bad argument");
+  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
+  return attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, steps_out, (hipStream_t)stream, false);
+}
+
+int d2t_decode_attn_greedy_submit(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
+                                  float* probs, float* alpha, d2t_stream stream, int64_t* ticket_out) {
+  DevGuard dg_(c);
+  if (int rc = attn_greedy_check(c, memory, B, T, tokens, probs)) return rc;
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, probs, "probs")) return rc;
+  const int rc = attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, nullptr, (hipStream_t)stream, true);
+  if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
+  return rc;
+}
+
+int d2t_decode_attn_beam(d2t_ctx* c, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out, int32_t* len_out,
+                         float* score_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  // Attention.forward_beam (prediction_head/seq2seq.py:83-222) / AttentionV2.forward_beam (seq2seq_v2.py:12-174) for
+  // one sample: the batched search with N = 1.
+  return d2t_decode_attn_beam_batch(c, memory, 1, T, beam_size, seq_out, len_out, score_out, stream);
+}
+
+int d2t_decode_attn_beam_batch(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
+                               int32_t* len_out, float* score_out, d2t_stream stream) {
+  return d2t_decode_attn_beam_batch_alpha(c, memory, N, T, beam_size, seq_out, len_out, score_out, nullptr, stream);
+}
+
+int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N, int32_t T, int32_t beam_size, int64_t* seq_out,
+                                     int32_t* len_out, float* score_out, float* alpha_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  if (!c || !memory || !seq_out || !len_out || !score_out || N < 1 || T < 1) return fail(c, D2T_EINVAL, "bad argument");
+  if (int rc = attn_beam_check(c, beam_size)) return rc;
+  const int Tk = T - (c->cfg.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0);
+  if (Tk < 1 || Tk > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
+  return attn_beam_impl(c, memory, N, T, nullptr, beam_size, seq_out, len_out, score_out, alpha_out, (hipStream_t)stream);
+}
+
+// 1: d2t_decode_attn_beam_batch_ragged serves this context (an LSTM-attention head whose beam search the engine has: the
+// coverage and Bahdanau cells); 0: it refuses with D2T_ESTATE
+int32_t d2t_decode_attn_supports_ragged_beam(const d2t_ctx* c) {
+  return c && c->finalized && c->cfg.decoder == D2T_DEC_ATTN && (c->cfg.attn_coverage || c->cfg.attn_cell == D2T_ATTN_CELL_BAHDANAU) ? 1 : 0;
+}
+
+int d2t_decode_attn_beam_batch_ragged(d2t_ctx* c, const float* memory, int32_t N, const int32_t* T, int32_t beam_size,
+                                      int64_t* seq_out, int32_t* len_out, float* score_out, float* alpha_out, d2t_stream stream) {
+  DevGuard dg_(c);
+  // d2t_decode_attn_beam_batch[_alpha] for N samples whose memories have DIFFERENT lengths, packed in `memory`: one step
+  // loop, so the batch_max_length + 1 round trips are paid once for all sizes.  Everything is checked before anything is
+  // enqueued; the context stays usable after a refusal.
+  if (!c || !memory || !T || !seq_out || !len_out || !score_out) return fail(c, D2T_EINVAL, "bad argument");
+  if (int rc = attn_beam_check(c, beam_size)) return rc;
+  if (N < 1 || N > ATTN_BEAM_MAX_N)
+    return fail(c, D2T_EINVAL, "ragged beam search takes 1 to %d samples per call, got %d", ATTN_BEAM_MAX_N, N);
+  const int key_off = c->cfg.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  for (int i = 0; i < N; ++i)
+    if (T[i] - key_off < 1 || T[i] - key_off > memory_cap(c))
+      return fail(c, D2T_EINVAL, "sample %d has memory length %d, supported are %d to %d", i, T[i], 1 + key_off, memory_cap(c) + key_off);
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, alpha_out, "alpha")) return rc;
+  return attn_beam_impl(c, memory, N, 0, T, beam_size, seq_out, len_out, score_out, alpha_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -523,6 +523,8 @@ int tokens_in_range(hipStream_t s, const int64_t* dev, size_t n, int V) {
   for (int64_t v : h) if (v < 0 || v >= V) return D2T_EINVAL;
   return D2T_OK;
 }
+int op_attn_decode(const d2t_op_attn_decode_args* a, bool ragged, const int32_t* smp_row0, const int32_t* smp_T, int st_ld,
+                   d2t_stream stream);
 }  // namespace
 
 int d2t_op_bilstm(const float* g, const float* whh_t, float* out, float* sv_gates, float* sv_c, int32_t B, int32_t T,
@@ -540,6 +542,19 @@ int d2t_op_bilstm_hprev(const float* out, float* hprev_fwd, float* hprev_rev, in
 }
 
 int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream) {
+  return op_attn_decode(a, false, nullptr, nullptr, 0, stream);
+}
+
+int d2t_op_attn_decode_ragged(const d2t_op_attn_decode_args* a, const int32_t* smp_row0, const int32_t* smp_T, int32_t st_ld,
+                              d2t_stream stream) {
+  return op_attn_decode(a, true, smp_row0, smp_T, st_ld, stream);
+}
+
+namespace {
+// d2t_op_attn_decode, and with `ragged` its ragged step: mem / kp packed, the per-sample device tables smp_row0 / smp_T
+// [a->samples] read back and checked against a->T (the largest length), the packed row total (the sum of the lengths) and st_ld
+int op_attn_decode(const d2t_op_attn_decode_args* a, bool ragged, const int32_t* smp_row0, const int32_t* smp_T, int st_ld,
+                   d2t_stream stream) {
   if (!a || !a->mem || !a->kp || !a->wq_t || !a->bq || !a->wloc || !a->bloc || !a->wscore || !a->wx_t || !a->bx || !a->wg_t ||
       !a->bg || !a->probs || !a->tokens || !a->end_step)
     return D2T_EINVAL;
@@ -570,6 +585,21 @@ int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream) {
   }
   if (a->teacher)
     if (int rc = tokens_in_range(s, a->teacher, (size_t)a->B * a->S, a->V)) return rc;
+  if (ragged) {
+    if (!a->step_mode || !smp_row0 || !smp_T || st_ld < 1 || st_ld > 4096) return D2T_EINVAL;
+    std::vector<int> r0, len;
+    if (!fetch_ints(s, smp_row0, a->samples, &r0) || !fetch_ints(s, smp_T, a->samples, &len)) return D2T_EHIP;
+    long long total = 0;
+    int longest = 0;
+    for (int v : len) {
+      if (v - a->key_off < 1 || v - a->key_off > 4096 || v - a->key_off > st_ld) return D2T_EINVAL;
+      total += v;
+      longest = std::max(longest, v);
+    }
+    if (longest != a->T) return D2T_EINVAL;
+    for (int i = 0; i < a->samples; ++i)
+      if (r0[i] < 0 || (long long)r0[i] + len[i] > total) return D2T_EINVAL;
+  }
   AttnDecP p{};
   p.mem = a->mem; p.T = a->T; p.D = 256; p.key_off = a->key_off; p.init_mode = a->init_mode;
   p.kp = a->kp; p.wq_t = a->wq_t; p.bq = a->bq; p.wloc = a->wloc; p.bloc = a->bloc; p.taps = a->taps;
@@ -585,6 +615,7 @@ int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream) {
   p.sv_tok = a->sv_tok; p.sv_hprev = a->sv_hprev; p.sv_cprev = a->sv_cprev; p.sv_hafter = a->sv_hafter; p.sv_cafter = a->sv_cafter;
   p.sv_gates = a->sv_gates; p.sv_alpha = a->sv_alpha; p.sv_hq = a->sv_hq; p.sv_x = a->sv_x;
   p.exit_state = reinterpret_cast<unsigned long long*>(a->exit_state);
+  if (ragged) { p.smp_row0 = smp_row0; p.smp_T = smp_T; p.st_ld = st_ld; }
   hipError_t e = hipMemsetAsync(a->end_step, 0xFF, (size_t)a->B * 4, s);  // -1 = never emitted the end token
   if (e == hipSuccess && a->exit_state) e = hipMemsetAsync(a->exit_state, 0, 8, s);
   if (e == hipSuccess) e = launch_attn_decode(p, s);
@@ -593,6 +624,7 @@ int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream) {
                                     a->sv_alpha, s);
   return op_status(e);
 }
+}  // namespace
 
 int d2t_op_attn_decode_finalize(const uint64_t* exit_state, int32_t* steps_dev, int32_t B, int32_t S, int32_t V, int32_t Tk,
                                 int64_t* tokens, float* probs, float* alpha, d2t_stream stream) {

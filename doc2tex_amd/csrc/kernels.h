@@ -188,6 +188,15 @@ struct AttnDecP {
   // compare-and-swap when a row ends and read with agent-scope loads between steps.  A block stops once all B rows have
   // ended and its next step lies beyond the largest end step; it never waits for another block.
   unsigned long long* exit_state;
+  // Ragged step mode (beam search over samples of DIFFERENT memory lengths; all three set, or none: the ragged build of the
+  // kernel).  mem and kp are then ONE packed [sum T_i][256] buffer each; row b's sample i = row_sample[b] owns the smp_T[i]
+  // rows from row smp_row0[i] on, attends over Tk_i = smp_T[i] - key_off keys, and takes its init_mode 1 mean over its own
+  // smp_T[i] rows.  st_mem_in / st_mem_out [B][st_ld] and sv_alpha [B][S][st_ld] have the row stride st_ld >= max Tk_i;
+  // a row's sv_alpha is written as zeros on [Tk_i, st_ld), its st_mem_out left alone there.  T = the largest smp_T[i].
+  // (Behind every older field: the uniform builds read their arguments at the offsets they always had.)
+  const int* smp_row0;  // device [samples]
+  const int* smp_T;     // device [samples]
+  int st_ld;
 };
 // After launch_attn_decode with an exit_state, on the same stream: steps = largest end step + 1 if all B rows ended, else
 // S; written to *steps_dev, and tokens [B][S], probs [B][S][V], alpha [B][S][Tk] (optional) zeroed for the steps

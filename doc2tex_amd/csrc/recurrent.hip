@@ -128,7 +128,10 @@ __device__ __forceinline__ void attn_end_step(const AttnDecP p, int b, int step,
   if constexpr (EXIT) *stop_s = attn_exit_reached(seen, p.B, step);
 }
 
-template <bool WIDE, bool EXIT>
+// RAGGED (step mode only): the row's sample has its own memory length and its own place in ONE packed memory
+// (AttnDecP::smp_row0 / smp_T), and the state / history rows have the stride st_ld.  The length is uniform within a block,
+// so every barrier is still reached by all of its threads; no shared array is added.
+template <bool WIDE, bool EXIT, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   constexpr int H = 256;
   __shared__ float x_s[3 * H];  // [context | embedding | h]  = LSTMCell input
@@ -141,11 +144,16 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   [[maybe_unused]] __shared__ int stop_s;  // EXIT: thread 0's decision, read by the block behind the step's last barrier
   __shared__ __attribute__((aligned(16))) float wloc_s[11 * H];  // folded location filter, [tap][n]
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int Tk = p.T - p.key_off;
   // beam search: every hypothesis attends over its sample's keys (sample 0 unless a row map is given)
   const int bm = p.step_mode ? (p.row_sample ? p.row_sample[b] : 0) : b;
-  const float* keys = p.mem + ((size_t)bm * p.T + p.key_off) * p.D;
-  const float* kp = p.kp + ((size_t)bm * p.T + p.key_off) * H;
+  // T: the sample's memory length, mrow: its first memory row, ld: the stride of the state and history rows.  RAGGED: Tk is
+  // held to st_ld <= AD_MAXT here as well, whatever the tables say (the hosts refuse such tables before the launch)
+  const int T = RAGGED ? p.smp_T[bm] : p.T;
+  const int Tk = RAGGED ? min(T - p.key_off, p.st_ld) : T - p.key_off;
+  const int ld = RAGGED ? p.st_ld : Tk;
+  const size_t mrow = RAGGED ? (size_t)p.smp_row0[bm] : (size_t)bm * T;
+  const float* keys = p.mem + (mrow + p.key_off) * p.D;
+  const float* kp = p.kp + (mrow + p.key_off) * H;
   float* ctx_s = x_s;
   float* emb_s = x_s + H;
   float* h_s = x_s + 2 * H;
@@ -155,10 +163,10 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   if (tid < H) {
     float init = 0.f;
     if (p.init_mode == 1) {
-      for (int t = 0; t < p.T; ++t) init += p.mem[((size_t)bm * p.T + t) * p.D + tid];
-      init /= (float)p.T;
+      for (int t = 0; t < T; ++t) init += p.mem[(mrow + t) * p.D + tid];
+      init /= (float)T;
     } else if (p.init_mode == 2) {
-      init = p.mem[(size_t)bm * p.T * p.D + tid];
+      init = p.mem[mrow * p.D + tid];
     }
     hq_s[tid] = init;  // scratch
   }
@@ -186,7 +194,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   __syncthreads();
   if (p.step_mode && !p.first) {  // resume a hypothesis from its stored state
     if (tid < H) { h_s[tid] = p.st_h_in[(size_t)b * H + tid]; c_s[tid] = p.st_c_in[(size_t)b * H + tid]; }
-    for (int t = tid; t < Tk; t += 1024) mem_s[t] = p.st_mem_in[(size_t)b * Tk + t];
+    for (int t = tid; t < Tk; t += 1024) mem_s[t] = p.st_mem_in[(size_t)b * ld + t];
     if (tid == 0) tok_s = (int)p.tok_in[b];
     __syncthreads();
   }
@@ -246,9 +254,12 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
       for (int t = tid; t < Tk; t += 1024) {
         const float a = alpha_s[t] * inv;
         alpha_s[t] = a;
-        if (p.sv_alpha) p.sv_alpha[((size_t)b * p.S + step) * Tk + t] = a;
+        if (p.sv_alpha) p.sv_alpha[((size_t)b * p.S + step) * ld + t] = a;
         mem_s[t] = p.coverage ? mem_s[t] + a : a;  // coverage: accumulated alignment (seq2seq.py:302-304)
       }
+      if constexpr (RAGGED)  // the history row beyond the sample's keys: zeros, so that a gathered map is defined there
+        if (p.sv_alpha)
+          for (int t = Tk + tid; t < ld; t += 1024) p.sv_alpha[((size_t)b * p.S + step) * ld + t] = 0.f;
     }
     __syncthreads();
     // (4) context = alpha^T keys : 4 key groups x 256 channels, reduced through LDS
@@ -320,7 +331,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   }
   if (p.step_mode) {
     if (tid < H) { p.st_h_out[(size_t)b * H + tid] = h_s[tid]; p.st_c_out[(size_t)b * H + tid] = c_s[tid]; }
-    for (int t = tid; t < Tk; t += 1024) p.st_mem_out[(size_t)b * Tk + t] = mem_s[t];
+    for (int t = tid; t < Tk; t += 1024) p.st_mem_out[(size_t)b * ld + t] = mem_s[t];
   }
 }
 
@@ -328,6 +339,15 @@ hipError_t launch_attn_decode(const AttnDecP& p, hipStream_t s) {
   if (p.H != 256 || p.D != 256 || p.E != 256 || p.V > D2T_ATTN_MAX_CLASSES || p.T - p.key_off > AD_MAXT ||
       p.taps > 11 || p.T - p.key_off < 1)
     return hipErrorInvalidValue;
+  // the ragged build: step mode only, both per-sample tables, and a stride the two LDS rows can hold
+  const bool ragged = p.smp_row0 || p.smp_T || p.st_ld;
+  if (ragged && (!p.step_mode || p.S != 1 || p.teacher || p.exit_state || !p.smp_row0 || !p.smp_T || p.st_ld < 1 || p.st_ld > AD_MAXT))
+    return hipErrorInvalidValue;
+  if (ragged) {
+    hipLaunchKernelGGL((p.V <= 1024 ? attn_decode_kernel<false, false, true> : attn_decode_kernel<true, false, true>), dim3(p.B),
+                       dim3(1024), 0, s, p);
+    return hipGetLastError();
+  }
   // EXIT builds (an exit_state is given: greedy is_test) carry the early exit across blocks; the others are the loop without
   // it, instruction for instruction (beam search's step mode, the training forward, greedy without is_test)
   if (p.exit_state && (p.step_mode || p.teacher)) return hipErrorInvalidValue;

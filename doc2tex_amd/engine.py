@@ -608,6 +608,36 @@ class Engine:
         return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i])), alpha[i, :n[i]])
                 for i in range(N)]
 
+    def decode_attn_beam_batch_ragged(self, packed, lengths, beam_size, return_alpha=False):
+        """decode_attn_beam_batch for samples whose memories have different lengths: packed [sum lengths, 256] holds sample
+        i's lengths[i] rows behind sample i-1's (pack_memories).  One shared step loop, so its batch_max_length + 1 host round
+        trips are paid once: [(LongTensor [1,len], score)] per sample, each equal to decode_attn_beam_batch on that sample
+        alone.  return_alpha: each entry also carries its alignment map cut to [len, Tk_i]; the call is refused when the
+        step history (at the longest sample's stride) exceeds _lib.ATTN_MAP_BUDGET bytes."""
+        packed = packed.float().contiguous()
+        lengths = [int(T) for T in lengths]
+        N, S = len(lengths), self.cfg.batch_max_length + 1
+        if packed.dim() != 2 or packed.shape[0] != sum(lengths):
+            raise ValueError(f"packed memory {tuple(packed.shape)} does not hold the {sum(lengths)} rows of `lengths`")
+        seq = (C.c_int64 * max(1, N * S))()
+        n = (C.c_int32 * max(1, N))()
+        score = (C.c_float * max(1, N))()
+        Ts = (C.c_int32 * max(1, N))(*lengths)
+        ld = self.attn_keys(max(lengths)) if lengths else 0
+        alpha = torch.empty((N, S, max(ld, 1)), dtype=torch.float32, device=packed.device) if return_alpha else None
+        self._check(self.lib.d2t_decode_attn_beam_batch_ragged(self.ctx, _lib.ptr(packed), N, Ts, int(beam_size), seq, n, score,
+                                                               _lib.ptr(alpha), _lib.stream_of(packed)),
+                    "decode_attn_beam_batch_ragged")
+        out = [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i]))) for i in range(N)]
+        if not return_alpha:
+            return out
+        return [r + (alpha[i, :n[i], :self.attn_keys(lengths[i])],) for i, r in enumerate(out)]
+
+    def supports_ragged_attn_beam(self):
+        """Whether decode_attn_beam_batch_ragged serves this context (an LSTM-attention head with the coverage or the
+        Bahdanau cell); the context itself answers, once the weights are finalized."""
+        return bool(self.lib.d2t_decode_attn_supports_ragged_beam(self.ctx))
+
     def attn_map_bytes(self, T, beam_size):
         """Bytes of alignment history one sample adds to a beam search with maps (d2t_decode_attn_beam_batch_alpha)."""
         return (self.cfg.batch_max_length + 1) * int(beam_size) * self.attn_keys(T) * 4

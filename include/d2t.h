@@ -309,6 +309,25 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* ctx, const float* memory, int32_t 
                                      int64_t* seq_out, int32_t* len_out, float* score_out, float* alpha_dev,
                                      d2t_stream stream);
 
+/* d2t_decode_attn_beam_batch[_alpha] for N samples whose memories have DIFFERENT lengths (crops of different sizes), in one
+ * step loop: memory_packed_dev [T[0] + .. + T[N-1]][256], sample i's rows behind sample i-1's; T: HOST array [N]; seq_out,
+ * len_out, score_out as d2t_decode_attn_beam_batch.  Every sample's sequence, length and score are those of its own
+ * d2t_decode_attn_beam_batch call, bit for bit; the loop's batch_max_length + 1 host round trips are paid once for all
+ * lengths.  The key projection runs once over the packed rows, the per-sample tables (first row, length) are uploaded once
+ * in front of the loop, and the step kernel's ragged build reads them through the row map.
+ * alpha_dev: NULL, or [N][S][max Tk] fp32 (device, 16-byte aligned; Tk = T[i], less one where the head drops the cls token
+ * from its keys): sample i's map as d2t_decode_attn_beam_batch_alpha returns it in columns [0, Tk_i), zeros behind.  The
+ * history is S * N * beam_size * max Tk floats and held to D2T_ATTN_MAP_BUDGET.
+ * Refused before anything is enqueued (D2T_EINVAL unless stated): N < 1 or N > 1024, a length with Tk < 1 or Tk > 4096,
+ * beam_size outside [1, 16], a history over the budget, a pointer of another device; a context without the Attn decoder
+ * (D2T_ESTATE); the 'loc_aware' cell (D2T_ESTATE, as the uniform call). */
+int d2t_decode_attn_beam_batch_ragged(d2t_ctx* ctx, const float* memory_packed_dev, int32_t N, const int32_t* T,
+                                      int32_t beam_size, int64_t* seq_out, int32_t* len_out, float* score_out, float* alpha_dev,
+                                      d2t_stream stream);
+/* 1 if d2t_decode_attn_beam_batch_ragged serves this context, 0 if it refuses with D2T_ESTATE.  Valid once the weights are
+ * finalized. */
+int32_t d2t_decode_attn_supports_ragged_beam(const d2t_ctx* ctx);
+
 /* Beam search for N samples at once (not in the reference, whose forward_beam is single-sample): the same results as
  * N calls of d2t_decode_beam, with the hypotheses of all samples advanced by one shared step loop.  memory [N][T][d];
  * seq_out (host) [N][max_seq_len + 1]; len_out, score_out (host) [N]. */
@@ -625,6 +644,15 @@ typedef struct d2t_op_attn_decode_args {
   int32_t B, T, S, V, taps, key_off, init_mode, coverage, end_token, step_mode, first, samples;
 } d2t_op_attn_decode_args;
 int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream);
+/* The ragged build of the step (step mode only; AttnDecP::smp_row0 / smp_T / st_ld): mem and kp are ONE packed
+ * [sum of lengths][256] buffer each, and row b's sample i = row_sample[b] (0 without a map) owns the smp_T[i] rows from row
+ * smp_row0[i] on.  smp_row0 / smp_T: DEVICE arrays [samples], read back and checked before the launch: 1 <= smp_T[i] -
+ * key_off <= st_ld, smp_row0[i] >= 0, smp_row0[i] + smp_T[i] <= the sum of the lengths; a->T is the largest length.
+ * st_mem_in / st_mem_out [B][st_ld] and sv_alpha [B][1][st_ld], 1 <= st_ld <= 4096: row b's first Tk_i elements are read /
+ * written, sv_alpha is zero on [Tk_i, st_ld), st_mem_out untouched there.  Everything else as d2t_op_attn_decode; a row's
+ * outputs equal d2t_op_attn_decode's on its sample's memory alone bit for bit. */
+int d2t_op_attn_decode_ragged(const d2t_op_attn_decode_args* a, const int32_t* smp_row0, const int32_t* smp_T, int32_t st_ld,
+                              d2t_stream stream);
 /* The finalize kernel alone on a caller-given exit word {rows ended : high 32 bits, largest end step : low 32 bits}:
  * *steps_dev = largest end step + 1 if all B rows ended and that is below S, else S; tokens [B][S], probs [B][S][V] and
  * alpha [B][S][Tk] (optional) zeroed for the steps [steps, S) of every row. */

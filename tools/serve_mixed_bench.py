@@ -13,6 +13,11 @@ set and consecutive forwards differ in row count and memory length.
               --mixed 1   the list form: the buckets are encoded one by one, their memories packed, ONE search per page set
                           (d2t_decode_beam_batch_ragged).
 
+  --head attnv2   the stack every shipped configuration of the reference serves: C4's encoder and geometry under the Attnv2
+                  coverage-LSTM head with the parameters of config/test.yaml:38-51.  Needs --beam K (the greedy decode groups
+                  are the TFM head's); --mixed 0 then pays the host-side step loop's batch_max_length + 1 round trips once per
+                  size bucket, --mixed 1 once per page set (d2t_decode_attn_beam_batch_ragged).
+
 Prints one JSON line: formulas/s end to end (uint8 pages -> LaTeX strings)."""
 import argparse
 import json
@@ -46,9 +51,16 @@ def main():
     ap.add_argument("--chains", type=int, default=3)
     ap.add_argument("--page-sets", type=int, default=4, help="distinct page sets cycled through")
     ap.add_argument("--beam", type=int, default=0, help="beam width; 0 = greedy decoding through the decode groups")
+    ap.add_argument("--head", default="tfm", choices=["tfm", "attnv2"], help="prediction head on C4's encoder")
     args = ap.parse_args()
+    if args.head == "attnv2" and not args.beam:
+        ap.error("--head attnv2 times the beam search: give --beam K")
     dev = torch.device("cuda", 0)
     cfg = synth.make_config("C4", device=str(dev))
+    if args.head == "attnv2":
+        cfg["Prediction"] = {"name": "Attnv2", "params": {
+            "seqmodel": "TFM", "input_size": 256, "hidden_size": 256, "kernel_size": 2, "kernel_dim": 128, "embed_target": True,
+            "enc_init": True, "attn_type": "coverage", "method": "concat", "teacher_forcing": 1.0, "droprate": 0.2}}
     model = Model(cfg)
     tmpl = {k: v for k, v in model.state_dict().items() if not k.endswith("image_positional_encoder.pe")}
     model.load_state_dict(synth.synth_state_dict(tmpl), strict=False)
@@ -59,8 +71,9 @@ def main():
     opt = {"imgH": None, "imgW": None, "max_dimension": cfg["max_dimension"], "min_dimension": [32, 32], "mean": 0.5,
            "std": 0.5, "rgb": False, "pad": False, "device": str(dev)}
     pre = Preprocessor(opt, "demo")
-    vocab = [SYMBOLS[i % len(SYMBOLS)] + ("" if i < len(SYMBOLS) else f"_{i}") for i in range(synth.VOCAB - 4)]
-    dec = LabelDecoder(vocab, head="TFM")
+    attn = args.head == "attnv2"
+    vocab = [SYMBOLS[i % len(SYMBOLS)] + ("" if i < len(SYMBOLS) else f"_{i}") for i in range(synth.VOCAB - (3 if attn else 4))]
+    dec = LabelDecoder(vocab, head="Attn" if attn else "TFM")
     rng = np.random.default_rng(3)
     n = args.per_size
 
@@ -75,7 +88,7 @@ def main():
     sets = [page_set(s) for s in range(args.page_sets)]
     go = torch.full((3 * n, 1), 1, dtype=torch.long, device=dev)
     side = torch.cuda.Stream(dev)
-    L = cfg["Prediction"]["params"]["max_seq_len"] + 1
+    L = (cfg["batch_max_length"] if attn else cfg["Prediction"]["params"]["max_seq_len"]) + 1
     ring = [torch.empty((3 * n, L), dtype=torch.int64).pin_memory() for _ in range(64)]
     state = {"done": 0, "t_post": 0.0, "seq": 0, "sample": ""}
     waiting, pending = [], []  # forwards whose decode may not be launched yet; copies in flight (pinned slot, rows, event)
@@ -123,7 +136,7 @@ def main():
                 else:
                     found = [r for x in buckets.values() for r in model.beam_search_batch(x, args.beam)]
             tokens = torch.zeros((len(found), L), dtype=torch.int64)  # PAD behind every hypothesis
-            for r, (seq, _) in enumerate(found):
+            for r, (seq, *_) in enumerate(found):
                 tokens[r, :seq.shape[1]] = seq[0]
             t = time.perf_counter()
             latex = dec.to_latex(tokens, "word", postprocess=True)
@@ -154,7 +167,7 @@ def main():
     assert state["done"] == 3 * n * args.steps, (state["done"], 3 * n * args.steps)
     print(json.dumps({"metric": "formulas/s end to end on mixed-size pages (uint8 pages -> LaTeX strings)",
                       "value": round(state["done"] / el, 1), "unit": "formulas/s", "mixed": args.mixed, "steps": args.steps,
-                      "per_size": n, "group": args.group, "beam": args.beam, "ms_per_page_set": round(el / args.steps * 1e3, 2),
+                      "per_size": n, "group": args.group, "beam": args.beam, "head": args.head, "ms_per_page_set": round(el / args.steps * 1e3, 2),
                       "postprocess_ms_per_page_set": round(state["t_post"] / args.steps * 1e3, 2),
                       "sizes": sorted(BUCKETS), "sample_latex_chars": len(state["sample"])}))
 
