@@ -58,6 +58,13 @@ class D2TOpAttnLstmBwdArgs(C.Structure):  # include/d2t.h d2t_op_attn_lstm_bwd_a
         "dbscore")] + [(n, C.c_int32) for n in ("B", "T", "S", "V", "taps", "key_off", "coverage")]
 
 
+class D2TOpAttnBeamRec(C.Structure):  # include/d2t.h d2t_op_attn_beam_rec
+    _fields_ = [(n, C.c_void_p) for n in (
+        "ctrl", "tok", "scores", "map", "idx_h", "idx_m", "seg", "comp_n", "fin", "last_completed", "comp_t", "comp_par",
+        "comp_score", "hist_par", "hist_tok", "topv", "topi")] + \
+        [(n, C.c_int32) for n in ("N", "beam", "cap", "V", "S", "end_token")]
+
+
 PREP_DEMO, PREP_API = 0, 1
 NORM_ALB, NORM_RAW = 0, 1
 PREP_OK, PREP_UNBOUND_LOCAL, PREP_FALLBACK = 0, 1, 2
@@ -108,6 +115,10 @@ SIGNATURES = {
                                                C.POINTER(C.c_float), _P, _P]),
     "d2t_decode_attn_supports_ragged_beam": (_I, [_P]),
     "d2t_decode_attn_beam": (_I, [_P, _P, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
+    "d2t_decode_attn_supports_device_beam": (_I, [_P]),
+    "d2t_set_attn_beam_device": (_I, [_P, _I]),
+    "d2t_decode_attn_beam_device_runs": (_L, [_P]),
+    "d2t_decode_attn_beam_batch_submit": (_I, [_P, _P, _I, C.POINTER(_I), _I, _P, _P, _P, _P, _P, C.POINTER(_L)]),
     "d2t_set_conv_precision": (_I, [_P, _I]),
     "d2t_set_mixed_units": (_I, [_P, _I]),
     "d2t_set_reserved_blocks": (_I, [_P, _I]),
@@ -171,6 +182,8 @@ SIGNATURES = {
     "d2t_op_attn_decode_ragged": (_I, [C.POINTER(D2TOpAttnDecodeArgs), _P, _P, _I, _P]),
     "d2t_op_attn_decode_finalize": (_I, [_P, _P] + [_I] * 4 + [_P] * 4),
     "d2t_op_attn_alpha_gather": (_I, [_P] * 4 + [_I] * 4 + [_P]),
+    "d2t_op_attn_beam_advance": (_I, [C.POINTER(D2TOpAttnBeamRec), _I, _L, _P]),
+    "d2t_op_attn_beam_finish": (_I, [C.POINTER(D2TOpAttnBeamRec)] + [_P] * 6),
     "d2t_op_attn_lstm_bwd": (_I, [C.POINTER(D2TOpAttnLstmBwdArgs), _P]),
     "d2t_op_loc_unfold_bwd": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I] + [_P] * 5),
 }

@@ -161,6 +161,39 @@ class DecodeHandle:
         self._eng.wait_ticket(self.ticket, host_sync=host_sync)
 
 
+class BeamSearchHandle:
+    """Completion handle of Model.beam_search_batch_async: the search runs on one of the engine's decode streams.
+    `done()` polls without blocking, `wait()` orders the current stream (optionally the host) after exactly this search,
+    `steps()` is the number of steps it executed, and `result()` waits and returns what beam_search_batch returns for the
+    same input: [(LongTensor [1, len], score)] per sample, with return_attn also each sample's map [len, Tk_i]."""
+
+    def __init__(self, eng, ticket, tensors, lengths, return_attn):
+        self._eng, self.ticket, self._tensors, self._lengths, self._attn = eng, ticket, tensors, lengths, return_attn
+        self._result = [] if ticket is None else None  # (an empty list of inputs: nothing was submitted)
+
+    def done(self):
+        return self.ticket is None or self._eng.ticket_done(self.ticket)
+
+    def wait(self, host_sync=False):
+        if self.ticket is not None:
+            self._eng.wait_ticket(self.ticket, host_sync=host_sync)
+
+    def steps(self):
+        return 0 if self.ticket is None else self._eng.decode_steps(self.ticket)[0]
+
+    def result(self):
+        if self._result is None:
+            self.wait(host_sync=True)
+            seq, n, score = (t.cpu() for t in self._tensors[:3])
+            out = [(torch.LongTensor(seq[i, :int(n[i])].tolist()).unsqueeze(0), torch.tensor(float(score[i])))
+                   for i in range(len(self._lengths))]
+            if self._attn:
+                alpha = self._tensors[3]
+                out = [r + (alpha[i, :int(n[i]), :self._eng.attn_keys(T)],) for i, (r, T) in enumerate(zip(out, self._lengths))]
+            self._result = out
+        return self._result
+
+
 class Model(nn.Module):
     def __init__(self, opt):
         super().__init__()
@@ -192,6 +225,10 @@ class Model(nn.Module):
         self.conv_fusion = (True, True)
         # beam search (TFM, d_model 256, beam <= 6): one cross-attention block per sample for all its hypotheses (default: per row)
         self.beam_shared_tile = False
+        # beam search of the LSTM-attention heads (coverage / Bahdanau cells): keep the hypothesis bookkeeping on the device --
+        # one captured graph per search instead of a host round trip per step, same results.  Off by
+        # default; heads without that search ignore it.  beam_search_batch_async always runs the device-side search.
+        self.attn_beam_device = False
         # pipelined mode: decode loops in flight side by side (1 .. 4)
         self.decode_chains = 1
         # (LSTM-attention heads: each of the chains holds one forward's whole loop, key projection and state block)
@@ -269,6 +306,39 @@ class Model(nn.Module):
         for a in range(0, memory.shape[0], per):
             out += eng.decode_attn_beam_batch(memory[a:a + per].contiguous(), beam, return_alpha=True)
         return out
+
+    def beam_search_batch_async(self, input, beam_size=None, return_attn=False):
+        """beam_search_batch without the wait, for the LSTM-attention heads whose search the engine keeps on the device
+        (Engine.supports_device_attn_beam): the encoders run on the current stream, the search is submitted to one of the
+        engine's decode chains (decode_chains of them take turns) and the call returns a BeamSearchHandle -- so the next
+        input's encoder can run beside the search.  input: a tensor, or a list / tuple of tensors of different sizes.
+        handle.result() is exactly what beam_search_batch returns for the same input.
+
+        Never falls back to a blocking search: a head without the device-side search (TFM, the 'loc_aware' cell) raises
+        NotImplementedError, and a return_attn input whose alignment history exceeds _lib.ATTN_MAP_BUDGET bytes raises
+        RuntimeError (submit fewer samples per call)."""
+        beam = int(beam_size or self.opt.get("beam_size", 1))
+        if self.stages["Pred"] == "TFM":
+            raise NotImplementedError("beam_search_batch_async: the TFM head's beam search cannot be submitted; use "
+                                      "beam_search_batch")
+        eng = self.engine()
+        if not eng.supports_device_attn_beam():
+            raise NotImplementedError("beam_search_batch_async: this head has no device-side beam search (the 'loc_aware' "
+                                      "cell has no beam search in the engine at all); use beam_search_batch")
+        from .engine import pack_memories
+        inputs = list(input) if isinstance(input, (list, tuple)) else [input]
+        if len(inputs) == 0:
+            return BeamSearchHandle(eng, None, (), [], return_attn)
+        packed, lengths = pack_memories([self.forward_encoder(x)[0] for x in inputs])
+        if return_attn:
+            from . import _lib
+            need = len(lengths) * eng.attn_map_bytes(max(lengths), beam)
+            if need > _lib.ATTN_MAP_BUDGET:
+                raise RuntimeError(f"beam_search_batch_async: the alignment history of {len(lengths)} samples ({need} bytes at "
+                                   f"the longest memory's stride) exceeds the {_lib.ATTN_MAP_BUDGET}-byte budget; submit fewer "
+                                   "samples per call")
+        out = eng.decode_attn_beam_batch_async(packed, lengths, beam, return_alpha=return_attn)
+        return BeamSearchHandle(eng, out[-1], out[:-1], lengths, return_attn)
 
     def _beam_search_mixed(self, inputs, beam, return_attn=False):
         """beam_search_batch for a list of image tensors [n_i, C, H_i, W_i] (crops of different sizes, e.g. the buckets of
@@ -431,6 +501,10 @@ class Model(nn.Module):
         if getattr(self._engine, "_beam_shared", None) != bool(self.beam_shared_tile):
             self._engine.set_beam_shared_tile(self.beam_shared_tile)
             self._engine._beam_shared = bool(self.beam_shared_tile)
+        want_abd = bool(self.attn_beam_device)
+        if getattr(self._engine, "_attn_beam_device", False) != want_abd and finalize and self._engine.supports_device_attn_beam():
+            self._engine.set_attn_beam_device(want_abd)
+            self._engine._attn_beam_device = want_abd
         if getattr(self._engine, "_fusion", None) != tuple(self.conv_fusion):
             self._engine.set_conv_fusion(*self.conv_fusion)
             self._engine._fusion = tuple(self.conv_fusion)

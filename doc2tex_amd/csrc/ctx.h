@@ -186,7 +186,7 @@ struct d2t_ctx {
   // Decode chains: each owns its stream, self-attention cache, workspace, state block and output staging, so that with two
   // or more the decode loops of consecutive async batches run side by side.  Chain i keeps its stream and buffers between
   // calls (their addresses are part of GraphKey); a decode entry picks its chain once and passes it down.  Everything
-  // synchronous and every beam search runs on chain 0.
+  // synchronous and every beam search runs on chain 0 -- except the submitted LSTM-attention searches, which take turns.
   struct Chain {
     hipStream_t stream = nullptr;
     float* skv = nullptr; size_t skv_cap = 0;  // self-attention cache
@@ -197,7 +197,21 @@ struct d2t_ctx {
     // decodes write logits | tokens here (fixed addresses, so one captured graph per chain serves every caller buffer) and
     // copy them out afterwards
     float* out = nullptr; size_t out_cap = 0;
+    // device-side beam search of the LSTM-attention heads (engine_attn.hip attn_beam_dev_impl), per chain so that two
+    // submitted searches share nothing: the record, state rows and result block | the staged packed memory | (maps) the
+    // alignment history and the chosen paths
+    float* abeam_ws = nullptr; size_t abeam_ws_cap = 0;
+    float* abeam_mem = nullptr; size_t abeam_mem_cap = 0;
+    float* abeam_hist = nullptr; size_t abeam_hist_cap = 0;
   } chains[MAXC];
+  // its per-sample tables [row0 | T] go up from a small ring of pinned buffers, on the search's own stream; a slot is
+  // rewritten only once its copy has run (abeam_tab_ev), which waits only when ABEAM_TABS searches are in flight
+  static constexpr int ABEAM_TABS = 8;
+  int* abeam_tab_host[ABEAM_TABS] = {};
+  hipEvent_t abeam_tab_ev[ABEAM_TABS] = {};
+  unsigned abeam_tab_seq = 0;
+  int attn_beam_device = 0;           // d2t_set_attn_beam_device: the synchronous Attn beam entries run the device-side loop
+  long long attn_beam_dev_runs = 0;   // searches the device-side loop has run (d2t_decode_attn_beam_device_runs)
   int n_chains = 1;
   hipEvent_t ev_in = nullptr;
   // ragged decode groups: per memory slot the device tables [row0 | len | row_batch] (rg_cap rows each) | batch_rows [64] |
@@ -213,10 +227,13 @@ struct d2t_ctx {
   // over T memory tokens, `steps` steps per graph, the engine buffers it touches, and per loop kind:
   //   greedy (one step replayed under the host's poll, or the whole loop): dev_exit, rows_per_batch
   //   device-side beam loop: N, beam
+  //   device-side beam loop of the LSTM-attention heads: B = N * beam, T = the row stride of state and history (a capacity,
+  //   not a length), N, beam, dev_exit = maps on; tok = the staged memory, logits = the workspace, ckv = the history, dws = the
+  //   key projection
   // ragged (greedy group or beam search): T and rows_per_batch are 0 and the layout is NOT part of the key -- the loop reads
   // lengths and offsets from the tables at rtab (rg_cap rows each; 0 for the beam tables) and the bf16 planes plane_elems
   // floats behind the slot's start (a function of the slot's capacity)
-  enum LoopKind : int { LOOP_GREEDY_STEP = 0, LOOP_GREEDY_WHOLE = 1, LOOP_BEAM_DEV = 2 };
+  enum LoopKind : int { LOOP_GREEDY_STEP = 0, LOOP_GREEDY_WHOLE = 1, LOOP_BEAM_DEV = 2, LOOP_ATTN_BEAM_DEV = 3 };
   struct GraphKey {
     int B, T, steps;
     const void *tok, *logits, *ckv, *dws, *skv, *dstate, *rtab;

@@ -542,12 +542,19 @@ void d2t_destroy(d2t_ctx* c) {
   if (c->brg_tab) hipFree(c->brg_tab);
   if (c->brg_host) hipHostFree(c->brg_host);
   if (c->h_steps) hipHostFree(c->h_steps);
+  for (int i = 0; i < d2t_ctx::ABEAM_TABS; ++i) {
+    if (c->abeam_tab_host[i]) hipHostFree(c->abeam_tab_host[i]);
+    if (c->abeam_tab_ev[i]) hipEventDestroy(c->abeam_tab_ev[i]);
+  }
   for (hipEvent_t ev : c->ticket_ev) if (ev) hipEventDestroy(ev);
   for (d2t_ctx::Chain& o : c->chains) {
     if (o.skv) hipFree(o.skv);
     if (o.dws) hipFree(o.dws);
     if (o.dstate) hipFree(o.dstate);
     if (o.out) hipFree(o.out);
+    if (o.abeam_ws) hipFree(o.abeam_ws);
+    if (o.abeam_mem) hipFree(o.abeam_mem);
+    if (o.abeam_hist) hipFree(o.abeam_hist);
   }
   // the streams go back to the process-wide pool, last acquired first (the next context takes them in the same roles)
   for (int i = d2t_ctx::MAXC - 1; i >= 0; --i)

@@ -1,7 +1,6 @@
-// libd2t engine, LSTM-attention heads: the greedy decode (synchronous and pipelined) and the beam search of the C-ABI.
-// Host code only: the kernels are recurrent.hip's.
-#include "engine_impl.h"
-#include "carve.h"
+// libd2t engine, LSTM-attention heads: the greedy decode (synchronous and pipelined) and the beam search of the C-ABI -- its
+// host loop and the device-side loop beside it.  Host code only: the kernels are recurrent.hip's and attn_beam.hip's.
+#include "engine_tfm.h"  // (engine_impl.h, carve.h; the captured-loop cache)
 
 extern "C" {
 
@@ -332,6 +331,189 @@ int attn_beam_impl(d2t_ctx* c, const float* memory, int N, int T, const int32_t*
   }
   return D2T_OK;
 }
+
+// ---- the device-side loop ----
+// Its workspace (per decode chain): logits [cap][V] | topv [cap] | topi [cap] | h_in c_in h_out c_out [cap][H] | mem_in mem_out
+// [cap][ld] | end_step [cap] | dummy tokens i64 [cap] | the per-sample tables row0 [N] | T [N] | the record (kernels.h
+// AttnBeamDev) | the result block seq i64 [N][S] | len [N] | score [N] | ctrl [4] (one device -> host copy at the end of a
+// synchronous search), each from a 16-byte boundary.  A function of N, beam, V, S and ld alone: no memory length moves it.
+struct AttnBeamDevWs {
+  float *logits, *topv, *st[6];
+  int *topi, *end, *tab;
+  int64_t* dummy;
+  AttnBeamDev rec;
+  char* res; size_t res_bytes;
+  int64_t* r_seq; int* r_len; float* r_score;
+};
+size_t attn_beam_dev_carve(Carver cv, int Hh, int ld, AttnBeamDevWs* w) {
+  AttnBeamDev& r = w->rec;
+  const size_t cap = (size_t)r.cap, N = (size_t)r.N, nb = N * r.beam;
+  w->logits = cv.take<float>(cap * r.V, 16);
+  w->topv = cv.take<float>(cap, 16);
+  w->topi = cv.take<int>(cap, 16);
+  for (int i = 0; i < 6; ++i) w->st[i] = cv.take<float>(cap * (i < 4 ? Hh : ld), 16);
+  w->end = cv.take<int>(cap, 16);
+  w->dummy = cv.take<int64_t>(cap, 16);
+  w->tab = cv.take<int>(2 * N, 16);
+  r.tok = cv.take<int64_t>(cap, 16);
+  r.scores = cv.take<float>(cap, 16);
+  r.map = cv.take<int>(cap, 16); r.idx_h = cv.take<int>(cap, 16); r.idx_m = cv.take<int>(cap, 16);
+  r.seg = cv.take<int>(3 * N, 16);
+  r.comp_n = cv.take<int>(N, 16); r.fin = cv.take<int>(N, 16); r.last_completed = cv.take<int>(N, 16);
+  r.comp_t = cv.take<int>(nb, 16); r.comp_par = cv.take<int>(nb, 16); r.comp_score = cv.take<float>(nb, 16);
+  r.hist_par = cv.take<int>((size_t)r.S * cap, 16); r.hist_tok = cv.take<int>((size_t)r.S * cap, 16);
+  cv.align(16);
+  w->res = cv.here();
+  w->r_seq = cv.take<int64_t>(N * r.S, 16);
+  w->r_len = cv.take<int>(N);
+  w->r_score = cv.take<float>(N);
+  r.ctrl = cv.take<int>(4);
+  w->res_bytes = (size_t)(cv.here() - w->res);
+  r.topv = w->topv; r.topi = w->topi;
+  return cv.total() + 64;
+}
+constexpr int ATTN_BEAM_LD_QUANTUM = 256;  // the row stride of state and history: the largest Tk rounded up to this
+
+// The search of attn_beam_impl with the bookkeeping ON THE DEVICE (attn_beam.hip): the reference's per-step walk is
+// attn_beam_dev_advance_kernel behind the per-sample top-k, the three gathers are one launch, the final pick is
+// attn_beam_dev_finish_kernel, and the step kernel runs for all N x beam row slots under a guard on the record's control
+// words -- no host round trip inside the search, which is therefore ONE captured graph: init, S x (step, top-k, advance,
+// gather), finish.  Always the ragged builds of the step kernel (a uniform call fills the tables with row0 = i * T), on the
+// row stride ld = the largest Tk rounded up to 256 (held to Tk where the history would otherwise leave the budget), so the
+// graph depends on N, beam, ld, maps on / off and the chain's buffers, and on no memory length.  The packed memory is copied
+// into the chain's own buffer in front of the key projection: every pointer inside the graph is the engine's.  The results
+// land in the chain's result block; the alignment gather and the copies into the caller's buffers follow the graph (they
+// name caller addresses, which the graph must not).
+// The search runs on its chain's stream, behind the caller's.  Synchronous (async == false): chain 0, one device -> host copy
+// of the result block, one synchronisation; seq_out / len_out / score_out are host arrays.  Submitted: the chains take turns,
+// the outputs are device buffers, ev_done orders later users of the chain's key-projection workspace, a ticket reports the
+// steps executed, and nothing here waits for the device (growing a buffer aside; and a table slot of the ring still waiting
+// for its upload, which takes ABEAM_TABS searches in flight).
+int attn_beam_dev_impl(d2t_ctx* c, const float* memory, int N, int T, const int32_t* Ts, int beam_size, int64_t* seq_out,
+                       int32_t* len_out, float* score_out, float* alpha_out, hipStream_t user, bool async) {
+  const d2t_config& g = c->cfg;
+  const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab, cap = N * beam_size;
+  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  if (N > ATTN_BEAM_MAX_N)
+    return fail(c, D2T_EINVAL, "the device-side beam search takes 1 to %d samples per call, got %d", ATTN_BEAM_MAX_N, N);
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, alpha_out, "alpha")) return rc;
+  std::vector<int32_t> uniform;
+  if (!Ts) { uniform.assign((size_t)N, T); Ts = uniform.data(); }
+  size_t mem_rows = 0;
+  T = 0;
+  for (int i = 0; i < N; ++i) { mem_rows += (size_t)Ts[i]; T = std::max(T, (int)Ts[i]); }
+  const int Tk = T - key_off;  // the largest
+  int ld = (Tk + ATTN_BEAM_LD_QUANTUM - 1) / ATTN_BEAM_LD_QUANTUM * ATTN_BEAM_LD_QUANTUM;
+  if (alpha_out) {
+    const size_t hist_bytes = (size_t)S * cap * Tk * 4;
+    if (hist_bytes > D2T_ATTN_MAP_BUDGET)
+      return fail(c, D2T_EINVAL, "beam alignment history of %zu bytes (%d steps x %d samples x beam %d x %d keys x 4) exceeds the "
+                  "%llu-byte budget: decode fewer samples per call", hist_bytes, S, N, beam_size, Tk, (unsigned long long)D2T_ATTN_MAP_BUDGET);
+    if ((size_t)S * cap * ld * 4 > D2T_ATTN_MAP_BUDGET) ld = Tk;
+  }
+  // ---- nothing is refused below this line ----
+  const int chain = async ? (int)(c->decode_seq++ % (unsigned)c->n_chains) : 0;
+  d2t_ctx::Chain& ch = c->chains[chain];
+  hipStream_t s = ch.stream;
+  int rc;
+  AttnBeamDevWs ws{};
+  ws.rec.N = N; ws.rec.beam = beam_size; ws.rec.cap = cap; ws.rec.V = V; ws.rec.S = S; ws.rec.end_token = 1;  // attn_converter.py:8
+  if ((rc = ensure(c, &ch.abeam_ws, &ch.abeam_ws_cap, attn_beam_dev_carve(Carver(), Hh, ld, &ws)))) return rc;
+  attn_beam_dev_carve(Carver(ch.abeam_ws), Hh, ld, &ws);
+  if ((rc = ensure(c, &ch.abeam_mem, &ch.abeam_mem_cap, (mem_rows * Hh + 16) * 4))) return rc;
+  if ((rc = ensure(c, &ch.dws, &ch.dws_cap, (mem_rows * Hh + 16) * 4))) return rc;
+  float* d_hist = nullptr;
+  int* d_path = nullptr;
+  if (alpha_out) {  // history [S][cap][ld] | chosen paths [N][S] | their lengths [N]
+    if ((rc = ensure(c, &ch.abeam_hist, &ch.abeam_hist_cap, ((size_t)S * cap * ld + (size_t)N * (S + 1) + 16) * 4))) return rc;
+    d_hist = ch.abeam_hist;
+    d_path = reinterpret_cast<int*>(d_hist + (size_t)S * cap * ld);
+  }
+  if (!async && (rc = ensure_host_beam(c, ws.res_bytes))) return rc;
+  // the per-sample tables: the next slot of the pinned ring, rewritten only once its last upload has run
+  const int slot = (int)(c->abeam_tab_seq++ % (unsigned)d2t_ctx::ABEAM_TABS);
+  if (!c->abeam_tab_host[slot]) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->abeam_tab_host[slot]), (size_t)2 * ATTN_BEAM_MAX_N * 4, hipHostMallocDefault) != hipSuccess) {
+      c->abeam_tab_host[slot] = nullptr;
+      return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
+    }
+    HIPCHK(c, hipEventCreateWithFlags(&c->abeam_tab_ev[slot], hipEventDisableTiming));
+  } else {
+    HIPCHK(c, hipEventSynchronize(c->abeam_tab_ev[slot]));
+  }
+  int* h_tab = c->abeam_tab_host[slot];
+  d2t_ragged_beam_tables(N, Ts, h_tab, h_tab + N);
+  HIPCHK(c, hipEventRecord(c->ev_in, user));  // the chain's stream starts behind the caller's work (the memory)
+  HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
+  HIPCHK(c, hipMemcpyAsync(ws.tab, h_tab, 2 * (size_t)N * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->abeam_tab_ev[slot], s));
+  HIPCHK(c, hipMemcpyAsync(ch.abeam_mem, memory, mem_rows * Hh * 4, hipMemcpyDeviceToDevice, s));
+  float* kp = ch.dws;
+  HIPCHK(c, linear_any(nullptr, s, ch.abeam_mem, c->attn.key, nullptr, kp, (int)mem_rows, ACT_NONE));
+  const AttnBeamDev& b = ws.rec;
+  AttnDecP p = attn_dec_params(c, ch.abeam_mem, T, kp);
+  p.probs = ws.logits; p.tokens = ws.dummy; p.end_step = ws.end;
+  p.B = cap; p.S = 1; p.coverage = 1;
+  p.step_mode = 1;
+  p.st_h_in = ws.st[0]; p.st_c_in = ws.st[1]; p.st_mem_in = ws.st[4];
+  p.st_h_out = ws.st[2]; p.st_c_out = ws.st[3]; p.st_mem_out = ws.st[5];
+  p.tok_in = b.tok; p.row_sample = b.map;
+  p.smp_row0 = ws.tab; p.smp_T = ws.tab + N; p.st_ld = ld;
+  p.guard = b.ctrl;
+  auto enqueue_loop = [&](hipStream_t st) -> hipError_t {
+    hipError_t e;
+#define LTRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+    LTRY(launch_attn_beam_dev_init(b, 0, st));  // [GO] = 0
+    for (int step = 0; step < S; ++step) {  // the steps differ in p.first and in their slice of the history
+      p.first = step == 0;
+      p.sv_alpha = d_hist ? d_hist + (size_t)step * cap * ld : nullptr;
+      LTRY(launch_attn_decode(p, st));
+      LTRY(launch_beam_topk_batch(ws.logits, b.scores, b.seg, N, V, beam_size, ws.topv, ws.topi, st, b.ctrl, b.ctrl + 2));
+      LTRY(launch_attn_beam_dev_advance(b, st));
+      if (step + 1 < S)
+        LTRY(launch_attn_beam_dev_gather(b.ctrl, b.idx_h, b.idx_m, ws.st[2], ws.st[3], ws.st[5], ws.st[0], ws.st[1], ws.st[4], cap, Hh, ld, st));
+    }
+    LTRY(launch_attn_beam_dev_finish(b, ws.r_seq, ws.r_len, ws.r_score, d_path, d_path ? d_path + (size_t)N * S : nullptr, st));
+#undef LTRY
+    return hipSuccess;
+  };
+  if (D2T_PROBE_ENV_STR("D2T_NO_GRAPH") == nullptr) {
+    d2t_ctx::GraphKey k;
+    memset(&k, 0, sizeof k);
+    k.loop = d2t_ctx::LOOP_ATTN_BEAM_DEV;
+    k.B = cap; k.T = ld; k.steps = S; k.N = N; k.beam = beam_size; k.dev_exit = d_hist ? 1 : 0;
+    k.tok = ch.abeam_mem; k.logits = ch.abeam_ws; k.ckv = d_hist; k.dws = ch.dws;
+    hipGraphExec_t exec = nullptr;
+    if ((rc = tfm::cached_graph(c, s, k, "Attn beam", enqueue_loop, &exec))) return rc;
+    HIPCHK(c, hipGraphLaunch(exec, s));
+  } else {
+    HIPCHK(c, enqueue_loop(s));
+  }
+  ++c->attn_beam_dev_runs;
+  if (alpha_out) HIPCHK(c, launch_attn_alpha_gather_ld(d_hist, d_path, d_path + (size_t)N * S, alpha_out, N, S, cap, ld, Tk, s));
+  if (async) {
+    HIPCHK(c, hipMemcpyAsync(seq_out, ws.r_seq, (size_t)N * S * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(len_out, ws.r_len, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(score_out, ws.r_score, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipEventRecord(c->ev_done[chain], s));
+    c->ev_done_valid[chain] = true;
+    return issue_ticket(c, s, 1, b.ctrl + 3);  // one entry: the steps the search executed
+  }
+  HIPCHK(c, hipMemcpyAsync(c->h_beam, ws.res, ws.res_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  // the host's view of the result block: the same offsets from the pinned copy's base
+  const int64_t* h_seq = reinterpret_cast<const int64_t*>(c->h_beam + (reinterpret_cast<char*>(ws.r_seq) - ws.res));
+  const int* h_len = reinterpret_cast<const int*>(c->h_beam + (reinterpret_cast<char*>(ws.r_len) - ws.res));
+  const float* h_score = reinterpret_cast<const float*>(c->h_beam + (reinterpret_cast<char*>(ws.r_score) - ws.res));
+  for (int i = 0; i < N; ++i) {  // as the host loop leaves them: the tokens of the sample's length, nothing behind
+    const int n = std::min(std::max(h_len[i], 0), S);
+    for (int j = 0; j < n; ++j) seq_out[(size_t)i * S + j] = h_seq[(size_t)i * S + j];
+    len_out[i] = n;
+    score_out[i] = h_score[i];
+  }
+  return D2T_OK;
+}
 }  // namespace
 
 int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
@@ -378,6 +560,8 @@ int d2t_decode_attn_beam_batch_alpha(d2t_ctx* c, const float* memory, int32_t N,
   if (int rc = attn_beam_check(c, beam_size)) return rc;
   const int Tk = T - (c->cfg.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0);
   if (Tk < 1 || Tk > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d unsupported", T);
+  if (c->attn_beam_device)
+    return attn_beam_dev_impl(c, memory, N, T, nullptr, beam_size, seq_out, len_out, score_out, alpha_out, (hipStream_t)stream, false);
   return attn_beam_impl(c, memory, N, T, nullptr, beam_size, seq_out, len_out, score_out, alpha_out, (hipStream_t)stream);
 }
 
@@ -403,7 +587,54 @@ int d2t_decode_attn_beam_batch_ragged(d2t_ctx* c, const float* memory, int32_t N
       return fail(c, D2T_EINVAL, "sample %d has memory length %d, supported are %d to %d", i, T[i], 1 + key_off, memory_cap(c) + key_off);
   if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
   if (int rc = check_dev_ptr(c, alpha_out, "alpha")) return rc;
+  if (c->attn_beam_device)
+    return attn_beam_dev_impl(c, memory, N, 0, T, beam_size, seq_out, len_out, score_out, alpha_out, (hipStream_t)stream, false);
   return attn_beam_impl(c, memory, N, 0, T, beam_size, seq_out, len_out, score_out, alpha_out, (hipStream_t)stream);
+}
+
+// 1: this context has the device-side LSTM-attention beam search (wherever it has the search at all: the coverage and
+// Bahdanau cells); 0: d2t_set_attn_beam_device(1) and d2t_decode_attn_beam_batch_submit refuse with D2T_ESTATE
+int32_t d2t_decode_attn_supports_device_beam(const d2t_ctx* c) { return d2t_decode_attn_supports_ragged_beam(c); }
+
+int d2t_set_attn_beam_device(d2t_ctx* c, int32_t on) {
+  if (!c) return D2T_EINVAL;
+  if (on) {
+    if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
+    if (int rc = attn_beam_check(c, 1)) return rc;
+  }
+  c->attn_beam_device = on ? 1 : 0;
+  return D2T_OK;
+}
+
+int64_t d2t_decode_attn_beam_device_runs(const d2t_ctx* c) { return c ? (int64_t)c->attn_beam_dev_runs : 0; }
+
+int d2t_decode_attn_beam_batch_submit(d2t_ctx* c, const float* memory, int32_t N, const int32_t* T, int32_t beam_size,
+                                      int64_t* seq_dev, int32_t* len_dev, float* score_dev, float* alpha_dev, d2t_stream stream,
+                                      int64_t* ticket_out) {
+  DevGuard dg_(c);
+  // the refusals of d2t_decode_attn_beam_batch_ragged, and outputs that the search's stream can write
+  if (!c || !memory || !T || !seq_dev || !len_dev || !score_dev) return fail(c, D2T_EINVAL, "bad argument");
+  if (int rc = attn_beam_check(c, beam_size)) return rc;
+  if (N < 1 || N > ATTN_BEAM_MAX_N)
+    return fail(c, D2T_EINVAL, "ragged beam search takes 1 to %d samples per call, got %d", ATTN_BEAM_MAX_N, N);
+  const int key_off = c->cfg.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  for (int i = 0; i < N; ++i)
+    if (T[i] - key_off < 1 || T[i] - key_off > memory_cap(c))
+      return fail(c, D2T_EINVAL, "sample %d has memory length %d, supported are %d to %d", i, T[i], 1 + key_off, memory_cap(c) + key_off);
+  const struct { const void* p; const char* what; } outs[] = {{seq_dev, "seq_dev"}, {len_dev, "len_dev"}, {score_dev, "score_dev"},
+                                                              {alpha_dev, "alpha_dev"}};
+  for (const auto& o : outs) {
+    if (!o.p) continue;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, o.p) != hipSuccess || a.type != hipMemoryTypeDevice) {
+      (void)hipGetLastError();
+      return fail(c, D2T_EINVAL, "%s must be a device buffer (a submitted search writes its results on the engine's stream)", o.what);
+    }
+    if (int rc = check_dev_ptr(c, o.p, o.what)) return rc;
+  }
+  const int rc = attn_beam_dev_impl(c, memory, N, 0, T, beam_size, seq_dev, len_dev, score_dev, alpha_dev, (hipStream_t)stream, true);
+  if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
+  return rc;
 }
 
 }  // extern "C"

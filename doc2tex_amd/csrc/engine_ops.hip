@@ -647,4 +647,88 @@ int d2t_op_attn_alpha_gather(const float* hist, const int32_t* path, const int32
   return op_status(launch_attn_alpha_gather(hist, path, len, out, N, S, cap, Tk, s));
 }
 
+namespace {
+// the caller's record as the kernels take it; false: a missing array or a size the kernels refuse
+bool attn_beam_rec(const d2t_op_attn_beam_rec* r, AttnBeamDev* b) {
+  if (!r || !r->ctrl || !r->tok || !r->scores || !r->map || !r->idx_h || !r->idx_m || !r->seg || !r->comp_n || !r->fin ||
+      !r->last_completed || !r->comp_t || !r->comp_par || !r->comp_score || !r->hist_par || !r->hist_tok)
+    return false;
+  if (r->N < 1 || r->N > 1024 || r->beam < 1 || r->beam > 16 || (long long)r->cap < (long long)r->N * r->beam || r->V < 1 ||
+      r->S < 1 || r->end_token < 0 || r->end_token >= r->V)
+    return false;
+  *b = AttnBeamDev{};
+  b->ctrl = r->ctrl; b->tok = r->tok; b->scores = r->scores; b->map = r->map; b->idx_h = r->idx_h; b->idx_m = r->idx_m;
+  b->seg = r->seg; b->comp_n = r->comp_n; b->fin = r->fin; b->last_completed = r->last_completed; b->comp_t = r->comp_t;
+  b->comp_par = r->comp_par; b->comp_score = r->comp_score; b->hist_par = r->hist_par; b->hist_tok = r->hist_tok;
+  b->topv = r->topv; b->topi = r->topi;
+  b->N = r->N; b->beam = r->beam; b->cap = r->cap; b->V = r->V; b->S = r->S; b->end_token = r->end_token;
+  return true;
+}
+}  // namespace
+
+int d2t_op_attn_beam_advance(const d2t_op_attn_beam_rec* r, int32_t init, int64_t go_token, d2t_stream stream) {
+  AttnBeamDev b;
+  if (!attn_beam_rec(r, &b)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (init) return op_status(launch_attn_beam_dev_init(b, go_token, s));
+  if (!b.topv || !b.topi) return D2T_EINVAL;
+  // the state as the kernel will read it: the step indexes the history, the candidates index rows of their segment
+  std::vector<int> c, sg, cn, fi, ti;
+  if (!fetch_ints(s, b.ctrl, 4, &c) || !fetch_ints(s, b.seg, (size_t)b.N * 3, &sg) || !fetch_ints(s, b.comp_n, b.N, &cn) ||
+      !fetch_ints(s, b.fin, b.N, &fi) || !fetch_ints(s, b.topi, (size_t)b.N * b.beam, &ti))
+    return D2T_EHIP;
+  if (c[0] < 0 || c[2] < 0) return D2T_EINVAL;
+  if (!(c[2] && c[0] >= c[2])) {  // the launch will do work
+    if (c[0] >= b.S) return D2T_EINVAL;
+    for (int i = 0; i < b.N; ++i) {
+      if (fi[i]) continue;
+      const int off = sg[3 * i], m = sg[3 * i + 1], k = sg[3 * i + 2];
+      if (k < 1 || k > b.beam || m < 1 || m > b.beam || off < 0 || off + std::max(m, k) > b.cap || cn[i] < 0 || cn[i] + k > b.beam)
+        return D2T_EINVAL;
+      for (int q = 0; q < k; ++q) {
+        const int idx = ti[(size_t)i * b.beam + q];
+        if (idx < 0 || idx / b.V >= m) return D2T_EINVAL;
+      }
+    }
+  }
+  return op_status(launch_attn_beam_dev_advance(b, s));
+}
+
+int d2t_op_attn_beam_finish(const d2t_op_attn_beam_rec* r, int64_t* seq, int32_t* len, float* score, int32_t* path, int32_t* plen,
+                            d2t_stream stream) {
+  AttnBeamDev b;
+  if (!attn_beam_rec(r, &b) || !seq || !len || !score || (path != nullptr) != (plen != nullptr)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  // the walk the kernel will take, on the host: every row it reads must lie inside the record
+  std::vector<int> c, sg, cn, lc, ct, cp, hp;
+  if (!fetch_ints(s, b.ctrl, 4, &c)) return D2T_EHIP;
+  if (c[3] < 0 || c[3] > b.S) return D2T_EINVAL;
+  if (!fetch_ints(s, b.seg, (size_t)b.N * 3, &sg) || !fetch_ints(s, b.comp_n, b.N, &cn) || !fetch_ints(s, b.last_completed, b.N, &lc) ||
+      !fetch_ints(s, b.comp_t, (size_t)b.N * b.beam, &ct) || !fetch_ints(s, b.comp_par, (size_t)b.N * b.beam, &cp) ||
+      !fetch_ints(s, b.hist_par, (size_t)c[3] * b.cap, &hp))
+    return D2T_EHIP;
+  for (int i = 0; i < b.N; ++i) {
+    int t = -1, row = 0;
+    if (!lc[i]) {
+      if (sg[3 * i + 1] > 0) { t = c[3] - 1; row = sg[3 * i]; }
+    } else {
+      if (cn[i] < 1 || cn[i] > b.beam) return D2T_EINVAL;
+      for (int j = 0; j < cn[i]; ++j) {  // any of them may be the best
+        const int tj = ct[(size_t)i * b.beam + j], pj = cp[(size_t)i * b.beam + j];
+        if (tj < 0 || tj >= c[3] || pj < 0 || pj >= b.cap) return D2T_EINVAL;
+        for (int u = tj - 1, rw = pj; u >= 0; --u) {
+          rw = hp[(size_t)u * b.cap + rw];
+          if (rw < 0 || rw >= b.cap) return D2T_EINVAL;
+        }
+      }
+    }
+    for (; t >= 0; --t) {
+      if (row < 0 || row >= b.cap) return D2T_EINVAL;
+      row = hp[(size_t)t * b.cap + row];
+    }
+    if (row < 0 || row >= b.cap) return D2T_EINVAL;
+  }
+  return op_status(launch_attn_beam_dev_finish(b, seq, len, score, path, plen, s));
+}
+
 }  // extern "C"

@@ -197,6 +197,10 @@ struct AttnDecP {
   const int* smp_row0;  // device [samples]
   const int* smp_T;     // device [samples]
   int st_ld;
+  // Device-side beam loop (ragged step mode only; its own builds of the kernel): the control words of the search's record
+  // (AttnBeamDev::ctrl).  The launch covers every row slot, and a block returns before its first barrier when
+  // b >= guard[1] (live rows) or the stop step is reached (guard[2] != 0 and guard[0] >= guard[2]) -- uniform per block.
+  const int* guard;
 };
 // After launch_attn_decode with an exit_state, on the same stream: steps = largest end step + 1 if all B rows ended, else
 // S; written to *steps_dev, and tokens [B][S], probs [B][S][V], alpha [B][S][Tk] (optional) zeroed for the steps
@@ -365,6 +369,43 @@ struct BeamDev {
 };
 hipError_t launch_beam_dev_init(const BeamDev& b, int64_t go_token, hipStream_t s);
 hipError_t launch_beam_dev_advance(const BeamDev& b, hipStream_t s);
+// The same for the LSTM-attention heads (Attention / AttentionV2.forward_beam; attn_beam.hip).  Modelled on BeamDev; what
+// differs is the reference's bookkeeping: step 0 ranks row 0 of a sample's `beam` identical rows, every completion lowers the
+// sample's k (so completions never exceed beam), the LSTM state of a survivor follows its parent row (idx_h) but its coverage
+// memory follows its candidate rank (idx_m), and the final pick depends on whether the sample's last step completed anything.
+struct AttnBeamDev {
+  int* ctrl;            // [0] step, [1] live rows, [2] stop-at step (0 = none), [3] steps run
+  int64_t* tok;         // [cap] input token of every live hypothesis row
+  float* scores;        // [cap]
+  int* map;             // [cap] sample of a row
+  int* idx_h;           // [cap] row of the step just run whose LSTM state the new row resumes (its parent)
+  int* idx_m;           // [cap] row of the step just run whose coverage memory it resumes (first row of the sample + rank)
+  int* seg;             // [N][3] first row, rows ranked, candidates wanted (k)
+  int* comp_n;          // [N] completed hypotheses
+  int* fin;             // [N] sample finished (k == 0)
+  int* last_completed;  // [N] the last step that processed the sample completed a hypothesis
+  int* comp_t;          // [N][beam] step at which a hypothesis completed
+  int* comp_par;        // [N][beam] its parent row (that step's row order)
+  float* comp_score;    // [N][beam]
+  int* hist_par;        // [S][cap] parent row of the hypothesis a step created at row r (the next step's row order)
+  int* hist_tok;        // [S][cap] its token
+  const float* topv; const int* topi;   // [N][beam] candidates of the step (launch_beam_topk_batch)
+  int N, beam, cap, V, S, end_token;
+};
+hipError_t launch_attn_beam_dev_init(const AttnBeamDev& b, int64_t go_token, hipStream_t s);
+hipError_t launch_attn_beam_dev_advance(const AttnBeamDev& b, hipStream_t s);
+// The three row gathers between two steps in one launch over all cap row slots, guarded by ctrl (live rows, stop step):
+// h_in / c_in [row] = h_out / c_out [idx_h[row]] (width H), mem_in [row] = mem_out [idx_m[row]] (width ld).
+hipError_t launch_attn_beam_dev_gather(const int* ctrl, const int* idx_h, const int* idx_m, const float* h_out, const float* c_out,
+                                       const float* mem_out, float* h_in, float* c_in, float* mem_in, int cap, int H, int ld,
+                                       hipStream_t s);
+// The final pick of every sample: seq [N][S] (zeros beyond the length), len [N], score [N]; with path != nullptr also
+// path [N][S] | plen [N], the rows of every step's launch that launch_attn_alpha_gather[_ld] reads.
+hipError_t launch_attn_beam_dev_finish(const AttnBeamDev& b, int64_t* seq, int* len, float* score, int* path, int* plen,
+                                       hipStream_t s);
+// launch_attn_alpha_gather for a history whose rows have the stride ld >= Tk: hist [S][cap][ld], out [N][S][Tk]
+hipError_t launch_attn_alpha_gather_ld(const float* hist, const int* path, const int* len, float* out, int N, int S, int cap,
+                                       int ld, int Tk, hipStream_t s);
 // anc_new[row][0 .. t-2] = anc_old[prev[row]][...], anc_new[row][t-1] = prev[row] (t = *step_in, published to *step_out):
 // which cache row holds each earlier position of hypothesis `row`.  rows_ptr / stop (optional): the device-side beam loop's
 // guards -- rows >= *rows_ptr are skipped, and nothing happens once *stop != 0 and t >= *stop.

@@ -131,9 +131,13 @@ __device__ __forceinline__ void attn_end_step(const AttnDecP p, int b, int step,
 // RAGGED (step mode only): the row's sample has its own memory length and its own place in ONE packed memory
 // (AttnDecP::smp_row0 / smp_T), and the state / history rows have the stride st_ld.  The length is uniform within a block,
 // so every barrier is still reached by all of its threads; no shared array is added.
-template <bool WIDE, bool EXIT, bool RAGGED = false>
+// GUARD (RAGGED builds of the device-side beam loop, launched for every row slot): a block whose row is not live, or whose
+// search has reached its stop step, returns here -- before any barrier, on words every thread of the block reads alike.
+template <bool WIDE, bool EXIT, bool RAGGED = false, bool GUARD = false>
 __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   constexpr int H = 256;
+  if constexpr (GUARD)
+    if ((int)blockIdx.x >= p.guard[1] || (p.guard[2] && p.guard[0] >= p.guard[2])) return;
   __shared__ float x_s[3 * H];  // [context | embedding | h]  = LSTMCell input
   __shared__ float c_s[H], hq_s[H];
   __shared__ float mem_s[AD_MAXT + 16], alpha_s[AD_MAXT], red_s[32];
@@ -343,6 +347,12 @@ hipError_t launch_attn_decode(const AttnDecP& p, hipStream_t s) {
   const bool ragged = p.smp_row0 || p.smp_T || p.st_ld;
   if (ragged && (!p.step_mode || p.S != 1 || p.teacher || p.exit_state || !p.smp_row0 || !p.smp_T || p.st_ld < 1 || p.st_ld > AD_MAXT))
     return hipErrorInvalidValue;
+  if (p.guard && !ragged) return hipErrorInvalidValue;
+  if (p.guard) {
+    hipLaunchKernelGGL((p.V <= 1024 ? attn_decode_kernel<false, false, true, true> : attn_decode_kernel<true, false, true, true>),
+                       dim3(p.B), dim3(1024), 0, s, p);
+    return hipGetLastError();
+  }
   if (ragged) {
     hipLaunchKernelGGL((p.V <= 1024 ? attn_decode_kernel<false, false, true> : attn_decode_kernel<true, false, true>), dim3(p.B),
                        dim3(1024), 0, s, p);

@@ -638,6 +638,48 @@ class Engine:
         Bahdanau cell); the context itself answers, once the weights are finalized."""
         return bool(self.lib.d2t_decode_attn_supports_ragged_beam(self.ctx))
 
+    def supports_device_attn_beam(self):
+        """Whether this context has the device-side LSTM-attention beam search (set_attn_beam_device,
+        decode_attn_beam_batch_async): an LSTM-attention head with the coverage or the Bahdanau cell."""
+        return bool(self.lib.d2t_decode_attn_supports_device_beam(self.ctx))
+
+    def set_attn_beam_device(self, on):
+        """on: decode_attn_beam / _batch / _batch_ragged keep the hypothesis bookkeeping on the device (one captured graph
+        per search, no host round trip per step) and return the same results; off (default): the host loop."""
+        self._check(self.lib.d2t_set_attn_beam_device(self.ctx, int(bool(on))), "set_attn_beam_device")
+
+    def attn_beam_device_runs(self):
+        """Searches this context has run on the device-side loop."""
+        return int(self.lib.d2t_decode_attn_beam_device_runs(self.ctx))
+
+    def decode_attn_beam_batch_async(self, packed, lengths, beam_size, return_alpha=False):
+        """decode_attn_beam_batch_ragged without the wait (d2t_decode_attn_beam_batch_submit): returns
+        (seq [N,S] int64, len [N] int32, score [N] float32[, alpha [N,S,max Tk]], ticket), tensors on the memory's device that
+        one of the engine's decode streams is still writing.  They are complete once `ticket` is (wait_ticket / ticket_done);
+        decode_steps(ticket) is then [the steps the search executed].  Sample i's result is seq[i, :len[i]], score[i] and
+        alpha[i, :len[i], :attn_keys(lengths[i])].  `packed` and the outputs stay referenced here until the ticket
+        completes."""
+        self._on_device(packed, "memory")
+        packed = packed.float().contiguous()
+        lengths = [int(T) for T in lengths]
+        N, S = len(lengths), self.cfg.batch_max_length + 1
+        if packed.dim() != 2 or packed.shape[0] != sum(lengths):
+            raise ValueError(f"packed memory {tuple(packed.shape)} does not hold the {sum(lengths)} rows of `lengths`")
+        dev = packed.device
+        seq = torch.empty((max(N, 1), S), dtype=torch.int64, device=dev)
+        n = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
+        score = torch.empty((max(N, 1),), dtype=torch.float32, device=dev)
+        ld = self.attn_keys(max(lengths)) if lengths else 0
+        alpha = torch.empty((max(N, 1), S, max(ld, 1)), dtype=torch.float32, device=dev) if return_alpha else None
+        Ts = (C.c_int32 * max(1, N))(*lengths)
+        t = C.c_int64(0)
+        self._check(self.lib.d2t_decode_attn_beam_batch_submit(self.ctx, _lib.ptr(packed), N, Ts, int(beam_size), _lib.ptr(seq),
+                                                               _lib.ptr(n), _lib.ptr(score), _lib.ptr(alpha),
+                                                               _lib.stream_of(packed), C.byref(t)),
+                    "decode_attn_beam_batch_submit")
+        ticket = self._hold(int(t.value), packed, (packed, seq, n, score, alpha))
+        return (seq, n, score, ticket) if alpha is None else (seq, n, score, alpha, ticket)
+
     def attn_map_bytes(self, T, beam_size):
         """Bytes of alignment history one sample adds to a beam search with maps (d2t_decode_attn_beam_batch_alpha)."""
         return (self.cfg.batch_max_length + 1) * int(beam_size) * self.attn_keys(T) * 4

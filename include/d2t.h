@@ -360,6 +360,34 @@ int64_t d2t_ragged_beam_tables(int32_t N, const int32_t* T, int32_t* row0_out, i
 int d2t_decode_attn_beam(d2t_ctx* ctx, const float* memory, int32_t T, int32_t beam_size, int64_t* seq_out,
                          int32_t* len_out, float* score_out, d2t_stream stream);
 
+/* ---- LSTM-attention beam search with the bookkeeping on the device ----------------------------------------------
+ * The searches above run a host loop: one device -> host copy, one synchronisation and one upload per step.  The
+ * device-side loop keeps the reference's hypothesis bookkeeping in a record on the device (AttnBeamDev), runs the step
+ * kernel for all N x beam row slots under a guard on the live row count, and is one captured graph per (N, beam, row
+ * stride capacity, maps on / off) -- no host round trip inside the search, so it can also be SUBMITTED.  Same results as the
+ * host loop, bit for bit.  The row stride of its state and history is the largest Tk rounded up to 256, so searches whose
+ * longest memories share that capacity replay one graph.
+ *
+ * d2t_decode_attn_supports_device_beam: 1 for an Attn context whose beam search exists (coverage / Bahdanau cells).
+ * d2t_set_attn_beam_device(ctx, 1): d2t_decode_attn_beam, _batch, _batch_alpha and _batch_ragged run the device-side loop
+ * (default 0: the host loop).  D2T_ESTATE where the context has no device-side search.
+ * d2t_decode_attn_beam_device_runs: searches this context has run on the device-side loop (synchronous or submitted).
+ *
+ * d2t_decode_attn_beam_batch_submit: d2t_decode_attn_beam_batch_ragged without the wait (equal lengths are the uniform
+ * case).  packed [sum T][256] and every output are DEVICE buffers: seq_dev [N][S] (zeros beyond a sample's length),
+ * len_dev [N], score_dev [N], alpha_dev NULL or [N][S][max Tk]; T is a host array.  The decode chains take turns
+ * (d2t_set_decode_chains); the search runs on its chain's stream behind the caller's stream and the call returns once it is
+ * enqueued.  The outputs are complete once *ticket_out is (d2t_decode_query / d2t_decode_wait_ticket); d2t_decode_steps then
+ * reports ONE entry, the steps the search executed.  `packed` may be released once the call has returned and the caller's
+ * stream work in front of it has run (the search reads its own copy).  Refusals are those of
+ * d2t_decode_attn_beam_batch_ragged, made before anything is enqueued; the context stays usable. */
+int32_t d2t_decode_attn_supports_device_beam(const d2t_ctx* ctx);
+int d2t_set_attn_beam_device(d2t_ctx* ctx, int32_t on);
+int64_t d2t_decode_attn_beam_device_runs(const d2t_ctx* ctx);
+int d2t_decode_attn_beam_batch_submit(d2t_ctx* ctx, const float* packed, int32_t N, const int32_t* T, int32_t beam_size,
+                                      int64_t* seq_dev, int32_t* len_dev, float* score_dev, float* alpha_dev, d2t_stream stream,
+                                      int64_t* ticket_out);
+
 /* ---- convolution arithmetic ------------------------------------------------
  * D2T_CONV_FP32   exact fp32 on v_mfma_f32_32x32x2_f32.
  * D2T_CONV_BF16X3 (default of d2t_create, as of doc2tex_amd.Model) backbone / patch-embed convolutions on the bf16 matrix cores with each fp32 operand
@@ -662,6 +690,27 @@ int d2t_op_attn_decode_finalize(const uint64_t* exit_state, int32_t* steps_dev, 
  * (values < cap where j < len[i]), len [N] in [0, S].  out must be 16-byte aligned. */
 int d2t_op_attn_alpha_gather(const float* hist, const int32_t* path, const int32_t* len, float* out, int32_t N, int32_t S,
                              int32_t cap, int32_t Tk, d2t_stream stream);
+/* The record of the device-side LSTM-attention beam search (kernels.h AttnBeamDev), every array a device buffer of the
+ * caller: ctrl [4] = {step, live rows, stop-at step, steps run}; tok (int64), scores, map, idx_h, idx_m [cap]; seg [N][3] =
+ * {first row, rows ranked, candidates wanted}; comp_n, fin, last_completed [N]; comp_t, comp_par, comp_score [N][beam];
+ * hist_par, hist_tok [S][cap]; topv, topi [N][beam] the step's candidates (d2t_op_beam_topk).  cap >= N * beam, N <= 1024,
+ * beam <= 16.
+ * d2t_op_attn_beam_advance: init != 0 lays out step 0 (beam rows per sample from go_token, seg = {i * beam, 1, beam});
+ * init == 0 is ONE step of the bookkeeping on the record (a stopped record is left alone).  D2T_EINVAL for a record whose
+ * step, segments or candidates would index outside it.
+ * d2t_op_attn_beam_finish: the final pick of every sample: seq [N][S] (zeros beyond the length), len [N], score [N], and with
+ * path / plen (both or neither) the chosen launch rows path [N][S] and their count plen [N]. */
+typedef struct d2t_op_attn_beam_rec {
+  int32_t* ctrl; int64_t* tok; float* scores;
+  int32_t *map, *idx_h, *idx_m, *seg, *comp_n, *fin, *last_completed, *comp_t, *comp_par;
+  float* comp_score;
+  int32_t *hist_par, *hist_tok;
+  const float* topv; const int32_t* topi;
+  int32_t N, beam, cap, V, S, end_token;
+} d2t_op_attn_beam_rec;
+int d2t_op_attn_beam_advance(const d2t_op_attn_beam_rec* r, int32_t init, int64_t go_token, d2t_stream stream);
+int d2t_op_attn_beam_finish(const d2t_op_attn_beam_rec* r, int64_t* seq, int32_t* len, float* score, int32_t* path, int32_t* plen,
+                            d2t_stream stream);
 
 /* ---- fused cross-entropy ------------------------------------------------------------------------------------------
  * The criterion of the reference's training step -- nn.CrossEntropyLoss(ignore_index = PAD, reduction = 'none') on

@@ -18,6 +18,14 @@ set and consecutive forwards differ in row count and memory length.
                   are the TFM head's); --mixed 0 then pays the host-side step loop's batch_max_length + 1 round trips once per
                   size bucket, --mixed 1 once per page set (d2t_decode_attn_beam_batch_ragged).
 
+  --device-beam 1   (with --head attnv2 --beam K) Model.attn_beam_device: the search's bookkeeping stays on the device, one
+                    captured graph per search instead of a host round trip per step;
+  --submit 1        (with --head attnv2 --beam K) Model.beam_search_batch_async: a page set's search is submitted and its
+                    results are read after the NEXT page set's encoders have been issued, which then run beside the search;
+  --end-bias B, --max-length L   the generator's [s] bias and batch_max_length of the attnv2 stack (default: the config's):
+                    with a bias at which searches end after a few tens of steps the host loop stops at once while the
+                    device-side graph still pays its empty launches up to L + 1.
+
 Prints one JSON line: formulas/s end to end (uint8 pages -> LaTeX strings)."""
 import argparse
 import json
@@ -52,22 +60,31 @@ def main():
     ap.add_argument("--page-sets", type=int, default=4, help="distinct page sets cycled through")
     ap.add_argument("--beam", type=int, default=0, help="beam width; 0 = greedy decoding through the decode groups")
     ap.add_argument("--head", default="tfm", choices=["tfm", "attnv2"], help="prediction head on C4's encoder")
+    ap.add_argument("--device-beam", type=int, default=0, choices=[0, 1], help="attnv2 beam search: bookkeeping on the device")
+    ap.add_argument("--submit", type=int, default=0, choices=[0, 1], help="attnv2 beam search: submitted, read one page set later")
+    ap.add_argument("--end-bias", type=float, default=None, help="attnv2: bias of the generator's [s] logit")
+    ap.add_argument("--max-length", type=int, default=None, help="attnv2: batch_max_length")
     args = ap.parse_args()
     if args.head == "attnv2" and not args.beam:
         ap.error("--head attnv2 times the beam search: give --beam K")
+    if (args.device_beam or args.submit or args.end_bias is not None or args.max_length) and args.head != "attnv2":
+        ap.error("--device-beam / --submit / --end-bias / --max-length belong to --head attnv2 --beam K")
     dev = torch.device("cuda", 0)
     cfg = synth.make_config("C4", device=str(dev))
     if args.head == "attnv2":
         cfg["Prediction"] = {"name": "Attnv2", "params": {
             "seqmodel": "TFM", "input_size": 256, "hidden_size": 256, "kernel_size": 2, "kernel_dim": 128, "embed_target": True,
             "enc_init": True, "attn_type": "coverage", "method": "concat", "teacher_forcing": 1.0, "droprate": 0.2}}
+        if args.max_length:
+            cfg["batch_max_length"] = args.max_length
     model = Model(cfg)
     tmpl = {k: v for k, v in model.state_dict().items() if not k.endswith("image_positional_encoder.pe")}
-    model.load_state_dict(synth.synth_state_dict(tmpl), strict=False)
+    model.load_state_dict(synth.synth_state_dict(tmpl, end_bias=args.end_bias or 0.0), strict=False)
     model.eval().to(dev)
     model.pipelined, model.decode_chains, model.decode_group, model.reserved_blocks = True, args.chains, args.group, 0
     if args.mixed:
         model.decode_group_mixed, model.decode_group_rows = True, args.group_rows
+    model.attn_beam_device = bool(args.device_beam)
     opt = {"imgH": None, "imgW": None, "max_dimension": cfg["max_dimension"], "min_dimension": [32, 32], "mean": 0.5,
            "std": 0.5, "rgb": False, "pad": False, "device": str(dev)}
     pre = Preprocessor(opt, "demo")
@@ -90,7 +107,8 @@ def main():
     side = torch.cuda.Stream(dev)
     L = (cfg["batch_max_length"] if attn else cfg["Prediction"]["params"]["max_seq_len"]) + 1
     ring = [torch.empty((3 * n, L), dtype=torch.int64).pin_memory() for _ in range(64)]
-    state = {"done": 0, "t_post": 0.0, "seq": 0, "sample": ""}
+    state = {"done": 0, "t_post": 0.0, "seq": 0, "sample": "", "lens": 0, "searches": 0, "search_steps": 0}
+    submitted = []  # --submit 1: the handles of the page set whose search is still running
     waiting, pending = [], []  # forwards whose decode may not be launched yet; copies in flight (pinned slot, rows, event)
 
     def copy_out(force):
@@ -122,6 +140,27 @@ def main():
             state["done"] += len(latex)
             state["sample"] = latex[0]
 
+    def emit(found):
+        tokens = torch.zeros((len(found), L), dtype=torch.int64)  # PAD behind every hypothesis
+        for r, (seq, *_) in enumerate(found):
+            tokens[r, :seq.shape[1]] = seq[0]
+            state["lens"] += seq.shape[1]
+        t = time.perf_counter()
+        latex = dec.to_latex(tokens, "word", postprocess=True)
+        state["t_post"] += time.perf_counter() - t
+        state["done"] += len(latex)
+        state["sample"] = latex[0]
+
+    def drain():
+        found = []
+        for h in submitted:
+            found += h.result()
+            state["searches"] += 1
+            state["search_steps"] += h.steps()
+        submitted.clear()
+        if found:
+            emit(found)
+
     def step(i):
         tensors, errors = pre.batch(sets[i % len(sets)])
         assert all(e is None for e in errors)
@@ -129,20 +168,22 @@ def main():
         for t in tensors:
             buckets.setdefault(t._base.data_ptr(), t._base)
         assert len(buckets) == 3 and {tuple(x.shape[2:]) for x in buckets.values()} == BUCKETS, [x.shape for x in buckets.values()]
+        if args.beam and args.submit:
+            with torch.no_grad():  # this page set's encoders are issued while the previous page set's search runs
+                if args.mixed:
+                    handles = [model.beam_search_batch_async(list(buckets.values()), args.beam)]
+                else:
+                    handles = [model.beam_search_batch_async(x, args.beam) for x in buckets.values()]
+            drain()
+            submitted.extend(handles)
+            return
         if args.beam:
             with torch.no_grad():
                 if args.mixed:
                     found = model.beam_search_batch(list(buckets.values()), args.beam)
                 else:
                     found = [r for x in buckets.values() for r in model.beam_search_batch(x, args.beam)]
-            tokens = torch.zeros((len(found), L), dtype=torch.int64)  # PAD behind every hypothesis
-            for r, (seq, *_) in enumerate(found):
-                tokens[r, :seq.shape[1]] = seq[0]
-            t = time.perf_counter()
-            latex = dec.to_latex(tokens, "word", postprocess=True)
-            state["t_post"] += time.perf_counter() - t
-            state["done"] += len(latex)
-            state["sample"] = latex[0]
+            emit(found)
             return
         for x in buckets.values():
             with torch.no_grad():
@@ -153,13 +194,15 @@ def main():
 
     for i in range(args.warmup):
         step(i)
+    drain()
     copy_out(True)
     consume(True)
     torch.cuda.synchronize(dev)
-    state["done"], state["t_post"] = 0, 0.0
+    state.update(done=0, t_post=0.0, lens=0, searches=0, search_steps=0)
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(args.warmup + i)
+    drain()
     copy_out(True)
     consume(True)
     torch.cuda.synchronize(dev)
@@ -169,7 +212,10 @@ def main():
                       "value": round(state["done"] / el, 1), "unit": "formulas/s", "mixed": args.mixed, "steps": args.steps,
                       "per_size": n, "group": args.group, "beam": args.beam, "head": args.head, "ms_per_page_set": round(el / args.steps * 1e3, 2),
                       "postprocess_ms_per_page_set": round(state["t_post"] / args.steps * 1e3, 2),
-                      "sizes": sorted(BUCKETS), "sample_latex_chars": len(state["sample"])}))
+                      "sizes": sorted(BUCKETS), "sample_latex_chars": len(state["sample"]),
+                      "device_beam": args.device_beam, "submit": args.submit, "end_bias": args.end_bias, "max_length": L - 1,
+                      "mean_result_len": round(state["lens"] / max(state["done"], 1), 1) if args.beam else None,
+                      "mean_search_steps": round(state["search_steps"] / state["searches"], 1) if state["searches"] else None}))
 
 
 if __name__ == "__main__":
