@@ -186,6 +186,21 @@ SIGNATURES = {
     "d2t_op_attn_beam_finish": (_I, [C.POINTER(D2TOpAttnBeamRec)] + [_P] * 6),
     "d2t_op_attn_lstm_bwd": (_I, [C.POINTER(D2TOpAttnLstmBwdArgs), _P]),
     "d2t_op_loc_unfold_bwd": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I] + [_P] * 5),
+    # the remaining kernels of the training step one at a time (test infrastructure)
+    "d2t_op_train_gc_pool": (_I, [_P] * 8 + [_I] * 4 + [_P]),
+    "d2t_op_train_bcast_add": (_I, [_P] * 6 + [_I] * 3 + [_P]),
+    "d2t_op_global_context": (_I, [_P] * 10 + [_I] * 3 + [_P]),
+    "d2t_op_embed_train": (_I, [_P] * 4 + [_I] * 4 + [C.c_float, _P]),
+    "d2t_op_embed_bwd": (_I, [_P] * 3 + [_I] * 3 + [C.c_float, _I, _P]),
+    "d2t_op_dropout_mask": (_I, [_P, _L, C.c_float, C.c_uint64, C.c_uint64, _P]),
+    "d2t_op_apply_mask": (_I, [_P, _P, C.c_float, _P, _L, _P]),
+    "d2t_op_bicubic_table": (_I, [_P, _P] + [_I] * 5 + [C.c_float, C.c_float, _I, _P]),
+    "d2t_op_sum_over_batch": (_I, [_P, _P, _I, _L, _L, _P]),
+    "d2t_op_token_rows": (_I, [_P, _P] + [_I] * 5 + [_P]),
+    "d2t_op_sum_rows_strided": (_I, [_P, _P, _I, _L, _I, _I, _P]),
+    "d2t_op_train_mean_h": (_I, [_P] * 4 + [_I] * 4 + [_P]),
+    "d2t_op_train_maxpool_w": (_I, [_P] * 4 + [_I] * 9 + [_P]),
+    "d2t_op_train_ew": (_I, [_P] * 4 + [_L, _I, _P]),
 }
 # include/d2t_prep.h
 SIGNATURES_PREP = {

@@ -132,6 +132,26 @@ int d2t_op_layernorm(const float* x, const float* gamma, const float* beta, floa
   return launch_layernorm(x, gamma, beta, y, rows, D, eps, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;
 }
 
+// The fused GlobalContext block as the encoder runs it (engine.hip, the end of a ResNet stage): one temporary workspace laid out
+// like the engine's gc_ws, logits [B*HW] | ctx [B][C] | y [B][C] without padding in between
+int d2t_op_global_context(float* x, const float* wg, const float* bg, const float* w1, const float* b1, const float* ln_g,
+                          const float* ln_b, const float* w2, const float* b2, float* ctx_out, int32_t B, int32_t HW, int32_t C,
+                          d2t_stream stream) {
+  if (!x || !wg || !bg || !w1 || !b1 || !ln_g || !ln_b || !w2 || !b2) return D2T_EINVAL;
+  if (B < 1 || B > 65535 || HW < 1 || HW > (1 << 24) || C < 4 || C > 512 || C % 4) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t nl = (size_t)B * HW, nc = (size_t)B * C;
+  float* buf = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&buf), (nl + 2 * nc) * 4) != hipSuccess) return D2T_ENOMEM;
+  float *logits = buf, *ctx = buf + nl, *y = ctx + nc;
+  const GCParams w{wg, bg, w1, b1, ln_g, ln_b, w2, b2};
+  hipError_t e = launch_global_context(x, w, logits, ctx, y, B, HW, C, s);
+  if (e == hipSuccess && ctx_out) e = hipMemcpyAsync(ctx_out, ctx, nc * 4, hipMemcpyDeviceToDevice, s);
+  hipStreamSynchronize(s);
+  hipFree(buf);
+  return op_status(e);
+}
+
 int d2t_op_vit_attention(const float* qkv, float* y, int32_t B, int32_t N, int32_t heads, d2t_stream stream) {
   if (!qkv || !y) return D2T_EINVAL;
   return launch_vit_attention(qkv, y, B, N, heads, (hipStream_t)stream) == hipSuccess ? D2T_OK : D2T_EHIP;

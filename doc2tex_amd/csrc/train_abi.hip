@@ -464,4 +464,163 @@ int d2t_op_loc_unfold_bwd(const float* dwloc, const float* dbloc, int32_t B, con
                                              d_proj_b, (hipStream_t)stream));
 }
 
+// The remaining kernels of the step one at a time (include/d2t.h): nodes of the tape through an OpCtx, launchers as they are.
+static bool gc_width(int C) { return C >= 4 && C <= 512 && C % 4 == 0; }  // thread = channel / float4 rows of the gc_* kernels
+
+int d2t_op_train_gc_pool(const float* x, const float* wg, const float* bg, const float* dctx, float* ctx, float* dx, float* dwg,
+                         float* dbg, int32_t B, int32_t H, int32_t W, int32_t C, d2t_stream stream) {
+  if (!x || !wg || !bg || !dctx) return D2T_EINVAL;
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > (1 << 24) || !gc_width(C)) return D2T_EINVAL;
+  OpCtx o(0, (hipStream_t)stream);
+  Tr& tr = o.tr;
+  o.put("g.weight", wg, {C});
+  o.put("g.bias", bg, {1});
+  auto run = [&]() -> int {
+    int xin, out;
+    RC(tr.new_tensor((long long)B * H * W, C, &xin, B, H, W, const_cast<float*>(x)));
+    RC(tr.gc_pool(xin, "g", &out));
+    RC(o.out(ctx, o.st.t[out].p, (size_t)B * C));
+    o.st.t[out].grad = const_cast<float*>(dctx);
+    RC(tr.backward());
+    RC(o.out(dx, o.st.t[xin].grad, (size_t)B * H * W * C));
+    RC(o.grad(dwg, "g.weight", C));
+    RC(o.grad(dbg, "g.bias", 1));
+    return D2T_OK;
+  };
+  return o.finish(run());
+}
+
+int d2t_op_train_bcast_add(const float* x, const float* y, const float* dout, float* out, float* dx, float* dy, int32_t B,
+                           int32_t HW, int32_t C, d2t_stream stream) {
+  if (!x || !y || !dout) return D2T_EINVAL;
+  if (B < 1 || B > 65535 || HW < 1 || HW > (1 << 24) || !gc_width(C)) return D2T_EINVAL;
+  OpCtx o(0, (hipStream_t)stream);
+  Tr& tr = o.tr;
+  auto run = [&]() -> int {
+    int xin, yin, res;
+    RC(tr.new_tensor((long long)B * HW, C, &xin, B, 1, HW, const_cast<float*>(x)));
+    RC(tr.new_tensor(B, C, &yin, 0, 0, 0, const_cast<float*>(y)));
+    RC(tr.bcast_add(xin, yin, &res));
+    RC(o.out(out, o.st.t[res].p, (size_t)B * HW * C));
+    o.st.t[res].grad = const_cast<float*>(dout);
+    RC(tr.backward());
+    RC(o.out(dx, o.st.t[xin].grad, (size_t)B * HW * C));
+    RC(o.out(dy, o.st.t[yin].grad, (size_t)B * C));
+    return D2T_OK;
+  };
+  return o.finish(run());
+}
+
+int d2t_op_train_mean_h(const float* x, const float* dy, float* y, float* dx, int32_t B, int32_t H, int32_t W, int32_t C,
+                        d2t_stream stream) {
+  if (!x || !dy || B < 1 || H < 1 || W < 1 || C < 1 || (long long)B * H * W * C > (1ll << 31)) return D2T_EINVAL;
+  OpCtx o(0, (hipStream_t)stream);
+  Tr& tr = o.tr;
+  auto run = [&]() -> int {
+    int xin, out;
+    RC(tr.new_tensor((long long)B * H * W, C, &xin, B, H, W, const_cast<float*>(x)));
+    RC(tr.mean_h(xin, &out));
+    RC(o.out(y, o.st.t[out].p, (size_t)B * W * C));
+    o.st.t[out].grad = const_cast<float*>(dy);
+    RC(tr.backward());
+    RC(o.out(dx, o.st.t[xin].grad, (size_t)B * H * W * C));
+    return D2T_OK;
+  };
+  return o.finish(run());
+}
+
+int d2t_op_train_maxpool_w(const float* x, const float* dy, float* y, float* dx, int32_t B, int32_t H, int32_t W, int32_t C,
+                           int32_t KW, int32_t SH, int32_t SW, int32_t PH, int32_t PW, d2t_stream stream) {
+  if (!x || !dy || (KW != 1 && KW != 2) || B < 1 || H < 1 || W < 1 || C < 4 || C % 4 || SH < 1 || SW < 1) return D2T_EINVAL;
+  if (PH < 0 || PH > 1 || PW < 0 || PW > KW / 2 || H + 2 * PH < 2 || W + 2 * PW < KW) return D2T_EINVAL;  // nn.MaxPool2d's own rule
+  if ((long long)B * H * W * C > (1ll << 31)) return D2T_EINVAL;
+  OpCtx o(0, (hipStream_t)stream);
+  Tr& tr = o.tr;
+  auto run = [&]() -> int {
+    int xin, out;
+    RC(tr.new_tensor((long long)B * H * W, C, &xin, B, H, W, const_cast<float*>(x)));
+    RC(tr.pool(xin, SH, SW, PH, PW, &out, KW));
+    const TT yo = o.st.t[out];
+    RC(o.out(y, yo.p, (size_t)yo.rows * C));
+    o.st.t[out].grad = const_cast<float*>(dy);
+    RC(tr.backward());
+    RC(o.out(dx, o.st.t[xin].grad, (size_t)B * H * W * C));
+    return D2T_OK;
+  };
+  return o.finish(run());
+}
+
+int d2t_op_train_ew(const float* x, const float* dy, float* y, float* dx, int64_t n, int32_t op, d2t_stream stream) {
+  if (!x || !dy || n < 4 || n % 4 || n > (1ll << 31) || (op != 0 && op != 1)) return D2T_EINVAL;
+  OpCtx o(0, (hipStream_t)stream);
+  Tr& tr = o.tr;
+  auto run = [&]() -> int {
+    int xin, out;
+    RC(tr.new_tensor(n / 4, 4, &xin, 0, 0, 0, const_cast<float*>(x)));
+    RC(op == 0 ? tr.gelu(xin, &out) : tr.relu(xin, &out));
+    RC(o.out(y, o.st.t[out].p, (size_t)n));
+    o.st.t[out].grad = const_cast<float*>(dy);
+    RC(tr.backward());
+    RC(o.out(dx, o.st.t[xin].grad, (size_t)n));
+    return D2T_OK;
+  };
+  return o.finish(run());
+}
+
+int d2t_op_embed_train(const float* E, const float* pe, const int64_t* tok, float* x, int32_t rows, int32_t L, int32_t V,
+                       int32_t D, float scale, d2t_stream stream) {
+  if (!E || !pe || !tok || !x || rows < 1 || L < 1 || V < 1 || D < 1) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int64_t> h((size_t)rows);  // the kernel indexes E by the token
+  if (hipMemcpyAsync(h.data(), tok, (size_t)rows * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return D2T_EHIP;
+  for (int64_t t : h)
+    if (t < 0 || t >= V) return D2T_EINVAL;
+  return op_status(launch_embed_train(E, pe, tok, x, rows, L, D, scale, s));
+}
+
+int d2t_op_embed_bwd(const float* dx, const int64_t* tok, float* dE, int32_t rows, int32_t V, int32_t D, float scale,
+                     int32_t pad_id, d2t_stream stream) {
+  if (!dx || !tok || !dE || rows < 1 || V < 1 || D < 1 || D > 1024) return D2T_EINVAL;  // four columns per thread of 256
+  return op_status(launch_embed_bwd(dx, tok, dE, rows, V, D, scale, pad_id, (hipStream_t)stream));
+}
+
+int d2t_op_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t stream_id, d2t_stream stream) {
+  if (!mask || n < 1 || !(p >= 0.f) || p >= 1.f) return D2T_EINVAL;
+  return op_status(launch_dropout_mask(mask, (size_t)n, p, seed, stream_id, (hipStream_t)stream));
+}
+
+int d2t_op_apply_mask(const float* a, const uint8_t* mask, float scale, float* out, int64_t n, d2t_stream stream) {
+  if (!a || !mask || !out || n < 1) return D2T_EINVAL;
+  return op_status(launch_apply_mask(a, mask, scale, out, (size_t)n, (hipStream_t)stream));
+}
+
+int d2t_op_bicubic_table(const float* src, float* dst, int32_t GH, int32_t GW, int32_t gh, int32_t gw, int32_t D, float scale_h,
+                         float scale_w, int32_t transpose, d2t_stream stream) {
+  if (!src || !dst || src == dst || GH < 1 || GW < 1 || gh < 1 || gw < 1 || D < 1) return D2T_EINVAL;
+  if ((long long)GH * GW * D > (1ll << 31) || (long long)gh * gw * D > (1ll << 31)) return D2T_EINVAL;
+  if (!(scale_h > 0.f) || !(scale_w > 0.f) || !(scale_h * (float)gh < 1e9f) || !(scale_w * (float)gw < 1e9f)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return op_status(transpose ? launch_bicubic_table_bwd(src, dst, GH, GW, gh, gw, D, scale_h, scale_w, s)
+                             : launch_bicubic_table(src, dst, GH, GW, gh, gw, D, scale_h, scale_w, s));
+}
+
+int d2t_op_sum_over_batch(const float* x, float* out, int32_t B, int64_t stride, int64_t n, d2t_stream stream) {
+  if (!x || !out || B < 1 || n < 1 || stride < n) return D2T_EINVAL;
+  return op_status(launch_sum_over_batch(x, out, B, stride, n, (hipStream_t)stream));
+}
+
+int d2t_op_token_rows(const float* src, float* dst, int32_t B, int32_t n, int32_t skip, int32_t D, int32_t scatter,
+                      d2t_stream stream) {
+  if (!src || !dst || src == dst || B < 1 || n < 1 || skip < 0 || D < 1 || (long long)B * ((long long)n + skip) * D > (1ll << 31))
+    return D2T_EINVAL;
+  return op_status(launch_token_rows(src, dst, B, n, skip, D, scatter != 0, (hipStream_t)stream));
+}
+
+int d2t_op_sum_rows_strided(const float* x, float* out, int32_t B, int64_t stride_rows, int32_t row, int32_t D,
+                            d2t_stream stream) {
+  if (!x || !out || B < 1 || D < 1 || stride_rows < 1 || row < 0 || row >= stride_rows) return D2T_EINVAL;
+  return op_status(launch_sum_rows_strided(x, out, B, stride_rows, row, D, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -793,6 +793,59 @@ int d2t_op_loc_unfold_bwd(const float* dwloc, const float* dbloc, int32_t B, con
                           const float* proj_w, int32_t H, int32_t kd, int32_t taps, float* d_conv_w, float* d_conv_b,
                           float* d_proj_w, float* d_proj_b, d2t_stream stream);
 
+/* ---- the remaining kernels of the training step one at a time (test infrastructure; tests/test_train_small_ops_gpu.py) ----
+ * Thin: each entry launches exactly what the tape (csrc/train.hip) or the engine launches, on caller tensors (fp32, device,
+ * maps NHWC).  Every size is checked before anything is launched; what a kernel does not serve is D2T_EINVAL with nothing
+ * written.  The d2t_op_train_* entries run one node of the tape, forward + backward, and are synchronous as the ones above
+ * (output pointers may be NULL); the others are asynchronous on the stream unless stated. */
+/* GlobalContext's pooling node (Tr::gc_pool / Tr::bwd_gc_pool): ctx[b] = sum_p softmax_p(x[b] . wg + bg)[p] x[b][p].
+ * x [B][H*W][C], wg [C], bg [1], dctx [B][C] -> ctx [B][C], dx as x, dwg [C], dbg [1].  C % 4 == 0, 4 <= C <= 512. */
+int d2t_op_train_gc_pool(const float* x, const float* wg, const float* bg, const float* dctx, float* ctx, float* dx, float* dwg,
+                         float* dbg, int32_t B, int32_t H, int32_t W, int32_t C, d2t_stream stream);
+/* GlobalContext's closing node (Tr::bcast_add): out[b][p] = x[b][p] + y[b].  x, dout, out, dx [B][HW][C]; y, dy [B][C].
+ * C % 4 == 0, 4 <= C <= 512. */
+int d2t_op_train_bcast_add(const float* x, const float* y, const float* dout, float* out, float* dx, float* dy, int32_t B,
+                           int32_t HW, int32_t C, d2t_stream stream);
+/* The fused GlobalContext block of the inference path (launch_global_context), in place on x [B][HW][C]: x += fc2(relu(
+ * LayerNorm(fc1(ctx)))), eps 1e-5.  wg [C], bg [1], w1 / w2 [C][C], b1 / ln_g / ln_b / b2 [C]; ctx_out (optional) [B][C]
+ * receives the pooled vector.  C % 4 == 0, 4 <= C <= 512.  Synchronous (temporary buffers). */
+int d2t_op_global_context(float* x, const float* wg, const float* bg, const float* w1, const float* b1, const float* ln_g,
+                          const float* ln_b, const float* w2, const float* b2, float* ctx_out, int32_t B, int32_t HW, int32_t C,
+                          d2t_stream stream);
+/* x[r] = E[tok[r]] * scale + pe[r % L]: E [V][D], pe [>= L][D], tok [rows], x [rows][D].  The tokens are copied to the host and
+ * checked against V first (the entry synchronises the stream for that). */
+int d2t_op_embed_train(const float* E, const float* pe, const int64_t* tok, float* x, int32_t rows, int32_t L, int32_t V,
+                       int32_t D, float scale, d2t_stream stream);
+/* dE[v] = scale * sum_{r: tok[r] == v} dx[r], rows added in ascending order; zero for v == pad_id and for absent tokens.
+ * dx [rows][D], dE [V][D], 1 <= D <= 1024. */
+int d2t_op_embed_bwd(const float* dx, const int64_t* tok, float* dE, int32_t rows, int32_t V, int32_t D, float scale,
+                     int32_t pad_id, d2t_stream stream);
+/* Philox4x32-10 keep mask (bytes, n of them) and its application out = mask ? a * scale : 0.  0 <= p < 1. */
+int d2t_op_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, uint64_t stream_id, d2t_stream stream);
+int d2t_op_apply_mask(const float* a, const uint8_t* mask, float scale, float* out, int64_t n, d2t_stream stream);
+/* ViTEncoder's learned table resized by ATen's bicubic rule (csrc/posembed.hip); scale_h / scale_w = 1 / scale_factor.
+ * transpose == 0: src [GH*GW][D] -> dst [gh*gw][D];  transpose != 0 (the gradient): src [gh*gw][D] -> dst [GH*GW][D]. */
+int d2t_op_bicubic_table(const float* src, float* dst, int32_t GH, int32_t GW, int32_t gh, int32_t gw, int32_t D, float scale_h,
+                         float scale_w, int32_t transpose, d2t_stream stream);
+/* out[i] = sum_b x[b * stride + i], i < n <= stride */
+int d2t_op_sum_over_batch(const float* x, float* out, int32_t B, int64_t stride, int64_t n, d2t_stream stream);
+/* scatter == 0: dst [B][n][D] = rows skip ... skip + n - 1 of every image of src [B][n + skip][D];  scatter != 0: the inverse,
+ * src [B][n][D] -> dst [B][n + skip][D] with zero skip rows */
+int d2t_op_token_rows(const float* src, float* dst, int32_t B, int32_t n, int32_t skip, int32_t D, int32_t scatter,
+                      d2t_stream stream);
+/* out[c] = sum_b x[(b * stride_rows + row) * D + c],  0 <= row < stride_rows */
+int d2t_op_sum_rows_strided(const float* x, float* out, int32_t B, int64_t stride_rows, int32_t row, int32_t D,
+                            d2t_stream stream);
+/* Tr::mean_h: y[b][w] = mean_h x[b][h][w].  x, dx [B][H][W][C]; y, dy [B][W][C]. */
+int d2t_op_train_mean_h(const float* x, const float* dy, float* y, float* dx, int32_t B, int32_t H, int32_t W, int32_t C,
+                        d2t_stream stream);
+/* Tr::pool with a 2 x KW window, KW 1 (VGG's (2,1) pools) or 2; otherwise as d2t_op_train_maxpool.  C % 4 == 0,
+ * PH <= 1, PW <= KW / 2. */
+int d2t_op_train_maxpool_w(const float* x, const float* dy, float* y, float* dx, int32_t B, int32_t H, int32_t W, int32_t C,
+                           int32_t KW, int32_t SH, int32_t SW, int32_t PH, int32_t PW, d2t_stream stream);
+/* Tr::gelu (op 0) or Tr::relu (op 1) over n elements, n % 4 == 0: y = f(x), dx = dy f'(x) */
+int d2t_op_train_ew(const float* x, const float* dy, float* y, float* dx, int64_t n, int32_t op, d2t_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

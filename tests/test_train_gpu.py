@@ -519,7 +519,10 @@ def oracle_to_model_state(m, sd):
 
 
 # (each case costs ~20 s of float64 autograd on the host; the exact-fp32 mode is replayed on the HybridViT + TFM stack, the
-# default split-bf16 mode on all three, and every backward kernel has its own fp32 / bf16x3 test in test_train_ops_gpu.py)
+# default split-bf16 mode on all three; the backward kernels have their own operator tests: convolution, linear, LayerNorm,
+# attention and the 2x2 max-pool in test_train_ops_gpu.py, the recurrent ones in test_recurrent_ops_gpu.py, the cross-entropy
+# in test_criterion_gpu.py, and GlobalContext, embedding, dropout masks, the position-table resize, mean over the height, the
+# (2,1) pool, GELU / ReLU and the token-row movers in test_train_small_ops_gpu.py)
 @pytest.mark.parametrize("name,precision", [("t2_train_step", "fp32"), ("t2_train_step", "bf16x3"),
                                             ("t1_train_step", "bf16x3"), ("ts0_train_step", "bf16x3"),
                                             ("c0_train_step", "bf16x3"), ("b0_train_step", "bf16x3"),

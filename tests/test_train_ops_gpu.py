@@ -1,7 +1,10 @@
-"""GPU: every BACKWARD kernel of the training step, one op at a time through the C-ABI test entry points
-(d2t_op_train_*: one node of the training tape, forward + backward, on caller tensors), against float64 torch autograd
-of the same op.  Both arithmetic modes where the op has them (fp32 MFMA / split-bf16 for the convolution, data-gradient
-and weight-gradient GEMMs).
+"""GPU: the large BACKWARD kernels of the training step -- convolution + BatchNorm, linear, LayerNorm, attention, the 2x2
+max-pool, the fused cross-entropy -- one op at a time through the C-ABI test entry points (d2t_op_train_*: one node of the
+training tape, forward + backward, on caller tensors), against float64 torch autograd of the same op.  Both arithmetic modes
+where the op has them (fp32 MFMA / split-bf16 for the convolution, data-gradient and weight-gradient GEMMs).  The other
+kernels of the step have their operator tests in test_train_small_ops_gpu.py (GlobalContext, embedding, dropout masks, the
+position-table resize, mean over the height, the (2,1) pool, GELU / ReLU, the token-row movers) and
+test_recurrent_ops_gpu.py (BiLSTM, LSTM-attention decoder).
 
 Tolerance = max |engine - fp64| relative to max |fp64| of that tensor: 1e-4 for fp32 arithmetic (fp32 accumulation
 over up to ~10^5 terms in the weight gradients), 1e-4 for split-bf16 (2^-16 per product, averaged over the same
@@ -166,7 +169,10 @@ def test_stem_conv_backward():
 @pytest.mark.parametrize("bf16x3", [0, 1], ids=["fp32", "bf16x3"])
 @pytest.mark.parametrize("M,K,N,relu,use_res", [(302, 256, 768, False, False), (302, 256, 256, False, True),
                                                  (453, 256, 1024, True, False), (453, 1024, 256, False, True),
-                                                 (151, 256, 500, False, False)])  # the vocabulary projection: N % 32 != 0
+                                                 (151, 256, 500, False, False),  # the vocabulary projection: N % 32 != 0
+                                                 # GlobalContext's ConvMLP runs fc1 / fc2 at M = batch size rows
+                                                 (1, 128, 128, False, False), (2, 512, 512, False, False),
+                                                 (3, 256, 256, False, False)])
 def test_linear_backward(M, K, N, relu, use_res, bf16x3):
     lib = _lib.require_device()
     x, w, b = _rand(M, K, seed=20), _rand(N, K, seed=21, scale=K ** -0.5), _rand(N, seed=22, scale=0.1)
@@ -199,7 +205,8 @@ def test_linear_backward(M, K, N, relu, use_res, bf16x3):
     assert max(errs.values()) <= tol, errs
 
 
-@pytest.mark.parametrize("rows,D,eps", [(522, 256, 1e-6), (302, 256, 1e-5), (390, 512, 1e-5)])
+@pytest.mark.parametrize("rows,D,eps", [(522, 256, 1e-6), (302, 256, 1e-5), (390, 512, 1e-5),
+                                        (1, 128, 1e-5), (3, 128, 1e-5), (2, 512, 1e-5)])  # the ConvMLP's norm: batch-size rows, D 128
 def test_layernorm_backward(rows, D, eps):
     lib = _lib.require_device()
     x, g, b, dy = _rand(rows, D, seed=30, scale=2.0), _rand(D, seed=31) * 0.2 + 1.0, _rand(D, seed=32, scale=0.1), _rand(rows, D, seed=33)
