@@ -65,6 +65,13 @@ class D2TOpAttnBeamRec(C.Structure):  # include/d2t.h d2t_op_attn_beam_rec
         [(n, C.c_int32) for n in ("N", "beam", "cap", "V", "S", "end_token")]
 
 
+class D2TOptimTensor(C.Structure):  # include/d2t.h d2t_optim_tensor
+    _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "mirror")] + [("numel", C.c_int64)] + \
+               [(n, C.c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps", "bc1", "sqrt_bc2")]
+
+
+OPTIM_CHUNK = 32768  # include/d2t.h D2T_OPTIM_CHUNK: elements one block of the optimizer kernels handles
+
 PREP_DEMO, PREP_API = 0, 1
 NORM_ALB, NORM_RAW = 0, 1
 PREP_OK, PREP_UNBOUND_LOCAL, PREP_FALLBACK = 0, 1, 2
@@ -169,6 +176,12 @@ SIGNATURES = {
     "d2t_ce_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _P]),
     "d2t_ce_smooth_forward": (_I, [_P] * 6 + [_I, _I, _L, C.c_float, C.c_float, _I, _L, _P]),
     "d2t_ce_smooth_backward": (_I, [_P] * 7 + [_I, _I, _L, C.c_float, C.c_float, _I, _L, _P]),
+    "d2t_optim_create": (_I, [C.POINTER(_P)]),
+    "d2t_optim_destroy": (None, [_P]),
+    "d2t_optim_last_error": (C.c_char_p, [_P]),
+    "d2t_optim_chunk": (_I, []),
+    "d2t_optim_step": (_I, [_P, C.POINTER(D2TOptimTensor), _I, _I, C.c_float, _P, _P]),
+    "d2t_weight_ptr": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_L)]),
     "d2t_op_train_conv": (_I, [_P] * 14 + [_I] * 13 + [_P]),
     "d2t_op_train_linear": (_I, [_P] * 10 + [_I] * 5 + [_P]),
     "d2t_op_train_layernorm": (_I, [_P] * 8 + [_I, _I, C.c_float, _P]),

@@ -107,6 +107,16 @@ int d2t_read_weight(d2t_ctx* c, const char* name, float* dst, int64_t numel, d2t
   return D2T_OK;
 }
 
+// where d2t_read_weight copies from: the fused optimizer writes the stepped parameter here as well (optim.hip)
+int d2t_weight_ptr(d2t_ctx* c, const char* name, float** ptr_out, int64_t* numel_out) {
+  if (!c || !name || !ptr_out || !numel_out) return fail(c, D2T_EINVAL, "bad argument");
+  const RawW* r = find(c, name);
+  if (!r || !r->p) return fail(c, D2T_ESTATE, "unknown tensor '%s'", name);
+  *ptr_out = r->p;
+  *numel_out = (int64_t)r->numel;
+  return D2T_OK;
+}
+
 int d2t_train_set_dropout(d2t_ctx* c, float p, uint64_t seed) {
   DevGuard dg_(c);
   if (!c || !(p >= 0.f) || p >= 1.f) return fail(c, D2T_EINVAL, "dropout probability must be in [0, 1)");

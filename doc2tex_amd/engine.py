@@ -173,6 +173,8 @@ class Engine:
             raise RuntimeError(f"d2t_create failed (code {rc}): {msg}")
         assert self.lib.d2t_device_of(self.ctx) == self.device
         self._sig = None
+        self.weight_uploads = 0  # sync_weights calls that moved tensors into the engine (load or reload)
+        self._load_epoch = object()  # replaced whenever d2t_load_weight may have re-allocated the raw copies (weight_ptr)
 
     def _on_device(self, t, what):
         """Tensors handed to the context must live on its device (the C side checks the raw pointers too)."""
@@ -233,11 +235,35 @@ class Engine:
                 self._check(self.lib.d2t_load_weight(self.ctx, name.encode(), _lib.ptr(td), shape, td.dim(), stream),
                             f"load_weight({name})")
             self._loaded_shapes = shapes
+            self._load_epoch = object()
+        self.weight_uploads += 1
         self._fin_sig = None
         if finalize:
             self._check(self.lib.d2t_finalize_weights(self.ctx, stream), "finalize_weights")
             self._fin_sig = sig
         self._sig = sig
+
+    def weight_ptr(self, name):
+        """(device pointer, numel) of the engine's raw copy of a loaded tensor (d2t_weight_ptr), None if it is not loaded.
+        The pointer holds until the tensors are loaded afresh (`_load_epoch` is then another object)."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        if self.lib.d2t_weight_ptr(self.ctx, name.encode(), C.byref(p), C.byref(n)) != _lib.D2T_OK:
+            return None
+        return p.value, int(n.value)
+
+    def weights_current(self, module, names):
+        """The caller states that the engine's RAW copies of the tensors `names` already hold the module's present values
+        (the fused optimizer wrote both; a training forward produced the running statistics it copied out): their
+        entries of the upload signature are re-taken from the module, so the next sync_weights does not upload on their
+        account.  Every other tensor keeps its old entry and is still re-uploaded if it changed.  The finalized (folded /
+        packed) weights are stale either way and are rebuilt by the next sync_weights that asks for them."""
+        self._fin_sig = None
+        if self._sig is None:
+            return
+        names = set(names)
+        cur = {n: t for n, t in list(module.named_parameters()) + list(module.named_buffers()) if n in names}
+        self._sig = tuple((e[0], cur[e[0]].data_ptr(), cur[e[0]]._version, tuple(cur[e[0]].shape)) if e[0] in cur else e
+                          for e in self._sig)
 
     # ---- training step -------------------------------------------------------
     def train_forward(self, image, tgt):

@@ -4,7 +4,8 @@ The reference trains through PyTorch autograd (`loss.backward()`, engine/trainin
 `model(image, text[:, :-1])` returns (`forward_step`, training.py:76-91).  Here the whole network is one
 `torch.autograd.Function`: forward = `d2t_train_forward` (BatchNorm on batch statistics, teacher-forced decoder),
 backward = `d2t_train_backward` on dL/dlogits, after which every parameter's gradient is copied out of the engine.
-The caller's criterion, `clip_grad_norm_` and optimizer (torch.optim, out of scope per SURVEY section 2) run unchanged.
+The caller's criterion, `clip_grad_norm_` and optimizer run unchanged (torch's, or the fused ones of doc2tex_amd.loss and
+doc2tex_amd.optim).
 """
 import torch
 
@@ -45,7 +46,8 @@ class _TrainStep(torch.autograd.Function):
             for name, buf in model.named_buffers():
                 if name.endswith("num_batches_tracked"):
                     buf += 1
-        eng._sig = None  # the buffers above changed: re-upload before the next eval forward
+        # the statistics copied out above are the engine's own: its raw copies are current, its finalized weights are not
+        eng.weights_current(model, [n for n, _ in stats])
         ctx.model, ctx.names, ctx.params = model, names, params
         return logits
 

@@ -742,6 +742,53 @@ int d2t_ce_smooth_backward(const float* logits, const int64_t* target, const flo
                            const float* dloss, float* dlogits, int32_t rows, int32_t V, int64_t ignore_index, float on,
                            float off, int32_t mode, int64_t pad_index, d2t_stream stream);
 
+/* ---- fused optimizer step ----------------------------------------------------------------------------------------
+ * What follows loss.backward() in the reference's training step (engine/training.py:139-150): clip_grad_norm_(max_norm)
+ * and Adam / AdamW .step(), as multi-tensor kernels over a table of chunks (one block = one run of at most
+ * D2T_OPTIM_CHUNK elements of one tensor; 16-byte accesses where all of a chunk's pointers allow, scalar ones otherwise):
+ *   1. norm = sqrt(sum over every record of g * g): one fp32 sum per thread, all above it in double and in a fixed order
+ *      (bit-reproducible, no atomics); coef = min(1, max_grad_norm / (norm + 1e-6)) stays in device memory;
+ *   2. per element, in fp32 and in torch's order of operations:
+ *        g' = g * coef;   decoupled (AdamW): p *= 1 - lr * wd;   otherwise (Adam): g' += wd * p;
+ *        m += (g' - m) * (1 - beta1);   v = beta2 * v + (1 - beta2) * g' * g';
+ *        p -= (lr / bc1) * (m / (sqrt(v) / sqrt_bc2 + eps));
+ *      p, m, v are stored in place and, where the record has a mirror, the new p there as well.  The gradients are read
+ *      only: they stay unclipped.
+ * The mirror is the engine's raw copy of the parameter (d2t_weight_ptr): with it the engine's weights follow the step
+ * and the next d2t_train_forward needs no d2t_reload_weights.  Finalized (folded / packed) inference weights are not
+ * rebuilt: d2t_finalize_weights before the next inference forward.
+ * The scalars of a record are doubles: bc1 = 1 - beta1^step and sqrt_bc2 = sqrt(1 - beta2^step) of that parameter's own
+ * step count, formed by the caller; the products above (1 - lr * wd, lr / bc1, 1 - beta) are formed from them in double
+ * and rounded to fp32 once, as torch's Python scalars are.
+ * A d2t_optim owns the staging buffers of the table, the partial sums and the coefficient; it lives on the HIP device
+ * that is current at d2t_optim_create, needs no d2t_ctx, and is not thread-safe.  d2t_optim_step enqueues at most three
+ * launches and one host-to-device copy on `stream` and never waits for the device.  max_grad_norm <= 0: no clipping, the
+ * norm is not computed and norm_dev (may be NULL) is not written; otherwise norm_dev [device float] receives the norm
+ * before clipping.  Every pointer of every record (and norm_dev) must be device memory of the optimizer's device, and
+ * every size non-negative: D2T_EINVAL before anything is enqueued otherwise, with a message in d2t_optim_last_error.
+ * Records must not overlap one another. */
+#define D2T_OPTIM_CHUNK 32768
+typedef struct d2t_optim d2t_optim;
+typedef struct d2t_optim_tensor {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* mirror; /* NULL: none */
+  int64_t numel;
+  double lr, weight_decay, beta1, beta2, eps, bc1, sqrt_bc2;
+} d2t_optim_tensor;
+int d2t_optim_create(d2t_optim** out);
+void d2t_optim_destroy(d2t_optim* opt);
+const char* d2t_optim_last_error(d2t_optim* opt);
+int32_t d2t_optim_chunk(void); /* D2T_OPTIM_CHUNK, for bindings */
+int d2t_optim_step(d2t_optim* opt, const d2t_optim_tensor* tensors, int32_t n, int32_t decoupled, float max_grad_norm,
+                   float* norm_dev, d2t_stream stream);
+/* Device pointer and element count of the engine's raw copy of a loaded tensor, by state_dict key: what d2t_read_weight
+ * copies from and d2t_reload_weights writes to.  Valid until the tensor is loaded again with another size or the context
+ * is destroyed.  D2T_ESTATE with a message for a name that is not loaded. */
+int d2t_weight_ptr(d2t_ctx* ctx, const char* name, float** ptr_out, int64_t* numel_out);
+
 /* ---- op-level TRAINING test entry points ---------------------------------------------------------------------
  * One node of the training tape, forward + backward, on caller tensors (fp32, device, row-major [rows][cols]; maps
  * NHWC; convolution weights OIHW as in the state_dict).  They run the very builders / backward functions of
