@@ -13,6 +13,7 @@ if os.environ.get("D2T_PROBE_LIB"):  # development tools only: a probe build of 
     LIB_PATH = os.path.abspath(os.environ["D2T_PROBE_LIB"])
 
 D2T_OK = 0
+D2T_EINVAL, D2T_ENOMEM, D2T_EHIP, D2T_ESTATE = 1, 2, 3, 4  # include/d2t.h
 ENC_RESNET, ENC_HYBRID_VIT, ENC_VGG_BILSTM, ENC_RESNET_BILSTM = 0, 1, 2, 3
 DEC_TFM, DEC_ATTN = 0, 1
 ATTN_KEYS_ALL_INIT_MEAN, ATTN_KEYS_NOCLS_INIT_CLS, ATTN_KEYS_ALL_INIT_FIRST = 0, 1, 2
@@ -79,6 +80,9 @@ PREP_FLAG_PASTE_MISMATCH = 1
 POST_NONE, POST_API, POST_DEMO = 0, 1, 2
 ATTN_MAP_BUDGET = 256 << 20  # include/d2t.h D2T_ATTN_MAP_BUDGET: bytes of a beam search's alignment history
 ATTN_MAX_CLASSES = 16384  # include/d2t.h D2T_ATTN_MAX_CLASSES: largest num_class of the Attn / Attnv2 heads
+METRIC_ED_MAX_LEN = 32768  # include/d2t.h D2T_METRIC_ED_MAX_LEN: longest string d2t_metric_edit_distance takes
+METRIC_ED_LDS_LEN = 4095  # include/d2t.h D2T_METRIC_ED_LDS_LEN: shorter string of a pair up to which the DP stays in LDS
+METRIC_BLEU_MAX_COLS = 2048  # include/d2t.h D2T_METRIC_BLEU_MAX_COLS: widest row d2t_metric_bleu_counts takes
 
 _P = C.c_void_p
 _I = C.c_int32
@@ -182,6 +186,10 @@ SIGNATURES = {
     "d2t_optim_chunk": (_I, []),
     "d2t_optim_step": (_I, [_P, C.POINTER(D2TOptimTensor), _I, _I, C.c_float, _P, _P]),
     "d2t_weight_ptr": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_L)]),
+    # validation metrics (csrc/metrics.hip)
+    "d2t_metric_edit_distance_workspace": (_I, [_I, _L, C.POINTER(_L)]),
+    "d2t_metric_edit_distance": (_I, [_P, _P, _L, _P, _P, _L, _P, _I, _L, _P, _L, _P]),
+    "d2t_metric_bleu_counts": (_I, [_P, _I, _P, _I, _I, _L, _I, _P, _P]),
     "d2t_op_train_conv": (_I, [_P] * 14 + [_I] * 13 + [_P]),
     "d2t_op_train_linear": (_I, [_P] * 10 + [_I] * 5 + [_P]),
     "d2t_op_train_layernorm": (_I, [_P] * 8 + [_I, _I, C.c_float, _P]),

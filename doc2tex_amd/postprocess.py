@@ -45,9 +45,11 @@ class LabelDecoder:
     """`character`: the vocabulary WITHOUT the special tokens, as the reference converters take it; `head` "TFM"
     prepends [PAD] [GO] [s] [UNK] (tfm_converter.py:8), "Attn" prepends [GO] [s] [UNK] (attn_converter.py:8)."""
 
-    def __init__(self, character, head="TFM"):
+    def __init__(self, character, head="TFM", device=None):
         special = ["[PAD]", "[GO]", "[s]", "[UNK]"] if head == "TFM" else ["[GO]", "[s]", "[UNK]"]
         self.character = special + list(character)
+        self.head, self.device = head, device
+        self.dict = {tok: i for i, tok in enumerate(self.character)}  # as the converters build it: a repeated entry keeps its last index
         enc = [t.encode("utf-8") for t in self.character]
         arr = (C.c_char_p * len(enc))(*enc)
         self.lib = _lib.load()
@@ -82,6 +84,29 @@ class LabelDecoder:
             raise RuntimeError(f"d2t_post_decode failed (code {rc})")
         raw = buf.raw
         return [raw[offs[r]:raw.index(b"\0", offs[r])].decode("utf-8") for r in range(rows)]
+
+    def encode(self, text, batch_max_length=25):
+        """converter.encode(text, batch_max_length) of both heads (tfm_converter.py:36-57, attn_converter.py:31-52): rows
+        [GO] tokens... [s] fill..., batch_max_length + 2 wide, filled with [PAD] ("TFM") or 0 = [GO] ("Attn"); tokens outside
+        the vocabulary become [UNK]; a label of more than batch_max_length + 1 tokens keeps its first batch_max_length (one
+        of exactly batch_max_length + 1 does not fit its row and raises, as there).  Returns (int64 rows, int32 lengths) with
+        lengths = len(label) + 1 of the UNCUT label, on `device` (the constructor's; None leaves them on the host)."""
+        import torch
+        width = batch_max_length + 1
+        rows = torch.full((len(text), width + 1), self.dict["[PAD]"] if self.head == "TFM" else 0, dtype=torch.long)
+        unk, end = self.dict["[UNK]"], self.dict["[s]"]
+        for i, label in enumerate(text):
+            toks = list(label)
+            if len(toks) > width:
+                toks = toks[:width - 1]
+            ids = [self.dict.get(t, unk) for t in toks] + [end]
+            if self.head == "TFM":
+                rows[i, 0] = self.dict["[GO]"]
+            rows[i, 1:1 + len(ids)] = torch.tensor(ids, dtype=torch.long)
+        length = torch.tensor([len(s) + 1 for s in text], dtype=torch.int32)
+        if self.device is not None:
+            rows, length = rows.to(self.device), length.to(self.device)
+        return rows, length
 
     def decode(self, text_index, token_level="word"):
         """converter.decode(text_index, token_level): every token of every row, joined."""

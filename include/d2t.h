@@ -789,6 +789,38 @@ int d2t_optim_step(d2t_optim* opt, const d2t_optim_tensor* tensors, int32_t n, i
  * is destroyed.  D2T_ESTATE with a message for a name that is not loaded. */
 int d2t_weight_ptr(d2t_ctx* ctx, const char* name, float** ptr_out, int64_t* numel_out);
 
+/* ---- validation metrics -------------------------------------------------------------------------------------------
+ * The quadratic half of the reference's validation_step (engine/inferencing.py:133-134,226: Levenshtein distances and
+ * BLEU's clipped n-gram counts) as two kernels (csrc/metrics.hip).  Stateless like the criterion: no ctx, device
+ * pointers and a stream in, asynchronous, integers out, one result per sample and no atomics.
+ *
+ * d2t_metric_edit_distance: dist[p] = Levenshtein distance (insert, delete, substitute, each 1) of the int32 symbol
+ * strings a_sym[a_off[p] .. a_off[p+1]) and b_sym[b_off[p] .. b_off[p+1]), p < N; symbols are compared as integers.
+ * a_off / b_off hold N + 1 int64 each; a_total / b_total are the element counts of a_sym / b_sym (a symbol pointer may be
+ * NULL where its count is 0).  One block per pair runs an anti-diagonal wavefront over three rolling diagonals as long as
+ * the pair's SHORTER string + 1: in LDS while that string has at most D2T_METRIC_ED_LDS_LEN symbols, otherwise in the
+ * caller's workspace.  max_len is the caller's bound on every string of the call, since the lengths themselves are device
+ * data: max_len > D2T_METRIC_ED_MAX_LEN, or a workspace smaller than d2t_metric_edit_distance_workspace(N, max_len)
+ * reports (0 bytes for max_len <= D2T_METRIC_ED_LDS_LEN; workspace may then be NULL), is D2T_EINVAL and nothing is
+ * launched.  Nothing is ever truncated: a pair whose offsets decrease, leave [0, total] or span more than max_len gets
+ * dist -1 and none of its symbols is read. */
+#define D2T_METRIC_ED_MAX_LEN 32768
+#define D2T_METRIC_ED_LDS_LEN 4095
+int d2t_metric_edit_distance_workspace(int32_t N, int64_t max_len, int64_t* bytes_out);
+int d2t_metric_edit_distance(const int32_t* a_sym, const int64_t* a_off, int64_t a_total, const int32_t* b_sym,
+                             const int64_t* b_off, int64_t b_total, int32_t* dist, int32_t N, int64_t max_len,
+                             void* workspace, int64_t workspace_bytes, d2t_stream stream);
+/* d2t_metric_bleu_counts: candidate rows cand [N][cand_cols] and reference rows ref [N][ref_cols], int64 tokens.  A row's
+ * length is the position of its first end_token, or the whole row without one (converter.detokenize).  out [N][2 + max_n]
+ * int64 = cand_len, ref_len, clipped_1 .. clipped_max_n, where clipped_n = sum over the distinct n-grams of min(count in
+ * the candidate, count in the reference) (modules/metrics/bleu.py:96-105 with one reference), counted without a hash
+ * table: candidate n-gram i counts when fewer equal candidate n-grams precede it than the reference holds.  One block per
+ * sample, both rows in LDS.  1 <= max_n <= 4; 1 <= cols <= D2T_METRIC_BLEU_MAX_COLS each: D2T_EINVAL and nothing launched
+ * otherwise. */
+#define D2T_METRIC_BLEU_MAX_COLS 2048
+int d2t_metric_bleu_counts(const int64_t* cand, int32_t cand_cols, const int64_t* ref, int32_t ref_cols, int32_t N,
+                           int64_t end_token, int32_t max_n, int64_t* out, d2t_stream stream);
+
 /* ---- op-level TRAINING test entry points ---------------------------------------------------------------------
  * One node of the training tape, forward + backward, on caller tensors (fp32, device, row-major [rows][cols]; maps
  * NHWC; convolution weights OIHW as in the state_dict).  They run the very builders / backward functions of
