@@ -205,6 +205,8 @@ SIGNATURES = {
     "d2t_op_attn_alpha_gather": (_I, [_P] * 4 + [_I] * 4 + [_P]),
     "d2t_op_attn_beam_advance": (_I, [C.POINTER(D2TOpAttnBeamRec), _I, _L, _P]),
     "d2t_op_attn_beam_finish": (_I, [C.POINTER(D2TOpAttnBeamRec)] + [_P] * 6),
+    "d2t_op_attn_beam_host_advance": (_I, [C.POINTER(D2TOpAttnBeamRec), _I, _L]),
+    "d2t_op_attn_beam_host_finish": (_I, [C.POINTER(D2TOpAttnBeamRec)] + [_P] * 5),
     "d2t_op_attn_lstm_bwd": (_I, [C.POINTER(D2TOpAttnLstmBwdArgs), _P]),
     "d2t_op_loc_unfold_bwd": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I] + [_P] * 5),
     # the remaining kernels of the training step one at a time (test infrastructure)

@@ -1,6 +1,8 @@
 // Device-side bookkeeping of the LSTM-attention beam search (Attention.forward_beam, prediction_head/seq2seq.py:83-222;
-// AttentionV2.forward_beam, seq2seq_v2.py:12-174): what the host loop of engine_attn.hip does between two steps, as kernels
-// over the record AttnBeamDev (kernels.h), so that the step loop needs no host round trip and can be captured as a graph.
+// AttentionV2.forward_beam, seq2seq_v2.py:12-174): what the host loop of engine_attn.hip does between two steps with the
+// host functions of attn_beam_host.h, as kernels over the same record (AttnBeamDev, defined there), so that the step loop
+// needs no host round trip and can be captured as a graph.  attn_beam_host_init / _advance / _finish and the three kernels
+// of those names write the same arrays; tests/attn_beam_refs.py holds both to one description.
 // Every kernel here is ordered by launches alone: no block waits for another one.
 #include <algorithm>
 #include <cstdint>

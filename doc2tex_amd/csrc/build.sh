@@ -15,7 +15,7 @@ objs=""
 for f in $SRCS; do
   o=$OBJ/$f.o
   objs="$objs $o"
-  if [ ! -f $o ] || [ $f.hip -nt $o ] || [ kernels.h -nt $o ] || [ conv_common.h -nt $o ] || [ train_common.h -nt $o ] || [ train_tape.h -nt $o ] || [ recurrent_common.h -nt $o ] || [ ctx.h -nt $o ] || [ engine_impl.h -nt $o ] || [ engine_tfm.h -nt $o ] || [ beam_host.h -nt $o ] || [ carve.h -nt $o ] || [ ../../include/d2t.h -nt $o ] || [ ../../include/d2t_prep.h -nt $o ] || [ unicode_tables.h -nt $o ] || [ build.sh -nt $o ]; then
+  if [ ! -f $o ] || [ $f.hip -nt $o ] || [ kernels.h -nt $o ] || [ conv_common.h -nt $o ] || [ train_common.h -nt $o ] || [ train_tape.h -nt $o ] || [ recurrent_common.h -nt $o ] || [ ctx.h -nt $o ] || [ engine_impl.h -nt $o ] || [ engine_tfm.h -nt $o ] || [ beam_host.h -nt $o ] || [ attn_beam_host.h -nt $o ] || [ carve.h -nt $o ] || [ ../../include/d2t.h -nt $o ] || [ ../../include/d2t_prep.h -nt $o ] || [ unicode_tables.h -nt $o ] || [ build.sh -nt $o ]; then
     (hipcc $OPT -c $f.hip -o $o.tmp && mv $o.tmp $o) &
     pids="$pids $!"
   fi

@@ -1,10 +1,10 @@
 // libd2t engine, LSTM-attention heads: the greedy decode (synchronous and pipelined) and the beam search of the C-ABI -- its
-// host loop and the device-side loop beside it.  Host code only: the kernels are recurrent.hip's and attn_beam.hip's.
+// host loop and the device-side loop beside it, which keep one bookkeeping record (attn_beam_host.h: the host loop runs its
+// host functions, the device-side loop the kernels of attn_beam.hip) in one workspace layout.  Host code only: the kernels
+// are recurrent.hip's and attn_beam.hip's.
 #include "engine_tfm.h"  // (engine_impl.h, carve.h; the captured-loop cache)
 
-extern "C" {
-
-namespace {
+namespace {  // (outside extern "C": what is local here stays out of the library's dynamic symbols)
 // The fields of the LSTM-attention decoder launch that every caller sets alike: memory [*][T][H], its key projection kp,
 // the weights.  The caller adds its outputs, row count, step count and (beam search) the step-mode fields.
 AttnDecP attn_dec_params(const d2t_ctx* c, const float* memory, int T, const float* kp) {
@@ -18,23 +18,6 @@ AttnDecP attn_dec_params(const d2t_ctx* c, const float* memory, int T, const flo
   p.wih_t = c->attn.wih_t; p.bih = c->attn.bih; p.wic_t = c->attn.wic_t; p.bic = c->attn.bic;
   p.emb = c->attn.emb; p.tokgate = c->attn.tokgate;
   p.V = g.vocab; p.H = g.attn_hidden; p.E = g.attn_hidden; p.coverage = g.attn_coverage; p.end_token = 1;  // attn_converter.py:8
-  return p;
-}
-// The step pack of the beam search (one host -> device copy per step), its size padded to 16 bytes:
-// tok i64 [cap] | scores [cap] | map [cap] | idx_h [cap] | idx_m [cap] | seg [N][3].  One layout for the device buffer and
-// its pinned host mirror.
-struct AttnBeamPack { char* base; size_t bytes; int64_t* tok; float* scores; int *map, *idx_h, *idx_m, *seg; };
-static AttnBeamPack attn_beam_pack(Carver& cv, int N, int cap) {
-  AttnBeamPack p;
-  cv.align(8);
-  const size_t at0 = cv.total();
-  p.base = cv.here();
-  p.tok = cv.take<int64_t>(cap);
-  p.scores = cv.take<float>(cap);
-  p.map = cv.take<int>(cap); p.idx_h = cv.take<int>(cap); p.idx_m = cv.take<int>(cap);
-  p.seg = cv.take<int>(3 * (size_t)N);
-  p.bytes = (cv.total() - at0 + 15) & ~(size_t)15;
-  cv.at = at0 + p.bytes;
   return p;
 }
 // What every greedy call of the LSTM-attention heads refuses, before anything is enqueued.
@@ -103,6 +86,7 @@ int attn_greedy_impl(d2t_ctx* c, const float* memory, int B, int T, int is_test,
   return D2T_OK;
 }
 
+// ---- beam search: what the two loops share ----
 constexpr int ATTN_BEAM_MAX_N = 1024;  // samples of one ragged search (as the TFM head's ragged search)
 // What every beam search of the LSTM-attention heads refuses, behind the entry's own argument check.
 int attn_beam_check(d2t_ctx* c, int beam_size) {
@@ -115,41 +99,128 @@ int attn_beam_check(d2t_ctx* c, int beam_size) {
   if (beam_size < 1 || beam_size > 16) return fail(c, D2T_EINVAL, "beam_size must be in [1,16]");
   return D2T_OK;
 }
+// What the ragged entries (synchronous and submitted) refuse alike: missing arguments, attn_beam_check, the sample count and
+// every sample's memory length.
+int attn_beam_ragged_check(d2t_ctx* c, const float* memory, int N, const int32_t* T, int beam_size, const void* seq,
+                           const void* len, const void* score) {
+  if (!c || !memory || !T || !seq || !len || !score) return fail(c, D2T_EINVAL, "bad argument");
+  if (int rc = attn_beam_check(c, beam_size)) return rc;
+  if (N < 1 || N > ATTN_BEAM_MAX_N)
+    return fail(c, D2T_EINVAL, "ragged beam search takes 1 to %d samples per call, got %d", ATTN_BEAM_MAX_N, N);
+  const int key_off = c->cfg.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  for (int i = 0; i < N; ++i)
+    if (T[i] - key_off < 1 || T[i] - key_off > memory_cap(c))
+      return fail(c, D2T_EINVAL, "sample %d has memory length %d, supported are %d to %d", i, T[i], 1 + key_off, memory_cap(c) + key_off);
+  return D2T_OK;
+}
+// Alignment maps (viz_attn): every step's launch writes its rows' alignments into its own slice of a history; the slices
+// [S][N * beam][Tk] of one search must fit the budget.
+int attn_beam_hist_check(d2t_ctx* c, int S, int N, int beam_size, int Tk) {
+  const size_t hist_bytes = (size_t)S * N * beam_size * Tk * 4;
+  if (hist_bytes > D2T_ATTN_MAP_BUDGET)
+    return fail(c, D2T_EINVAL, "beam alignment history of %zu bytes (%d steps x %d samples x beam %d x %d keys x 4) exceeds the "
+                "%llu-byte budget: decode fewer samples per call", hist_bytes, S, N, beam_size, Tk, (unsigned long long)D2T_ATTN_MAP_BUDGET);
+  return D2T_OK;
+}
+// The memory rows of a search: uniform (Ts == nullptr) N * *T; ragged the sum of Ts [N], and *T becomes the largest.
+size_t attn_beam_mem_rows(int N, const int32_t* Ts, int* T) {
+  if (!Ts) return (size_t)N * *T;
+  size_t rows = 0;
+  *T = 0;
+  for (int i = 0; i < N; ++i) { rows += (size_t)Ts[i]; *T = std::max(*T, (int)Ts[i]); }
+  return rows;
+}
+
+// The workspace of a search: logits [cap][V] | topv [cap] | topi [cap] (adjacent: the host loop fetches both in one copy per
+// step) | h_in c_in h_out c_out [cap][H] | mem_in mem_out [cap][ld] | end_step [cap] | dummy tokens i64 [cap] | the per-sample
+// tables row0 [N] | T [N] | the live rows of the record (attn_beam_rows_carve: the host loop's one upload per step), and for
+// the device-side loop the result block seq i64 [N][S] | len [N] | score [N] | ctrl [4] (one device -> host copy at the end
+// of a synchronous search; ctrl heads the record's bookkeeping, which follows it).  Every array but topi from a 16-byte
+// boundary.  A function of N, beam, V, S and ld alone: no memory length moves it.
+struct AttnBeamWs {
+  float *logits, *topv, *st[6];  // st: h_in c_in h_out c_out mem_in mem_out
+  int *topi, *end, *tab;
+  int64_t* dummy;
+  AttnBeamDev rec;
+  char* rows; size_t rows_bytes;
+  char* res; size_t res_bytes;
+  int64_t* r_seq; int* r_len; float* r_score;
+};
+void attn_beam_rows(Carver& cv, AttnBeamWs* w) {
+  cv.align(16);
+  w->rows = cv.here();
+  attn_beam_rows_carve(cv, w->rec);
+  w->rows_bytes = (size_t)(cv.here() - w->rows);
+}
+size_t attn_beam_ws_carve(Carver cv, int Hh, int ld, bool device_book, AttnBeamWs* w) {
+  AttnBeamDev& r = w->rec;
+  const size_t cap = (size_t)r.cap, N = (size_t)r.N;
+  w->logits = cv.take<float>(cap * r.V, 16);
+  w->topv = cv.take<float>(cap, 16);
+  w->topi = cv.take<int>(cap);
+  for (int i = 0; i < 6; ++i) w->st[i] = cv.take<float>(cap * (i < 4 ? Hh : ld), 16);
+  w->end = cv.take<int>(cap, 16);
+  w->dummy = cv.take<int64_t>(cap, 16);
+  w->tab = cv.take<int>(2 * N, 16);
+  attn_beam_rows(cv, w);
+  if (device_book) {
+    w->res = cv.here();
+    w->r_seq = cv.take<int64_t>(N * r.S, 16);
+    w->r_len = cv.take<int>(N, 16);
+    w->r_score = cv.take<float>(N, 16);
+    attn_beam_book_carve(cv, r);
+    w->res_bytes = (size_t)(reinterpret_cast<char*>(r.ctrl + 4) - w->res);
+  }
+  r.topv = w->topv; r.topi = w->topi;
+  return cv.total() + 64;
+}
+// The host loop's pinned mirror: the live rows | topv [cap] | topi [cap] | the tables
+size_t attn_beam_mirror_carve(Carver cv, AttnBeamWs* w) {
+  attn_beam_rows(cv, w);
+  w->topv = cv.take<float>(w->rec.cap, 16);
+  w->topi = cv.take<int>(w->rec.cap);
+  w->tab = cv.take<int>(2 * (size_t)w->rec.N, 16);
+  return cv.total();
+}
+// The step launch of a search, on top of attn_dec_params: one step per launch (the greedy kernel in step mode, one block per
+// hypothesis row) from and into the workspace's state buffers, its token and sample per row from the record's live rows.
+// ragged: the per-sample tables and the row stride st_ld of the coverage memory (the ragged builds of the step kernel).
+AttnDecP attn_beam_step_params(const d2t_ctx* c, const float* memory, int T, const float* kp, const AttnBeamWs& w, bool ragged,
+                               int st_ld) {
+  AttnDecP p = attn_dec_params(c, memory, T, kp);
+  p.probs = w.logits; p.tokens = w.dummy; p.end_step = w.end;
+  p.S = 1; p.coverage = 1;
+  p.step_mode = 1;
+  p.st_h_in = w.st[0]; p.st_c_in = w.st[1]; p.st_mem_in = w.st[4];
+  p.st_h_out = w.st[2]; p.st_c_out = w.st[3]; p.st_mem_out = w.st[5];
+  p.tok_in = w.rec.tok; p.row_sample = w.rec.map;
+  if (ragged) { p.smp_row0 = w.tab; p.smp_T = w.tab + w.rec.N; p.st_ld = st_ld; }
+  return p;
+}
 
 // Attention / AttentionV2.forward_beam for N samples in one step loop: rows = live hypotheses of all samples, each
 // attending over its own sample's keys (row map).  The attention cell + LSTMCell + generator of every live hypothesis run
-// as ONE launch per step (the greedy kernel in step mode, one block per hypothesis), log_softmax + top-k per sample
-// segment on the device, the reference's bookkeeping per sample on the host -- including its quirks: step 0 ranks row 0
-// only; the LSTM state follows prev_word_inds[incomplete] but the coverage memory only `incomplete`; if the last executed
-// step completed nothing the first live sequence is returned; otherwise the best score/len sequence with the MAXIMUM raw
-// score.
+// as ONE launch per step, log_softmax + top-k per sample segment on the device, the reference's bookkeeping -- with its
+// quirks -- on the host in the record of attn_beam_host.h: its live rows lie in the pinned mirror and go to the device in one
+// copy per step, its bookkeeping half is pageable (only the host reads it).  Any N: nothing here has the kernels' sample limit.
 // Uniform (Ts == nullptr): memory [N][T][H].  Ragged (Ts = host [N], T unused): memory is packed, sample i's Ts[i] rows
 // behind sample i-1's; ONE key projection over all packed rows (linear_any computes a row from that row alone, so each
 // sample's projection is its uniform call's bit for bit), the per-sample tables [row0 | T] uploaded once in front of the
 // loop, and the coverage memory, the alignment history and alpha_out [N][S][st_ld] on the row stride st_ld = the largest Tk.
-// The bookkeeping below does not know which of the two it serves.  The caller has checked the lengths.
+// The bookkeeping does not know which of the two it serves.  The caller has checked the lengths.
 int attn_beam_impl(d2t_ctx* c, const float* memory, int N, int T, const int32_t* Ts, int beam_size, int64_t* seq_out,
                    int32_t* len_out, float* score_out, float* alpha_out, hipStream_t s) {
   const d2t_config& g = c->cfg;
   const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab, cap = N * beam_size;
-  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
-  size_t mem_rows = (size_t)N * T;
-  if (Ts) {
-    mem_rows = 0; T = 0;
-    for (int i = 0; i < N; ++i) { mem_rows += (size_t)Ts[i]; T = std::max(T, (int)Ts[i]); }
-  }
-  const int Tk = T - key_off;  // ragged: the largest, = st_ld
+  const size_t mem_rows = attn_beam_mem_rows(N, Ts, &T);
+  const int Tk = T - (g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0);  // ragged: the largest, = st_ld
   int rc;
-  // alignment maps (viz_attn): every step's launch writes its rows' alignments into its own slice of a history
-  // [S][cap][Tk], kept apart from the workspace below; the chosen paths [N][S] and lengths [N] follow it
+  // the alignment history [S][cap][Tk], kept apart from the workspace; the chosen paths [N][S] and lengths [N] follow it
   float* d_hist = nullptr;
   int* d_path = nullptr;
   if (alpha_out) {
-    const size_t hist_bytes = (size_t)S * cap * Tk * 4;
-    if (hist_bytes > D2T_ATTN_MAP_BUDGET)
-      return fail(c, D2T_EINVAL, "beam alignment history of %zu bytes (%d steps x %d samples x beam %d x %d keys x 4) exceeds the "
-                  "%llu-byte budget: decode fewer samples per call", hist_bytes, S, N, beam_size, Tk, (unsigned long long)D2T_ATTN_MAP_BUDGET);
-    if ((rc = ensure(c, &c->beam_hist, &c->beam_hist_cap, hist_bytes + ((size_t)N * (S + 1) + 16) * 4))) return rc;
+    if ((rc = attn_beam_hist_check(c, S, N, beam_size, Tk))) return rc;
+    if ((rc = ensure(c, &c->beam_hist, &c->beam_hist_cap, ((size_t)S * cap * Tk + (size_t)N * (S + 1) + 16) * 4))) return rc;
     d_hist = c->beam_hist;
     d_path = reinterpret_cast<int*>(d_hist + (size_t)S * cap * Tk);
   }
@@ -159,220 +230,57 @@ int attn_beam_impl(d2t_ctx* c, const float* memory, int N, int T, const int32_t*
   if (c->ev_done_valid[0]) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done[0], 0));
   if ((rc = ensure(c, &ch.dws, &ch.dws_cap, (mem_rows * Hh + 16) * 4))) return rc;
   float* kp = ch.dws;
-  // workspace: logits [cap][V] | topv [cap] | topi [cap] (one device -> host copy per step) | h_in c_in h_out c_out [cap][H]
-  //            | mem_in mem_out [cap][Tk] | end_step [cap] | dummy tokens i64 [cap] | step pack (one host -> device copy per
-  //            step): tok i64 [cap] | scores [cap] | map [cap] | idx_h [cap] | idx_m [cap] | seg [N][3]
-  //            | ragged: the per-sample tables row0 [N] | T [N]
-  float *d_logits, *d_topv, *st[6];  // st: h_in c_in h_out c_out mem_in mem_out
-  int *d_topi, *d_end, *d_tab;
-  int64_t* d_dummy;
-  AttnBeamPack dp, hpk;  // the step pack on the device and in the pinned mirror
-  auto ws_carve = [&](Carver cv) {
-    d_logits = cv.take<float>((size_t)cap * V);
-    d_topv = cv.take<float>(cap);
-    d_topi = cv.take<int>(cap);
-    for (int i = 0; i < 6; ++i) st[i] = cv.take<float>((size_t)cap * (i < 4 ? Hh : Tk));
-    d_end = cv.take<int>(cap);
-    d_dummy = cv.take<int64_t>(cap, 16);
-    dp = attn_beam_pack(cv, N, cap);
-    d_tab = cv.take<int>(Ts ? 2 * (size_t)N : 0);
-    return cv.total() + 64;
-  };
-  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, ws_carve(Carver())))) return rc;
-  ws_carve(Carver(c->beam_ws));
-  // pinned host mirror: the step pack | topv [cap] | topi [cap] | ragged: the tables
-  float* h_topv;
-  int *h_topi, *h_tab;
-  auto mirror_carve = [&](Carver cv) {
-    hpk = attn_beam_pack(cv, N, cap);
-    h_topv = cv.take<float>(cap);
-    h_topi = cv.take<int>(cap);
-    h_tab = cv.take<int>(Ts ? 2 * (size_t)N : 0);
-    return cv.total();
-  };
-  if ((rc = ensure_host_beam(c, mirror_carve(Carver())))) return rc;
-  mirror_carve(Carver(c->h_beam));
-  char *const d_pack = dp.base, *const hp = hpk.base;
-  const size_t pack_bytes = dp.bytes;
-  int64_t *const d_tok = dp.tok, *const h_tok = hpk.tok;
-  float *const d_scores = dp.scores, *const h_scores = hpk.scores;
-  int *const d_map = dp.map, *const d_idxh = dp.idx_h, *const d_idxm = dp.idx_m, *const d_seg = dp.seg;
-  int *const h_map = hpk.map, *const h_idxh = hpk.idx_h, *const h_idxm = hpk.idx_m, *const h_seg = hpk.seg;
+  AttnBeamWs dv{}, hv{};  // the device view and the host's
+  dv.rec.N = N; dv.rec.beam = beam_size; dv.rec.cap = cap; dv.rec.V = V; dv.rec.S = S; dv.rec.end_token = 1;  // attn_converter.py:8
+  hv.rec = dv.rec;
+  if ((rc = ensure(c, &c->beam_ws, &c->beam_ws_cap, attn_beam_ws_carve(Carver(), Hh, Tk, false, &dv)))) return rc;
+  attn_beam_ws_carve(Carver(c->beam_ws), Hh, Tk, false, &dv);
+  if ((rc = ensure_host_beam(c, attn_beam_mirror_carve(Carver(), &hv)))) return rc;
+  attn_beam_mirror_carve(Carver(c->h_beam), &hv);
+  AttnBeamDev& r = hv.rec;
+  Carver measure;
+  attn_beam_book_carve(measure, r);
+  std::vector<char> book(measure.total());
+  Carver bc(book.data());
+  attn_beam_book_carve(bc, r);
   HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, (int)mem_rows, ACT_NONE));
-  AttnDecP p = attn_dec_params(c, memory, T, kp);
-  p.probs = d_logits; p.tokens = d_dummy; p.end_step = d_end;
-  p.S = 1; p.coverage = 1;
-  p.step_mode = 1;
-  p.st_h_in = st[0]; p.st_c_in = st[1]; p.st_mem_in = st[4];
-  p.st_h_out = st[2]; p.st_c_out = st[3]; p.st_mem_out = st[5];
-  p.tok_in = d_tok; p.row_sample = d_map;
+  AttnDecP p = attn_beam_step_params(c, memory, T, kp, dv, Ts != nullptr, Tk);
   if (Ts) {  // (the previous search has synchronised: the mirror is idle)
-    d2t_ragged_beam_tables(N, Ts, h_tab, h_tab + N);
-    HIPCHK(c, hipMemcpyAsync(d_tab, h_tab, 2 * (size_t)N * 4, hipMemcpyHostToDevice, s));
-    p.smp_row0 = d_tab; p.smp_T = d_tab + N; p.st_ld = Tk;
+    d2t_ragged_beam_tables(N, Ts, hv.tab, hv.tab + N);
+    HIPCHK(c, hipMemcpyAsync(dv.tab, hv.tab, 2 * (size_t)N * 4, hipMemcpyHostToDevice, s));
   }
-
-  struct Smp {
-    std::vector<std::vector<int64_t>> seqs, complete;
-    std::vector<std::vector<int>> paths, cpaths;  // maps only: per hypothesis, the launch row of its parent at every step
-    std::vector<float> live, cscores;
-    int k;
-    bool last_completed = false, finished = false;
-  };
-  std::vector<Smp> sm((size_t)N);
-  for (auto& x : sm) {
-    x.seqs.assign((size_t)beam_size, std::vector<int64_t>{0});  // each starts with [GO] = 0
-    x.live.assign((size_t)beam_size, 0.f);
-    x.k = beam_size;
-    if (alpha_out) x.paths.assign((size_t)beam_size, std::vector<int>{});
-  }
-  // the rows of a step in sample order: segments, scores and row map into the pack; returns the row count
-  auto stage = [&](int step) {
-    int rows = 0;
-    for (int i = 0; i < N; ++i) {
-      Smp& x = sm[i];
-      const int M = x.finished ? 0 : (int)x.seqs.size();
-      // step 0: all rows of a sample are identical and the reference ranks its row 0 only (seq2seq.py:145-146)
-      h_seg[3 * i] = rows; h_seg[3 * i + 1] = M ? (step == 0 ? 1 : M) : 0; h_seg[3 * i + 2] = x.finished ? 0 : x.k;
-      for (int j = 0; j < M; ++j) { h_scores[rows + j] = x.live[j]; h_map[rows + j] = i; }
-      rows += M;
-    }
-    return rows;
-  };
-  int rows = stage(0);
-  HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
+  attn_beam_host_init(r, 0);  // [GO] = 0
+  HIPCHK(c, hipMemcpyAsync(dv.rows, hv.rows, hv.rows_bytes, hipMemcpyHostToDevice, s));
   for (int step = 0; step < S; ++step) {
-    p.B = rows; p.first = step == 0;
+    p.B = r.ctrl[1]; p.first = step == 0;
     if (d_hist) p.sv_alpha = d_hist + (size_t)step * cap * Tk;
     HIPCHK(c, launch_attn_decode(p, s));
-    HIPCHK(c, launch_beam_topk_batch(d_logits, d_scores, d_seg, N, V, beam_size, d_topv, d_topi, s));
-    HIPCHK(c, hipMemcpyAsync(h_topv, d_topv, 2 * (size_t)cap * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, launch_beam_topk_batch(dv.logits, dv.rec.scores, dv.rec.seg, N, V, beam_size, dv.topv, dv.topi, s));
+    HIPCHK(c, hipMemcpyAsync(hv.topv, dv.topv, 2 * (size_t)cap * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    int nrows = 0;
-    for (int i = 0; i < N; ++i) {
-      Smp& x = sm[i];
-      if (x.finished) continue;
-      const int off = h_seg[3 * i];
-      std::vector<std::vector<int64_t>> nseqs;
-      std::vector<std::vector<int>> npaths;
-      std::vector<float> nscores;
-      x.last_completed = false;
-      for (int r = 0; r < x.k; ++r) {
-        const int idx = h_topi[(size_t)i * beam_size + r], prev = idx / V, word = idx % V;
-        std::vector<int64_t> sq = x.seqs[prev];
-        sq.push_back(word);
-        std::vector<int> pa;
-        if (alpha_out) {  // the step's alignment row of this hypothesis = its parent's row: seqs_alpha[prev_word_inds]
-          pa = x.paths[prev];
-          pa.push_back(off + prev);
-        }
-        if (word == 1) {  // [s] (attn_converter.py:8)
-          x.complete.push_back(std::move(sq));
-          if (alpha_out) x.cpaths.push_back(std::move(pa));
-          x.cscores.push_back(h_topv[(size_t)i * beam_size + r]);
-          x.last_completed = true;
-        } else {
-          h_idxh[nrows] = off + prev;  // LSTM state: hidden[prev_word_inds[incomplete]]
-          h_idxm[nrows] = off + r;     // coverage memory: (alpha_cum + alpha)[incomplete]
-          h_tok[nrows] = word;
-          ++nrows;
-          nseqs.push_back(std::move(sq));
-          if (alpha_out) npaths.push_back(std::move(pa));
-          nscores.push_back(h_topv[(size_t)i * beam_size + r]);
-        }
-      }
-      x.seqs.swap(nseqs);
-      x.paths.swap(npaths);
-      x.live.swap(nscores);
-      x.k = (int)x.seqs.size();
-      if (x.k == 0) x.finished = true;
-    }
-    if (!nrows || step + 1 == S) break;
-    rows = stage(step + 1);  // == nrows: the survivors, in the order of their gather indices
-    HIPCHK(c, hipMemcpyAsync(d_pack, hp, pack_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(c, launch_gather_rows(st[2], st[0], d_idxh, rows, Hh, s));
-    HIPCHK(c, launch_gather_rows(st[3], st[1], d_idxh, rows, Hh, s));
-    HIPCHK(c, launch_gather_rows(st[5], st[4], d_idxm, rows, Tk, s));
+    const int rows = attn_beam_host_advance(r, hv.topv, hv.topi);
+    if (!rows || step + 1 == S) break;
+    HIPCHK(c, hipMemcpyAsync(dv.rows, hv.rows, hv.rows_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, launch_gather_rows(dv.st[2], dv.st[0], dv.rec.idx_h, rows, Hh, s));
+    HIPCHK(c, launch_gather_rows(dv.st[3], dv.st[1], dv.rec.idx_h, rows, Hh, s));
+    HIPCHK(c, launch_gather_rows(dv.st[5], dv.st[4], dv.rec.idx_m, rows, Tk, s));
   }
   HIPCHK(c, hipStreamSynchronize(s));
-  std::vector<int> h_path;  // maps: [N][S] chosen paths | [N] lengths, uploaded in one copy
-  if (alpha_out) h_path.assign((size_t)N * (S + 1), 0);
-  for (int i = 0; i < N; ++i) {
-    Smp& x = sm[i];
-    std::vector<int64_t> out;
-    const std::vector<int>* path = nullptr;
-    float score;
-    if (!x.last_completed) {  // seq2seq.py:209-216
-      out.assign(x.seqs[0].begin() + 1, x.seqs[0].end());
-      score = x.live[0];
-      if (alpha_out) path = &x.paths[0];
-    } else {
-      size_t best = 0;
-      for (size_t j = 1; j < x.complete.size(); ++j)
-        if ((double)x.cscores[j] / (double)x.complete[j].size() > (double)x.cscores[best] / (double)x.complete[best].size()) best = j;
-      out.assign(x.complete[best].begin() + 1, x.complete[best].end());
-      score = *std::max_element(x.cscores.begin(), x.cscores.end());
-      if (alpha_out) path = &x.cpaths[best];
-    }
-    const int n = (int)std::min<size_t>(out.size(), (size_t)S);
-    for (int j = 0; j < n; ++j) seq_out[(size_t)i * S + j] = out[j];
-    len_out[i] = n;
-    score_out[i] = score;
-    if (alpha_out) {  // one path entry per emitted token; entries index rows of that step's launch (< cap)
-      const int m = (int)std::min<size_t>(path->size(), (size_t)n);
-      for (int j = 0; j < m; ++j) h_path[(size_t)i * S + j] = (*path)[j];
-      h_path[(size_t)N * S + i] = m;
-    }
-  }
+  std::vector<int64_t> seq((size_t)N * S);
+  std::vector<int> path(alpha_out ? (size_t)N * (S + 1) : 0);  // maps: [N][S] chosen paths | [N] lengths, uploaded in one copy
+  attn_beam_host_finish(r, seq.data(), len_out, score_out, alpha_out ? path.data() : nullptr,
+                        alpha_out ? path.data() + (size_t)N * S : nullptr);
+  for (int i = 0; i < N; ++i)  // the tokens of the sample's length, nothing behind
+    std::copy_n(seq.begin() + (size_t)i * S, len_out[i], seq_out + (size_t)i * S);
   if (alpha_out) {  // seqs_alpha[best][1:] of every sample: one upload, one gather over all samples
-    HIPCHK(c, hipMemcpyAsync(d_path, h_path.data(), h_path.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_path, path.data(), path.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, launch_attn_alpha_gather(d_hist, d_path, d_path + (size_t)N * S, alpha_out, N, S, cap, Tk, s));
-    HIPCHK(c, hipStreamSynchronize(s));  // h_path is pageable and local
+    HIPCHK(c, hipStreamSynchronize(s));  // path is pageable and local
   }
   return D2T_OK;
 }
 
-// ---- the device-side loop ----
-// Its workspace (per decode chain): logits [cap][V] | topv [cap] | topi [cap] | h_in c_in h_out c_out [cap][H] | mem_in mem_out
-// [cap][ld] | end_step [cap] | dummy tokens i64 [cap] | the per-sample tables row0 [N] | T [N] | the record (kernels.h
-// AttnBeamDev) | the result block seq i64 [N][S] | len [N] | score [N] | ctrl [4] (one device -> host copy at the end of a
-// synchronous search), each from a 16-byte boundary.  A function of N, beam, V, S and ld alone: no memory length moves it.
-struct AttnBeamDevWs {
-  float *logits, *topv, *st[6];
-  int *topi, *end, *tab;
-  int64_t* dummy;
-  AttnBeamDev rec;
-  char* res; size_t res_bytes;
-  int64_t* r_seq; int* r_len; float* r_score;
-};
-size_t attn_beam_dev_carve(Carver cv, int Hh, int ld, AttnBeamDevWs* w) {
-  AttnBeamDev& r = w->rec;
-  const size_t cap = (size_t)r.cap, N = (size_t)r.N, nb = N * r.beam;
-  w->logits = cv.take<float>(cap * r.V, 16);
-  w->topv = cv.take<float>(cap, 16);
-  w->topi = cv.take<int>(cap, 16);
-  for (int i = 0; i < 6; ++i) w->st[i] = cv.take<float>(cap * (i < 4 ? Hh : ld), 16);
-  w->end = cv.take<int>(cap, 16);
-  w->dummy = cv.take<int64_t>(cap, 16);
-  w->tab = cv.take<int>(2 * N, 16);
-  r.tok = cv.take<int64_t>(cap, 16);
-  r.scores = cv.take<float>(cap, 16);
-  r.map = cv.take<int>(cap, 16); r.idx_h = cv.take<int>(cap, 16); r.idx_m = cv.take<int>(cap, 16);
-  r.seg = cv.take<int>(3 * N, 16);
-  r.comp_n = cv.take<int>(N, 16); r.fin = cv.take<int>(N, 16); r.last_completed = cv.take<int>(N, 16);
-  r.comp_t = cv.take<int>(nb, 16); r.comp_par = cv.take<int>(nb, 16); r.comp_score = cv.take<float>(nb, 16);
-  r.hist_par = cv.take<int>((size_t)r.S * cap, 16); r.hist_tok = cv.take<int>((size_t)r.S * cap, 16);
-  cv.align(16);
-  w->res = cv.here();
-  w->r_seq = cv.take<int64_t>(N * r.S, 16);
-  w->r_len = cv.take<int>(N);
-  w->r_score = cv.take<float>(N);
-  r.ctrl = cv.take<int>(4);
-  w->res_bytes = (size_t)(cv.here() - w->res);
-  r.topv = w->topv; r.topi = w->topi;
-  return cv.total() + 64;
-}
-constexpr int ATTN_BEAM_LD_QUANTUM = 256;  // the row stride of state and history: the largest Tk rounded up to this
+constexpr int ATTN_BEAM_LD_QUANTUM = 256;  // the device-side loop's row stride of state and history: the largest Tk rounded up to this
 
 // The search of attn_beam_impl with the bookkeeping ON THE DEVICE (attn_beam.hip): the reference's per-step walk is
 // attn_beam_dev_advance_kernel behind the per-sample top-k, the three gathers are one launch, the final pick is
@@ -393,23 +301,17 @@ int attn_beam_dev_impl(d2t_ctx* c, const float* memory, int N, int T, const int3
                        int32_t* len_out, float* score_out, float* alpha_out, hipStream_t user, bool async) {
   const d2t_config& g = c->cfg;
   const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab, cap = N * beam_size;
-  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
   if (N > ATTN_BEAM_MAX_N)
     return fail(c, D2T_EINVAL, "the device-side beam search takes 1 to %d samples per call, got %d", ATTN_BEAM_MAX_N, N);
   if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
   if (int rc = check_dev_ptr(c, alpha_out, "alpha")) return rc;
   std::vector<int32_t> uniform;
   if (!Ts) { uniform.assign((size_t)N, T); Ts = uniform.data(); }
-  size_t mem_rows = 0;
-  T = 0;
-  for (int i = 0; i < N; ++i) { mem_rows += (size_t)Ts[i]; T = std::max(T, (int)Ts[i]); }
-  const int Tk = T - key_off;  // the largest
+  const size_t mem_rows = attn_beam_mem_rows(N, Ts, &T);
+  const int Tk = T - (g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0);  // the largest
   int ld = (Tk + ATTN_BEAM_LD_QUANTUM - 1) / ATTN_BEAM_LD_QUANTUM * ATTN_BEAM_LD_QUANTUM;
   if (alpha_out) {
-    const size_t hist_bytes = (size_t)S * cap * Tk * 4;
-    if (hist_bytes > D2T_ATTN_MAP_BUDGET)
-      return fail(c, D2T_EINVAL, "beam alignment history of %zu bytes (%d steps x %d samples x beam %d x %d keys x 4) exceeds the "
-                  "%llu-byte budget: decode fewer samples per call", hist_bytes, S, N, beam_size, Tk, (unsigned long long)D2T_ATTN_MAP_BUDGET);
+    if (int rc = attn_beam_hist_check(c, S, N, beam_size, Tk)) return rc;
     if ((size_t)S * cap * ld * 4 > D2T_ATTN_MAP_BUDGET) ld = Tk;
   }
   // ---- nothing is refused below this line ----
@@ -417,10 +319,10 @@ int attn_beam_dev_impl(d2t_ctx* c, const float* memory, int N, int T, const int3
   d2t_ctx::Chain& ch = c->chains[chain];
   hipStream_t s = ch.stream;
   int rc;
-  AttnBeamDevWs ws{};
+  AttnBeamWs ws{};
   ws.rec.N = N; ws.rec.beam = beam_size; ws.rec.cap = cap; ws.rec.V = V; ws.rec.S = S; ws.rec.end_token = 1;  // attn_converter.py:8
-  if ((rc = ensure(c, &ch.abeam_ws, &ch.abeam_ws_cap, attn_beam_dev_carve(Carver(), Hh, ld, &ws)))) return rc;
-  attn_beam_dev_carve(Carver(ch.abeam_ws), Hh, ld, &ws);
+  if ((rc = ensure(c, &ch.abeam_ws, &ch.abeam_ws_cap, attn_beam_ws_carve(Carver(), Hh, ld, true, &ws)))) return rc;
+  attn_beam_ws_carve(Carver(ch.abeam_ws), Hh, ld, true, &ws);
   if ((rc = ensure(c, &ch.abeam_mem, &ch.abeam_mem_cap, (mem_rows * Hh + 16) * 4))) return rc;
   if ((rc = ensure(c, &ch.dws, &ch.dws_cap, (mem_rows * Hh + 16) * 4))) return rc;
   float* d_hist = nullptr;
@@ -452,14 +354,8 @@ int attn_beam_dev_impl(d2t_ctx* c, const float* memory, int N, int T, const int3
   float* kp = ch.dws;
   HIPCHK(c, linear_any(nullptr, s, ch.abeam_mem, c->attn.key, nullptr, kp, (int)mem_rows, ACT_NONE));
   const AttnBeamDev& b = ws.rec;
-  AttnDecP p = attn_dec_params(c, ch.abeam_mem, T, kp);
-  p.probs = ws.logits; p.tokens = ws.dummy; p.end_step = ws.end;
-  p.B = cap; p.S = 1; p.coverage = 1;
-  p.step_mode = 1;
-  p.st_h_in = ws.st[0]; p.st_c_in = ws.st[1]; p.st_mem_in = ws.st[4];
-  p.st_h_out = ws.st[2]; p.st_c_out = ws.st[3]; p.st_mem_out = ws.st[5];
-  p.tok_in = b.tok; p.row_sample = b.map;
-  p.smp_row0 = ws.tab; p.smp_T = ws.tab + N; p.st_ld = ld;
+  AttnDecP p = attn_beam_step_params(c, ch.abeam_mem, T, kp, ws, true, ld);
+  p.B = cap;
   p.guard = b.ctrl;
   auto enqueue_loop = [&](hipStream_t st) -> hipError_t {
     hipError_t e;
@@ -508,13 +404,15 @@ int attn_beam_dev_impl(d2t_ctx* c, const float* memory, int N, int T, const int3
   const float* h_score = reinterpret_cast<const float*>(c->h_beam + (reinterpret_cast<char*>(ws.r_score) - ws.res));
   for (int i = 0; i < N; ++i) {  // as the host loop leaves them: the tokens of the sample's length, nothing behind
     const int n = std::min(std::max(h_len[i], 0), S);
-    for (int j = 0; j < n; ++j) seq_out[(size_t)i * S + j] = h_seq[(size_t)i * S + j];
+    std::copy_n(h_seq + (size_t)i * S, n, seq_out + (size_t)i * S);
     len_out[i] = n;
     score_out[i] = h_score[i];
   }
   return D2T_OK;
 }
 }  // namespace
+
+extern "C" {
 
 int d2t_decode_attn_greedy(d2t_ctx* c, const float* memory, int32_t B, int32_t T, int32_t is_test, int64_t* tokens,
                            float* probs, int32_t* steps_out, d2t_stream stream) {
@@ -577,14 +475,7 @@ int d2t_decode_attn_beam_batch_ragged(d2t_ctx* c, const float* memory, int32_t N
   // d2t_decode_attn_beam_batch[_alpha] for N samples whose memories have DIFFERENT lengths, packed in `memory`: one step
   // loop, so the batch_max_length + 1 round trips are paid once for all sizes.  Everything is checked before anything is
   // enqueued; the context stays usable after a refusal.
-  if (!c || !memory || !T || !seq_out || !len_out || !score_out) return fail(c, D2T_EINVAL, "bad argument");
-  if (int rc = attn_beam_check(c, beam_size)) return rc;
-  if (N < 1 || N > ATTN_BEAM_MAX_N)
-    return fail(c, D2T_EINVAL, "ragged beam search takes 1 to %d samples per call, got %d", ATTN_BEAM_MAX_N, N);
-  const int key_off = c->cfg.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
-  for (int i = 0; i < N; ++i)
-    if (T[i] - key_off < 1 || T[i] - key_off > memory_cap(c))
-      return fail(c, D2T_EINVAL, "sample %d has memory length %d, supported are %d to %d", i, T[i], 1 + key_off, memory_cap(c) + key_off);
+  if (int rc = attn_beam_ragged_check(c, memory, N, T, beam_size, seq_out, len_out, score_out)) return rc;
   if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
   if (int rc = check_dev_ptr(c, alpha_out, "alpha")) return rc;
   if (c->attn_beam_device)
@@ -613,14 +504,7 @@ int d2t_decode_attn_beam_batch_submit(d2t_ctx* c, const float* memory, int32_t N
                                       int64_t* ticket_out) {
   DevGuard dg_(c);
   // the refusals of d2t_decode_attn_beam_batch_ragged, and outputs that the search's stream can write
-  if (!c || !memory || !T || !seq_dev || !len_dev || !score_dev) return fail(c, D2T_EINVAL, "bad argument");
-  if (int rc = attn_beam_check(c, beam_size)) return rc;
-  if (N < 1 || N > ATTN_BEAM_MAX_N)
-    return fail(c, D2T_EINVAL, "ragged beam search takes 1 to %d samples per call, got %d", ATTN_BEAM_MAX_N, N);
-  const int key_off = c->cfg.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
-  for (int i = 0; i < N; ++i)
-    if (T[i] - key_off < 1 || T[i] - key_off > memory_cap(c))
-      return fail(c, D2T_EINVAL, "sample %d has memory length %d, supported are %d to %d", i, T[i], 1 + key_off, memory_cap(c) + key_off);
+  if (int rc = attn_beam_ragged_check(c, memory, N, T, beam_size, seq_dev, len_dev, score_dev)) return rc;
   const struct { const void* p; const char* what; } outs[] = {{seq_dev, "seq_dev"}, {len_dev, "len_dev"}, {score_dev, "score_dev"},
                                                               {alpha_dev, "alpha_dev"}};
   for (const auto& o : outs) {

@@ -1,4 +1,6 @@
 // libd2t engine: the d2t_op_* entries of the C-ABI -- single kernels behind argument checks, for the operator tests and tools.
+#include <climits>
+
 #include "engine_impl.h"
 
 extern "C" {
@@ -668,12 +670,13 @@ int d2t_op_attn_alpha_gather(const float* hist, const int32_t* path, const int32
 }
 
 namespace {
-// the caller's record as the kernels take it; false: a missing array or a size the kernels refuse
-bool attn_beam_rec(const d2t_op_attn_beam_rec* r, AttnBeamDev* b) {
+// the caller's record as the kernels and the host functions take it; false: a missing array or a size they refuse (max_n:
+// the kernels' sample limit; the host functions have none)
+static bool attn_beam_rec(const d2t_op_attn_beam_rec* r, AttnBeamDev* b, int max_n = 1024) {  // (static: we are inside extern "C")
   if (!r || !r->ctrl || !r->tok || !r->scores || !r->map || !r->idx_h || !r->idx_m || !r->seg || !r->comp_n || !r->fin ||
       !r->last_completed || !r->comp_t || !r->comp_par || !r->comp_score || !r->hist_par || !r->hist_tok)
     return false;
-  if (r->N < 1 || r->N > 1024 || r->beam < 1 || r->beam > 16 || (long long)r->cap < (long long)r->N * r->beam || r->V < 1 ||
+  if (r->N < 1 || r->N > max_n || r->beam < 1 || r->beam > 16 || (long long)r->cap < (long long)r->N * r->beam || r->V < 1 ||
       r->S < 1 || r->end_token < 0 || r->end_token >= r->V)
     return false;
   *b = AttnBeamDev{};
@@ -684,6 +687,54 @@ bool attn_beam_rec(const d2t_op_attn_beam_rec* r, AttnBeamDev* b) {
   b->N = r->N; b->beam = r->beam; b->cap = r->cap; b->V = r->V; b->S = r->S; b->end_token = r->end_token;
   return true;
 }
+// The state as one step of the bookkeeping will read it, h's ctrl, seg, comp_n, fin and topi being HOST arrays: the step
+// indexes the history, the candidates index rows of their segment.
+static bool attn_beam_advance_ok(const AttnBeamDev& h) {
+  const int* c = h.ctrl;
+  if (c[0] < 0 || c[2] < 0) return false;
+  if (c[2] && c[0] >= c[2]) return true;  // stopped: the step does nothing
+  if (c[0] >= h.S) return false;
+  for (int i = 0; i < h.N; ++i) {
+    if (h.fin[i]) continue;
+    const int off = h.seg[3 * i], m = h.seg[3 * i + 1], k = h.seg[3 * i + 2];
+    if (k < 1 || k > h.beam || m < 1 || m > h.beam || off < 0 || off + std::max(m, k) > h.cap || h.comp_n[i] < 0 ||
+        h.comp_n[i] + k > h.beam)
+      return false;
+    for (int q = 0; q < k; ++q) {
+      const int idx = h.topi[(size_t)i * h.beam + q];
+      if (idx < 0 || idx / h.V >= m) return false;
+    }
+  }
+  return true;
+}
+// The walk the final pick will take, h's ctrl, seg, comp_n, last_completed, comp_t, comp_par and the first ctrl[3] steps of
+// hist_par being HOST arrays: every row it reads must lie inside the record.
+static bool attn_beam_finish_ok(const AttnBeamDev& h) {
+  const int steps = h.ctrl[3];
+  if (steps < 0 || steps > h.S) return false;
+  for (int i = 0; i < h.N; ++i) {
+    int t = -1, row = 0;
+    if (!h.last_completed[i]) {
+      if (h.seg[3 * i + 1] > 0) { t = steps - 1; row = h.seg[3 * i]; }
+    } else {
+      if (h.comp_n[i] < 1 || h.comp_n[i] > h.beam) return false;
+      for (int j = 0; j < h.comp_n[i]; ++j) {  // any of them may be the best
+        const int tj = h.comp_t[(size_t)i * h.beam + j], pj = h.comp_par[(size_t)i * h.beam + j];
+        if (tj < 0 || tj >= steps || pj < 0 || pj >= h.cap) return false;
+        for (int u = tj - 1, rw = pj; u >= 0; --u) {
+          rw = h.hist_par[(size_t)u * h.cap + rw];
+          if (rw < 0 || rw >= h.cap) return false;
+        }
+      }
+    }
+    for (; t >= 0; --t) {
+      if (row < 0 || row >= h.cap) return false;
+      row = h.hist_par[(size_t)t * h.cap + row];
+    }
+    if (row < 0 || row >= h.cap) return false;
+  }
+  return true;
+}
 }  // namespace
 
 int d2t_op_attn_beam_advance(const d2t_op_attn_beam_rec* r, int32_t init, int64_t go_token, d2t_stream stream) {
@@ -692,25 +743,13 @@ int d2t_op_attn_beam_advance(const d2t_op_attn_beam_rec* r, int32_t init, int64_
   hipStream_t s = (hipStream_t)stream;
   if (init) return op_status(launch_attn_beam_dev_init(b, go_token, s));
   if (!b.topv || !b.topi) return D2T_EINVAL;
-  // the state as the kernel will read it: the step indexes the history, the candidates index rows of their segment
   std::vector<int> c, sg, cn, fi, ti;
   if (!fetch_ints(s, b.ctrl, 4, &c) || !fetch_ints(s, b.seg, (size_t)b.N * 3, &sg) || !fetch_ints(s, b.comp_n, b.N, &cn) ||
       !fetch_ints(s, b.fin, b.N, &fi) || !fetch_ints(s, b.topi, (size_t)b.N * b.beam, &ti))
     return D2T_EHIP;
-  if (c[0] < 0 || c[2] < 0) return D2T_EINVAL;
-  if (!(c[2] && c[0] >= c[2])) {  // the launch will do work
-    if (c[0] >= b.S) return D2T_EINVAL;
-    for (int i = 0; i < b.N; ++i) {
-      if (fi[i]) continue;
-      const int off = sg[3 * i], m = sg[3 * i + 1], k = sg[3 * i + 2];
-      if (k < 1 || k > b.beam || m < 1 || m > b.beam || off < 0 || off + std::max(m, k) > b.cap || cn[i] < 0 || cn[i] + k > b.beam)
-        return D2T_EINVAL;
-      for (int q = 0; q < k; ++q) {
-        const int idx = ti[(size_t)i * b.beam + q];
-        if (idx < 0 || idx / b.V >= m) return D2T_EINVAL;
-      }
-    }
-  }
+  AttnBeamDev h = b;
+  h.ctrl = c.data(); h.seg = sg.data(); h.comp_n = cn.data(); h.fin = fi.data(); h.topi = ti.data();
+  if (!attn_beam_advance_ok(h)) return D2T_EINVAL;
   return op_status(launch_attn_beam_dev_advance(b, s));
 }
 
@@ -719,36 +758,38 @@ int d2t_op_attn_beam_finish(const d2t_op_attn_beam_rec* r, int64_t* seq, int32_t
   AttnBeamDev b;
   if (!attn_beam_rec(r, &b) || !seq || !len || !score || (path != nullptr) != (plen != nullptr)) return D2T_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  // the walk the kernel will take, on the host: every row it reads must lie inside the record
   std::vector<int> c, sg, cn, lc, ct, cp, hp;
   if (!fetch_ints(s, b.ctrl, 4, &c)) return D2T_EHIP;
-  if (c[3] < 0 || c[3] > b.S) return D2T_EINVAL;
+  if (c[3] < 0 || c[3] > b.S) return D2T_EINVAL;  // (the steps of the history to fetch)
   if (!fetch_ints(s, b.seg, (size_t)b.N * 3, &sg) || !fetch_ints(s, b.comp_n, b.N, &cn) || !fetch_ints(s, b.last_completed, b.N, &lc) ||
       !fetch_ints(s, b.comp_t, (size_t)b.N * b.beam, &ct) || !fetch_ints(s, b.comp_par, (size_t)b.N * b.beam, &cp) ||
       !fetch_ints(s, b.hist_par, (size_t)c[3] * b.cap, &hp))
     return D2T_EHIP;
-  for (int i = 0; i < b.N; ++i) {
-    int t = -1, row = 0;
-    if (!lc[i]) {
-      if (sg[3 * i + 1] > 0) { t = c[3] - 1; row = sg[3 * i]; }
-    } else {
-      if (cn[i] < 1 || cn[i] > b.beam) return D2T_EINVAL;
-      for (int j = 0; j < cn[i]; ++j) {  // any of them may be the best
-        const int tj = ct[(size_t)i * b.beam + j], pj = cp[(size_t)i * b.beam + j];
-        if (tj < 0 || tj >= c[3] || pj < 0 || pj >= b.cap) return D2T_EINVAL;
-        for (int u = tj - 1, rw = pj; u >= 0; --u) {
-          rw = hp[(size_t)u * b.cap + rw];
-          if (rw < 0 || rw >= b.cap) return D2T_EINVAL;
-        }
-      }
-    }
-    for (; t >= 0; --t) {
-      if (row < 0 || row >= b.cap) return D2T_EINVAL;
-      row = hp[(size_t)t * b.cap + row];
-    }
-    if (row < 0 || row >= b.cap) return D2T_EINVAL;
-  }
+  AttnBeamDev h = b;
+  h.ctrl = c.data(); h.seg = sg.data(); h.comp_n = cn.data(); h.last_completed = lc.data(); h.comp_t = ct.data();
+  h.comp_par = cp.data(); h.hist_par = hp.data();
+  if (!attn_beam_finish_ok(h)) return D2T_EINVAL;
   return op_status(launch_attn_beam_dev_finish(b, seq, len, score, path, plen, s));
+}
+
+// The same two operators on the host functions of attn_beam_host.h, which the host loop of the search runs: every pointer
+// is a host pointer, there is no device and no context, and N has no upper limit.
+int d2t_op_attn_beam_host_advance(const d2t_op_attn_beam_rec* r, int32_t init, int64_t go_token) {
+  AttnBeamDev b;
+  if (!attn_beam_rec(r, &b, INT_MAX)) return D2T_EINVAL;
+  if (init) { attn_beam_host_init(b, go_token); return D2T_OK; }
+  if (!b.topv || !b.topi || !attn_beam_advance_ok(b)) return D2T_EINVAL;
+  attn_beam_host_advance(b, b.topv, b.topi);
+  return D2T_OK;
+}
+
+int d2t_op_attn_beam_host_finish(const d2t_op_attn_beam_rec* r, int64_t* seq, int32_t* len, float* score, int32_t* path,
+                                 int32_t* plen) {
+  AttnBeamDev b;
+  if (!attn_beam_rec(r, &b, INT_MAX) || !seq || !len || !score || (path != nullptr) != (plen != nullptr)) return D2T_EINVAL;
+  if (!attn_beam_finish_ok(b)) return D2T_EINVAL;
+  attn_beam_host_finish(b, seq, len, score, path, plen);
+  return D2T_OK;
 }
 
 }  // extern "C"

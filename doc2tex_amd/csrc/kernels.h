@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#pragma GCC visibility push(hidden)  // (its inline functions are not part of the library's surface)
+#include "attn_beam_host.h"  // AttnBeamDev: the record of the LSTM-attention beam search, shared with the host loop
+#pragma GCC visibility pop
+
 // Timing-probe / ablation switches (D2T_CONV_ABL, D2T_WGRAD_ABL, D2T_LSTM_BWD_PROBE, D2T_ATTN_BWD_PROBE) skip kernel phases
 // or launch kernels whose results are garbage by construction.  They exist only in a probe build (build.sh with
 // D2T_PROBES=1 -> -DD2T_PROBES); the shipped library never reads them, so a stray variable in a serving or training
@@ -369,29 +373,7 @@ struct BeamDev {
 };
 hipError_t launch_beam_dev_init(const BeamDev& b, int64_t go_token, hipStream_t s);
 hipError_t launch_beam_dev_advance(const BeamDev& b, hipStream_t s);
-// The same for the LSTM-attention heads (Attention / AttentionV2.forward_beam; attn_beam.hip).  Modelled on BeamDev; what
-// differs is the reference's bookkeeping: step 0 ranks row 0 of a sample's `beam` identical rows, every completion lowers the
-// sample's k (so completions never exceed beam), the LSTM state of a survivor follows its parent row (idx_h) but its coverage
-// memory follows its candidate rank (idx_m), and the final pick depends on whether the sample's last step completed anything.
-struct AttnBeamDev {
-  int* ctrl;            // [0] step, [1] live rows, [2] stop-at step (0 = none), [3] steps run
-  int64_t* tok;         // [cap] input token of every live hypothesis row
-  float* scores;        // [cap]
-  int* map;             // [cap] sample of a row
-  int* idx_h;           // [cap] row of the step just run whose LSTM state the new row resumes (its parent)
-  int* idx_m;           // [cap] row of the step just run whose coverage memory it resumes (first row of the sample + rank)
-  int* seg;             // [N][3] first row, rows ranked, candidates wanted (k)
-  int* comp_n;          // [N] completed hypotheses
-  int* fin;             // [N] sample finished (k == 0)
-  int* last_completed;  // [N] the last step that processed the sample completed a hypothesis
-  int* comp_t;          // [N][beam] step at which a hypothesis completed
-  int* comp_par;        // [N][beam] its parent row (that step's row order)
-  float* comp_score;    // [N][beam]
-  int* hist_par;        // [S][cap] parent row of the hypothesis a step created at row r (the next step's row order)
-  int* hist_tok;        // [S][cap] its token
-  const float* topv; const int* topi;   // [N][beam] candidates of the step (launch_beam_topk_batch)
-  int N, beam, cap, V, S, end_token;
-};
+// The same for the LSTM-attention heads (attn_beam.hip), over the record AttnBeamDev of attn_beam_host.h.
 hipError_t launch_attn_beam_dev_init(const AttnBeamDev& b, int64_t go_token, hipStream_t s);
 hipError_t launch_attn_beam_dev_advance(const AttnBeamDev& b, hipStream_t s);
 // The three row gathers between two steps in one launch over all cap row slots, guarded by ctrl (live rows, stop step):

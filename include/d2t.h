@@ -690,7 +690,7 @@ int d2t_op_attn_decode_finalize(const uint64_t* exit_state, int32_t* steps_dev, 
  * (values < cap where j < len[i]), len [N] in [0, S].  out must be 16-byte aligned. */
 int d2t_op_attn_alpha_gather(const float* hist, const int32_t* path, const int32_t* len, float* out, int32_t N, int32_t S,
                              int32_t cap, int32_t Tk, d2t_stream stream);
-/* The record of the device-side LSTM-attention beam search (kernels.h AttnBeamDev), every array a device buffer of the
+/* The record of the LSTM-attention beam search (csrc/attn_beam_host.h AttnBeamDev), every array a device buffer of the
  * caller: ctrl [4] = {step, live rows, stop-at step, steps run}; tok (int64), scores, map, idx_h, idx_m [cap]; seg [N][3] =
  * {first row, rows ranked, candidates wanted}; comp_n, fin, last_completed [N]; comp_t, comp_par, comp_score [N][beam];
  * hist_par, hist_tok [S][cap]; topv, topi [N][beam] the step's candidates (d2t_op_beam_topk).  cap >= N * beam, N <= 1024,
@@ -711,6 +711,12 @@ typedef struct d2t_op_attn_beam_rec {
 int d2t_op_attn_beam_advance(const d2t_op_attn_beam_rec* r, int32_t init, int64_t go_token, d2t_stream stream);
 int d2t_op_attn_beam_finish(const d2t_op_attn_beam_rec* r, int64_t* seq, int32_t* len, float* score, int32_t* path, int32_t* plen,
                             d2t_stream stream);
+/* The same two operators as the HOST loop of the search runs them (csrc/attn_beam_host.h): every array of the record and
+ * every output is a host array, nothing touches a device or a context, and N has no upper limit.  They write what the device
+ * operators write, array for array, and refuse the same records with D2T_EINVAL, writing nothing. */
+int d2t_op_attn_beam_host_advance(const d2t_op_attn_beam_rec* r, int32_t init, int64_t go_token);
+int d2t_op_attn_beam_host_finish(const d2t_op_attn_beam_rec* r, int64_t* seq, int32_t* len, float* score, int32_t* path,
+                                 int32_t* plen);
 
 /* ---- fused cross-entropy ------------------------------------------------------------------------------------------
  * The criterion of the reference's training step -- nn.CrossEntropyLoss(ignore_index = PAD, reduction = 'none') on

@@ -1,11 +1,13 @@
 """Pure-Python statements of the LSTM-attention beam search's bookkeeping (Attention / AttentionV2.forward_beam), for the
-tests of the device-side search:
+tests of both step loops:
 
-* `Rec` + `rec_init` / `rec_advance` / `rec_finish`: the rules on the record the kernels keep (kernels.h AttnBeamDev) -- what
+* `Rec` + `rec_init` / `rec_advance` / `rec_finish`: the rules on the record both loops keep (csrc/attn_beam_host.h
+  AttnBeamDev) -- what the host loop's attn_beam_host_init / _advance / _finish and the device-side loop's
   attn_beam_dev_init / _advance / _finish_kernel must write, array for array.  A Rec starts filled with canaries, and these
-  functions write exactly the entries the kernels write, so comparing whole arrays also shows that nothing else was touched.
-* `brute_force`: the same search restated the way the host loop of engine_attn.hip keeps it -- whole token sequences and
-  whole row paths in lists, no record, no history -- which the record-based rules are checked against on the CPU.
+  functions write exactly the entries the C++ writes, so comparing whole arrays also shows that nothing else was touched.
+* `brute_force`: the same search restated the way the reference keeps it -- whole token sequences and whole row paths in
+  lists, no record, no history.  It mirrors no C++ text: it is the only whole-sequence statement left, and the record-based
+  rules are checked against it on the CPU.
 
 Both read their candidates from a `Stream`: seeded, and a function of (step, sample, k, rows ranked) alone, so two
 implementations that disagree about a sample's state draw different candidates and cannot agree by accident.  numpy only."""
@@ -160,7 +162,7 @@ def run_record(N, beam, S, V, stream):
 
 
 def brute_force(N, beam, S, V, stream):
-    """The host loop's bookkeeping (engine_attn.hip attn_beam_impl), whole sequences in lists.  Returns per sample
+    """The reference's bookkeeping (forward_beam), whole sequences and whole launch-row paths in lists.  Returns per sample
     (tokens without [GO], score, path), the steps executed, and the set of things that happened on the way."""
     sm = [dict(seqs=[[0] for _ in range(beam)], paths=[[] for _ in range(beam)], live=[np.float32(0)] * beam, complete=[],
                cpaths=[], cscores=[], k=beam, last=False, fin=False) for _ in range(N)]

@@ -1,7 +1,8 @@
 """CPU: the device-side LSTM-attention beam search's interface -- its C-ABI entries in the ctypes table with the header's
 argument counts, the record struct, the Engine and Model surface -- and the record-based bookkeeping rules that the GPU tests
 hold the kernels to (attn_beam_refs.rec_*), checked here against a brute-force restatement that keeps whole sequences in
-lists, as the host loop does."""
+lists; and the host loop's bookkeeping (csrc/attn_beam_host.h), run through its two device-free operators and held to the
+same rules array for array."""
 import ctypes as C
 import os
 import re
@@ -16,7 +17,8 @@ from doc2tex_amd.engine import Engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["d2t_decode_attn_supports_device_beam", "d2t_set_attn_beam_device", "d2t_decode_attn_beam_device_runs",
-           "d2t_decode_attn_beam_batch_submit", "d2t_op_attn_beam_advance", "d2t_op_attn_beam_finish"]
+           "d2t_decode_attn_beam_batch_submit", "d2t_op_attn_beam_advance", "d2t_op_attn_beam_finish",
+           "d2t_op_attn_beam_host_advance", "d2t_op_attn_beam_host_finish"]
 
 
 def _header():
@@ -100,3 +102,142 @@ def test_a_stopped_record_is_left_alone():
     before = {f: getattr(r, f).copy() for f in AR.FIELDS}
     AR.rec_advance(r, *AR.candidates(r, stream))
     assert all(np.array_equal(before[f], getattr(r, f)) for f in AR.FIELDS)
+
+
+# =====================================================================================================================
+# the host loop's bookkeeping (csrc/attn_beam_host.h) through its operators: no device, every array a numpy array
+# =====================================================================================================================
+D2T_EINVAL = 1  # include/d2t.h
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.int32) if a.dtype == np.float32 else a
+
+
+class HostRec:
+    """a canary-filled record in host memory, laid out as the reference record `r`"""
+
+    def __init__(self, r):
+        self.t = {f: getattr(r, f).copy() for f in AR.FIELDS}
+        self.topv = np.full((r.N, r.beam), AR.FCAN, np.float32)
+        self.topi = np.full((r.N, r.beam), AR.ICAN, np.int32)
+        self.a = a = _lib.D2TOpAttnBeamRec()
+        for f in AR.FIELDS:
+            setattr(a, f, self.t[f].ctypes.data)
+        a.topv, a.topi = self.topv.ctypes.data, self.topi.ctypes.data
+        a.N, a.beam, a.cap, a.V, a.S, a.end_token = r.N, r.beam, r.cap, r.V, r.S, AR.END
+
+    def advance(self, init=False, cands=None):
+        if cands is not None:
+            self.topv[...], self.topi[...] = cands
+        return _lib.load().d2t_op_attn_beam_host_advance(C.byref(self.a), int(init), 0)
+
+    def finish(self, with_path=True):
+        N, Sx = self.a.N, self.a.S
+        out = [np.full((N, Sx), AR.ICAN, np.int64), np.full(N, AR.ICAN, np.int32), np.full(N, AR.FCAN, np.float32),
+               np.full((N, Sx), AR.ICAN, np.int32), np.full(N, AR.ICAN, np.int32)]
+        ptr = [o.ctypes.data for o in out]
+        rc = _lib.load().d2t_op_attn_beam_host_finish(C.byref(self.a), ptr[0], ptr[1], ptr[2], ptr[3] if with_path else None,
+                                                      ptr[4] if with_path else None)
+        return rc, out
+
+    def differs_from(self, r):
+        """names of the arrays that are not the reference's, bit for bit (canaries included)"""
+        return [f for f in AR.FIELDS if not np.array_equal(_bits(self.t[f]), _bits(getattr(r, f)))]
+
+
+@pytest.mark.parametrize("N,beam,seed,p_end,end_from", CASES)
+def test_host_operator_chain_equals_the_record_rules(N, beam, seed, p_end, end_from):
+    """init, S chained steps of the host loop's bookkeeping (those behind the stop step included: they must leave the record
+    alone) and its final pick: every array of the record after every step, and every output of finish, is the reference's --
+    integers exactly, floats by their bits, canaries where nothing is to be written (cap > N x beam)."""
+    stream = AR.Stream(V, seed, p_end, end_from)
+    r = AR.Rec(N, beam, S, V, cap=N * beam + 3)
+    h = HostRec(r)
+    assert h.advance(init=True) == 0
+    AR.rec_init(r)
+    assert h.differs_from(r) == [], "after init"
+    for step in range(S):
+        cands = AR.candidates(r, stream)
+        assert h.advance(cands=cands) == 0, f"step {step}"
+        AR.rec_advance(r, *cands)
+        assert h.differs_from(r) == [], f"after step {step}"
+    want = AR.rec_finish(r)
+    rc, got = h.finish()
+    assert rc == 0
+    for name, g, w in zip(("seq", "len", "score", "path", "plen"), got, want):
+        assert np.array_equal(_bits(g), _bits(w)), f"finish: {name}"
+    rc, got = h.finish(with_path=False)
+    assert rc == 0
+    assert all(np.array_equal(_bits(g), _bits(w)) for g, w in zip(got[:3], want[:3]))
+    assert (got[3] == AR.ICAN).all() and (got[4] == AR.ICAN).all()
+    assert h.differs_from(r) == [], "finish writes nothing into the record"
+
+
+def test_host_operators_leave_a_stopped_record_alone():
+    stream = AR.Stream(V, 2, 0.2, 4)
+    r = AR.Rec(5, 3, S, V, cap=5 * 3 + 3)
+    h = HostRec(r)
+    assert h.advance(init=True) == 0
+    AR.rec_init(r)
+    for _ in range(5):
+        cands = AR.candidates(r, stream)
+        assert h.advance(cands=cands) == 0
+        AR.rec_advance(r, *cands)
+    assert h.t["ctrl"].tolist() == [5, 0, 5, 5] and h.differs_from(r) == []
+    poison = (np.full((5, 3), AR.FCAN, np.float32), np.full((5, 3), 1 << 30, np.int32))
+    assert h.advance(cands=poison) == 0
+    assert h.differs_from(r) == []
+
+
+def test_host_operator_refusals_write_nothing():
+    """what test_operator_refusals_write_nothing asks of the device operators"""
+    stream = AR.Stream(V, 1)
+    r = AR.Rec(5, 3, S, V)
+    h = HostRec(r)
+    lib = _lib.load()
+    for field, value in (("N", 0), ("beam", 0), ("beam", 17), ("cap", 14), ("V", 0), ("S", 0), ("end_token", V), ("seg", None),
+                         ("hist_tok", None), ("last_completed", None)):
+        keep = getattr(h.a, field)
+        setattr(h.a, field, value)
+        assert h.advance(init=True) == D2T_EINVAL, (field, value)
+        assert h.finish()[0] == D2T_EINVAL, (field, value)
+        setattr(h.a, field, keep)
+    assert lib.d2t_op_attn_beam_host_advance(None, 1, 0) == D2T_EINVAL
+    assert h.differs_from(r) == []
+    assert h.advance(init=True) == 0
+    AR.rec_init(r)
+    topv, topi = AR.candidates(r, stream)
+    for bad in (-1, V, 3 * V):  # a candidate of a row the segment does not rank (step 0 ranks one row)
+        t2 = topi.copy()
+        t2[2, 1] = bad
+        assert h.advance(cands=(topv, t2)) == D2T_EINVAL, bad
+    h.t["ctrl"][0] = S  # a step beyond the history
+    assert h.advance(cands=(topv, topi)) == D2T_EINVAL
+    h.t["ctrl"][0] = 0
+    assert h.differs_from(r) == []
+    h.t["last_completed"][1] = 1  # "completed" with an empty completed set
+    rc, out = h.finish()
+    assert rc == D2T_EINVAL
+    assert all((o == (AR.FCAN if o.dtype == np.float32 else AR.ICAN)).all() for o in out)
+    h.t["last_completed"][1] = 0
+    assert h.advance(cands=(topv, topi)) == 0
+    AR.rec_advance(r, topv, topi)
+    assert h.differs_from(r) == []
+
+
+def test_host_operators_have_no_sample_limit():
+    """N = 1025 is beyond the kernels' 1024 samples; the host functions take it (the uniform entries of the host loop do)"""
+    stream = AR.Stream(V, 1, 0.2, 2)
+    r = AR.Rec(1025, 2, 4, V)
+    h = HostRec(r)
+    assert h.advance(init=True) == 0
+    AR.rec_init(r)
+    for _ in range(4):
+        cands = AR.candidates(r, stream)
+        assert h.advance(cands=cands) == 0
+        AR.rec_advance(r, *cands)
+    assert h.differs_from(r) == []
+    rc, got = h.finish()
+    assert rc == 0 and all(np.array_equal(_bits(g), _bits(w)) for g, w in zip(got, AR.rec_finish(r)))

@@ -452,3 +452,17 @@ def test_with_the_switch_off_every_entry_takes_the_host_loop():
         eng.set_attn_beam_device(False)
     calls[1]()
     assert eng.attn_beam_device_runs() == runs + len(calls)
+
+
+def test_the_host_loop_takes_more_samples_than_the_kernels():
+    """1025 samples through the uniform entry with the switch off: the host loop's bookkeeping has no sample limit (the
+    device-side kernels stop at 1024), and every sample's result is that of the same search split into two calls"""
+    eng = rag._engine(L=8).engine()
+    mem = torch.randn(1025, 3, H, generator=torch.Generator().manual_seed(1025)).to(DEV)
+    assert 9 * 1025 * 2 * eng.attn_keys(3) * 4 <= _lib.ATTN_MAP_BUDGET
+    runs = eng.attn_beam_device_runs()
+    for maps in (False, True):
+        whole = eng.decode_attn_beam_batch(mem, 2, return_alpha=maps)
+        parts = eng.decode_attn_beam_batch(mem[:512], 2, return_alpha=maps) + eng.decode_attn_beam_batch(mem[512:], 2, return_alpha=maps)
+        rag._same(whole, parts, f"1025 samples, maps {maps}")
+    assert eng.attn_beam_device_runs() == runs
