@@ -13,8 +13,9 @@ import os
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import params as P
-from .engine import Engine
+from .engine import Engine, apply_settings, beam_results, pack_memories
 
 
 def decoder_attn_outputs(stages, decoder_attn, output_shape, feat_pad):
@@ -148,7 +149,7 @@ class DecodeHandle:
 
     def _launch(self):
         if self.ticket is None:  # the group this forward belongs to has not been launched yet
-            self._model._flush_group(self._eng)
+            self._model.launch_decode_group()
         assert self.ticket is not None
 
     def done(self):
@@ -185,13 +186,81 @@ class BeamSearchHandle:
         if self._result is None:
             self.wait(host_sync=True)
             seq, n, score = (t.cpu() for t in self._tensors[:3])
-            out = [(torch.LongTensor(seq[i, :int(n[i])].tolist()).unsqueeze(0), torch.tensor(float(score[i])))
-                   for i in range(len(self._lengths))]
-            if self._attn:
-                alpha = self._tensors[3]
-                out = [r + (alpha[i, :int(n[i]), :self._eng.attn_keys(T)],) for i, (r, T) in enumerate(zip(out, self._lengths))]
-            self._result = out
+            self._result = beam_results(seq.flatten().tolist(), n.tolist(), score.tolist(), len(self._lengths), seq.shape[1], True,
+                                        self._tensors[3] if self._attn else None, [self._eng.attn_keys(T) for T in self._lengths])
         return self._result
+
+
+class DecodeGroup:
+    """The forwards of a pipelined TFM head that share ONE step loop (Model.decode_group > 1): their memories lie back to back
+    in one packed [memory rows, d] buffer and their outputs are views of one tokens / logits pair.  Every group writes into
+    fresh tensors (no ring to overrun): the views handed out stay valid for as long as the caller keeps them, and become
+    readable once the group's ticket -- shared by its handles -- is complete.  Two layouts of the same object:
+      uniform (row_budget 0)  every batch has the first one's (B, T), which are part of the key; room for `batches` of them;
+                              launched through decode_greedy_async_into(rows_per_batch=B);
+      mixed (row_budget > 0)  batches of any (B, T) -- Model.decode_group_mixed -- up to max(row_budget, first B) rows; the
+                              packed memory grows as needed; launched through decode_greedy_ragged_into with the layout."""
+
+    @staticmethod
+    def key_of(eng, memory, is_test, batches, mixed):
+        """What the batches of one group have in common; a batch with another key launches what has been collected."""
+        B, T, d = memory.shape
+        tail = (d, eng.cfg.max_seq_len + 1, eng.cfg.vocab, memory.device, bool(is_test))
+        return ("mixed",) + tail if mixed else (batches, B, T) + tail
+
+    def __init__(self, model, eng, memory, is_test, batches, row_budget=0):
+        B, T, d = memory.shape
+        S, V, dev = eng.cfg.max_seq_len + 1, eng.cfg.vocab, memory.device
+        self._model, self._eng, self.is_test = model, eng, bool(is_test)
+        self.key = self.key_of(eng, memory, is_test, batches, row_budget > 0)
+        self.rows_per_batch = 0 if row_budget else B
+        if row_budget:
+            self.cap = max(row_budget, B)  # a single batch beyond the row budget is a group of its own
+            # the packed memory starts at what `batches` batches like this one need and grows with longer / larger ones
+            mem_rows = min(self.cap, max(1, batches) * B) * T
+        else:
+            self.cap, mem_rows = batches * B, batches * B * T
+        self.layout, self.handles, self.rows, self.mem_rows = [], [], 0, 0  # [(B, T)] per batch; output / memory rows in use
+        self.mem = torch.empty((mem_rows, d), dtype=torch.float32, device=dev)
+        self.start = torch.empty((self.cap,), dtype=torch.int64, device=dev)
+        self.tokens = torch.empty((self.cap, S), dtype=torch.int64, device=dev)
+        self.logits = torch.empty((self.cap, S, V), dtype=torch.float32, device=dev)
+
+    def fits(self, key, B):
+        """Whether a batch of B rows with this key joins the group; if not, the group is launched first."""
+        return key == self.key and self.rows + B <= self.cap
+
+    def full(self, batches):
+        return len(self.layout) >= batches
+
+    def add(self, memory, start):
+        """Copy a batch in; returns (tokens view, logits view, handle) of its rows."""
+        B, T, d = memory.shape
+        r0, m0 = self.rows, self.mem_rows
+        if m0 + B * T > self.mem.shape[0]:  # (mixed) longer memories than the first batch's: grow the packed buffer
+            grown = torch.empty((max(2 * self.mem.shape[0], m0 + B * T), d), dtype=torch.float32, device=memory.device)
+            grown[:m0].copy_(self.mem[:m0])
+            self.mem = grown
+        self.mem[m0:m0 + B * T].copy_(memory.reshape(B * T, d))
+        self.start[r0:r0 + B].copy_(start.to(device=memory.device, dtype=torch.int64))
+        views = self.tokens[r0:r0 + B], self.logits[r0:r0 + B]
+        handle = DecodeHandle(self._model, self._eng, None, len(self.layout), views)
+        self.handles.append(handle)
+        self.layout.append((B, T))
+        self.rows, self.mem_rows = r0 + B, m0 + B * T
+        return views + (handle,)
+
+    def launch(self, eng):
+        """Submit the collected rows as one decode; its ticket goes to every handle."""
+        r, m = self.rows, self.mem_rows
+        if self.rows_per_batch:
+            ticket = eng.decode_greedy_async_into(self.mem[:m].view(r, self.layout[0][1], -1), self.start[:r], self.tokens[:r],
+                                                  self.logits[:r], is_test=self.is_test, rows_per_batch=self.rows_per_batch)
+        else:
+            ticket = eng.decode_greedy_ragged_into(self.mem[:m], self.layout, self.start[:r], self.tokens[:r], self.logits[:r],
+                                                   is_test=self.is_test)
+        for h in self.handles:
+            h.ticket = ticket
 
 
 class Model(nn.Module):
@@ -248,7 +317,7 @@ class Model(nn.Module):
         # group collected so far, as before.  Other decoders (d_model 512) keep that behaviour whatever the switch says.
         self.decode_group_mixed = False
         self.decode_group_rows = 384
-        self._grp = None
+        self._group = None  # the DecodeGroup that is still collecting forwards
         # Arithmetic of the backbone / large GEMMs:
         #   'bf16x3'  (default) split-bf16: 3 bf16 MFMAs per product, fp32 accumulate; max |dlogit| ~5e-5 against the 1e-3 bar
         #             on every fixture and on fresh seeds (tools/probe/fp16x2_margin.py);
@@ -300,7 +369,6 @@ class Model(nn.Module):
         eng = self.engine()
         if not return_attn:
             return eng.decode_attn_beam_batch(memory.contiguous(), beam)
-        from . import _lib
         per = max(1, _lib.ATTN_MAP_BUDGET // max(1, eng.attn_map_bytes(memory.shape[1], beam)))
         out = []
         for a in range(0, memory.shape[0], per):
@@ -325,13 +393,11 @@ class Model(nn.Module):
         if not eng.supports_device_attn_beam():
             raise NotImplementedError("beam_search_batch_async: this head has no device-side beam search (the 'loc_aware' "
                                       "cell has no beam search in the engine at all); use beam_search_batch")
-        from .engine import pack_memories
         inputs = list(input) if isinstance(input, (list, tuple)) else [input]
         if len(inputs) == 0:
             return BeamSearchHandle(eng, None, (), [], return_attn)
         packed, lengths = pack_memories([self.forward_encoder(x)[0] for x in inputs])
         if return_attn:
-            from . import _lib
             need = len(lengths) * eng.attn_map_bytes(max(lengths), beam)
             if need > _lib.ATTN_MAP_BUDGET:
                 raise RuntimeError(f"beam_search_batch_async: the alignment history of {len(lengths)} samples ({need} bytes at "
@@ -355,12 +421,10 @@ class Model(nn.Module):
         tfm = self.stages["Pred"] == "TFM"
         if (return_attn and tfm) or not (eng.supports_ragged_beam() if tfm else eng.supports_ragged_attn_beam()):
             return self._beam_search_each(inputs, beam, return_attn)
-        from .engine import pack_memories
         packed, lengths = pack_memories([self.forward_encoder(x)[0] for x in inputs])
         if tfm:
             return eng.decode_beam_batch_ragged(packed, lengths, beam)
         if return_attn:
-            from . import _lib
             if len(lengths) * eng.attn_map_bytes(max(lengths), beam) > _lib.ATTN_MAP_BUDGET:
                 del packed
                 return self._beam_search_each(inputs, beam, return_attn)  # (which splits each tensor's batch as it needs)
@@ -372,94 +436,30 @@ class Model(nn.Module):
             out += self.beam_search_batch(x, beam, return_attn)
         return out
 
-    def _group_decode(self, eng, memory, start, is_test=False):
-        """pipelined + decode_group > 1: collect the encoder memories of consecutive calls, launch one decode per group.
-        Every group writes into fresh tensors (no ring to overrun): the views handed out stay valid for as long as the
-        caller keeps them, and become readable once the group's ticket is complete."""
-        import torch
+    def _collect_decode(self, eng, memory, start, is_test=False):
+        """pipelined + decode_group > 1: collect the encoder memories of consecutive calls, launch one decode per group --
+        when it holds decode_group batches, or when the next batch does not fit it (another key; decode_group_mixed: more
+        rows than decode_group_rows)."""
         G = int(self.decode_group)
-        B, T, d = memory.shape
-        S, V = eng.cfg.max_seq_len + 1, eng.cfg.vocab
-        if self.decode_group_mixed and eng.supports_ragged_groups():
-            return self._group_decode_mixed(eng, memory, start, is_test)
-        key = (G, B, T, d, S, V, memory.device, bool(is_test))
-        g = self._grp
-        if g is not None and g["key"] != key:
-            self._flush_group(eng)
-            g = None
-        if g is None:
-            g = self._grp = {"key": key, "n": 0, "handles": [],
-                             "mem": torch.empty((G * B, T, d), dtype=torch.float32, device=memory.device),
-                             "start": torch.empty((G * B,), dtype=torch.int64, device=memory.device),
-                             "tokens": torch.empty((G * B, S), dtype=torch.int64, device=memory.device),
-                             "logits": torch.empty((G * B, S, V), dtype=torch.float32, device=memory.device)}
-        k = g["n"]
-        g["mem"][k * B:(k + 1) * B].copy_(memory)
-        g["start"][k * B:(k + 1) * B].copy_(start.to(device=memory.device, dtype=torch.int64))
-        views = g["tokens"][k * B:(k + 1) * B], g["logits"][k * B:(k + 1) * B]
-        handle = DecodeHandle(self, eng, None, k, views)
-        g["handles"].append(handle)
-        out = views + (handle,)
-        g["n"] += 1
-        if g["n"] == G:
-            self._flush_group(eng)
+        mixed = bool(self.decode_group_mixed and eng.supports_ragged_groups())
+        if self._group is not None and not self._group.fits(DecodeGroup.key_of(eng, memory, is_test, G, mixed), memory.shape[0]):
+            self.launch_decode_group()
+        if self._group is None:
+            self._group = DecodeGroup(self, eng, memory, is_test, G, max(1, int(self.decode_group_rows)) if mixed else 0)
+        out = self._group.add(memory, start)
+        if self._group.full(G):
+            self.launch_decode_group()
         return out
 
-    def _group_decode_mixed(self, eng, memory, start, is_test):
-        """decode_group_mixed: the group is keyed on (d, S, V, device, is_test) only; memories of any (B, T) are packed
-        back to back into one flat [rows, d] buffer, outputs are views of [decode_group_rows, S] / [.., S, V] tensors."""
-        import torch
-        G, R = int(self.decode_group), max(1, int(self.decode_group_rows))
-        B, T, d = memory.shape
-        S, V = eng.cfg.max_seq_len + 1, eng.cfg.vocab
-        key = ("mixed", d, S, V, memory.device, bool(is_test))
-        g = self._grp
-        if g is not None and (g["key"] != key or g["rows"] + B > g["cap"]):
-            self._flush_group(eng)
-            g = None
-        if g is None:
-            cap = max(R, B)  # a single batch beyond the row budget is a group of its own
-            # the packed memory starts at what `decode_group` batches like this one need and grows with longer / larger ones
-            g = self._grp = {"key": key, "n": 0, "handles": [], "rows": 0, "cap": cap, "layout": [], "mem_rows": 0,
-                             "mem": torch.empty((min(cap, max(1, G) * B) * T, d), dtype=torch.float32, device=memory.device),
-                             "start": torch.empty((cap,), dtype=torch.int64, device=memory.device),
-                             "tokens": torch.empty((cap, S), dtype=torch.int64, device=memory.device),
-                             "logits": torch.empty((cap, S, V), dtype=torch.float32, device=memory.device)}
-        r0, m0 = g["rows"], g["mem_rows"]
-        if m0 + B * T > g["mem"].shape[0]:  # longer memories than the first batch's: grow the packed buffer
-            grown = torch.empty((max(2 * g["mem"].shape[0], m0 + B * T), d), dtype=torch.float32, device=memory.device)
-            grown[:m0].copy_(g["mem"][:m0])
-            g["mem"] = grown
-        g["mem"][m0:m0 + B * T].copy_(memory.reshape(B * T, d))
-        g["start"][r0:r0 + B].copy_(start.to(device=memory.device, dtype=torch.int64))
-        views = g["tokens"][r0:r0 + B], g["logits"][r0:r0 + B]
-        handle = DecodeHandle(self, eng, None, g["n"], views)
-        g["handles"].append(handle)
-        g["layout"].append((B, T))
-        g["rows"], g["mem_rows"] = r0 + B, m0 + B * T
-        g["n"] += 1
-        if g["n"] >= G:
-            self._flush_group(eng)
-        return views + (handle,)
+    def launch_decode_group(self):
+        """Launch the decode group that is still collecting forwards, if there is one."""
+        group, self._group = self._group, None
+        if group is not None:
+            group.launch(self._engine)
 
-    def _flush_group(self, eng):
-        g = self._grp
-        if g is None or g["n"] == 0:
-            return
-        if g["key"][0] == "mixed":
-            rows = g["rows"]
-            ticket = eng.decode_greedy_ragged_into(g["mem"][:g["mem_rows"]], g["layout"], g["start"][:rows], g["tokens"][:rows],
-                                                   g["logits"][:rows], is_test=g["key"][-1])
-            for h in g["handles"]:
-                h.ticket = ticket
-            self._grp = None
-            return
-        rows = g["n"] * g["key"][1]
-        ticket = eng.decode_greedy_async_into(g["mem"][:rows], g["start"][:rows], g["tokens"][:rows], g["logits"][:rows],
-                                              is_test=g["key"][-1], rows_per_batch=g["key"][1])
-        for h in g["handles"]:
-            h.ticket = ticket
-        self._grp = None
+    def drop_decode_group(self):
+        """Forget the collected forwards without decoding them (their handles never complete)."""
+        self._group = None
 
     def synchronize(self, host_sync=True, flush=True):
         """Order the current stream (and optionally the host) after every outstanding pipelined decode.  `flush` also
@@ -467,7 +467,7 @@ class Model(nn.Module):
         consumer stream after the groups already launched passes flush=False."""
         if self._engine is not None:
             if flush:
-                self._flush_group(self._engine)
+                self.launch_decode_group()
             self._engine.decode_wait(host_sync=host_sync)
 
     # -- engine plumbing -----------------------------------------------------
@@ -479,45 +479,21 @@ class Model(nn.Module):
         dev = p0.device if p0.is_cuda else None
         if self._engine is not None and dev is not None and self._engine.device != dev.index:
             self.synchronize()
-            self._engine, self._grp = None, None  # parameters were moved to another GPU: a fresh context there
+            self._engine, self._group = None, None  # parameters were moved to another GPU: a fresh context there
         if self._engine is None:
             self._engine = Engine(self.opt, device=dev)
         self._engine.sync_weights(self, finalize=finalize)
-        want = self.reserved_blocks if self.pipelined else 0
-        if getattr(self._engine, "_reserved", None) != want:
-            self._engine.set_reserved_blocks(want)
-            self._engine._reserved = want
-        want_cus = self.reserved_cus if self.pipelined else 0
-        if getattr(self._engine, "_reserved_cus", None) != want_cus:
-            self._engine.set_reserved_cus(want_cus)
-            self._engine._reserved_cus = want_cus
-        prec = self.effective_conv_precision()
-        if prec not in ("fp16x2", "mixed") and getattr(self._engine, "_precision", None) != prec:  # (before a change of the kernel)
-            self._engine.set_conv_precision(prec)
-            self._engine._precision = prec
-        if getattr(self._engine, "_conv_kernel", None) != self.conv_kernel:
-            self._engine.set_conv_kernel(self.conv_kernel)
-            self._engine._conv_kernel = self.conv_kernel
-        if getattr(self._engine, "_beam_shared", None) != bool(self.beam_shared_tile):
-            self._engine.set_beam_shared_tile(self.beam_shared_tile)
-            self._engine._beam_shared = bool(self.beam_shared_tile)
-        want_abd = bool(self.attn_beam_device)
-        if getattr(self._engine, "_attn_beam_device", False) != want_abd and finalize and self._engine.supports_device_attn_beam():
-            self._engine.set_attn_beam_device(want_abd)
-            self._engine._attn_beam_device = want_abd
-        if getattr(self._engine, "_fusion", None) != tuple(self.conv_fusion):
-            self._engine.set_conv_fusion(*self.conv_fusion)
-            self._engine._fusion = tuple(self.conv_fusion)
-        if getattr(self._engine, "_chains", None) != self.decode_chains:
-            self._engine.set_decode_chains(self.decode_chains)
-            self._engine._chains = self.decode_chains
-        if prec in ("fp16x2", "mixed") and getattr(self._engine, "_precision", None) != prec:  # (after the kernel choice: needs pipelined16)
-            self._engine.set_conv_precision(prec)
-            self._engine._precision = prec
-            self._engine._mixed_units = None
-        if prec == "mixed" and getattr(self._engine, "_mixed_units", None) != int(self.mixed_units):
-            self._engine.set_mixed_units(int(self.mixed_units))
-            self._engine._mixed_units = int(self.mixed_units)
+        # what the context should run with; engine.SETTINGS holds the order and the conditions of the set_* calls
+        apply_settings(self._engine, {
+            "reserved_blocks": self.reserved_blocks if self.pipelined else 0,
+            "reserved_cus": self.reserved_cus if self.pipelined else 0,
+            "conv_precision": self.effective_conv_precision(),
+            "conv_kernel": self.conv_kernel,
+            "beam_shared_tile": bool(self.beam_shared_tile),
+            "attn_beam_device": bool(self.attn_beam_device),
+            "conv_fusion": tuple(self.conv_fusion),
+            "decode_chains": self.decode_chains,
+            "mixed_units": int(self.mixed_units)}, finalize)
         return self._engine
 
     @property
@@ -535,7 +511,6 @@ class Model(nn.Module):
         """True when the caller's torch.autocast("cuda") asks for reduced precision and this model may follow it."""
         if not (self._precision_auto and self.amp_conv_precision) or self.training or self.stages["Seq"] != "ViT":
             return False
-        import torch
         try:
             return bool(torch.is_autocast_enabled("cuda"))
         except TypeError:  # older signature: no device argument, CUDA implied
@@ -660,7 +635,7 @@ class Model(nn.Module):
             # taken on the device; prediction / logits are then FULL-SIZE tensors whose valid length is only known once the
             # decode is complete -- addition_outputs["decode"].result() waits and returns them cut as the reference does
             if self.pipelined and int(self.decode_group) > 1:
-                prediction, logits, handle = self._group_decode(eng, contextual_feature.contiguous(), text[:, 0], is_test)
+                prediction, logits, handle = self._collect_decode(eng, contextual_feature.contiguous(), text[:, 0], is_test)
                 return prediction, logits, None, {"decode": handle}
             elif self.pipelined:
                 prediction, logits, ticket = eng.decode_greedy_async(contextual_feature.contiguous(), text[:, 0], is_test)

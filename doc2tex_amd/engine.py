@@ -154,30 +154,103 @@ def pack_memories(memories):
     return packed, lengths
 
 
+_LATE_PRECISIONS = ("fp16x2", "mixed")  # they need the pipelined16 kernel, so they follow the kernel choice
+
+# The engine settings Model.engine() keeps in step with the model's switches, in the order they are sent:
+# (name, Engine method, what a fresh context already has (None: unknown, always sent), condition or None).  A setting is
+# sent when the wanted value differs from the applied one AND its condition holds; the condition is only evaluated for a
+# value that differs.  A wanted tuple is passed as the method's arguments.
+SETTINGS = (
+    ("reserved_blocks", "set_reserved_blocks", None, None),
+    ("reserved_cus", "set_reserved_cus", None, None),
+    # 'fp32' / 'bf16x3' go before a change of the kernel, the others after it (below)
+    ("conv_precision", "set_conv_precision", None, lambda eng, want, finalize: want["conv_precision"] not in _LATE_PRECISIONS),
+    ("conv_kernel", "set_conv_kernel", None, None),
+    ("beam_shared_tile", "set_beam_shared_tile", None, None),
+    # only a context with finalized weights can say whether it has the device-side search
+    ("attn_beam_device", "set_attn_beam_device", False, lambda eng, want, finalize: finalize and eng.supports_device_attn_beam()),
+    ("conv_fusion", "set_conv_fusion", None, None),
+    ("decode_chains", "set_decode_chains", None, None),
+    ("conv_precision", "set_conv_precision", None, lambda eng, want, finalize: want["conv_precision"] in _LATE_PRECISIONS),
+    ("mixed_units", "set_mixed_units", None, lambda eng, want, finalize: want["conv_precision"] == "mixed"),
+)
+
+
+def apply_settings(eng, want, finalize=True):
+    """Send the settings of SETTINGS whose wanted value (want[name]) is not the one `eng.applied` records.  A value is
+    recorded only after its setter returned, so one that raised is sent again by the next call."""
+    for name, setter, fresh, when in SETTINGS:
+        value = want[name]
+        if eng.applied.get(name, fresh) == value or (when is not None and not when(eng, want, finalize)):
+            continue
+        getattr(eng, setter)(*(value if isinstance(value, tuple) else (value,)))
+        eng.applied[name] = value
+        if name == "conv_precision":  # the units are sent again with the next 'mixed'
+            eng.applied.pop("mixed_units", None)
+
+
+def beam_arrays(N, S):
+    """Host result arrays of a beam search over N samples of up to S tokens: (seq [N * S] int64, len [N] int32, score [N]
+    float).  Never empty, so that an empty list of samples still reaches the C side with valid pointers."""
+    return (C.c_int64 * max(1, N * S))(), (C.c_int32 * max(1, N))(), (C.c_float * max(1, N))()
+
+
+def beam_results(seq, n, score, N, S, tensor_score, alpha=None, keys=None):
+    """The filled arrays of a beam search (flat seq [N * S], len [N], score [N]; anything that indexes like a list) ->
+    [(LongTensor [1, len] on the CPU, score)] per sample.  The score is a Python float for the TFM head and a 0-dim tensor
+    for the LSTM-attention heads, as in the reference.  alpha [N, S, >= max keys]: each entry also carries its alignment
+    map, a view cut to [len, keys[i]]."""
+    out = []
+    for i in range(N):
+        r = (torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0),
+             torch.tensor(float(score[i])) if tensor_score else float(score[i]))
+        out.append(r if alpha is None else r + (alpha[i, :n[i], :keys[i]],))
+    return out
+
+
+def packed_rows(packed, lengths):
+    """A packed memory and the lengths of its samples as the C side takes them: (fp32 contiguous [sum lengths, d], [int],
+    int32 array of the lengths -- never empty, like beam_arrays)."""
+    packed = packed.float().contiguous()
+    lengths = [int(T) for T in lengths]
+    if packed.dim() != 2 or packed.shape[0] != sum(lengths):
+        raise ValueError(f"packed memory {tuple(packed.shape)} does not hold the {sum(lengths)} rows of `lengths`")
+    return packed, lengths, (C.c_int32 * max(1, len(lengths)))(*lengths)
+
+
 class Engine:
     def __init__(self, opt, device=None):
+        self.ctx = None
         self.lib = _lib.require_device()
         self.cfg = config_from_opt(opt)
-        self.ctx = C.c_void_p()
         # the context lives on ONE device: opt["device"] (build_pred.py:17) unless the module has been moved since
         self.device = device_index(opt.get("device") if device is None else device)
         if not 0 <= self.device < torch.cuda.device_count():
             raise RuntimeError(f"doc2tex_amd: no HIP device {self.device} (visible: {torch.cuda.device_count()})")
+        self.ctx = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self.lib.d2t_create(C.byref(self.cfg), C.byref(self.ctx))
-        if rc != _lib.D2T_OK:
-            msg = self.lib.d2t_last_error(self.ctx).decode() if self.ctx else ""
-            if self.ctx:
-                self.lib.d2t_destroy(self.ctx)
-            self.ctx = None
-            raise RuntimeError(f"d2t_create failed (code {rc}): {msg}")
+        try:
+            self._check(rc, "d2t_create")
+        except RuntimeError:
+            self.__del__()
+            raise
         assert self.lib.d2t_device_of(self.ctx) == self.device
-        self._sig = None
+        # the upload signature (None forces an upload), the one the finalized weights were built from, the shapes loaded last
+        self._sig, self._fin_sig, self._loaded_shapes = None, None, None
         self.weight_uploads = 0  # sync_weights calls that moved tensors into the engine (load or reload)
         self._load_epoch = object()  # replaced whenever d2t_load_weight may have re-allocated the raw copies (weight_ptr)
+        self.applied = {}  # settings sent to the context so far (apply_settings): name -> value
+        self._train_keep = None  # (image, tgt) of a training forward until its backward has read them
+        # submitted decodes: [(ticket, tensors)] referenced until the ticket completes, ticket -> per-batch step counts, the
+        # device whose current stream decode_wait orders (None before the first submission)
+        self._held, self._steps_cache, self._wait_dev = [], {}, None
 
     def _on_device(self, t, what):
-        """Tensors handed to the context must live on its device (the C side checks the raw pointers too)."""
+        """Tensors handed to the context must live on its device (the C side checks the raw pointers too).  Which calls
+        check here is uneven -- the TFM greedy calls, the submitted calls and the ragged group do; the synchronous greedy
+        call of the LSTM-attention heads and the synchronous beam searches leave it to the C side -- and stays so: unifying
+        it would change the exception their callers see."""
         if not t.is_cuda:
             raise RuntimeError(f"doc2tex_amd: {what} must be a ROCm (cuda) tensor; the engine has no CPU path")
         if t.device.index != self.device:
@@ -185,7 +258,7 @@ class Engine:
                                "move the input, or the Model with .to(device), so that they agree")
 
     def __del__(self):
-        ctx, self.ctx = getattr(self, "ctx", None), None
+        ctx, self.ctx = getattr(self, "ctx", None), None  # (an object whose __init__ never ran has no ctx)
         if ctx:
             try:
                 self.lib.d2t_destroy(ctx)
@@ -206,7 +279,7 @@ class Engine:
             items.append((name, t))
         sig = tuple((n, t.data_ptr(), t._version, tuple(t.shape)) for n, t in items)
         if sig == self._sig:
-            if finalize and getattr(self, "_fin_sig", None) != sig:
+            if finalize and self._fin_sig != sig:
                 self._check(self.lib.d2t_finalize_weights(self.ctx, _lib.stream_of(items[0][1])), "finalize_weights")
                 self._fin_sig = sig
             return
@@ -222,7 +295,7 @@ class Engine:
             tds.append(td)
             stream = _lib.stream_of(td)
         shapes = tuple((n, tuple(t.shape)) for n, t in items)
-        if shapes == getattr(self, "_loaded_shapes", None):
+        if shapes == self._loaded_shapes:
             # same tensors as last time with new contents (an optimizer step): one copy kernel instead of one copy each
             n = len(items)
             self._check(self.lib.d2t_reload_weights(
@@ -434,14 +507,19 @@ class Engine:
         return [(M[i], N[i], K[i], ms[i]) for i in range(n.value)]
 
     # ---- decoder -----------------------------------------------------------
+    def _greedy_outputs(self, memory, S, alloc):
+        """(tokens [B, S] int64, logits / probs [B, S, V] fp32) of a greedy decode beside its memory.  alloc: torch.zeros for
+        the synchronous calls (what lies behind an is_test exit is read as zeros), torch.empty for the submitted ones."""
+        B = memory.shape[0]
+        return (alloc((B, S), dtype=torch.int64, device=memory.device),
+                alloc((B, S, self.cfg.vocab), dtype=torch.float32, device=memory.device))
+
     def decode_greedy(self, memory, start_tokens, is_test):
         self._on_device(memory, "memory")
         memory = memory.float().contiguous()
         B, T, _ = memory.shape
-        S, V = self.cfg.max_seq_len + 1, self.cfg.vocab
         start = start_tokens.to(device=memory.device, dtype=torch.int64).contiguous()
-        tokens = torch.zeros((B, S), dtype=torch.int64, device=memory.device)
-        logits = torch.zeros((B, S, V), dtype=torch.float32, device=memory.device)
+        tokens, logits = self._greedy_outputs(memory, self.cfg.max_seq_len + 1, torch.zeros)
         steps = C.c_int32(0)
         self._check(self.lib.d2t_decode_greedy(self.ctx, _lib.ptr(memory), B, T, _lib.ptr(start), int(bool(is_test)),
                                                _lib.ptr(tokens), _lib.ptr(logits), C.byref(steps),
@@ -458,9 +536,8 @@ class Engine:
         return_alpha also the alignment of every step, [B,S,Tk] (zeros after an is_test early exit)."""
         memory = memory.float().contiguous()
         B, T, _ = memory.shape
-        S, V = self.cfg.batch_max_length + 1, self.cfg.vocab
-        tokens = torch.zeros((B, S), dtype=torch.int64, device=memory.device)
-        probs = torch.zeros((B, S, V), dtype=torch.float32, device=memory.device)
+        S = self.cfg.batch_max_length + 1
+        tokens, probs = self._greedy_outputs(memory, S, torch.zeros)
         steps = C.c_int32(0)
         if not return_alpha:
             self._check(self.lib.d2t_decode_attn_greedy(self.ctx, _lib.ptr(memory), B, T, int(bool(is_test)),
@@ -482,9 +559,8 @@ class Engine:
         self._on_device(memory, "memory")
         memory = memory.float().contiguous()
         B, T, _ = memory.shape
-        S, V = self.cfg.batch_max_length + 1, self.cfg.vocab
-        tokens = torch.empty((B, S), dtype=torch.int64, device=memory.device)
-        probs = torch.empty((B, S, V), dtype=torch.float32, device=memory.device)
+        S = self.cfg.batch_max_length + 1
+        tokens, probs = self._greedy_outputs(memory, S, torch.empty)
         alpha = torch.empty((B, S, self.attn_keys(T)), dtype=torch.float32, device=memory.device) if return_alpha else None
         t = C.c_int64(0)
         self._check(self.lib.d2t_decode_attn_greedy_submit(self.ctx, _lib.ptr(memory), B, T, int(bool(is_test)),
@@ -500,11 +576,8 @@ class Engine:
         decode_wait) and are never recycled behind the caller's back -- the engine keeps them alive until then."""
         self._on_device(memory, "memory")
         memory = memory.float().contiguous()
-        B, T, _ = memory.shape
-        S, V = self.cfg.max_seq_len + 1, self.cfg.vocab
         start = start_tokens.to(device=memory.device, dtype=torch.int64).contiguous()
-        tokens = torch.empty((B, S), dtype=torch.int64, device=memory.device)
-        logits = torch.empty((B, S, V), dtype=torch.float32, device=memory.device)
+        tokens, logits = self._greedy_outputs(memory, self.cfg.max_seq_len + 1, torch.empty)
         ticket = self.decode_greedy_async_into(memory, start, tokens, logits, is_test=is_test)
         return tokens, logits, ticket
 
@@ -554,9 +627,7 @@ class Engine:
     def _hold(self, ticket, memory, tensors):
         """Keep the buffers of the asynchronous decode `ticket` referenced until it completes; returns the ticket."""
         self._wait_dev = memory.device
-        held = getattr(self, "_held", None)
-        if held is None:
-            held = self._held = []
+        held = self._held
         held.append((ticket, tensors))
         while held and self.ticket_done(held[0][0]):  # tickets complete in order per chain; at most a few stay pending
             self.decode_steps(held.pop(0)[0])  # keep its step counts past the C side's 64-entry ring
@@ -568,7 +639,7 @@ class Engine:
         """Per-batch step counts of an asynchronous decode (waits for it): [steps of batch 0, batch 1, ...]; ONE entry
         (max_seq_len + 1) for a decode without early exit.  Remembered on this side, so a handle consumed more than 64
         decodes later still learns its length."""
-        cache = self.__dict__.setdefault("_steps_cache", {})
+        cache = self._steps_cache
         ticket = int(ticket)
         if ticket not in cache:
             out = (C.c_int32 * 64)()
@@ -591,13 +662,12 @@ class Engine:
         self._check(self.lib.d2t_decode_wait_ticket(self.ctx, int(ticket), stream, int(bool(host_sync))), "decode_wait_ticket")
 
     def decode_wait(self, host_sync=False):
-        dev = getattr(self, "_wait_dev", None)
-        if dev is None:
+        if self._wait_dev is None:
             return
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = C.c_void_p(torch.cuda.current_stream(self._wait_dev).cuda_stream)
         self._check(self.lib.d2t_decode_wait(self.ctx, stream, int(bool(host_sync))), "decode_wait")
         if host_sync:
-            for t, _ in getattr(self, "_held", None) or []:
+            for t, _ in self._held:
                 self.decode_steps(t)
             self._held = []
 
@@ -606,12 +676,10 @@ class Engine:
         memory = memory.float().contiguous()
         assert memory.shape[0] == 1  # seq2seq.py:90
         S = self.cfg.batch_max_length + 1
-        seq = (C.c_int64 * S)()
-        n = C.c_int32(0)
-        score = C.c_float(0.0)
+        seq, n, score = beam_arrays(1, S)
         self._check(self.lib.d2t_decode_attn_beam(self.ctx, _lib.ptr(memory), memory.shape[1], int(beam_size), seq,
-                                                  C.byref(n), C.byref(score), _lib.stream_of(memory)), "decode_attn_beam")
-        return torch.LongTensor(list(seq[: n.value])).unsqueeze(0), torch.tensor(float(score.value))
+                                                  n, score, _lib.stream_of(memory)), "decode_attn_beam")
+        return beam_results(seq, n, score, 1, S, True)[0]
 
     def decode_attn_beam_batch(self, memory, beam_size, return_alpha=False):
         """LSTM-attention beam search for every sample of memory [N,T,256] in one step loop.  return_alpha: each entry
@@ -619,20 +687,16 @@ class Engine:
         memory's device; the call is refused when the step history exceeds _lib.ATTN_MAP_BUDGET bytes."""
         memory = memory.float().contiguous()
         N, T, S = memory.shape[0], memory.shape[1], self.cfg.batch_max_length + 1
-        seq = (C.c_int64 * (N * S))()
-        n = (C.c_int32 * N)()
-        score = (C.c_float * N)()
+        seq, n, score = beam_arrays(N, S)
         if not return_alpha:
             self._check(self.lib.d2t_decode_attn_beam_batch(self.ctx, _lib.ptr(memory), N, T, int(beam_size), seq,
                                                             n, score, _lib.stream_of(memory)), "decode_attn_beam_batch")
-            return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i])))
-                    for i in range(N)]
+            return beam_results(seq, n, score, N, S, True)
         alpha = torch.empty((N, S, self.attn_keys(T)), dtype=torch.float32, device=memory.device)
         self._check(self.lib.d2t_decode_attn_beam_batch_alpha(self.ctx, _lib.ptr(memory), N, T, int(beam_size), seq, n, score,
                                                               _lib.ptr(alpha), _lib.stream_of(memory)),
                     "decode_attn_beam_batch_alpha")
-        return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i])), alpha[i, :n[i]])
-                for i in range(N)]
+        return beam_results(seq, n, score, N, S, True, alpha, [alpha.shape[2]] * N)
 
     def decode_attn_beam_batch_ragged(self, packed, lengths, beam_size, return_alpha=False):
         """decode_attn_beam_batch for samples whose memories have different lengths: packed [sum lengths, 256] holds sample
@@ -640,24 +704,15 @@ class Engine:
         trips are paid once: [(LongTensor [1,len], score)] per sample, each equal to decode_attn_beam_batch on that sample
         alone.  return_alpha: each entry also carries its alignment map cut to [len, Tk_i]; the call is refused when the
         step history (at the longest sample's stride) exceeds _lib.ATTN_MAP_BUDGET bytes."""
-        packed = packed.float().contiguous()
-        lengths = [int(T) for T in lengths]
+        packed, lengths, Ts = packed_rows(packed, lengths)
         N, S = len(lengths), self.cfg.batch_max_length + 1
-        if packed.dim() != 2 or packed.shape[0] != sum(lengths):
-            raise ValueError(f"packed memory {tuple(packed.shape)} does not hold the {sum(lengths)} rows of `lengths`")
-        seq = (C.c_int64 * max(1, N * S))()
-        n = (C.c_int32 * max(1, N))()
-        score = (C.c_float * max(1, N))()
-        Ts = (C.c_int32 * max(1, N))(*lengths)
+        seq, n, score = beam_arrays(N, S)
         ld = self.attn_keys(max(lengths)) if lengths else 0
         alpha = torch.empty((N, S, max(ld, 1)), dtype=torch.float32, device=packed.device) if return_alpha else None
         self._check(self.lib.d2t_decode_attn_beam_batch_ragged(self.ctx, _lib.ptr(packed), N, Ts, int(beam_size), seq, n, score,
                                                                _lib.ptr(alpha), _lib.stream_of(packed)),
                     "decode_attn_beam_batch_ragged")
-        out = [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), torch.tensor(float(score[i]))) for i in range(N)]
-        if not return_alpha:
-            return out
-        return [r + (alpha[i, :n[i], :self.attn_keys(lengths[i])],) for i, r in enumerate(out)]
+        return beam_results(seq, n, score, N, S, True, alpha, [self.attn_keys(T) for T in lengths])
 
     def supports_ragged_attn_beam(self):
         """Whether decode_attn_beam_batch_ragged serves this context (an LSTM-attention head with the coverage or the
@@ -686,18 +741,14 @@ class Engine:
         alpha[i, :len[i], :attn_keys(lengths[i])].  `packed` and the outputs stay referenced here until the ticket
         completes."""
         self._on_device(packed, "memory")
-        packed = packed.float().contiguous()
-        lengths = [int(T) for T in lengths]
+        packed, lengths, Ts = packed_rows(packed, lengths)
         N, S = len(lengths), self.cfg.batch_max_length + 1
-        if packed.dim() != 2 or packed.shape[0] != sum(lengths):
-            raise ValueError(f"packed memory {tuple(packed.shape)} does not hold the {sum(lengths)} rows of `lengths`")
         dev = packed.device
         seq = torch.empty((max(N, 1), S), dtype=torch.int64, device=dev)
         n = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
         score = torch.empty((max(N, 1),), dtype=torch.float32, device=dev)
         ld = self.attn_keys(max(lengths)) if lengths else 0
         alpha = torch.empty((max(N, 1), S, max(ld, 1)), dtype=torch.float32, device=dev) if return_alpha else None
-        Ts = (C.c_int32 * max(1, N))(*lengths)
         t = C.c_int64(0)
         self._check(self.lib.d2t_decode_attn_beam_batch_submit(self.ctx, _lib.ptr(packed), N, Ts, int(beam_size), _lib.ptr(seq),
                                                                _lib.ptr(n), _lib.ptr(score), _lib.ptr(alpha),
@@ -715,29 +766,21 @@ class Engine:
         each equal to decode_beam on that sample alone."""
         memory = memory.float().contiguous()
         N, S = memory.shape[0], self.cfg.max_seq_len + 1
-        seq = (C.c_int64 * (N * S))()
-        n = (C.c_int32 * N)()
-        score = (C.c_float * N)()
+        seq, n, score = beam_arrays(N, S)
         self._check(self.lib.d2t_decode_beam_batch(self.ctx, _lib.ptr(memory), N, memory.shape[1], int(beam_size), seq, n,
                                                    score, _lib.stream_of(memory)), "decode_beam_batch")
-        return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), float(score[i])) for i in range(N)]
+        return beam_results(seq, n, score, N, S, False)
 
     def decode_beam_batch_ragged(self, packed, lengths, beam_size):
         """decode_beam_batch for samples whose memories have different lengths: packed [sum lengths, d] holds sample i's
         lengths[i] rows behind sample i-1's.  One shared step loop (one captured graph per sample count and beam width,
         whatever the lengths): [(LongTensor [1,len], score)] per sample, each equal to decode_beam on that sample alone."""
-        packed = packed.float().contiguous()
-        lengths = [int(T) for T in lengths]
+        packed, lengths, Ts = packed_rows(packed, lengths)
         N, S = len(lengths), self.cfg.max_seq_len + 1
-        if packed.dim() != 2 or packed.shape[0] != sum(lengths):
-            raise ValueError(f"packed memory {tuple(packed.shape)} does not hold the {sum(lengths)} rows of `lengths`")
-        seq = (C.c_int64 * max(1, N * S))()
-        n = (C.c_int32 * max(1, N))()
-        score = (C.c_float * max(1, N))()
-        Ts = (C.c_int32 * max(1, N))(*lengths)
+        seq, n, score = beam_arrays(N, S)
         self._check(self.lib.d2t_decode_beam_batch_ragged(self.ctx, _lib.ptr(packed), N, Ts, int(beam_size), seq, n, score,
                                                           _lib.stream_of(packed)), "decode_beam_batch_ragged")
-        return [(torch.LongTensor(list(seq[i * S: i * S + n[i]])).unsqueeze(0), float(score[i])) for i in range(N)]
+        return beam_results(seq, n, score, N, S, False)
 
     def supports_ragged_beam(self):
         """Whether decode_beam_batch_ragged serves this context (the device-side beam loop: TFM head, d_model 256 on the
@@ -750,9 +793,7 @@ class Engine:
             raise AssertionError(
                 f"beam search should only have signle source, encounter with batch size: {memory.shape[0]}")
         S = self.cfg.max_seq_len + 1
-        seq = (C.c_int64 * S)()
-        n = C.c_int32(0)
-        score = C.c_float(0.0)
-        self._check(self.lib.d2t_decode_beam(self.ctx, _lib.ptr(memory), memory.shape[1], int(beam_size), seq,
-                                             C.byref(n), C.byref(score), _lib.stream_of(memory)), "decode_beam")
-        return torch.LongTensor(list(seq[: n.value])).unsqueeze(0), float(score.value)
+        seq, n, score = beam_arrays(1, S)
+        self._check(self.lib.d2t_decode_beam(self.ctx, _lib.ptr(memory), memory.shape[1], int(beam_size), seq, n, score,
+                                             _lib.stream_of(memory)), "decode_beam")
+        return beam_results(seq, n, score, 1, S, False)[0]

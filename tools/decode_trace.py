@@ -44,7 +44,7 @@ with torch.no_grad():
     torch.cuda.synchronize()
     buf = np.zeros((8192, 2), np.uint64)
     n = lib.d2t_debug_trace(eng.ctx, buf.ctypes.data_as(C.c_void_p), 8192, 0)
-m._grp = None
+m.drop_decode_group()
 t = buf[:n].astype(np.int64)
 ok = t[:, 1] > 0
 print(f"{n} kernel nodes, {int(ok.sum())} recorded")

@@ -70,7 +70,7 @@ def main():
     if (args.device_beam or args.submit or args.end_bias is not None or args.max_length) and args.head != "attnv2":
         ap.error("--device-beam / --submit / --end-bias / --max-length belong to --head attnv2 --beam K")
     dev = torch.device("cuda", 0)
-    cfg = synth.make_config("C4", device=str(dev))
+    cfg = synth.make_config("C4", device=str(dev), beam_size=1)  # (C4 asks for width 5; the searches here take --beam, forward() decodes greedily)
     if args.head == "attnv2":
         cfg["Prediction"] = {"name": "Attnv2", "params": {
             "seqmodel": "TFM", "input_size": 256, "hidden_size": 256, "kernel_size": 2, "kernel_dim": 128, "embed_target": True,
