@@ -52,6 +52,15 @@ class D2TOpAttnDecodeArgs(C.Structure):  # include/d2t.h d2t_op_attn_decode_args
                                   "first", "samples")]
 
 
+class D2TOpConvRecordsArgs(C.Structure):  # include/d2t.h d2t_op_conv_records_args
+    _fields_ = [(n, C.c_void_p) for n in (
+        "x_rec", "x_f32", "x2_rec", "w", "w2", "bias", "bias2", "res_rec", "res_f32", "row_add", "out_rec", "out_f32")] + \
+        [(n, C.c_int32) for n in (
+            "in_fmt", "res_fmt", "out_fmt", "B", "H", "W", "Cin", "Cin2", "Cout", "KH", "KW", "SH", "SW", "PH", "PW", "OH", "OW",
+            "act", "pool2", "rows_per_img", "img_stride", "row_off", "row_add_off", "row_add_rows", "out_rows", "kind",
+            "split_tail")]
+
+
 class D2TOpAttnLstmBwdArgs(C.Structure):  # include/d2t.h d2t_op_attn_lstm_bwd_args
     _fields_ = [(n, C.c_void_p) for n in (
         "dlogits", "mem", "kp", "wg_t", "wih_raw", "whh_raw", "wq_raw", "wloc", "bloc", "wscore", "sv_cprev", "sv_cafter",
@@ -176,6 +185,14 @@ SIGNATURES = {
     "d2t_op_beam_advance": (_I, [_I, _L] + [_P] * 15 + [_I] * 6 + [_P]),
     "d2t_op_beam_ancestry": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "d2t_op_cache_gather": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
+    # the encoder's record path one kernel at a time (test infrastructure)
+    "d2t_op_records_split": (_I, [_P, _P, _L, _I, _I, _P]),
+    "d2t_op_records_merge": (_I, [_P, _P, _L, _I, _I, _P]),
+    "d2t_op_conv_records": (_I, [C.POINTER(D2TOpConvRecordsArgs), _P]),
+    "d2t_op_linear_kv": (_I, [_P] * 4 + [_I] * 7 + [_P]),
+    "d2t_op_maxpool_records": (_I, [_P, _P] + [_I] * 9 + [_P]),
+    "d2t_op_stem_records": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "d2t_op_pack_conv": (_I, [_P] * 6 + [C.c_float] + [_P] * 6 + [_I] * 4 + [_P]),
     "d2t_ce_forward": (_I, [_P, _P, _P, _P, _I, _I, _L, _P]),
     "d2t_ce_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _P]),
     "d2t_ce_smooth_forward": (_I, [_P] * 6 + [_I, _I, _L, C.c_float, C.c_float, _I, _L, _P]),

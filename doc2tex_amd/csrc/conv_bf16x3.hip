@@ -459,13 +459,13 @@ __global__ __launch_bounds__(512, 4) void conv_f16x2g_128x128_w8(const ConvP p) 
 hipError_t launch_conv_bf16x3(const ConvP& p, hipStream_t s) {
   if (p.M <= 0 || p.Cout <= 0) return hipSuccess;
   if (p.pool2) {  // fused 2x2 max-pool: split-record LDS-DMA kernels with the wide epilogue only (g body, 16x16x32 pipelined body)
-    const bool wide = p.store_mode == STORE_ROWS && p.rows_per_img == 0 && !p.row_add && (p.Cout & 31) == 0;
-    if (!p.in_hi || !wide || p.res || p.res_hi || (p.M & 3) || p.M != 4 * p.B * (p.OH / 2) * (p.OW / 2) ||
+    if (!p.in_hi || !wide_epilogue_ok(p) || p.res || p.res_hi || (p.M & 3) || p.M != 4 * p.B * (p.OH / 2) * (p.OW / 2) ||
         (p.Cout >= 128 && p.pipelined != 3) || (p.Cout > 64 && p.Cout < 128))
       return hipErrorInvalidValue;
   }
   if (!p.w_hi || !p.w_lo || p.Cin % XBK != 0 || p.K != p.KH * p.KW * p.Cin + p.Cin2 || p.m_base != 0) return hipErrorInvalidValue;
-  // a second (1x1) input along K: the DMA issuer of the pipelined 16x16x32 kernel only (no tail hand-over, not the patch forms)
+  // a second (1x1) input along K: the DMA issuer of the pipelined 16x16x32 kernel only, its 64 x 128 tail build included
+  // (launch_conv_bf16x3p hands over as for any layer); not the patch forms
   if (p.Cin2 && (!p.in_hi || !p.in2_hi || p.Cin2 % XBK || p.Cout < 128 || p.pipelined != 3 || p.pool2 || p.OH != p.H || p.OW != p.W))
     return hipErrorInvalidValue;
   if (p.f16 && (!p.in_hi || (p.Cout >= 128 && p.pipelined != 3))) return hipErrorInvalidValue;  // fp16 records: split-record kernels only
@@ -475,6 +475,10 @@ hipError_t launch_conv_bf16x3(const ConvP& p, hipStream_t s) {
     // layers with >= 128 output channels: the pipelined 256x128 kernel (one block per CU, three LDS stages); dispatch by
     // layer shape only (never by the row count), so a sample's results do not depend on its batch
     if (p.pipelined && p.Cout >= 128) return launch_conv_bf16x3p(p, s);
+    // the 32x32 bodies honour ConvP::out_fmt / res_fmt in their tile epilogue (store_rec / add_rec); their element-wise
+    // epilogue (ElemTwoWay: a row remap or a positional table) knows the input's format only
+    if (!wide_epilogue_ok(p) && ((p.out_hi && p.out_fmt && p.out_fmt - 1 != p.f16) || (p.res_hi && p.res_fmt && p.res_fmt - 1 != p.f16)))
+      return hipErrorInvalidValue;
     int tiles = mt * ((p.Cout + (p.Cout <= 64 ? 63 : 127)) / (p.Cout <= 64 ? 64 : 128));
     const int grid = (p.max_blocks > 0 && tiles > p.max_blocks) ? p.max_blocks : tiles;
     if (p.Cout <= 64) {
@@ -530,31 +534,31 @@ __global__ void split_f16_kernel(const float* __restrict__ w, uint16_t* __restri
     lo[i] = f32_to_f16_bits(x - f16_bits_to_f32(h));
   }
 }
-__global__ void split_act_kernel(const float* __restrict__ x, uint16_t* __restrict__ planes, size_t rows, int C, int f16) {
+__global__ void split_act_kernel(const float* __restrict__ x, uint16_t* __restrict__ planes, size_t rows, int C, int fmt) {
   const size_t n = rows * C;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     uint16_t hi, lo;
-    split_rec(x[i], hi, lo, f16);
+    split_rec(x[i], hi, lo, fmt);
     const size_t o = plane_idx(i / C, (int)(i % C), C);
     planes[o] = hi;
     planes[o + 32] = lo;
   }
 }
-__global__ void merge_act_kernel(const uint16_t* __restrict__ planes, float* __restrict__ x, size_t rows, int C, int f16) {
+__global__ void merge_act_kernel(const uint16_t* __restrict__ planes, float* __restrict__ x, size_t rows, int C, int fmt) {
   const size_t n = rows * C;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const size_t o = plane_idx(i / C, (int)(i % C), C);
-    x[i] = join_rec(planes[o], planes[o + 32], f16);
+    x[i] = join_rec(planes[o], planes[o + 32], fmt);
   }
 }
 // the same, eight channels per thread: two 16-byte loads, one 16-byte store into each half of the record (C % 32 == 0)
-__global__ void split_act8_kernel(const float* __restrict__ x, uint16_t* __restrict__ planes, size_t n8, int f16) {
+__global__ void split_act8_kernel(const float* __restrict__ x, uint16_t* __restrict__ planes, size_t n8, int fmt) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
     const float4 a = reinterpret_cast<const float4*>(x)[2 * i], b = reinterpret_cast<const float4*>(x)[2 * i + 1];
     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     uint16_t hi[8], lo[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) split_rec(v[k], hi[k], lo[k], f16);
+    for (int k = 0; k < 8; ++k) split_rec(v[k], hi[k], lo[k], fmt);
     // element e = 8 i of the row-major [rows][C] tensor lies in record e / 32 at position e % 32 (C % 32 == 0)
     const size_t rec = i >> 2, pos = (i & 3) * 8;
     uint16_t* dst = planes + rec * 64 + pos;
@@ -564,22 +568,22 @@ __global__ void split_act8_kernel(const float* __restrict__ x, uint16_t* __restr
                                                      lo[4] | (uint32_t)lo[5] << 16, lo[6] | (uint32_t)lo[7] << 16);
   }
 }
-hipError_t launch_split_act(const float* x, uint16_t* planes, size_t rows, int C, hipStream_t s, int f16) {
+hipError_t launch_split_act(const float* x, uint16_t* planes, size_t rows, int C, hipStream_t s, int fmt) {
   const size_t n = rows * C;
   if (C % 32 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
     const size_t n8 = n / 8;
     hipLaunchKernelGGL(split_act8_kernel, grid_1d(n8, 8192), dim3(256), 0, s, x,
-                       planes, n8, f16);
+                       planes, n8, fmt);
     return hipGetLastError();
   }
   hipLaunchKernelGGL(split_act_kernel, grid_1d(n, 4096), dim3(256), 0,
-                     s, x, planes, rows, C, f16);
+                     s, x, planes, rows, C, fmt);
   return hipGetLastError();
 }
-hipError_t launch_merge_act(const uint16_t* planes, float* x, size_t rows, int C, hipStream_t s, int f16) {
+hipError_t launch_merge_act(const uint16_t* planes, float* x, size_t rows, int C, hipStream_t s, int fmt) {
   const size_t n = rows * C;
   hipLaunchKernelGGL(merge_act_kernel, grid_1d(n, 4096), dim3(256), 0,
-                     s, planes, x, rows, C, f16);
+                     s, planes, x, rows, C, fmt);
   return hipGetLastError();
 }
 

@@ -166,9 +166,10 @@ struct Map16 {  // v_mfma_f32_16x16x32_*: lc = lane & 15 -> n, lr = lane >> 4, r
 };
 
 // What the element-wise epilogue below compiles in, by what a kernel's launcher lets through.
-// The 32x32 kernels: records are bf16 hi | lo or, with ConvP::f16, one fp16 -- they never see the mixed-precision formats
-// ConvP::out_fmt / res_fmt (launch_conv / launch_conv_bf16x3 reject them), and the three-way format code costs the fp32
-// kernel, which runs at the VGPR limit, 700 bytes of scratch per lane and half its speed.
+// The 32x32 kernels: records are bf16 hi | lo or, with ConvP::f16, one fp16 -- HERE they never see another format in
+// ConvP::out_fmt / res_fmt (launch_conv_bf16x3 rejects a record launch that would bring one to this epilogue; their tile
+// epilogue below honours all three through store_rec / add_rec), and the three-way format code costs the fp32 kernel, which
+// runs at the VGPR limit, 700 bytes of scratch per lane and half its speed.
 struct ElemTwoWay {
   static constexpr bool kv_store = true;
   static __device__ __forceinline__ float res_at(const ConvP& p, size_t ri) {
@@ -277,7 +278,8 @@ __device__ __forceinline__ void acc_to_tile(typename Map::acc_t (&acc)[MI][NJ], 
 //         (measured: 1139 instead of 1210 formulas/s).
 // All need Cout % 32 == 0; the head-split store also head_dim % W == 0.
 enum class Epi { lean, pool, full };
-__device__ __forceinline__ bool wide_epilogue_ok(const ConvP& p) {
+// (host too: launch_conv_bf16x3 decides by the same predicate which launches it lets through)
+__host__ __device__ __forceinline__ bool wide_epilogue_ok(const ConvP& p) {
   return p.store_mode == STORE_ROWS && p.rows_per_img == 0 && !p.row_add && (p.Cout & 31) == 0;
 }
 __device__ __forceinline__ bool wide_epilogue_full_ok(const ConvP& p) {

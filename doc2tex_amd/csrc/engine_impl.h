@@ -10,6 +10,11 @@ namespace eng {
 int f16_planes(d2t_ctx* c, ConvW& w, hipStream_t s);
 // engine_weights.hip: frees every packed buffer and leaves the context unfinalized (re-finalize, destroy)
 void free_packed(d2t_ctx* c);
+// engine_weights.hip: two packed weight sets of the same Cout concatenated along K for a launch with a second input
+// (ConvP::in2_hi) -- w [Co][K1 + K2] = [w1 row | w2 row], bias = b1 + b2 -- and the bf16 hi / lo planes of the result.
+// pack_block's conv2 | shortcut, and the operator entry d2t_op_conv_records
+hipError_t concat_k(const float* w1, const float* b1, int K1, const float* w2, const float* b2, int K2, int Co, float* w,
+                    float* bias, uint16_t* w_hi, uint16_t* w_lo, hipStream_t s);
 }  // namespace eng
 #pragma GCC visibility pop
 

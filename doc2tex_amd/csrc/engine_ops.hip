@@ -115,6 +115,172 @@ int d2t_op_conv2d_bf16x3_split_pool(const float* x, const float* w, const float*
   return op_conv_split(true, x, w, bias, nullptr, y, B, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW, act, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// the encoder's record path one kernel at a time (test infrastructure; see include/d2t.h): the engine's own launchers and
+// its weight concatenation on caller buffers.  Sizes are checked here; what a launcher itself refuses (hipErrorInvalidValue,
+// before it launches anything) comes back as D2T_EINVAL.
+// ---------------------------------------------------------------------------
+namespace {
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool rec_fmt_ok(int f) { return f >= 0 && f <= 2; }  // conv_common.h REC_BF16, REC_F16, REC_F16_PAIR
+// the stream drained, the temporary freed, the launches' status as a return code
+int rec_op_finish(hipStream_t s, void* buf, hipError_t e) {
+  const hipError_t e2 = hipStreamSynchronize(s);
+  if (buf) hipFree(buf);
+  return e != hipSuccess ? op_status(e) : op_status(e2);
+}
+}  // namespace
+
+int d2t_op_records_split(const float* x, uint16_t* planes, int64_t rows, int32_t C, int32_t fmt, d2t_stream stream) {
+  if (!x || !planes || rows < 1 || C < 32 || C % 32 || !rec_fmt_ok(fmt) || rows * C > (1LL << 31)) return D2T_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(x) & 3) || !aligned16(planes)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return rec_op_finish(s, nullptr, launch_split_act(x, planes, (size_t)rows, C, s, fmt));
+}
+
+int d2t_op_records_merge(const uint16_t* planes, float* x, int64_t rows, int32_t C, int32_t fmt, d2t_stream stream) {
+  if (!x || !planes || rows < 1 || C < 32 || C % 32 || !rec_fmt_ok(fmt) || rows * C > (1LL << 31)) return D2T_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(planes) & 1)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return rec_op_finish(s, nullptr, launch_merge_act(planes, x, (size_t)rows, C, s, fmt));
+}
+
+int d2t_op_conv_records(const d2t_op_conv_records_args* a, d2t_stream stream) {
+  if (!a || !a->w) return D2T_EINVAL;
+  const bool rec_in = rec_fmt_ok(a->in_fmt);
+  if (rec_in ? (!a->x_rec || a->x_f32) : ((a->in_fmt != 3 && a->in_fmt != 4) || !a->x_f32 || a->x_rec)) return D2T_EINVAL;
+  if ((a->out_rec != nullptr) == (a->out_f32 != nullptr) || (a->res_rec && a->res_f32)) return D2T_EINVAL;
+  if ((a->out_rec && !rec_fmt_ok(a->out_fmt)) || (a->res_rec && !rec_fmt_ok(a->res_fmt))) return D2T_EINVAL;
+  if (a->B < 1 || a->H < 1 || a->W < 1 || a->Cin < 32 || a->Cin % 32 || a->Cout < 32 || a->Cout % 32 || a->KH < 1 || a->KW < 1 ||
+      a->KH * a->KW > 16 || a->SH < 1 || a->SW < 1 || a->PH < 0 || a->PW < 0 || a->PH >= a->KH || a->PW >= a->KW)
+    return D2T_EINVAL;
+  if (a->act < ACT_NONE || a->act > ACT_GELU || (a->kind != 0 && a->kind != 3) || a->out_rows < 1) return D2T_EINVAL;
+  if (a->in_fmt == 3 && a->Cout < 64) return D2T_EINVAL;  // (launch_conv sends fp32 rows with fewer channels to the fp32 kernel)
+  if (a->H + 2 * a->PH < a->KH || a->W + 2 * a->PW < a->KW) return D2T_EINVAL;
+  const int OH = a->OH >= 0 ? a->OH : (a->H + 2 * a->PH - a->KH) / a->SH + 1;
+  const int OW = a->OW >= 0 ? a->OW : (a->W + 2 * a->PW - a->KW) / a->SW + 1;
+  // an overridden grid: every window still starts inside the image or its padding (the taps beyond read the zero page)
+  if (OH < 1 || OW < 1 || (long long)(OH - 1) * a->SH - a->PH >= a->H || (long long)(OW - 1) * a->SW - a->PW >= a->W) return D2T_EINVAL;
+  const long long M = a->pool2 ? 4LL * a->B * (OH / 2) * (OW / 2) : (long long)a->B * OH * OW;
+  if (M < 1 || M > (1 << 24) || (long long)a->B * a->H * a->W * a->Cin * 2 > INT_MAX) return D2T_EINVAL;
+  const bool second = a->x2_rec || a->w2 || a->bias2 || a->Cin2;
+  if (second) {  // (Cin2 % 32 and the layer shapes this mode serves: the launcher's own refusals)
+    if (!rec_in || !a->x2_rec || !a->w2 || !a->bias || !a->bias2 || a->Cin2 < 1) return D2T_EINVAL;
+    if (M * a->Cin2 * 2 > INT_MAX) return D2T_EINVAL;  // DmaIssuer::a_off2 is an int
+  }
+  // the rows the launch writes, and the table rows it reads
+  long long last_row;
+  if (a->rows_per_img < 0 || a->row_add_off < 0) return D2T_EINVAL;
+  if (a->rows_per_img > 0) {
+    if (a->pool2 || a->row_off < 0 || (long long)a->row_off + a->rows_per_img > a->img_stride || M % a->rows_per_img) return D2T_EINVAL;
+    last_row = (M / a->rows_per_img - 1) * a->img_stride + a->row_off + a->rows_per_img - 1;
+  } else {
+    last_row = (a->pool2 ? M / 4 : M) - 1;
+  }
+  if (last_row >= a->out_rows) return D2T_EINVAL;
+  if (a->row_add && (a->pool2 || (long long)a->row_add_off + (a->rows_per_img > 0 ? a->rows_per_img : 1) > a->row_add_rows)) return D2T_EINVAL;
+  if (!aligned16(a->x_rec) || !aligned16(a->x_f32) || !aligned16(a->x2_rec) || !aligned16(a->res_rec) || !aligned16(a->res_f32) ||
+      !aligned16(a->row_add) || !aligned16(a->out_rec) || !aligned16(a->out_f32) || !aligned16(a->bias) || !aligned16(a->bias2))
+    return D2T_EINVAL;
+
+  hipStream_t s = (hipStream_t)stream;
+  const int K1 = a->KH * a->KW * a->Cin, K2 = second ? a->Cin2 : 0, Co = a->Cout;
+  const size_t n1 = (size_t)Co * K1, n = (size_t)Co * (K1 + K2);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  void* buf = nullptr;
+  if (hipMalloc(&buf, up(n1 * 4) + up(n * 4) + up((size_t)Co * 4) + 2 * up(n * 2) + 256) != hipSuccess) return D2T_ENOMEM;
+  char* q = (char*)buf;
+  float* wp = (float*)q; q += up(n1 * 4);     // w in the kernels' K order
+  float* wcat = (float*)q; q += up(n * 4);    // [w | w2] along K
+  float* bcat = (float*)q; q += up((size_t)Co * 4);
+  uint16_t* whi = (uint16_t*)q; q += up(n * 2);
+  uint16_t* wlo = (uint16_t*)q; q += up(n * 2);
+  void* zero = q;
+  const int f16 = rec_in && a->in_fmt != 0;  // fp16 records in: the two-MFMA arithmetic, as conv_operands
+  ConvP p{};
+  hipError_t e = hipMemsetAsync(zero, 0, 256, s);
+  if (e == hipSuccess) e = launch_repack_ohwi(a->w, wp, Co, a->KH, a->KW, a->Cin, s);
+  if (second) {  // (a 1x1 layer's K order is plain)
+    if (e == hipSuccess) e = eng::concat_k(wp, a->bias, K1, a->w2, a->bias2, K2, Co, wcat, bcat, whi, wlo, s);
+    p.w = wcat; p.bias = bcat; p.in2_hi = a->x2_rec; p.Cin2 = K2;
+  } else {
+    if (e == hipSuccess && a->in_fmt != 4) e = launch_split_bf16(wp, whi, wlo, n, s);
+    p.w = wp; p.bias = a->bias;
+  }
+  if (e == hipSuccess && f16) e = launch_split_f16(p.w, whi, wlo, n, s);  // as eng::f16_planes
+  if (a->in_fmt != 4) { p.w_hi = whi; p.w_lo = wlo; }
+  if (rec_in) { p.in_hi = a->x_rec; p.zero16 = zero; p.f16 = f16; } else p.in = a->x_f32;
+  p.pipelined = a->kind; p.split_tail = a->split_tail != 0;
+  p.res = a->res_f32;
+  if (a->res_rec) { p.res_hi = a->res_rec; p.res_fmt = 1 + a->res_fmt; }
+  if (a->out_rec) { p.out_hi = a->out_rec; p.out_fmt = 1 + a->out_fmt; } else p.out = a->out_f32;
+  conv_shape(p, a->B, a->H, a->W, a->Cin, Co, a->KH, a->KW, a->SH, a->SW, a->PH, a->PW, OH, OW);
+  p.K += K2;
+  p.act = a->act;
+  if (a->pool2) { p.pool2 = 1; p.M = (int)M; }
+  p.row_add = a->row_add; p.rows_per_img = a->rows_per_img; p.img_stride = a->img_stride; p.row_off = a->row_off;
+  p.row_add_off = a->row_add_off;
+  if (e == hipSuccess) e = launch_conv(p, s);
+  return rec_op_finish(s, buf, e);
+}
+
+int d2t_op_linear_kv(const float* x, const float* w, const float* bias, float* y, int32_t K, int32_t N, int32_t kv_B, int32_t kv_T,
+                     int32_t heads, int32_t hd, int32_t bf16x3, d2t_stream stream) {
+  if (!x || !w || !y || K < 32 || K % 32 || N < 1 || kv_B < 1 || kv_T < 1 || heads < 1 || hd < 1) return D2T_EINVAL;
+  const long long d = (long long)heads * hd, M = (long long)kv_B * kv_T;
+  if (d > N || N % d || M > (1 << 24) || N > (1 << 20) || (bf16x3 && N < 64)) return D2T_EINVAL;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(bias) || !aligned16(y)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ConvP p{};
+  p.in = x; p.w = w; p.bias = bias; p.out = y;
+  linear_shape(p, (int)M, K, N);
+  p.store_mode = STORE_KV; p.kv_T = kv_T; p.kv_heads = heads; p.kv_hd = hd; p.kv_B = kv_B;
+  void* buf = nullptr;
+  hipError_t e = hipSuccess;
+  if (bf16x3) {
+    const size_t n = (size_t)N * K;
+    if (hipMalloc(&buf, n * 4) != hipSuccess) return D2T_ENOMEM;
+    uint16_t* hi = (uint16_t*)buf;
+    p.w_hi = hi; p.w_lo = hi + n;
+    e = launch_split_bf16(w, hi, hi + n, n, s);
+  }
+  if (e == hipSuccess) e = launch_conv(p, s);
+  return rec_op_finish(s, buf, e);
+}
+
+int d2t_op_maxpool_records(const uint16_t* x, uint16_t* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t SH, int32_t SW,
+                           int32_t PH, int32_t PW, int32_t fmt, d2t_stream stream) {
+  if (!x || !y || x == y || B < 1 || H < 1 || W < 1 || C < 32 || C % 32 || SH < 1 || SW < 1 || !rec_fmt_ok(fmt)) return D2T_EINVAL;
+  // padding below the window size: every window holds at least one pixel of the map
+  if (PH < 0 || PH > 1 || PW < 0 || PW > 1 || H + 2 * PH < 2 || W + 2 * PW < 2) return D2T_EINVAL;
+  if ((long long)B * H * W * C > (1LL << 31) || !aligned16(x) || !aligned16(y)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return rec_op_finish(s, nullptr, launch_maxpool_split(x, y, B, H, W, C, SH, SW, PH, PW, s, fmt));
+}
+
+int d2t_op_stem_records(const float* img, const float* w, const float* bias, uint16_t* out, int32_t B, int32_t Cin, int32_t H,
+                        int32_t W, int32_t act, int32_t fmt, d2t_stream stream) {
+  if (!img || !w || !out || B < 1 || H < 1 || W < 1 || (Cin != 1 && Cin != 3) || (act != ACT_NONE && act != ACT_RELU)) return D2T_EINVAL;
+  if ((fmt != 0 && fmt != 1) || (long long)B * H * W * 32 > (1LL << 31) || !aligned16(out)) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return rec_op_finish(s, nullptr, launch_stem_split(img, w, bias, out, B, Cin, H, W, 32, act, s, fmt));
+}
+
+int d2t_op_pack_conv(const float* w_oihw, const float* conv_bias, const float* bn_w, const float* bn_b, const float* bn_mean,
+                     const float* bn_var, float eps, float* w_out, float* bias_out, uint16_t* bf16_hi, uint16_t* bf16_lo,
+                     uint16_t* f16_hi, uint16_t* f16_lo, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, d2t_stream stream) {
+  if (!w_oihw || !w_out || !bias_out || !bf16_hi || !bf16_lo || !f16_hi || !f16_lo || w_oihw == w_out) return D2T_EINVAL;
+  if (Cout < 1 || Cin < 1 || KH < 1 || KW < 1 || (long long)Cout * Cin * KH * KW > (1LL << 28)) return D2T_EINVAL;
+  const int nbn = (bn_w != nullptr) + (bn_b != nullptr) + (bn_mean != nullptr) + (bn_var != nullptr);
+  if (nbn != 0 && nbn != 4) return D2T_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)Cout * Cin * KH * KW;
+  hipError_t e = launch_pack_conv(w_oihw, conv_bias, bn_w, bn_b, bn_mean, bn_var, eps, w_out, bias_out, Cout, Cin, KH, KW, s);
+  if (e == hipSuccess) e = launch_split_bf16(w_out, bf16_hi, bf16_lo, n, s);
+  if (e == hipSuccess) e = launch_split_f16(w_out, f16_hi, f16_lo, n, s);
+  return rec_op_finish(s, nullptr, e);
+}
+
 int d2t_op_linear(const float* x, const float* w, const float* bias, const float* residual, float* y, int32_t M,
                   int32_t K, int32_t N, int32_t act, d2t_stream stream) {
   if (!x || !w || !y || K % 16) return D2T_EINVAL;

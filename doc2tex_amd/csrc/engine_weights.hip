@@ -89,11 +89,7 @@ int pack_block(d2t_ctx* c, const std::string& p, Block* b, hipStream_t s) {
   if ((rc = owned_alloc(c, &cat.w, n)) || (rc = owned_alloc(c, &cat.bias, (size_t)Co)) || (rc = owned_alloc(c, &cat.w_hi, n)) ||
       (rc = owned_alloc(c, &cat.w_lo, n)))
     return rc;
-  HIPCHK(c, hipMemcpy2DAsync(cat.w, (size_t)(K2 + Kd) * 4, b->c2.w, (size_t)K2 * 4, (size_t)K2 * 4, Co, hipMemcpyDeviceToDevice, s));
-  HIPCHK(c, hipMemcpy2DAsync(cat.w + K2, (size_t)(K2 + Kd) * 4, b->down.w, (size_t)Kd * 4, (size_t)Kd * 4, Co,
-                             hipMemcpyDeviceToDevice, s));
-  HIPCHK(c, launch_add_rows(b->c2.bias, b->down.bias, cat.bias, Co, s));
-  HIPCHK(c, launch_split_bf16(cat.w, cat.w_hi, cat.w_lo, n, s));
+  HIPCHK(c, eng::concat_k(b->c2.w, b->c2.bias, K2, b->down.w, b->down.bias, Kd, Co, cat.w, cat.bias, cat.w_hi, cat.w_lo, s));
   return D2T_OK;
 }
 
@@ -391,6 +387,16 @@ int pack_tfm_head(d2t_ctx* c, const std::string& pp, hipStream_t s) {
 }  // namespace
 
 namespace eng {
+
+hipError_t concat_k(const float* w1, const float* b1, int K1, const float* w2, const float* b2, int K2, int Co, float* w,
+                    float* bias, uint16_t* w_hi, uint16_t* w_lo, hipStream_t s) {
+  const size_t ld = (size_t)(K1 + K2) * 4;
+  hipError_t e = hipMemcpy2DAsync(w, ld, w1, (size_t)K1 * 4, (size_t)K1 * 4, Co, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(w + K1, ld, w2, (size_t)K2 * 4, (size_t)K2 * 4, Co, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = launch_add_rows(b1, b2, bias, Co, s);
+  if (e == hipSuccess) e = launch_split_bf16(w, w_hi, w_lo, (size_t)Co * (K1 + K2), s);
+  return e;
+}
 
 // fp16 hi / lo planes of a packed convolution weight (fp16x2 / mixed precision), created the first time a launch needs them:
 // contexts that never leave split-bf16 (the default; training; fp32) do not pay their memory

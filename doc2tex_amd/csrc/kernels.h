@@ -131,17 +131,17 @@ hipError_t launch_skinny(const SkinnyP& p, hipStream_t s);
 // w [Cout][9][Cin] (pack_conv's layout).
 hipError_t launch_stem(const float* img, const float* w, const float* bias, float* out, int B, int Cin, int H, int W, int Cout,
                        int act, hipStream_t s);
-// same, writing split-bf16 planes
+// same, writing split records of format fmt (conv_common.h REC_*)
 hipError_t launch_stem_split(const float* img, const float* w, const float* bias, uint16_t* out, int B, int Cin, int H, int W,
-                             int Cout, int act, hipStream_t s, int f16 = 0);
-// fp32 [rows][C] <-> split-activation records (C % 32 == 0); used by the test entry point
-hipError_t launch_split_act(const float* x, uint16_t* planes, size_t rows, int C, hipStream_t s, int f16 = 0);
-hipError_t launch_merge_act(const uint16_t* planes, float* x, size_t rows, int C, hipStream_t s, int f16 = 0);
+                             int Cout, int act, hipStream_t s, int fmt = 0);
+// fp32 [rows][C] <-> split-activation records (C % 32 == 0) of format fmt (conv_common.h REC_*); used by the test entry points
+hipError_t launch_split_act(const float* x, uint16_t* planes, size_t rows, int C, hipStream_t s, int fmt = 0);
+hipError_t launch_merge_act(const uint16_t* planes, float* x, size_t rows, int C, hipStream_t s, int fmt = 0);
 hipError_t launch_maxpool(const float* x, float* y, int B, int H, int W, int C, int SH, int SW, int PH, int PW,
                           hipStream_t s);  // 2x2 window
-// 2x2 max-pool on split-bf16 planes (reconstruct, max, re-split)
+// 2x2 max-pool on split records (join, max, re-split); fmt: the record format of both sides (conv_common.h REC_*: 0, 1 or 2)
 hipError_t launch_maxpool_split(const uint16_t* x, uint16_t* y, int B, int H, int W, int C, int SH, int SW, int PH,
-                                int PW, hipStream_t s, int f16 = 0);
+                                int PW, hipStream_t s, int fmt = 0);
 hipError_t launch_maxpool_k(const float* x, float* y, int B, int H, int W, int C, int KH, int KW, int SH, int SW,
                             int PH, int PW, hipStream_t s);
 // y[b][w][c] = mean_h x[b][h][w][c]   (AdaptiveAvgPool2d((None,1)) on the permuted map, build_feat.py:50-55)

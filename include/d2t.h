@@ -628,6 +628,59 @@ int d2t_op_beam_ancestry(const int32_t* anc_old, int32_t* anc_new, const int32_t
 int d2t_op_cache_gather(const float* src, float* dst, const int32_t* prev, int32_t slabs, int32_t cap, int32_t M, int32_t heads,
                         int32_t Lmax, int32_t hd, int32_t rows, d2t_stream stream);
 
+/* ---- the encoder's record path, one kernel at a time ---------------------------------------------------------------
+ * TEST INFRASTRUCTURE (tests/test_conv_records_gpu.py): the serving paths never call these.  No context, device pointers,
+ * synchronous; every size is checked before anything is launched (D2T_EINVAL), and what a kernel's own launcher refuses
+ * comes back as D2T_EINVAL with nothing launched on the caller's buffers.
+ * RECORDS: an activation [rows][C], C % 32 == 0, as raw uint16 planes -- per row and 32-channel group one 128-byte record
+ * [32 x hi | 32 x lo].  Formats: 0 = bf16 hi | lo, 1 = ONE fp16 in the hi half, 2 = fp16 hi | fp16 lo. */
+/* fp32 [rows][C] -> records (a source that is not 16-byte aligned takes the scalar kernel), and back */
+int d2t_op_records_split(const float* x, uint16_t* planes, int64_t rows, int32_t C, int32_t fmt, d2t_stream stream);
+int d2t_op_records_merge(const uint16_t* planes, float* x, int64_t rows, int32_t C, int32_t fmt, d2t_stream stream);
+/* One launch_conv with every field of the record path settable.
+ * Input: x_rec, records [B*H*W][Cin] of format in_fmt (1 and 2 select the two-MFMA arithmetic on fp16 hi / lo weights, whose
+ * MFMAs read the hi half alone) -- or x_f32, fp32 rows, with in_fmt 3 (split-bf16 kernel, split on the fly; Cout >= 64)
+ * or 4 (fp32 kernel).  w [Cout][KH][KW][Cin] (OHWI), bias [Cout] or NULL.
+ * Second input (records only): x2_rec [M][Cin2] in the format of x_rec, w2 [Cout][Cin2], bias2 [Cout]; bias is then
+ * required, and the launch adds bias + bias2.
+ * Residual: res_rec (records, res_fmt 0/1/2) or res_f32, rows indexed like the output's; never both.
+ * Output: out_rec (records, out_fmt 0/1/2) or out_f32, a buffer of out_rows rows that the CALLER allocates and prefills:
+ * the entry never clears it.  Without a remap the launch writes rows [0, M) (pool2: the M / 4 pooled rows).
+ * OH / OW < 0: what the convolution formula gives; otherwise the patch embedding's override.  M = B * OH * OW, with
+ * pool2 4 * B * (OH/2) * (OW/2) rows in pooled order.
+ * Remap (rows_per_img > 0): GEMM row m goes to output row (m / rows_per_img) * img_stride + row_off + m % rows_per_img.
+ * row_add [row_add_rows][Cout] (optional): row row_add_off + m % rows_per_img (row_add_off without a remap) is added
+ * behind the activation.
+ * kind: 0 / 3 as d2t_set_conv_kernel; split_tail: ConvP::split_tail. */
+typedef struct d2t_op_conv_records_args {
+  const uint16_t* x_rec; const float* x_f32; const uint16_t* x2_rec;
+  const float* w; const float* w2; const float* bias; const float* bias2;
+  const uint16_t* res_rec; const float* res_f32; const float* row_add;
+  uint16_t* out_rec; float* out_f32;
+  int32_t in_fmt, res_fmt, out_fmt;
+  int32_t B, H, W, Cin, Cin2, Cout, KH, KW, SH, SW, PH, PW, OH, OW, act, pool2;
+  int32_t rows_per_img, img_stride, row_off, row_add_off, row_add_rows, out_rows;
+  int32_t kind, split_tail;
+} d2t_op_conv_records_args;
+int d2t_op_conv_records(const d2t_op_conv_records_args* a, d2t_stream stream);
+/* The head-split K / V store of cross_kv (STORE_KV): y [slabs][kv_B][heads][kv_T][hd] from x [M = kv_B * kv_T][K] @ w [N][K]^T
+ * + bias, N = slabs * heads * hd, K % 32 == 0; bf16x3 != 0: the split-bf16 kernel (N >= 64), else the fp32 kernel. */
+int d2t_op_linear_kv(const float* x, const float* w, const float* bias, float* y, int32_t K, int32_t N, int32_t kv_B, int32_t kv_T,
+                     int32_t heads, int32_t hd, int32_t bf16x3, d2t_stream stream);
+/* 2x2 max-pool over records of format fmt, [B][H][W][C] -> [B][OH][OW][C], stride >= 1, padding 0 or 1 */
+int d2t_op_maxpool_records(const uint16_t* x, uint16_t* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t SH, int32_t SW,
+                           int32_t PH, int32_t PW, int32_t fmt, d2t_stream stream);
+/* The stem (3x3, padding 1) writing records [B*H*W][32] of format 0 or 1: img NCHW planar [B][Cin][H][W], Cin 1 or 3,
+ * w [32][3][3][Cin], bias [32] or NULL */
+int d2t_op_stem_records(const float* img, const float* w, const float* bias, uint16_t* out, int32_t B, int32_t Cin, int32_t H,
+                        int32_t W, int32_t act, int32_t fmt, d2t_stream stream);
+/* Weight packing as d2t_finalize_weights does it: w_oihw [Cout][Cin][KH][KW] with the optional convolution bias [Cout] and the
+ * optional eval-BatchNorm (all four of bn_w, bn_b, bn_mean, bn_var, or none) folded in -> w_out in the kernels' K order
+ * (Cin % 32 == 0; plain OHWI otherwise), bias_out [Cout], and the bf16 (RNE hi) and fp16 hi / lo planes of w_out. */
+int d2t_op_pack_conv(const float* w_oihw, const float* conv_bias, const float* bn_w, const float* bn_b, const float* bn_mean,
+                     const float* bn_var, float eps, float* w_out, float* bias_out, uint16_t* bf16_hi, uint16_t* bf16_lo,
+                     uint16_t* f16_hi, uint16_t* f16_lo, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, d2t_stream stream);
+
 /* ---- the recurrent kernels, one at a time ------------------------------------------------------------------------
  * TEST INFRASTRUCTURE (tests/test_recurrent_ops_gpu.py): the BiLSTM recurrence, the LSTM-attention decoder loop and their
  * small helpers (csrc/recurrent.hip), behind the same rules as the decode-step entries above -- no context, device

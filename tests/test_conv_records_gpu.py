@@ -1,0 +1,641 @@
+"""GPU: the encoder's record path one kernel at a time (the d2t_op_* entries of the record path in include/d2t.h): how the
+convolution GEMM leaves its kernels -- the second K input, the three record formats, the row remap, position rows, the
+head-split store -- and the small kernels around it (record split / merge, record max-pool, record stem, weight packing).
+
+Two kinds of assertion.  BITWISE: two runs of the same arithmetic (records out vs split of the fp32 rows out, a remapped launch
+vs the plain one permuted, one kernel build vs another, the device's split vs tests/conv_record_refs.py) must give equal bits.
+BOUNDED: against float64, with the bounds of tests/test_ops_gpu.py on the same input recipe (seeded normals, weights * sqrt(2 /
+K), bias * 0.1) --
+    split-bf16 arithmetic vs float64 of the unrounded inputs   4e-4
+    fp16x2 arithmetic vs float64 of the ROUNDED inputs         2e-4 (fp32 accumulation)
+    fp32 kernel                                                2e-4
+    stem                                                       1e-5
+plus the rounding of the output's own format where it is a record, relative to |ref|: 2^-10 for one fp16 (test_ops_gpu.py), 2^-16
+for a bf16 pair (hi truncated to 8 bits, lo rounded to 8 more), 2^-21 for an fp16 pair (11 + 11 bits, lo's rounding at 2^-22 of
+hi's binade).  A residual enters the reference as the value its record holds.  Two weight sets summed in one accumulator are
+each scaled by 1 / sqrt(2), so the output keeps the magnitude of one layer.
+The two tail cases assume 256 CUs (as test_pipelined_convolution_vs_the_128_row_kernel_and_float64 does).
+"""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import conv_record_refs as R
+from doc2tex_amd import _lib
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+SENT16 = 0xDEAD  # prefill of record outputs: a finite value in every format, never produced by zeros
+OUT_ROUND = {None: 0.0, 0: 2.0 ** -16, 1: 2.0 ** -10, 2: 2.0 ** -21}  # relative rounding of an output format (None: fp32 rows)
+
+
+def _rand(*shape, seed=0, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g) * scale
+
+
+def dev16(a):
+    """numpy uint16 -> device int16 tensor (the raw planes)"""
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16).copy()).to(DEV)
+
+
+def host16(t):
+    return t.cpu().numpy().view(np.uint16)
+
+
+def sent_planes(rows, C):
+    return torch.full((rows * C * 2,), SENT16 - 65536, dtype=torch.int16, device=DEV)
+
+
+def mixed_values(n, seed, finite=False):
+    """n values: scales 1e-3 / 1 / 300 interleaved, the edge values planted over the front (as many as fit)"""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(n, generator=g) * torch.tensor([1e-3, 1.0, 300.0]).repeat(n // 3 + 1)[:n]).numpy()
+    e = R.edge_values()
+    if finite:
+        e = e[np.isfinite(e)]
+    e = np.roll(e, -(seed % len(e)))[:n]
+    x[:len(e)] = e
+    return x
+
+
+def kind_of(fmt):
+    return "bf16" if fmt == 0 else "f16"
+
+
+def assert_records_equal(got, want, rows, C, fmt, lo_sentinel=False):
+    """raw planes equal, half by half (any NaN equals any NaN); lo_sentinel: the lo halves still hold the caller's prefill"""
+    gh, gl = R.from_planes(got, rows, C)
+    wh, wl = R.from_planes(want, rows, C)
+    assert R.same_bits(gh, wh, kind_of(fmt)), int((gh != wh).sum())
+    if lo_sentinel:
+        assert (gl == SENT16).all()
+    else:
+        assert R.same_bits(gl, wl, kind_of(fmt)), int((gl != wl).sum())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# records round trip
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("aligned", [True, False])
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+@pytest.mark.parametrize("rows,C", [(1, 32), (3, 64), (257, 96)])
+def test_records_round_trip(rows, C, fmt, aligned):
+    """split_act8_kernel (16-byte aligned source) and split_act_kernel (a source one float further): the raw planes equal the
+    restatement bit for bit -- the layout, truncated / rounded / saturated halves, zeros in the lo half of one-fp16 records --
+    and merge_act_kernel returns join() of them"""
+    lib = _lib.require_device()
+    x = mixed_values(rows * C, seed=rows + fmt).reshape(rows, C)
+    buf = torch.zeros(rows * C + 4, device=DEV)
+    src = buf[0 if aligned else 1:][:rows * C]
+    src.copy_(torch.from_numpy(x).reshape(-1))
+    assert (src.data_ptr() % 16 == 0) == aligned
+    planes = sent_planes(rows, C)
+    assert lib.d2t_op_records_split(_lib.ptr(src), _lib.ptr(planes), rows, C, fmt, _lib.stream_of(src)) == 0
+    want = R.records_of(x, fmt)
+    assert_records_equal(host16(planes), want, rows, C, fmt)
+    if fmt == 1:
+        assert not R.from_planes(host16(planes), rows, C)[1].any()
+    back = torch.full((rows, C), 7.0, device=DEV)
+    assert lib.d2t_op_records_merge(_lib.ptr(planes), _lib.ptr(back), rows, C, fmt, _lib.stream_of(src)) == 0
+    assert np.array_equal(back.cpu().numpy(), R.values_of(host16(planes), rows, C, fmt), equal_nan=True)
+    # refusals: a channel count that is no multiple of 32, an unknown format
+    assert lib.d2t_op_records_split(_lib.ptr(src), _lib.ptr(planes), rows, C - 1, fmt, _lib.stream_of(src)) == _lib.D2T_EINVAL
+    assert lib.d2t_op_records_split(_lib.ptr(src), _lib.ptr(planes), rows, C, 3, _lib.stream_of(src)) == _lib.D2T_EINVAL
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the record convolution
+# ---------------------------------------------------------------------------------------------------------------------
+def to_records(x_rows, fmt):
+    """fp32 [rows][C] on the device -> raw planes on the device (d2t_op_records_split, pinned by test_records_round_trip)"""
+    lib = _lib.require_device()
+    rows, Cc = x_rows.shape
+    planes = sent_planes(rows, Cc)
+    assert lib.d2t_op_records_split(_lib.ptr(x_rows), _lib.ptr(planes), rows, Cc, fmt, _lib.stream_of(x_rows)) == 0
+    return planes
+
+
+def held(x, fmt):
+    """the value a record of format fmt holds for x (torch fp32 -> float64 numpy): what a residual add reads"""
+    return R.join_act(*R.split_act(x.numpy(), fmt), fmt).astype(np.float64)
+
+
+def conv_records(geom, x, w, bias, in_fmt, out=None, res=None, res_fmt=None, x2=None, w2=None, bias2=None, row_add=None,
+                 remap=None, kind=3, split_tail=1, pool2=0, act=1, out_rows=None, guard=0, grid=None):
+    """One d2t_op_conv_records.  geom = (B, H, W, Cin, Cout, (KH, KW), (SH, SW), (PH, PW)); x: device planes (in_fmt 0-2) or
+    fp32 rows (3, 4); w [Cout][KH][KW][Cin]; out: None = fp32 rows, 0-2 = records of that format; res: device planes (res_fmt
+    0-2) or fp32 rows (res_fmt None); remap = (rows_per_img, img_stride, row_off, row_add_off); grid = (OH, OW) override.
+    The output holds out_rows + guard rows prefilled with NaN / SENT16.  -> (rc, output on the host: fp32 [rows][Cout] or raw
+    planes)"""
+    lib = _lib.require_device()
+    B, H, W, Cin, Cout, k, st, pd = geom
+    OH, OW = grid if grid else ((H + 2 * pd[0] - k[0]) // st[0] + 1, (W + 2 * pd[1] - k[1]) // st[1] + 1)
+    M = 4 * B * (OH // 2) * (OW // 2) if pool2 else B * OH * OW
+    if out_rows is None:
+        out_rows = M // 4 if pool2 else M
+    a = _lib.D2TOpConvRecordsArgs()
+    if in_fmt <= 2:
+        a.x_rec = x.data_ptr()
+    else:
+        a.x_f32 = x.data_ptr()
+    a.w = w.data_ptr()
+    keep = [x, w, bias, res, x2, w2, bias2, row_add]
+    for name, t in (("bias", bias), ("x2_rec", x2), ("w2", w2), ("bias2", bias2), ("row_add", row_add)):
+        if t is not None:
+            setattr(a, name, t.data_ptr())
+    if res is not None:
+        setattr(a, "res_rec" if res_fmt is not None else "res_f32", res.data_ptr())
+    if out is None:
+        y = torch.full((out_rows + guard, Cout), float("nan"), device=DEV)
+        a.out_f32 = y.data_ptr()
+    else:
+        y = sent_planes(out_rows + guard, Cout)
+        a.out_rec = y.data_ptr()
+    a.in_fmt, a.res_fmt, a.out_fmt = in_fmt, res_fmt or 0, out or 0
+    a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW = B, H, W, Cin, Cout, k[0], k[1], st[0], st[1], pd[0], pd[1]
+    a.Cin2 = 0 if w2 is None else w2.shape[1]
+    a.OH, a.OW = grid if grid else (-1, -1)
+    a.act, a.pool2, a.kind, a.split_tail, a.out_rows = act, pool2, kind, split_tail, out_rows
+    if remap:
+        a.rows_per_img, a.img_stride, a.row_off, a.row_add_off = remap
+    a.row_add_rows = 0 if row_add is None else row_add.shape[0]
+    rc = lib.d2t_op_conv_records(C.byref(a), _lib.stream_of(w))
+    torch.cuda.synchronize()
+    del keep
+    return rc, (y.cpu().numpy() if out is None else host16(y))
+
+
+# --- the second input ---
+SECOND_SHAPES = [
+    # B, H, W, Cin = Cout, Cin2
+    (3, 7, 37, 128, 64),     # ragged rows, one column tile
+    (1, 257, 256, 128, 64),  # 257 row tiles: one whole round on 256 CUs + one tile, so the 64 x 128 tail build reads x2
+    (1, 257, 256, 256, 128),  # the same with two column tiles
+]
+
+
+@functools.lru_cache(maxsize=2)
+def second_inputs(shape, fmt):
+    B, H, W, Cc, C2 = shape
+    M = B * H * W
+    t = _rand(M, Cc, seed=61)
+    x = _rand(M, C2, seed=62)
+    w = _rand(Cc, 3, 3, Cc, seed=63, scale=(2.0 / (9 * Cc)) ** 0.5 * 2 ** -0.5)   # OHWI
+    wd = _rand(Cc, C2, seed=64, scale=(2.0 / C2) ** 0.5 * 2 ** -0.5)
+    b2, bd = _rand(Cc, seed=65, scale=0.1), _rand(Cc, seed=66, scale=0.1)
+    dev = {n: v.to(DEV) for n, v in dict(w=w, wd=wd, b2=b2, bd=bd, bsum=b2 + bd).items()}
+    dev["t"], dev["x"] = to_records(t.to(DEV), fmt), to_records(x.to(DEV), fmt)
+    dev["w0"], dev["wd0"] = torch.zeros_like(dev["w"]), torch.zeros_like(dev["wd"])
+    return dict(t=t, x=x, w=w, wd=wd, b2=b2, bd=bd), dev
+
+
+def ref_rows_second(host, shape, fmt, h0, h1):
+    """float64 conv2(t) + down(x) + b2 + b_down, ReLU, for the output rows of image rows [h0, h1) of sample 0 (computed on the
+    crop that those rows read; its first / last row is dropped where the crop cut real rows off)"""
+    B, H, W, Cc, C2 = shape
+    lo, hi = max(0, h0 - 1), min(H, h1 + 1)
+    t, x, w, wd = host["t"], host["x"], host["w"], host["wd"]
+    if fmt != 0:  # the two-MFMA arithmetic: fp16 activations, fp16 hi + lo weights
+        t, x = t.half().float(), x.half().float()
+        w = torch.from_numpy(R.f16_bits_to_f32(R.split_weight_f16(w.numpy())[0]).astype(np.float64) +
+                             R.f16_bits_to_f32(R.split_weight_f16(w.numpy())[1]))
+        wd = torch.from_numpy(R.f16_bits_to_f32(R.split_weight_f16(wd.numpy())[0]).astype(np.float64) +
+                              R.f16_bits_to_f32(R.split_weight_f16(wd.numpy())[1]))
+    tc = t[:H * W].view(H, W, Cc)[lo:hi].reshape(-1, Cc).double().numpy()
+    y = R.conv_ref(tc, 1, hi - lo, W, w.double().permute(0, 3, 1, 2).numpy(), (host["b2"] + 0).double().numpy(), (1, 1), (1, 1))
+    y = y.reshape(hi - lo, W, Cc)[h0 - lo:h1 - lo].reshape(-1, Cc)
+    xr = x[:H * W].view(H, W, C2)[h0:h1].reshape(-1, C2).double().numpy()
+    y = y + xr @ wd.double().numpy().T + host["bd"].double().numpy()
+    return np.maximum(y, 0.0)
+
+
+@pytest.mark.parametrize("fmt", [0, 1])
+@pytest.mark.parametrize("shape", SECOND_SHAPES)
+def test_second_input_is_the_shortcut_added_in_the_accumulator(shape, fmt):
+    """ConvP::in2_hi / Cin2 (DmaIssuer::a_off2): a 1x1 convolution over x2 appended along K, weights concatenated by the
+    engine's own eng::concat_k.  Against float64; with either weight set zero the launch equals the plain launch of the other
+    bit for bit (zero products leave an fp32 accumulator as it is); the 64 x 128 tail build equals the 256 x 128 one; a sample
+    alone equals its rows in the batch."""
+    B, H, W, Cc, C2 = shape
+    host, d = second_inputs(shape, fmt)
+    geom = (B, H, W, Cc, Cc, (3, 3), (1, 1), (1, 1))
+    rc, y = conv_records(geom, d["t"], d["w"], d["b2"], fmt, x2=d["x"], w2=d["wd"], bias2=d["bd"])
+    assert rc == 0 and np.isfinite(y).all()
+    bound, rel = (4e-4, 0.0) if fmt == 0 else (2e-4, 0.0)
+    for h0, h1 in {(0, min(H, 3)), (H - min(H, 3), H)}:  # the first rows and the last ones (the tail tile's)
+        ref = ref_rows_second(host, shape, fmt, h0, h1)
+        err = np.abs(y[h0 * W:h1 * W] - ref)
+        print("second input", shape, fmt, (h0, h1), "max err", float(err.max()))
+        assert (err <= bound + rel * np.abs(ref)).all(), float(err.max())
+    # shortcut weights zero == the plain launch (same bias sum); 3x3 weights zero == the 1x1 launch over x2
+    rc, y0 = conv_records(geom, d["t"], d["w"], d["b2"], fmt, x2=d["x"], w2=d["wd0"], bias2=d["bd"])
+    rc1, yp = conv_records(geom, d["t"], d["w"], d["bsum"], fmt)
+    assert rc == 0 and rc1 == 0 and np.array_equal(y0, yp)
+    rc, y1 = conv_records(geom, d["t"], d["w0"], d["b2"], fmt, x2=d["x"], w2=d["wd"], bias2=d["bd"])
+    rc1, yd = conv_records((B, H, W, C2, Cc, (1, 1), (1, 1), (0, 0)), d["x"], d["wd"].view(Cc, 1, 1, C2), d["bsum"], fmt)
+    assert rc == 0 and rc1 == 0 and np.array_equal(y1, yd)
+    assert not np.array_equal(y, y0) and not np.array_equal(y, y1)
+    # the tail hand-over does not show in the values
+    rc, yt = conv_records(geom, d["t"], d["w"], d["b2"], fmt, x2=d["x"], w2=d["wd"], bias2=d["bd"], split_tail=0)
+    assert rc == 0 and np.array_equal(y, yt)
+    # the last sample alone
+    if B > 1:
+        n = H * W * 2
+        g1 = (1,) + geom[1:]
+        rc, ys = conv_records(g1, d["t"][(B - 1) * n * Cc:], d["w"], d["b2"], fmt, x2=d["x"][(B - 1) * n * C2:], w2=d["wd"],
+                              bias2=d["bd"])
+        assert rc == 0 and np.array_equal(ys, y[(B - 1) * H * W:])
+
+
+def test_second_input_refusals_leave_the_output_alone():
+    """what launch_conv_bf16x3 refuses for a second input -- Cout < 128, a stride, the fused pool, the 128-row kernels, Cin2 that
+    is no multiple of 32 -- and what the entry refuses itself (a_off2 is an int: M * Cin2 * 2 beyond INT_MAX): an error code,
+    nothing written"""
+    B, H, W = 1, 8, 12
+    M = B * H * W
+    x128, x64 = to_records(_rand(M, 128, seed=71).to(DEV), 0), to_records(_rand(M, 64, seed=72).to(DEV), 0)
+    w128 = _rand(128, 3, 3, 128, seed=73, scale=0.03).to(DEV)
+    w64 = _rand(64, 3, 3, 64, seed=74, scale=0.03).to(DEV)
+    wd = _rand(128, 64, seed=75, scale=0.1).to(DEV)
+    b = torch.zeros(128, device=DEV)
+    g = (B, H, W, 128, 128, (3, 3), (1, 1), (1, 1))
+    ok = dict(x2=x64, w2=wd, bias2=b)
+    cases = {
+        "valid": (conv_records(g, x128, w128, b, 0, **ok), True),
+        "Cout < 128": (conv_records((B, H, W, 64, 64, (3, 3), (1, 1), (1, 1)), x64, w64, b[:64], 0, x2=x64, w2=wd[:64], bias2=b[:64]), False),
+        "stride 2": (conv_records((B, H, W, 128, 128, (3, 3), (2, 2), (1, 1)), x128, w128, b, 0, **ok), False),
+        "pool2": (conv_records(g, x128, w128, b, 0, pool2=1, **ok), False),
+        "kind 0": (conv_records(g, x128, w128, b, 0, kind=0, **ok), False),
+        "Cin2 % 32": (conv_records(g, x128, w128, b, 0, x2=x64, w2=wd[:, :48].contiguous(), bias2=b), False),
+        "no bias2": (conv_records(g, x128, w128, b, 0, x2=x64, w2=wd), False),
+    }
+    for name, ((rc, y), valid) in cases.items():
+        if valid:
+            assert rc == 0 and np.isfinite(y).all(), name
+        else:
+            assert rc == _lib.D2T_EINVAL and np.isnan(y).all(), (name, rc)
+    # M * Cin2 * 2 > INT_MAX: refused on the sizes alone, before any buffer is read (x2 is far smaller than the sizes claim).
+    # Every other field is what a valid 1x1 launch of this geometry carries (the fields not set below are zero: format 0, no
+    # padding, no pool, no remap), M = 2^24 is the largest the entry takes and the first input stays below INT_MAX (asserted),
+    # so by the entry's code only the a_off2 check is left to refuse.  The test cannot SHOW that: every refusal of the entry
+    # is D2T_EINVAL, and the companion call that differs in Cin2 alone (32: 2^30) would pass the check and launch on buffers
+    # that are far too small, which no test may do.
+    lib = _lib.require_device()
+    a = _lib.D2TOpConvRecordsArgs()
+    y = torch.full((16, 128), float("nan"), device=DEV)
+    a.x_rec, a.x2_rec, a.w, a.w2, a.bias, a.bias2, a.out_f32 = (x128.data_ptr(), x64.data_ptr(), w128.data_ptr(), wd.data_ptr(),
+                                                                 b.data_ptr(), b.data_ptr(), y.data_ptr())
+    a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.SH, a.SW, a.OH, a.OW = 1, 4096, 4096, 32, 128, 1, 1, 1, 1, -1, -1
+    a.Cin2, a.kind, a.out_rows, a.act = 64, 3, 1 << 24, 1
+    assert 4096 * 4096 * 64 * 2 > 2 ** 31 - 1 >= 4096 * 4096 * 32 * 2
+    assert lib.d2t_op_conv_records(C.byref(a), _lib.stream_of(y)) == _lib.D2T_EINVAL and torch.isnan(y).all()
+
+
+# --- the record formats ---
+ENGINE_FORMATS = [(0, 0, 0), (0, 0, 2), (2, None, 1), (1, 2, 2), (1, 2, 0), (2, None, 0), (1, 1, 1)]  # basic_block, run_backbone
+OTHER_FORMATS = [(0, r, o) for r in (0, 1, 2) for o in (0, 1, 2) if (0, r, o) not in ENGINE_FORMATS]
+
+
+@functools.lru_cache(maxsize=4)
+def format_inputs(Cout):
+    B, H, W, Cin = 2, 7, 37, 128
+    M = B * H * W
+    x = _rand(M, Cin, seed=81)
+    w = _rand(Cout, 3, 3, Cin, seed=82, scale=(2.0 / (9 * Cin)) ** 0.5)
+    b = _rand(Cout, seed=83, scale=0.1)
+    res = _rand(M, Cout, seed=84)
+    dev = dict(w=w.to(DEV), b=b.to(DEV), x={f: to_records(x.to(DEV), f) for f in (0, 1, 2)},
+               res={f: to_records(res.to(DEV), f) for f in (0, 1, 2)})
+    return (B, H, W, Cin, Cout, (3, 3), (1, 1), (1, 1)), dict(x=x, w=w, b=b, res=res), dev
+
+
+def format_reference(host, geom, in_fmt, res_fmt):
+    B, H, W, Cin, Cout = geom[:5]
+    x, w = host["x"], host["w"]
+    if in_fmt == 0:  # float64 of the unrounded inputs
+        xr, wr = x.double().numpy(), w.double()
+    else:            # the MFMAs read the hi half of the record alone; fp16 hi + lo weights
+        xr = R.mma_operand(*R.split_act(x.numpy(), in_fmt), in_fmt)
+        wh, wl = R.split_weight_f16(w.numpy())
+        wr = torch.from_numpy(R.f16_bits_to_f32(wh).astype(np.float64) + R.f16_bits_to_f32(wl))
+    y = R.conv_ref(xr, B, H, W, wr.permute(0, 3, 1, 2).numpy(), host["b"].double().numpy(), (1, 1), (1, 1))
+    return R.finish_ref(y, 1, None if res_fmt is None else held(host["res"], res_fmt))  # the residual: hi + lo of its record
+
+
+@pytest.mark.parametrize("Cout", [384, 64])
+@pytest.mark.parametrize("fmts", ENGINE_FORMATS + OTHER_FORMATS)
+def test_record_formats_of_input_residual_and_output(fmts, Cout):
+    """ConvP::out_fmt / res_fmt with an input of another format, on the pipelined kernel (Cout 384: tile_rows_epilogue with
+    W = 8) and on conv_bf16x3g_128x64 (Cout 64: W = 4; the 32x32 bodies honour the formats in their tile epilogue).  The record
+    output is split() of the same launch's fp32 rows bit for bit; a residual given as records equals the fp32 residual
+    join(records) bit for bit; the fp32 rows meet the float64 bound of the arithmetic the INPUT format selects."""
+    in_fmt, res_fmt, out_fmt = fmts
+    geom, host, d = format_inputs(Cout)
+    M = geom[0] * geom[1] * geom[2]
+    res = None if res_fmt is None else d["res"][res_fmt]
+    rc, y32 = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, res=res, res_fmt=res_fmt)
+    assert rc == 0 and np.isfinite(y32).all()
+    rc, rec = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, out=out_fmt, res=res, res_fmt=res_fmt, guard=1)
+    assert rc == 0
+    want = R.records_of(y32, out_fmt)
+    # one-fp16 records: the 8-wide store leaves the lo half alone (it is never read), the 4-wide store writes its zeros
+    assert_records_equal(rec[:M * Cout * 2], want, M, Cout, out_fmt, lo_sentinel=(out_fmt == 1 and Cout == 384))
+    assert (rec[M * Cout * 2:] == SENT16).all()  # nothing behind the last row
+    if res_fmt is not None:
+        rj = torch.from_numpy(R.values_of(host16(res), M, Cout, res_fmt)).to(DEV)
+        rc, y32b = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, res=rj)
+        assert rc == 0 and np.array_equal(y32, y32b)
+    ref = format_reference(host, geom, in_fmt, res_fmt)
+    err = np.abs(y32 - ref)
+    print("formats", fmts, Cout, "fp32 rows max err", float(err.max()))
+    assert (err <= (4e-4 if in_fmt == 0 else 2e-4)).all(), float(err.max())
+    got = R.values_of(rec[:M * Cout * 2], M, Cout, out_fmt).astype(np.float64)
+    err = np.abs(got - ref)
+    assert (err <= (4e-4 if in_fmt == 0 else 2e-4) + np.abs(ref) * OUT_ROUND[out_fmt]).all(), float(err.max())
+
+
+def test_element_wise_epilogue_of_the_32x32_bodies_refuses_a_foreign_format():
+    """ElemTwoWay (conv_common.h) knows the input's format only: a record launch that would reach it -- a remap on the 128-row
+    kernels -- with another out_fmt / res_fmt is refused by launch_conv_bf16x3; the input's own format passes"""
+    geom, host, d = format_inputs(64)
+    M = geom[0] * geom[1] * geom[2]
+    remap = (M // 2, M // 2, 0, 0)
+    rc, y = conv_records(geom, d["x"][0], d["w"], d["b"], 0, out=2, remap=remap)
+    assert rc == _lib.D2T_EINVAL and (y == SENT16).all()
+    rc, y = conv_records(geom, d["x"][0], d["w"], d["b"], 0, res=d["res"][1], res_fmt=1, remap=remap)
+    assert rc == _lib.D2T_EINVAL and np.isnan(y).all()
+    rc, y = conv_records(geom, d["x"][0], d["w"], d["b"], 0, out=0, res=d["res"][0], res_fmt=0, remap=remap)
+    rc1, y1 = conv_records(geom, d["x"][0], d["w"], d["b"], 0, out=0, res=d["res"][0], res_fmt=0)
+    assert rc == 0 and rc1 == 0 and np.array_equal(y, y1)  # (the identity remap: the element-wise epilogue, same values)
+
+
+@pytest.mark.parametrize("fmts", [(0, 2, 1), (0, 1, 2), (1, 2, 0), (2, 0, 2)])
+def test_element_wise_epilogue_of_the_pipelined_kernel_honours_the_formats(fmts):
+    """conv_epilogue<Map16, ElemThreeWay> (an identity remap sends the pipelined kernel there): res_fmt and out_fmt each of a
+    format of its own give the bits of the tile epilogue; the lo half of one-fp16 records is written as zeros here"""
+    in_fmt, res_fmt, out_fmt = fmts
+    geom, host, d = format_inputs(384)
+    M, Cout = geom[0] * geom[1] * geom[2], 384
+    kw = dict(out=out_fmt, res=d["res"][res_fmt], res_fmt=res_fmt)
+    rc, tile = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, **kw)
+    rc1, elem = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, remap=(M // 2, M // 2, 0, 0), **kw)
+    assert rc == 0 and rc1 == 0
+    th, tl = R.from_planes(tile, M, Cout)
+    eh, el = R.from_planes(elem, M, Cout)
+    assert np.array_equal(th, eh) and (np.array_equal(tl, el) if out_fmt != 1 else (not el.any() and (tl == SENT16).all()))
+
+
+# --- remap and position rows ---
+@functools.lru_cache(maxsize=2)
+def patch_inputs():
+    B, H, W, Cin, Cout = 3, 5, 9, 64, 256
+    x = _rand(B * H * W, Cin, seed=91)
+    w = _rand(Cout, 2, 2, Cin, seed=92, scale=(2.0 / (4 * Cin)) ** 0.5)
+    b = _rand(Cout, seed=93, scale=0.1)
+    table = _rand(16, Cout, seed=94)
+    ref = np.maximum(R.conv_ref(x.double().numpy(), B, H, W, w.double().permute(0, 3, 1, 2).numpy(), b.double().numpy(), (2, 2),
+                                (0, 0), 3, 5), 0.0)
+    return (B, H, W, Cin, Cout, (2, 2), (2, 2), (0, 0)), x, table, ref, dict(x=x.to(DEV), w=w.to(DEV), b=b.to(DEV), table=table.to(DEV))
+
+
+@pytest.mark.parametrize("path", ["records kind 3", "records kind 0", "on the fly", "fp32"])
+def test_patch_grid_remap_and_position_rows(path):
+    """The patch embedding's launch: OH x OW overridden to the patch grid (3 x 5 over a 5 x 9 map: the bottom row and right
+    column of patches read zeros), rows remapped so that row 0 of every image is left to the cls token, position rows added
+    behind the activation.  conv_epilogue<Map16, ElemThreeWay> (pipelined), conv_epilogue<Map32, ElemTwoWay> (kind 0) and the
+    Epi::full tile epilogue (on-the-fly split-bf16 kernel, fp32 kernel)."""
+    geom, x, table, ref, d = patch_inputs()
+    B, Cout = geom[0], geom[4]
+    in_fmt = {"records kind 3": 0, "records kind 0": 0, "on the fly": 3, "fp32": 4}[path]
+    xin = to_records(d["x"], 0) if in_fmt == 0 else d["x"]
+    kw = dict(kind=0 if path == "records kind 0" else 3, grid=(3, 5))
+    rc, plain = conv_records(geom, xin, d["w"], d["b"], in_fmt, **kw)
+    assert rc == 0 and np.isfinite(plain).all()
+    err = np.abs(plain - ref)
+    print("patch grid", path, "max err", float(err.max()))
+    assert (err <= (2e-4 if path == "fp32" else 4e-4)).all(), float(err.max())
+    remap = (15, 16, 1, 1)
+    rows = R.remap_rows(45, 15, 16, 1)
+    rc, y = conv_records(geom, xin, d["w"], d["b"], in_fmt, remap=remap, out_rows=48, guard=3, **kw)
+    assert rc == 0
+    assert np.array_equal(y[rows], plain)                          # the un-remapped launch, rows permuted
+    rest = np.setdiff1d(np.arange(51), rows)
+    assert list(rest) == [0, 16, 32, 48, 49, 50] and np.isnan(y[rest]).all()  # the cls rows and everything behind the last row
+    rc, yt = conv_records(geom, xin, d["w"], d["b"], in_fmt, remap=remap, row_add=d["table"], out_rows=48, guard=3, **kw)
+    assert rc == 0 and np.isnan(yt[rest]).all()
+    want = y[rows] + table.numpy()[R.row_add_rows(45, 15, 1)]      # one fp32 add behind the activation
+    assert np.array_equal(yt[rows], want)
+    if path == "on the fly":  # fewer than 64 channels would go to the fp32 kernel (launch_conv): the entry refuses
+        g32 = geom[:4] + (32,) + geom[5:]
+        rc, y32 = conv_records(g32, xin, d["w"][:32].contiguous(), d["b"][:32].contiguous(), 3, grid=(3, 5))
+        assert rc == _lib.D2T_EINVAL and np.isnan(y32).all()
+    # a table or an output too short for the remap: refused
+    rc, y = conv_records(geom, xin, d["w"], d["b"], in_fmt, remap=remap, row_add=d["table"][:15], out_rows=48, **kw)
+    assert rc == _lib.D2T_EINVAL and np.isnan(y).all()
+    rc, y = conv_records(geom, xin, d["w"], d["b"], in_fmt, remap=remap, out_rows=47, **kw)
+    assert rc == _lib.D2T_EINVAL and np.isnan(y).all()
+
+
+@pytest.mark.parametrize("in_fmt", [0, 1, 3, 4])
+def test_identity_remap_with_a_position_table(in_fmt):
+    """encode_resnet_flat's form of conv4_2: rows_per_img = img_stride, no offset, the 2-D position table added"""
+    B, H, W, Cc = 2, 4, 12, 512
+    x = _rand(B * H * W, Cc, seed=95)
+    w = _rand(Cc, 2, 2, Cc, seed=96, scale=(2.0 / (4 * Cc)) ** 0.5)
+    b = _rand(Cc, seed=97, scale=0.1)
+    table = _rand(33, Cc, seed=98)
+    geom = (B, H, W, Cc, Cc, (2, 2), (1, 1), (0, 0))
+    xd, wd, bd, td = x.to(DEV), w.to(DEV), b.to(DEV), table.to(DEV)
+    xin = to_records(xd, in_fmt) if in_fmt <= 2 else xd
+    rc, plain = conv_records(geom, xin, wd, bd, in_fmt)
+    rc1, y = conv_records(geom, xin, wd, bd, in_fmt, remap=(33, 33, 0, 0), row_add=td, guard=2)
+    assert rc == 0 and rc1 == 0 and np.isnan(y[66:]).all()
+    assert np.array_equal(y[:66], plain + np.tile(table.numpy(), (2, 1)))
+    if in_fmt == 1:
+        xr, (wh, wl) = x.half().double().numpy(), R.split_weight_f16(w.numpy())
+        wr = torch.from_numpy(R.f16_bits_to_f32(wh).astype(np.float64) + R.f16_bits_to_f32(wl))
+    else:
+        xr, wr = x.double().numpy(), w.double()
+    ref = np.maximum(R.conv_ref(xr, B, H, W, wr.permute(0, 3, 1, 2).numpy(), b.double().numpy(), (1, 1), (0, 0)), 0.0)
+    err = np.abs(plain - ref)
+    print("identity remap", in_fmt, "max err", float(err.max()))
+    assert (err <= {0: 4e-4, 1: 2e-4, 3: 4e-4, 4: 2e-4}[in_fmt]).all(), float(err.max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# head-split store
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bf16x3", [0, 1])
+@pytest.mark.parametrize("slabs", [2, 6])
+@pytest.mark.parametrize("heads,hd", [(8, 32), (4, 64), (3, 20), (16, 6)])
+@pytest.mark.parametrize("B,T", [(3, 37), (1, 129)])
+def test_head_split_store(B, T, heads, hd, slabs, bf16x3):
+    """STORE_KV of cross_kv: the plain-rows launch of the same kernel, permuted by the restated index, bit for bit -- through the
+    Epi::full tile epilogue (head sizes 32, 64) and the element-wise one, which wide_epilogue_full_ok selects by either half of
+    its condition alone: 3 x 20 has N % 32 != 0 (N = 120, 360) with a head size that IS a multiple of 4; 16 x 6 has N % 32 == 0
+    (N = 192, 576) with kv_hd % 4 != 0, where a four-wide store of the tile epilogue would straddle two heads -- and float64"""
+    lib = _lib.require_device()
+    K, N, M = 256, slabs * heads * hd, B * T
+    x, w, b = _rand(M, K, seed=101), _rand(N, K, seed=102, scale=(2.0 / K) ** 0.5), _rand(N, seed=103, scale=0.1)
+    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
+    plain = torch.full((M, N), float("nan"), device=DEV)
+    if bf16x3:
+        assert lib.d2t_op_conv2d_bf16x3(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), None, _lib.ptr(plain), 1, 1, M, K, N, 1, 1, 1, 1,
+                                        0, 0, 0, _lib.stream_of(xd)) == 0
+    else:
+        assert lib.d2t_op_linear(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), None, _lib.ptr(plain), M, K, N, 0, _lib.stream_of(xd)) == 0
+    y = torch.full((M * N + 64,), float("nan"), device=DEV)
+    assert lib.d2t_op_linear_kv(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(y), K, N, B, T, heads, hd, bf16x3,
+                                _lib.stream_of(xd)) == 0
+    torch.cuda.synchronize()
+    y, plain = y.cpu().numpy(), plain.cpu().numpy()
+    assert np.isnan(y[M * N:]).all() and np.isfinite(y[:M * N]).all()
+    idx = R.kv_index(B, T, heads, hd, N)
+    assert np.array_equal(y[idx], plain)
+    ref = (x.double() @ w.double().T + b.double()).numpy()
+    err = np.abs(plain - ref)
+    print("head split", (B, T, heads, hd, slabs, bf16x3), "max err", float(err.max()))
+    assert (err <= (4e-4 if bf16x3 else 2e-4)).all(), float(err.max())
+    # N that is no whole number of slabs: refused, nothing written
+    y2 = torch.full((M * N,), float("nan"), device=DEV)
+    assert lib.d2t_op_linear_kv(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(y2), K, N, B, T, heads + 1, hd, bf16x3,
+                                _lib.stream_of(xd)) == _lib.D2T_EINVAL
+    assert torch.isnan(y2).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# record max-pool
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+@pytest.mark.parametrize("B,H,W,Cc,s,p", [(2, 9, 11, 64, (2, 2), (0, 0)), (2, 8, 13, 256, (2, 1), (0, 1))])
+def test_record_max_pool(B, H, W, Cc, s, p, fmt):
+    """maxpool_split_kernel with the record format passed through (Net::pool): join, maximum, re-split -- the output records
+    are split(max_pool2d(join(in))) bit for bit, format 2 included; a padded window never yields -Inf.  The values include
+    remainders that round up to the next hi step, a channel of -0 and an all-negative channel."""
+    lib = _lib.require_device()
+    M = B * H * W
+    x = mixed_values(M * Cc, seed=111 + fmt, finite=True).reshape(M, Cc)
+    x[:, 1] = -0.0
+    x[:, 2] = -np.abs(x[:, 2]) - 1.0
+    planes = R.records_of(x, fmt)
+    xin = R.values_of(planes, M, Cc, fmt)  # what the records hold
+    want = F.max_pool2d(torch.from_numpy(xin).view(B, H, W, Cc).permute(0, 3, 1, 2), 2, s, p).permute(0, 2, 3, 1)
+    OH, OW = want.shape[1:3]
+    assert torch.isfinite(want).all()
+    out = sent_planes(B * OH * OW + 1, Cc)
+    xp = dev16(planes)
+    assert lib.d2t_op_maxpool_records(_lib.ptr(xp), _lib.ptr(out), B, H, W, Cc, s[0], s[1], p[0], p[1], fmt, _lib.stream_of(xp)) == 0
+    got = host16(out)
+    n = B * OH * OW * Cc * 2
+    assert (got[n:] == SENT16).all()
+    assert_records_equal(got[:n], R.records_of(want.reshape(-1, Cc).numpy(), fmt), B * OH * OW, Cc, fmt)
+    assert np.isfinite(R.values_of(got[:n], B * OH * OW, Cc, fmt)).all()
+    assert lib.d2t_op_maxpool_records(_lib.ptr(xp), _lib.ptr(out), B, H, W, Cc, s[0], s[1], 2, p[1], fmt, _lib.stream_of(xp)) == _lib.D2T_EINVAL
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# record stem
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", [0, 1])
+@pytest.mark.parametrize("H,W", [(20, 36), (37, 53)])
+@pytest.mark.parametrize("Cin", [1, 3])
+def test_record_stem(Cin, H, W, fmt):
+    """stem_split_kernel<1|3>: the records are split() of the fp32 stem's output (d2t_op_conv2d) bit for bit -- both kernels run
+    one fmaf chain in the same order -- and within 1e-5 plus the format's rounding of float64"""
+    lib = _lib.require_device()
+    B = 2
+    x = _rand(B, Cin, H, W, seed=121)
+    w = _rand(32, Cin, 3, 3, seed=122, scale=0.3)
+    b = _rand(32, seed=123, scale=0.1)
+    xd, wd, bd = x.to(DEV), w.permute(0, 2, 3, 1).contiguous().to(DEV), b.to(DEV)
+    y = torch.full((B * H * W, 32), float("nan"), device=DEV)
+    assert lib.d2t_op_conv2d(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), None, _lib.ptr(y), B, H, W, Cin, 32, 3, 3, 1, 1, 1, 1, 1,
+                             _lib.stream_of(xd)) == 0
+    out = sent_planes(B * H * W + 1, 32)
+    assert lib.d2t_op_stem_records(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(out), B, Cin, H, W, 1, fmt, _lib.stream_of(xd)) == 0
+    torch.cuda.synchronize()
+    got, y = host16(out), y.cpu().numpy()
+    n = B * H * W * 64
+    assert (got[n:] == SENT16).all()
+    assert_records_equal(got[:n], R.records_of(y, fmt), B * H * W, 32, fmt)
+    ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), 1, 1)).permute(0, 2, 3, 1).reshape(-1, 32).numpy()
+    err = np.abs(R.values_of(got[:n], B * H * W, 32, fmt) - ref)
+    print("stem", (Cin, H, W, fmt), "max err", float(err.max()))
+    assert (err <= 1e-5 + np.abs(ref) * OUT_ROUND[fmt]).all(), float(err.max())
+    assert lib.d2t_op_stem_records(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(out), B, 2, H, W, 1, fmt, _lib.stream_of(xd)) == _lib.D2T_EINVAL
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# weight packing
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_bn", [True, False])
+@pytest.mark.parametrize("with_bias", [True, False])
+@pytest.mark.parametrize("Cout,Cin,k", [(64, 32, 3), (128, 64, 1), (32, 3, 3), (96, 160, 2)])
+def test_weight_packing(Cout, Cin, k, with_bias, with_bn):
+    """pack_conv_kernel, then launch_split_bf16 / launch_split_f16 of its result.
+    Fold: s = gamma / sqrt(var + eps) and w * s are a sum, a square root, a division and a product with one fp32 rounding each
+    (half an ulp), so the folded weights lie within 4 ulp (4 * 2^-23 relative) of the float64 fold.  Bias: the same, plus one
+    ulp of each term that enters its sum, since the sum may cancel.  The issue names two such terms, |beta| + |mean * s|; with
+    a convolution bias the kernel sums a third rounded term, conv_bias * s + beta - mean * s, so |conv_bias * s| * 2^-23 is
+    added for those cases -- the one place where this file's bound is wider than the issue's formula.  Measured on an MI355X:
+    the bias error is at most 4.3e-6, 0.20 of this bound, with a convolution bias (and 0.20 of the issue's two-term bound, which
+    those cases meet as well), and at most 3.5e-6, 0.22 of the issue's own bound, without one.
+    Layout: without BatchNorm and bias the fold multiplies by 1.0, so w_out is the input permuted into the restated K order
+    EXACTLY (edge values planted); the plain OHWI order for Cin % 32 != 0.  Planes: the restatement of the device's w_out bit
+    for bit (RNE hi for bf16; saturating fp16 hi, fp16 of the remainder)."""
+    lib = _lib.require_device()
+    n = Cout * Cin * k * k
+    w = _rand(Cout, Cin, k, k, seed=131, scale=(2.0 / (Cin * k * k)) ** 0.5)
+    if not with_bn:
+        e = R.edge_values()
+        w.view(-1)[:len(e)] = torch.from_numpy(e)
+    cb = _rand(Cout, seed=132, scale=0.1) if with_bias else None
+    g = torch.Generator().manual_seed(133)
+    gamma = _rand(Cout, seed=134)
+    gamma[::7] = 0.0
+    beta, mean = _rand(Cout, seed=135), (torch.rand(Cout, generator=g) * 6 - 3)
+    var = torch.exp(torch.rand(Cout, generator=g) * (np.log(10.0) - np.log(1e-2)) + np.log(1e-2))
+    assert (gamma < 0).any() and (gamma == 0).any() and float(var.min()) >= 1e-2 * 0.999 and float(var.max()) <= 10.001
+    bn = (gamma, beta, mean, var) if with_bn else (None,) * 4
+    dv = [None if t is None else t.to(DEV) for t in (w, cb) + bn]
+    w_out = torch.full((n,), float("nan"), device=DEV)
+    b_out = torch.full((Cout,), float("nan"), device=DEV)
+    planes = [torch.zeros(n, dtype=torch.int16, device=DEV) for _ in range(4)]
+    eps = 1e-5
+    rc = lib.d2t_op_pack_conv(*[_lib.ptr(t) for t in dv], eps, _lib.ptr(w_out), _lib.ptr(b_out), *[_lib.ptr(t) for t in planes],
+                              Cout, Cin, k, k, _lib.stream_of(w_out))
+    assert rc == 0
+    w_dev, b_dev = w_out.cpu().numpy().reshape(Cout, -1), b_out.cpu().numpy()
+    wf, bf = R.bn_fold(w.numpy(), None if cb is None else cb.numpy(), tuple(t.numpy() for t in bn) if with_bn else None, eps)
+    want = R.pack_rows(wf)
+    if not with_bn:
+        assert np.array_equal(w_dev, R.pack_rows(w.numpy()), equal_nan=True)  # the layout, exactly
+        assert np.array_equal(b_dev, (cb.numpy() if with_bias else np.zeros(Cout, dtype=np.float32)))
+    fin = np.isfinite(want)
+    assert np.array_equal(np.isfinite(w_dev), fin)
+    err = np.abs(w_dev[fin].astype(np.float64) - want[fin])
+    print("pack", (Cout, Cin, k, with_bias, with_bn), "max err / |w| in ulp", float((err / np.maximum(np.abs(want[fin]), 1e-300)).max() * 2 ** 23))
+    assert (err <= 4 * 2.0 ** -23 * np.abs(want[fin])).all()
+    s = (gamma.double() / torch.sqrt(var.double() + float(np.float32(eps)))).numpy() if with_bn else np.ones(Cout)
+    terms = (np.abs(beta.double().numpy()) + np.abs(mean.double().numpy() * s) if with_bn else 0.0) + \
+        (np.abs(cb.double().numpy() * s) if with_bias else 0.0)
+    berr, bbound = np.abs(b_dev - bf), 4 * 2.0 ** -23 * np.abs(bf) + terms * 2.0 ** -23
+    two = 4 * 2.0 ** -23 * np.abs(bf) + (terms - (np.abs(cb.double().numpy() * s) if with_bias else 0.0)) * 2.0 ** -23
+    print("pack bias", (Cout, Cin, k, with_bias, with_bn), "max err", float(berr.max()), "err / bound",
+          float((berr / np.maximum(bbound, 1e-300)).max()), "err / the issue's two-term bound",
+          float((berr / np.maximum(two, 1e-300)).max()) if with_bn else 0.0)
+    assert (berr <= bbound).all(), float(berr.max())
+    bh, bl, fh, fl = (host16(t) for t in planes)
+    wh, wl = R.split_weight_bf16(w_dev.reshape(-1))
+    assert R.same_bits(bh, wh, "bf16") and R.same_bits(bl, wl, "bf16")
+    wh, wl = R.split_weight_f16(w_dev.reshape(-1))
+    assert R.same_bits(fh, wh, "f16") and R.same_bits(fl, wl, "f16")
+    if with_bn:  # a lone BatchNorm pointer: refused
+        dv[3] = None
+        assert lib.d2t_op_pack_conv(*[_lib.ptr(t) for t in dv], eps, _lib.ptr(w_out), _lib.ptr(b_out), *[_lib.ptr(t) for t in planes],
+                                    Cout, Cin, k, k, _lib.stream_of(w_out)) == _lib.D2T_EINVAL
