@@ -118,6 +118,8 @@ SIGNATURES = {
     "d2t_decode_graph_count": (_I, [_P]),
     "d2t_decode_supports_ragged": (_I, [_P]),
     "d2t_decode_attn_greedy_submit": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_L)]),
+    "d2t_decode_attn_greedy_submit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P, _P, C.POINTER(_L)]),
+    "d2t_decode_attn_supports_ragged_greedy": (_I, [_P]),
     "d2t_decode_steps": (_I, [_P, _L, C.POINTER(_I), _I, C.POINTER(_I)]),
     "d2t_decode_last_ticket": (_L, [_P]),
     "d2t_decode_query": (_I, [_P, _L]),
@@ -218,6 +220,7 @@ SIGNATURES = {
     "d2t_op_bilstm_bwd": (_I, [_P] * 6 + [_I] * 3 + [_P]),
     "d2t_op_attn_decode": (_I, [C.POINTER(D2TOpAttnDecodeArgs), _P]),
     "d2t_op_attn_decode_ragged": (_I, [C.POINTER(D2TOpAttnDecodeArgs), _P, _P, _I, _P]),
+    "d2t_op_attn_decode_group": (_I, [C.POINTER(D2TOpAttnDecodeArgs), _P, _P, _P, _P, _I, _P, _P]),
     "d2t_op_attn_decode_finalize": (_I, [_P, _P] + [_I] * 4 + [_P] * 4),
     "d2t_op_attn_alpha_gather": (_I, [_P] * 4 + [_I] * 4 + [_P]),
     "d2t_op_attn_beam_advance": (_I, [C.POINTER(D2TOpAttnBeamRec), _I, _L, _P]),

@@ -192,27 +192,34 @@ class BeamSearchHandle:
 
 
 class DecodeGroup:
-    """The forwards of a pipelined TFM head that share ONE step loop (Model.decode_group > 1): their memories lie back to back
+    """The forwards of a pipelined head that share ONE step loop (TFM: Model.decode_group > 1; LSTM-attention heads:
+    Model.attn_decode_group > 1, always the mixed layout, no start tokens): their memories lie back to back
     in one packed [memory rows, d] buffer and their outputs are views of one tokens / logits pair.  Every group writes into
     fresh tensors (no ring to overrun): the views handed out stay valid for as long as the caller keeps them, and become
     readable once the group's ticket -- shared by its handles -- is complete.  Two layouts of the same object:
       uniform (row_budget 0)  every batch has the first one's (B, T), which are part of the key; room for `batches` of them;
                               launched through decode_greedy_async_into(rows_per_batch=B);
       mixed (row_budget > 0)  batches of any (B, T) -- Model.decode_group_mixed -- up to max(row_budget, first B) rows; the
-                              packed memory grows as needed; launched through decode_greedy_ragged_into with the layout."""
+                              packed memory grows as needed; launched through decode_greedy_ragged_into with the layout
+                              (attn: decode_attn_greedy_ragged_into; the handles are full-size ones)."""
 
     @staticmethod
-    def key_of(eng, memory, is_test, batches, mixed):
+    def steps_of(eng, attn=False):
+        """Steps of the head's loop: the second dimension of its tokens / logits."""
+        return (eng.cfg.batch_max_length if attn else eng.cfg.max_seq_len) + 1
+
+    @staticmethod
+    def key_of(eng, memory, is_test, batches, mixed, attn=False):
         """What the batches of one group have in common; a batch with another key launches what has been collected."""
         B, T, d = memory.shape
-        tail = (d, eng.cfg.max_seq_len + 1, eng.cfg.vocab, memory.device, bool(is_test))
+        tail = (d, DecodeGroup.steps_of(eng, attn), eng.cfg.vocab, memory.device, bool(is_test))
         return ("mixed",) + tail if mixed else (batches, B, T) + tail
 
-    def __init__(self, model, eng, memory, is_test, batches, row_budget=0):
+    def __init__(self, model, eng, memory, is_test, batches, row_budget=0, attn=False):
         B, T, d = memory.shape
-        S, V, dev = eng.cfg.max_seq_len + 1, eng.cfg.vocab, memory.device
-        self._model, self._eng, self.is_test = model, eng, bool(is_test)
-        self.key = self.key_of(eng, memory, is_test, batches, row_budget > 0)
+        S, V, dev = self.steps_of(eng, attn), eng.cfg.vocab, memory.device
+        self._model, self._eng, self.is_test, self.attn = model, eng, bool(is_test), bool(attn)
+        self.key = self.key_of(eng, memory, is_test, batches, row_budget > 0, attn)
         self.rows_per_batch = 0 if row_budget else B
         if row_budget:
             self.cap = max(row_budget, B)  # a single batch beyond the row budget is a group of its own
@@ -222,7 +229,7 @@ class DecodeGroup:
             self.cap, mem_rows = batches * B, batches * B * T
         self.layout, self.handles, self.rows, self.mem_rows = [], [], 0, 0  # [(B, T)] per batch; output / memory rows in use
         self.mem = torch.empty((mem_rows, d), dtype=torch.float32, device=dev)
-        self.start = torch.empty((self.cap,), dtype=torch.int64, device=dev)
+        self.start = None if attn else torch.empty((self.cap,), dtype=torch.int64, device=dev)
         self.tokens = torch.empty((self.cap, S), dtype=torch.int64, device=dev)
         self.logits = torch.empty((self.cap, S, V), dtype=torch.float32, device=dev)
 
@@ -233,7 +240,7 @@ class DecodeGroup:
     def full(self, batches):
         return len(self.layout) >= batches
 
-    def add(self, memory, start):
+    def add(self, memory, start=None):
         """Copy a batch in; returns (tokens view, logits view, handle) of its rows."""
         B, T, d = memory.shape
         r0, m0 = self.rows, self.mem_rows
@@ -242,9 +249,10 @@ class DecodeGroup:
             grown[:m0].copy_(self.mem[:m0])
             self.mem = grown
         self.mem[m0:m0 + B * T].copy_(memory.reshape(B * T, d))
-        self.start[r0:r0 + B].copy_(start.to(device=memory.device, dtype=torch.int64))
+        if self.start is not None:
+            self.start[r0:r0 + B].copy_(start.to(device=memory.device, dtype=torch.int64))
         views = self.tokens[r0:r0 + B], self.logits[r0:r0 + B]
-        handle = DecodeHandle(self._model, self._eng, None, len(self.layout), views)
+        handle = DecodeHandle(self._model, self._eng, None, len(self.layout), views, full_size=self.attn)
         self.handles.append(handle)
         self.layout.append((B, T))
         self.rows, self.mem_rows = r0 + B, m0 + B * T
@@ -253,7 +261,10 @@ class DecodeGroup:
     def launch(self, eng):
         """Submit the collected rows as one decode; its ticket goes to every handle."""
         r, m = self.rows, self.mem_rows
-        if self.rows_per_batch:
+        if self.attn:
+            ticket = eng.decode_attn_greedy_ragged_into(self.mem[:m], self.layout, self.tokens[:r], self.logits[:r],
+                                                        is_test=self.is_test)
+        elif self.rows_per_batch:
             ticket = eng.decode_greedy_async_into(self.mem[:m].view(r, self.layout[0][1], -1), self.start[:r], self.tokens[:r],
                                                   self.logits[:r], is_test=self.is_test, rows_per_batch=self.rows_per_batch)
         else:
@@ -303,7 +314,7 @@ class Model(nn.Module):
         # (LSTM-attention heads: each of the chains holds one forward's whole loop, key projection and state block)
         # pipelined mode, TFM head: decode the rows of this many consecutive forward() calls in ONE step loop.  Ignored by the
         # LSTM-attention heads, whose loop already is one launch with one block per row and whose early exit is decided over
-        # the forward's own batch.  The decode step is a
+        # the forward's own batch (their groups have a switch of their own, attn_decode_group below).  The decode step is a
         # chain of small latency-bound kernels whose duration barely depends on the row count, so two batches per loop halve
         # the launches (and the interference with the next encoders) per formula.  Rows are independent and every kernel is
         # dispatched by layer shape only, so each row's tokens / logits are bit-identical to an ungrouped decode.  Results
@@ -317,6 +328,16 @@ class Model(nn.Module):
         # group collected so far, as before.  Other decoders (d_model 512) keep that behaviour whatever the switch says.
         self.decode_group_mixed = False
         self.decode_group_rows = 384
+        # pipelined mode, LSTM-attention heads (opt-in): decode the rows of up to this many consecutive greedy forward() calls
+        # -- crops of any size -- in ONE launch of the step loop.  That loop has one 1024-thread block per row, so a bucket of
+        # 8 crops keeps 8 compute units busy for all of its steps; the rows of several batches fill the chip with the same
+        # blocks, each bit-identical to its own batch's decode, and each batch keeps its own is_test exit step (DESIGN.md
+        # section 5.4e).  A group is launched when it holds `attn_decode_group` batches (at most 64), when the next batch
+        # would exceed `attn_decode_group_rows` rows (one block per compute unit on a 256-CU part; at most 1024), when is_test
+        # changes, on synchronize() and on a handle's wait().  A forward with viz_attn on launches what has been collected
+        # and runs alone.  1: one launch per forward, as before.  Beam search and synchronous forwards are untouched.
+        self.attn_decode_group = 1
+        self.attn_decode_group_rows = 256
         self._group = None  # the DecodeGroup that is still collecting forwards
         # Arithmetic of the backbone / large GEMMs:
         #   'bf16x3'  (default) split-bf16: 3 bf16 MFMAs per product, fp32 accumulate; max |dlogit| ~5e-5 against the 1e-3 bar
@@ -436,16 +457,22 @@ class Model(nn.Module):
             out += self.beam_search_batch(x, beam, return_attn)
         return out
 
-    def _collect_decode(self, eng, memory, start, is_test=False):
+    def _collect_decode(self, eng, memory, start, is_test=False, attn=False):
         """pipelined + decode_group > 1: collect the encoder memories of consecutive calls, launch one decode per group --
         when it holds decode_group batches, or when the next batch does not fit it (another key; decode_group_mixed: more
-        rows than decode_group_rows)."""
-        G = int(self.decode_group)
-        mixed = bool(self.decode_group_mixed and eng.supports_ragged_groups())
-        if self._group is not None and not self._group.fits(DecodeGroup.key_of(eng, memory, is_test, G, mixed), memory.shape[0]):
+        rows than decode_group_rows).  attn: the LSTM-attention heads' groups (attn_decode_group / attn_decode_group_rows),
+        always mixed, within the engine's 64 batches and 1024 rows per launch."""
+        if attn:
+            G, mixed = min(64, int(self.attn_decode_group)), True
+            budget = min(1024, max(1, int(self.attn_decode_group_rows)))
+        else:
+            G = int(self.decode_group)
+            mixed = bool(self.decode_group_mixed and eng.supports_ragged_groups())
+            budget = max(1, int(self.decode_group_rows)) if mixed else 0
+        if self._group is not None and not self._group.fits(DecodeGroup.key_of(eng, memory, is_test, G, mixed, attn), memory.shape[0]):
             self.launch_decode_group()
         if self._group is None:
-            self._group = DecodeGroup(self, eng, memory, is_test, G, max(1, int(self.decode_group_rows)) if mixed else 0)
+            self._group = DecodeGroup(self, eng, memory, is_test, G, budget, attn)
         out = self._group.add(memory, start)
         if self._group.full(G):
             self.launch_decode_group()
@@ -603,6 +630,16 @@ class Model(nn.Module):
                 prediction, logits, alphas = eng.decode_attn_beam_batch(contextual_feature.contiguous(), beam_size,
                                                                         return_alpha=True)[0]
                 return prediction, logits, alphas, {}
+            if self.pipelined and int(self.attn_decode_group) > 1:
+                # several forwards, one launch (attn_decode_group): the rows join a DecodeGroup; a forward with viz_attn on,
+                # with more rows than one launch takes, or with a memory length the engine refuses (the refusal is then this
+                # forward's alone, not its group's) sends what has been collected first and runs alone below
+                memory = contextual_feature.contiguous()
+                if (not viz and memory.shape[0] <= 1024 and 1 <= eng.attn_keys(memory.shape[1]) <= 4096
+                        and eng.supports_ragged_attn_greedy()):
+                    prediction, logits, handle = self._collect_decode(eng, memory, None, is_test, attn=True)
+                    return prediction, logits, None, {"decode": handle}
+                self.launch_decode_group()
             if self.pipelined:
                 # the forward returns while the loop runs on one of the engine's decode streams; tensors are full size as in
                 # the synchronous call and complete (zeros after an is_test exit included) once the handle is

@@ -192,7 +192,8 @@ struct d2t_ctx {
     float* skv = nullptr; size_t skv_cap = 0;  // self-attention cache
     float* dws = nullptr; size_t dws_cap = 0;  // step workspace (LSTM-attention heads: the key projection)
     int* dstate = nullptr;   // TFM: [0]=step [1]=end_count [2]=steps_done [3..]=ended[B]
-                             // LSTM-attention heads: [0..1]=exit word (AttnDecP::exit_state) [2]=steps [3]=pad [4..]=end_step[B]
+                             // LSTM-attention heads: [0..1]=exit word (AttnDecP::exit_state) [2]=steps [3]=pad [4..]=end_step[B];
+                             // a greedy decode group: exit words | steps | the four tables | end_step (engine_attn.hip)
     size_t dstate_cap = 0;
     // decodes write logits | tokens here (fixed addresses, so one captured graph per chain serves every caller buffer) and
     // copy them out afterwards
@@ -203,6 +204,12 @@ struct d2t_ctx {
     float* abeam_ws = nullptr; size_t abeam_ws_cap = 0;
     float* abeam_mem = nullptr; size_t abeam_mem_cap = 0;
     float* abeam_hist = nullptr; size_t abeam_hist_cap = 0;
+    // greedy decode groups of the LSTM-attention heads (engine_attn.hip attn_greedy_group_impl): the pinned staging of the
+    // group's tables [batch_rows 64 | row0 | len | row_batch, 1024 rows at most], two slots that take turns; a slot is
+    // rewritten only once its last upload has run (agrp_ev)
+    int* agrp_host[2] = {};
+    hipEvent_t agrp_ev[2] = {};
+    unsigned agrp_seq = 0;
   } chains[MAXC];
   // its per-sample tables [row0 | T] go up from a small ring of pinned buffers, on the search's own stream; a slot is
   // rewritten only once its copy has run (abeam_tab_ev), which waits only when ABEAM_TABS searches are in flight

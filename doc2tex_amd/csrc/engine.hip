@@ -555,6 +555,10 @@ void d2t_destroy(d2t_ctx* c) {
     if (o.abeam_ws) hipFree(o.abeam_ws);
     if (o.abeam_mem) hipFree(o.abeam_mem);
     if (o.abeam_hist) hipFree(o.abeam_hist);
+    for (int i = 0; i < 2; ++i) {
+      if (o.agrp_host[i]) hipHostFree(o.agrp_host[i]);
+      if (o.agrp_ev[i]) hipEventDestroy(o.agrp_ev[i]);
+    }
   }
   // the streams go back to the process-wide pool, last acquired first (the next context takes them in the same roles)
   for (int i = d2t_ctx::MAXC - 1; i >= 0; --i)

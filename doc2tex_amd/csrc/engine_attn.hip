@@ -86,6 +86,81 @@ int attn_greedy_impl(d2t_ctx* c, const float* memory, int B, int T, int is_test,
   return D2T_OK;
 }
 
+// ---- greedy decode groups: several encoder batches of different sizes in one launch ----
+constexpr int ATTN_GRP_MAXROWS = 1024;  // rows of one group (one 1024-thread block each: four rounds of a 256-CU part)
+// The chain's state block as a group lays it out (ints): exit words u64 [64] | steps [64] | batch_rows [64] | row0 [B] | len [B]
+// | row_batch [B] | end_step [B].  The pinned staging holds the part from batch_rows up to end_step, so the four tables go
+// up in one copy.  Every decode of a chain sets its state block up on the chain's in-order stream before it reads it, so the
+// uniform layout ([0..1] exit word, [2] steps, [4..] end_step) and this one can take turns.
+constexpr int ATTN_GRP_STEPS = 2 * GRP_MAXB, ATTN_GRP_TABS = 3 * GRP_MAXB, ATTN_GRP_ROW0 = 4 * GRP_MAXB;
+
+// d2t_decode_attn_greedy_submit for the rows of nb batches, batch k with rows[k] rows over a memory of Ts[k] tokens, packed in
+// `memory` ([mem_rows][H], batch after batch): the next chain in turn, its stream behind the caller's; the tables uploaded
+// from one of the chain's two pinned staging slots (rewritten only once its last upload has run); ONE key projection over all packed rows
+// (linear_any computes a row from that row alone, so each batch's projection is its uniform call's bit for bit), the state
+// block set up, one loop launch over all B rows (the group builds of attn_decode_kernel), one finalize launch, one ticket
+// with a step count per batch.  The caller has checked everything: nothing is refused here.
+int attn_greedy_group_impl(d2t_ctx* c, const float* memory, int nb, const int32_t* rows, const int32_t* Ts, int B, size_t mem_rows,
+                           int Tmax, int is_test, int64_t* tokens, float* probs, hipStream_t user) {
+  const d2t_config& g = c->cfg;
+  const int Hh = g.attn_hidden, S = g.batch_max_length + 1, V = g.vocab;
+  const int chain = (int)(c->decode_seq++ % (unsigned)c->n_chains);
+  d2t_ctx::Chain& ch = c->chains[chain];
+  hipStream_t s = ch.stream;
+  int rc;
+  if ((rc = ensure(c, &ch.dws, &ch.dws_cap, (mem_rows * Hh + 16) * 4))) return rc;
+  if ((rc = ensure(c, &ch.dstate, &ch.dstate_cap, ((size_t)ATTN_GRP_ROW0 + 4 * (size_t)B + 4) * 4))) return rc;
+  // the chain's two staging slots take turns: a slot is rewritten only once its last upload has run, and that upload stands
+  // in front of the chain's loop before last, so the host waits here only when three groups of one chain are backed up
+  const int slot = (int)(ch.agrp_seq++ & 1u);
+  if (!ch.agrp_host[slot]) {
+    int* host = nullptr;
+    hipEvent_t ev = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void**>(&host), ((size_t)GRP_MAXB + 3 * ATTN_GRP_MAXROWS) * 4, hipHostMallocDefault) != hipSuccess)
+      return fail(c, D2T_ENOMEM, "hipHostMalloc failed");
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {  // (a slot exists with its event or not at all)
+      hipHostFree(host);
+      return fail(c, D2T_EHIP, "hipEventCreateWithFlags failed");
+    }
+    ch.agrp_host[slot] = host;
+    ch.agrp_ev[slot] = ev;
+  } else {
+    HIPCHK(c, hipEventSynchronize(ch.agrp_ev[slot]));
+  }
+  int* h = ch.agrp_host[slot];
+  int *h_rows = h, *h_row0 = h + GRP_MAXB, *h_len = h_row0 + B, *h_rb = h_len + B;
+  for (int k = 0, b = 0, base = 0; k < nb; ++k) {
+    h_rows[k] = rows[k];
+    for (int i = 0; i < rows[k]; ++i, ++b) { h_row0[b] = base + i * Ts[k]; h_len[b] = Ts[k]; h_rb[b] = k; }
+    base += rows[k] * Ts[k];
+  }
+  for (int k = nb; k < GRP_MAXB; ++k) h_rows[k] = 0;
+  float* kp = ch.dws;
+  unsigned long long* exit_state = reinterpret_cast<unsigned long long*>(ch.dstate);
+  int* steps_dev = ch.dstate + ATTN_GRP_STEPS;
+  int* tab = ch.dstate + ATTN_GRP_TABS;
+  int* end_step = ch.dstate + ATTN_GRP_ROW0 + 3 * (size_t)B;
+  // the tables go up first: the upload needs nothing of the caller's stream, so it does not wait for the caller's encoder
+  HIPCHK(c, hipMemcpyAsync(tab, h, ((size_t)GRP_MAXB + 3 * (size_t)B) * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(ch.agrp_ev[slot], s));
+  HIPCHK(c, hipEventRecord(c->ev_in, user));  // the rest of the chain's work starts behind the caller's (the memory)
+  HIPCHK(c, hipStreamWaitEvent(s, c->ev_in, 0));
+  HIPCHK(c, linear_any(nullptr, s, memory, c->attn.key, nullptr, kp, (int)mem_rows, ACT_NONE));
+  HIPCHK(c, hipMemsetAsync(ch.dstate, 0, (size_t)ATTN_GRP_TABS * 4, s));  // the exit words and the steps
+  HIPCHK(c, hipMemsetAsync(end_step, 0xFF, (size_t)B * 4, s));            // -1 = never emitted [s]
+  AttnDecP p = attn_dec_params(c, memory, Tmax, kp);
+  p.probs = probs; p.tokens = tokens; p.end_step = end_step;
+  p.B = B; p.S = S;
+  p.exit_state = is_test ? exit_state : nullptr;
+  p.grp_row0 = tab + GRP_MAXB; p.grp_len = p.grp_row0 + B; p.grp_row_batch = p.grp_len + B; p.grp_batch_rows = tab;
+  HIPCHK(c, launch_attn_decode(p, s));
+  if (is_test)
+    HIPCHK(c, launch_attn_decode_finalize_group(exit_state, steps_dev, p.grp_row_batch, p.grp_batch_rows, nb, B, S, V, tokens, probs, s));
+  HIPCHK(c, hipEventRecord(c->ev_done[chain], s));
+  c->ev_done_valid[chain] = true;
+  return issue_ticket(c, s, is_test ? nb : -S, steps_dev);
+}
+
 // ---- beam search: what the two loops share ----
 constexpr int ATTN_BEAM_MAX_N = 1024;  // samples of one ragged search (as the TFM head's ragged search)
 // What every beam search of the LSTM-attention heads refuses, behind the entry's own argument check.
@@ -434,6 +509,43 @@ int d2t_decode_attn_greedy_submit(d2t_ctx* c, const float* memory, int32_t B, in
   if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
   if (int rc = check_dev_ptr(c, probs, "probs")) return rc;
   const int rc = attn_greedy_impl(c, memory, B, T, is_test, tokens, probs, alpha, nullptr, (hipStream_t)stream, true);
+  if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
+  return rc;
+}
+
+// 1: d2t_decode_attn_greedy_submit_ragged serves this context (any finalized LSTM-attention head); 0: it refuses with D2T_ESTATE
+int32_t d2t_decode_attn_supports_ragged_greedy(const d2t_ctx* c) {
+  return c && c->finalized && c->cfg.decoder == D2T_DEC_ATTN && c->cfg.vocab <= D2T_ATTN_MAX_CLASSES ? 1 : 0;
+}
+
+int d2t_decode_attn_greedy_submit_ragged(d2t_ctx* c, const float* memory, int32_t n_batches, const int32_t* batch_rows,
+                                         const int32_t* batch_T, int32_t is_test, int64_t* tokens, float* probs, d2t_stream stream,
+                                         int64_t* ticket_out) {
+  DevGuard dg_(c);
+  // everything is checked before anything is enqueued; the context stays usable after a refusal
+  if (!c || !memory || !batch_rows || !batch_T || !tokens || !probs) return fail(c, D2T_EINVAL, "bad argument");
+  if (!c->finalized) return fail(c, D2T_ESTATE, "weights not finalized");
+  const d2t_config& g = c->cfg;
+  if (g.decoder != D2T_DEC_ATTN) return fail(c, D2T_ESTATE, "context was not created with the Attn decoder");
+  if (g.vocab > D2T_ATTN_MAX_CLASSES) return fail(c, D2T_EINVAL, "Attn decoder supports num_class <= %d, got %d", D2T_ATTN_MAX_CLASSES, g.vocab);
+  if (n_batches < 1 || n_batches > GRP_MAXB) return fail(c, D2T_EINVAL, "a decode group holds 1 to %d batches, got %d", GRP_MAXB, n_batches);
+  const int key_off = g.attn_keys == D2T_ATTN_KEYS_NOCLS_INIT_CLS ? 1 : 0;
+  long long B = 0, mem_rows = 0;
+  int Tmax = 0;
+  for (int k = 0; k < n_batches; ++k) {
+    if (batch_rows[k] < 1) return fail(c, D2T_EINVAL, "batch %d of the group has %d rows", k, batch_rows[k]);
+    if (batch_T[k] - key_off < 1 || batch_T[k] - key_off > memory_cap(c))
+      return fail(c, D2T_EINVAL, "batch %d has memory length %d, supported are %d to %d", k, batch_T[k], 1 + key_off, memory_cap(c) + key_off);
+    B += batch_rows[k];
+    if (B > ATTN_GRP_MAXROWS) return fail(c, D2T_EINVAL, "a decode group of the Attn heads holds at most %d rows", ATTN_GRP_MAXROWS);
+    mem_rows += (long long)batch_rows[k] * batch_T[k];
+    Tmax = std::max(Tmax, (int)batch_T[k]);
+  }
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, tokens, "tokens")) return rc;
+  if (int rc = check_dev_ptr(c, probs, "probs")) return rc;
+  const int rc = attn_greedy_group_impl(c, memory, n_batches, batch_rows, batch_T, (int)B, (size_t)mem_rows, Tmax, is_test, tokens, probs,
+                                        (hipStream_t)stream);
   if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
   return rc;
 }

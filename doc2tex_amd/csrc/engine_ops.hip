@@ -711,8 +711,10 @@ int tokens_in_range(hipStream_t s, const int64_t* dev, size_t n, int V) {
   for (int64_t v : h) if (v < 0 || v >= V) return D2T_EINVAL;
   return D2T_OK;
 }
+// the device tables of a greedy decode group (AttnDecP::grp_*) and where its per-batch step counts go
+struct OpAttnGroup { const int32_t *row0, *len, *row_batch, *batch_rows; int n_batches; int32_t* steps_dev; };
 int op_attn_decode(const d2t_op_attn_decode_args* a, bool ragged, const int32_t* smp_row0, const int32_t* smp_T, int st_ld,
-                   d2t_stream stream);
+                   d2t_stream stream, const OpAttnGroup* grp = nullptr);
 }  // namespace
 
 int d2t_op_bilstm(const float* g, const float* whh_t, float* out, float* sv_gates, float* sv_c, int32_t B, int32_t T,
@@ -738,11 +740,21 @@ int d2t_op_attn_decode_ragged(const d2t_op_attn_decode_args* a, const int32_t* s
   return op_attn_decode(a, true, smp_row0, smp_T, st_ld, stream);
 }
 
+int d2t_op_attn_decode_group(const d2t_op_attn_decode_args* a, const int32_t* row0, const int32_t* len, const int32_t* row_batch,
+                             const int32_t* batch_rows, int32_t n_batches, int32_t* steps_dev, d2t_stream stream) {
+  const OpAttnGroup grp{row0, len, row_batch, batch_rows, n_batches, steps_dev};
+  return op_attn_decode(a, false, nullptr, nullptr, 0, stream, &grp);
+}
+
 namespace {
 // d2t_op_attn_decode, and with `ragged` its ragged step: mem / kp packed, the per-sample device tables smp_row0 / smp_T
 // [a->samples] read back and checked against a->T (the largest length), the packed row total (the sum of the lengths) and st_ld
+// grp: the group build of the loop -- mem / kp packed, the per-row and per-batch device tables read back and checked: every
+// length in range and a->T the largest, every row's slice inside the packed rows (their total: the sum of the rows' lengths),
+// the rows in batch order and batch_rows their counts; a->exit_state is then one word per batch, and the per-batch finalize
+// kernel follows the loop
 int op_attn_decode(const d2t_op_attn_decode_args* a, bool ragged, const int32_t* smp_row0, const int32_t* smp_T, int st_ld,
-                   d2t_stream stream) {
+                   d2t_stream stream, const OpAttnGroup* grp) {
   if (!a || !a->mem || !a->kp || !a->wq_t || !a->bq || !a->wloc || !a->bloc || !a->wscore || !a->wx_t || !a->bx || !a->wg_t ||
       !a->bg || !a->probs || !a->tokens || !a->end_step)
     return D2T_EINVAL;
@@ -755,9 +767,37 @@ int op_attn_decode(const d2t_op_attn_decode_args* a, bool ragged, const int32_t*
   if ((a->sv_hprev == nullptr) != (a->sv_cprev == nullptr)) return D2T_EINVAL;
   if ((a->sv_gates == nullptr) != (a->sv_hafter == nullptr) || (a->sv_gates == nullptr) != (a->sv_cafter == nullptr)) return D2T_EINVAL;
   if ((a->use_teacher || a->sv_tok) && !a->teacher) return D2T_EINVAL;
-  if (a->exit_state && (!a->steps_dev || a->step_mode || a->teacher)) return D2T_EINVAL;
-  if (!a->exit_state && a->steps_dev) return D2T_EINVAL;
+  if (a->exit_state && ((!grp && !a->steps_dev) || a->step_mode || a->teacher)) return D2T_EINVAL;
+  if ((!a->exit_state || grp) && a->steps_dev) return D2T_EINVAL;
   hipStream_t s = (hipStream_t)stream;
+  if (grp) {
+    if (!grp->row0 || !grp->len || !grp->row_batch || !grp->batch_rows || !grp->steps_dev || grp->n_batches < 1 ||
+        grp->n_batches > 64 || grp->n_batches > a->B || a->B > 1024)
+      return D2T_EINVAL;
+    if (a->step_mode || a->teacher || a->use_teacher || a->out_dropmask || a->sv_tok || a->sv_hprev || a->sv_gates || a->sv_alpha ||
+        a->sv_hq || a->sv_x)
+      return D2T_EINVAL;
+    std::vector<int> r0, len, rb, br;
+    if (!fetch_ints(s, grp->row0, a->B, &r0) || !fetch_ints(s, grp->len, a->B, &len) || !fetch_ints(s, grp->row_batch, a->B, &rb) ||
+        !fetch_ints(s, grp->batch_rows, grp->n_batches, &br))
+      return D2T_EHIP;
+    long long total = 0;
+    int longest = 0;
+    for (int v : len) {
+      if (v - a->key_off < 1 || v - a->key_off > 4096) return D2T_EINVAL;
+      total += v;
+      longest = std::max(longest, v);
+    }
+    if (longest != a->T) return D2T_EINVAL;
+    std::vector<int> count(grp->n_batches, 0);
+    for (int b = 0; b < a->B; ++b) {
+      if (r0[b] < 0 || (long long)r0[b] + len[b] > total) return D2T_EINVAL;
+      if (rb[b] < 0 || rb[b] >= grp->n_batches || rb[b] != (b ? rb[b - 1] + (rb[b] != rb[b - 1]) : 0)) return D2T_EINVAL;
+      ++count[rb[b]];
+    }
+    for (int k = 0; k < grp->n_batches; ++k)
+      if (br[k] != count[k] || count[k] < 1) return D2T_EINVAL;
+  }
   if (a->step_mode) {
     if (a->S != 1 || a->teacher || a->samples < 1 || !a->st_h_out || !a->st_c_out || !a->st_mem_out) return D2T_EINVAL;
     if (!a->first && (!a->st_h_in || !a->st_c_in || !a->st_mem_in || !a->tok_in)) return D2T_EINVAL;
@@ -804,9 +844,13 @@ int op_attn_decode(const d2t_op_attn_decode_args* a, bool ragged, const int32_t*
   p.sv_gates = a->sv_gates; p.sv_alpha = a->sv_alpha; p.sv_hq = a->sv_hq; p.sv_x = a->sv_x;
   p.exit_state = reinterpret_cast<unsigned long long*>(a->exit_state);
   if (ragged) { p.smp_row0 = smp_row0; p.smp_T = smp_T; p.st_ld = st_ld; }
+  if (grp) { p.grp_row0 = grp->row0; p.grp_len = grp->len; p.grp_row_batch = grp->row_batch; p.grp_batch_rows = grp->batch_rows; }
   hipError_t e = hipMemsetAsync(a->end_step, 0xFF, (size_t)a->B * 4, s);  // -1 = never emitted the end token
-  if (e == hipSuccess && a->exit_state) e = hipMemsetAsync(a->exit_state, 0, 8, s);
+  if (e == hipSuccess && a->exit_state) e = hipMemsetAsync(a->exit_state, 0, grp ? (size_t)grp->n_batches * 8 : 8, s);
   if (e == hipSuccess) e = launch_attn_decode(p, s);
+  if (e == hipSuccess && grp)
+    return op_status(launch_attn_decode_finalize_group(p.exit_state, grp->steps_dev, grp->row_batch, grp->batch_rows, grp->n_batches,
+                                                       a->B, a->S, a->V, a->tokens, a->probs, s));
   if (e == hipSuccess && a->exit_state)
     e = launch_attn_decode_finalize(p.exit_state, a->steps_dev, a->B, a->S, a->V, a->T - a->key_off, a->tokens, a->probs,
                                     a->sv_alpha, s);

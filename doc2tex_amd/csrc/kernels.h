@@ -205,12 +205,29 @@ struct AttnDecP {
   // (AttnBeamDev::ctrl).  The launch covers every row slot, and a block returns before its first barrier when
   // b >= guard[1] (live rows) or the stop step is reached (guard[2] != 0 and guard[0] >= guard[2]) -- uniform per block.
   const int* guard;
+  // Greedy decode group (loop mode: neither step mode nor teacher-forced; all four set, or none: the group builds of the
+  // kernel).  The B rows are the rows of several encoder batches of DIFFERENT row counts and memory lengths, in batch order;
+  // mem and kp are ONE packed [sum rows_k * T_k][256] buffer each.  Row b owns the grp_len[b] rows from row grp_row0[b] on,
+  // attends over Tk_b = grp_len[b] - key_off keys (held to AD_MAXT in the kernel) and takes its init_mode 1 mean over its
+  // own grp_len[b] rows.  exit_state (optional) is then ONE WORD PER BATCH, [batches]: row b publishes its end into word
+  // grp_row_batch[b] and stops by that word and grp_batch_rows[grp_row_batch[b]] -- a batch's rows stop at that batch's stop
+  // step whatever the other batches of the launch do.  No alignment history (sv_alpha null).  T = the largest grp_len[b].
+  const int* grp_row0;        // device [B]
+  const int* grp_len;         // device [B]
+  const int* grp_row_batch;   // device [B]
+  const int* grp_batch_rows;  // device [batches]
 };
 // After launch_attn_decode with an exit_state, on the same stream: steps = largest end step + 1 if all B rows ended, else
 // S; written to *steps_dev, and tokens [B][S], probs [B][S][V], alpha [B][S][Tk] (optional) zeroed for the steps
 // [steps, S) of every row -- whatever the buffers held and however far single blocks ran past the exit.
 hipError_t launch_attn_decode_finalize(const unsigned long long* exit_state, int* steps_dev, int B, int S, int V, int Tk,
                                        int64_t* tokens, float* probs, float* alpha, hipStream_t s);
+// The same behind a group launch (AttnDecP::grp_*), per batch: steps_dev[k] by the rule above from exit_state[k] and
+// batch_rows[k], and tokens / probs of batch k's rows zeroed on [steps_k, S).  row_batch [B], batch_rows [batches]: the
+// launch's device tables.  exit_state null (a group without is_test): every steps_dev[k] = S, nothing zeroed.
+hipError_t launch_attn_decode_finalize_group(const unsigned long long* exit_state, int* steps_dev, const int* row_batch,
+                                             const int* batch_rows, int batches, int B, int S, int V, int64_t* tokens,
+                                             float* probs, hipStream_t s);
 // Backward of the teacher-forced loop above (one block per batch row, steps in reverse).  Gradients that are sums
 // over (row, step) of outer products are left as per-(row, step) factors for GEMMs: dgates, dhq, demb, dh0 / dc0.
 struct AttnTrainBwdP {

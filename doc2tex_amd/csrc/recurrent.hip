@@ -114,18 +114,21 @@ __device__ __forceinline__ float attn_logit(const AttnDecP p, const float* h_s, 
 
 // The electing thread (thread 0) ends the step with the winning class: the next input token, the output token, the row's
 // end step, and (EXIT) the row's end published to the other blocks and this block's decision to stop.
-template <bool EXIT>
+// GROUP: the row's batch has its own exit word `gword` and counts `grows` rows (AttnDecP::grp_*).
+template <bool EXIT, bool GROUP = false>
 __device__ __forceinline__ void attn_end_step(const AttnDecP p, int b, int step, int bi, int& ended,
-                                              unsigned long long seen, int* tok_s, int* stop_s) {
+                                              unsigned long long seen, int* tok_s, int* stop_s,
+                                              [[maybe_unused]] unsigned long long* gword = nullptr,
+                                              [[maybe_unused]] int grows = 0) {
   if (bi >= p.V) bi = 0;
   *tok_s = bi;
   p.tokens[(size_t)b * p.S + step] = bi;
   if (bi == p.end_token && !ended) {
     ended = 1;
     p.end_step[b] = step;
-    if constexpr (EXIT) attn_exit_publish(p.exit_state, step);
+    if constexpr (EXIT) attn_exit_publish(GROUP ? gword : p.exit_state, step);
   }
-  if constexpr (EXIT) *stop_s = attn_exit_reached(seen, p.B, step);
+  if constexpr (EXIT) *stop_s = attn_exit_reached(seen, GROUP ? grows : p.B, step);
 }
 
 // RAGGED (step mode only): the row's sample has its own memory length and its own place in ONE packed memory
@@ -133,7 +136,11 @@ __device__ __forceinline__ void attn_end_step(const AttnDecP p, int b, int step,
 // so every barrier is still reached by all of its threads; no shared array is added.
 // GUARD (RAGGED builds of the device-side beam loop, launched for every row slot): a block whose row is not live, or whose
 // search has reached its stop step, returns here -- before any barrier, on words every thread of the block reads alike.
-template <bool WIDE, bool EXIT, bool RAGGED = false, bool GUARD = false>
+// GROUP (loop mode only: a greedy decode group, AttnDecP::grp_*): the row's memory length and first packed row come from
+// the per-row tables, and (EXIT) the exit word and row count are those of the row's batch.  The table entries are read
+// into scalar registers once, in front of the loop: everything derived from them is uniform in the block, as the uniform
+// builds' kernel arguments are.
+template <bool WIDE, bool EXIT, bool RAGGED = false, bool GUARD = false, bool GROUP = false>
 __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   constexpr int H = 256;
   if constexpr (GUARD)
@@ -152,10 +159,18 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
   const int bm = p.step_mode ? (p.row_sample ? p.row_sample[b] : 0) : b;
   // T: the sample's memory length, mrow: its first memory row, ld: the stride of the state and history rows.  RAGGED: Tk is
   // held to st_ld <= AD_MAXT here as well, whatever the tables say (the hosts refuse such tables before the launch)
-  const int T = RAGGED ? p.smp_T[bm] : p.T;
-  const int Tk = RAGGED ? min(T - p.key_off, p.st_ld) : T - p.key_off;
+  // GROUP: Tk is held to AD_MAXT, likewise
+  const int T = GROUP ? __builtin_amdgcn_readfirstlane(p.grp_len[b]) : RAGGED ? p.smp_T[bm] : p.T;
+  const int Tk = GROUP ? min(T - p.key_off, AD_MAXT) : RAGGED ? min(T - p.key_off, p.st_ld) : T - p.key_off;
   const int ld = RAGGED ? p.st_ld : Tk;
-  const size_t mrow = RAGGED ? (size_t)p.smp_row0[bm] : (size_t)bm * T;
+  const size_t mrow = GROUP ? (size_t)__builtin_amdgcn_readfirstlane(p.grp_row0[b]) : RAGGED ? (size_t)p.smp_row0[bm] : (size_t)bm * T;
+  [[maybe_unused]] unsigned long long* gword = nullptr;  // GROUP, EXIT: the exit word of the row's batch and that batch's rows
+  [[maybe_unused]] int grows = 0;
+  if constexpr (GROUP && EXIT) {
+    const int k = __builtin_amdgcn_readfirstlane(p.grp_row_batch[b]);
+    gword = p.exit_state + k;
+    grows = __builtin_amdgcn_readfirstlane(p.grp_batch_rows[k]);
+  }
   const float* keys = p.mem + (mrow + p.key_off) * p.D;
   const float* kp = p.kp + (mrow + p.key_off) * H;
   float* ctx_s = x_s;
@@ -207,7 +222,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
     // early exit: ONE lane looks at the word now (a load that bypasses the L1; nothing waits for it here) and the block
     // acts on it behind the step's last barrier
     if constexpr (EXIT)
-      if (tid == 0) seen = __hip_atomic_load(p.exit_state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tid == 0) seen = __hip_atomic_load(GROUP ? gword : p.exit_state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (p.teacher && tid == 0) {
       if (step == 0 || !p.use_teacher || p.use_teacher[step]) tok_s = (int)p.teacher[(size_t)b * p.S + step];
       if (p.sv_tok) p.sv_tok[(size_t)b * p.S + step] = tok_s;  // otherwise: the argmax of the previous step
@@ -288,8 +303,21 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
       float a = p.bx[tid];
       if (p.tokgate) a += p.tokgate[(size_t)tok_s * 4 * H + tid];  // W_ih . onehot(token) = one column of W_ih
       const float* w = p.wx_t + tid;
+      if constexpr (GROUP && WIDE && EXIT) {
+        // the same sums in the same order, eight weight loads issued in front of their eight FMAs: left to the loop below,
+        // the compiler waited for every load in this one build (s_waitcnt vmcnt(0) in front of each FMA);
+        // the other three group builds keep eight loads in flight as they are
+        for (int k = 0; k < 3 * H; k += 8) {
+          float wv[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) wv[u] = w[(size_t)(k + u) * 4 * H];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) a = fmaf(x_s[k + u], wv[u], a);
+        }
+      } else {
 #pragma unroll 8
-      for (int k = 0; k < 3 * H; ++k) a = fmaf(x_s[k], w[(size_t)k * 4 * H], a);
+        for (int k = 0; k < 3 * H; ++k) a = fmaf(x_s[k], w[(size_t)k * 4 * H], a);
+      }
       gate_s[tid] = a;
     }
     __syncthreads();
@@ -328,7 +356,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(const AttnDecP p) {
         wave_argmax_first(best, bi);
       }
     }
-    if (tid == 0) attn_end_step<EXIT>(p, b, step, bi, ended, seen, &tok_s, &stop_s);
+    if (tid == 0) attn_end_step<EXIT, GROUP>(p, b, step, bi, ended, seen, &tok_s, &stop_s, gword, grows);
     __syncthreads();
     if constexpr (EXIT)
       if (stop_s) break;
@@ -348,6 +376,16 @@ hipError_t launch_attn_decode(const AttnDecP& p, hipStream_t s) {
   if (ragged && (!p.step_mode || p.S != 1 || p.teacher || p.exit_state || !p.smp_row0 || !p.smp_T || p.st_ld < 1 || p.st_ld > AD_MAXT))
     return hipErrorInvalidValue;
   if (p.guard && !ragged) return hipErrorInvalidValue;
+  // the group builds: loop mode only, all four tables, no alignment history; one exit word per batch or none
+  const bool group = p.grp_row0 || p.grp_len || p.grp_row_batch || p.grp_batch_rows;
+  if (group) {
+    if (ragged || p.step_mode || p.teacher || p.sv_alpha || !p.grp_row0 || !p.grp_len || !p.grp_row_batch || !p.grp_batch_rows)
+      return hipErrorInvalidValue;
+    auto k = p.V <= 1024 ? (p.exit_state ? attn_decode_kernel<false, true, false, false, true> : attn_decode_kernel<false, false, false, false, true>)
+                         : (p.exit_state ? attn_decode_kernel<true, true, false, false, true> : attn_decode_kernel<true, false, false, false, true>);
+    hipLaunchKernelGGL(k, dim3(p.B), dim3(1024), 0, s, p);
+    return hipGetLastError();
+  }
   if (p.guard) {
     hipLaunchKernelGGL((p.V <= 1024 ? attn_decode_kernel<false, false, true, true> : attn_decode_kernel<true, false, true, true>),
                        dim3(p.B), dim3(1024), 0, s, p);
@@ -402,6 +440,44 @@ hipError_t launch_attn_decode_finalize(const unsigned long long* exit_state, int
   const unsigned gx = (unsigned)std::min<size_t>(64, (row_vec + 255) / 256);
   hipLaunchKernelGGL(attn_decode_finalize_kernel, dim3(gx, (unsigned)std::min(B, 256)), dim3(256), 0, s, exit_state,
                      steps_dev, B, S, V, Tk, tokens, probs, alpha);
+  return hipGetLastError();
+}
+
+// The finalize kernel behind a group launch: row b belongs to batch row_batch[b], whose word and row count give its steps.
+// Rows lie in batch order, so the first row of a batch is the one whose predecessor belongs to another batch: it stores
+// the batch's step count.  grid as above.
+__global__ __launch_bounds__(256) void attn_decode_finalize_group_kernel(const unsigned long long* exit_state, int* steps_dev,
+                                                                         const int* __restrict__ row_batch,
+                                                                         const int* __restrict__ batch_rows, int batches, int B,
+                                                                         int S, int V, int64_t* tokens, float* probs) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, n = (size_t)gridDim.x * blockDim.x;
+  if (!exit_state) {  // no early exit: every batch ran all S steps
+    if (blockIdx.y == 0)
+      for (size_t k = i; k < (size_t)batches; k += n) steps_dev[k] = S;
+    return;
+  }
+  for (size_t b = blockIdx.y; b < (size_t)B; b += gridDim.y) {
+    const int k = row_batch[b];
+    const unsigned long long w = __hip_atomic_load(exit_state + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned mx = (unsigned)w;
+    const int steps = ((unsigned)(w >> 32) == (unsigned)batch_rows[k] && mx + 1u < (unsigned)S) ? (int)mx + 1 : S;
+    if (i == 0 && (b == 0 || row_batch[b - 1] != k)) steps_dev[k] = steps;
+    if (steps >= S) continue;
+    const size_t r0 = b * S + steps, r1 = (b + 1) * S;  // (row, step) pairs to clear
+    zero_words(reinterpret_cast<uint32_t*>(tokens + r0), reinterpret_cast<uint32_t*>(tokens + r1), i, n);
+    zero_words(reinterpret_cast<uint32_t*>(probs + r0 * V), reinterpret_cast<uint32_t*>(probs + r1 * V), i, n);
+  }
+}
+
+hipError_t launch_attn_decode_finalize_group(const unsigned long long* exit_state, int* steps_dev, const int* row_batch,
+                                             const int* batch_rows, int batches, int B, int S, int V, int64_t* tokens,
+                                             float* probs, hipStream_t s) {
+  if (!steps_dev || !row_batch || !batch_rows || !tokens || !probs || batches < 1 || B < batches || S < 1 || V < 1)
+    return hipErrorInvalidValue;
+  const size_t row_vec = ((size_t)S * (size_t)V + 3) / 4;  // 16-byte stores of a whole row, at most
+  const unsigned gx = (unsigned)std::min<size_t>(64, (row_vec + 255) / 256);
+  hipLaunchKernelGGL(attn_decode_finalize_group_kernel, dim3(gx, (unsigned)std::min(B, 256)), dim3(256), 0, s, exit_state,
+                     steps_dev, row_batch, batch_rows, batches, B, S, V, tokens, probs);
   return hipGetLastError();
 }
 

@@ -570,6 +570,35 @@ class Engine:
         ticket = self._hold(int(t.value), memory, (memory, tokens, probs, alpha))
         return (tokens, probs, ticket) if alpha is None else (tokens, probs, alpha, ticket)
 
+    def decode_attn_greedy_ragged_into(self, packed, layout, tokens, probs, is_test=False):
+        """d2t_decode_attn_greedy_submit_ragged on caller-held buffers: packed [sum rows_i * T_i, 256] holds the batches'
+        memories back to back, layout = [(rows_i, T_i)], tokens [B, S], probs [B, S, V] with B = sum rows_i, rows in batch
+        order.  One launch decodes all rows; every row equals its own batch's decode_attn_greedy_async bit for bit.  Returns
+        the ticket; decode_steps(ticket) has one entry per batch with is_test (one entry, S, without)."""
+        self._on_device(packed, "memory")
+        n = len(layout)
+        tab = ragged_tables(layout) if n else {"rows": 0, "mem_rows": 0}
+        d, S, V, B = self.cfg.attn_hidden, self.cfg.batch_max_length + 1, self.cfg.vocab, tab["rows"]
+        if tuple(packed.shape) != (tab["mem_rows"], d) or not packed.is_contiguous() or packed.dtype != torch.float32:
+            raise ValueError(f"packed memory must be a contiguous float32 [{tab['mem_rows']}, {d}] tensor, got "
+                             f"{packed.dtype} {tuple(packed.shape)}")
+        for what, t, shape, dtype in (("tokens", tokens, (B, S), torch.int64), ("probs", probs, (B, S, V), torch.float32)):
+            self._on_device(t, what)
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+        rows = (C.c_int32 * max(n, 1))(*[int(r) for r, _ in layout])
+        Ts = (C.c_int32 * max(n, 1))(*[int(t) for _, t in layout])
+        t = C.c_int64(0)
+        self._check(self.lib.d2t_decode_attn_greedy_submit_ragged(self.ctx, _lib.ptr(packed), n, rows, Ts, int(bool(is_test)),
+                                                                  _lib.ptr(tokens), _lib.ptr(probs), _lib.stream_of(packed),
+                                                                  C.byref(t)), "decode_attn_greedy_submit_ragged")
+        return self._hold(int(t.value), packed, (packed, tokens, probs))
+
+    def supports_ragged_attn_greedy(self):
+        """Whether this context decodes greedy groups of the LSTM-attention heads (d2t_decode_attn_supports_ragged_greedy);
+        the context itself answers, once the weights are finalized."""
+        return bool(self.lib.d2t_decode_attn_supports_ragged_greedy(self.ctx))
+
     def decode_greedy_async(self, memory, start_tokens, is_test=False):
         """Pipelined greedy decode (max_seq_len+1 steps; with is_test the device stops early): returns (tokens, logits, ticket).  The tensors are fresh
         allocations written by the engine's decode stream; they are valid once `ticket` is complete (wait_ticket /

@@ -25,7 +25,7 @@
  *   d2t_train_forward / d2t_train_backward / d2t_train_grad (+ dropout, scheduled-sampling setters)
  *        <- Model.forward under module.train() and loss.backward(): forward_step / train_one_step
  *           engine/training.py:76-164 (tfm.py:103-118, seq2seq.py:224-331 with is_train)
- *   d2t_decode_greedy_async / d2t_decode_greedy_submit / d2t_decode_attn_greedy_submit / d2t_decode_wait,
+ *   d2t_decode_greedy_async / d2t_decode_greedy_submit / d2t_decode_attn_greedy_submit[_ragged] / d2t_decode_wait,
  *   d2t_set_reserved_blocks / d2t_set_decode_chains, d2t_decode_beam_batch[_ragged] / d2t_decode_attn_beam_batch
  *        -- serving extensions without a reference counterpart (cross-batch pipelining, batched beam search);
  *           their results equal the corresponding reference-shaped calls bit for bit
@@ -275,6 +275,29 @@ int32_t d2t_decode_graph_count(const d2t_ctx* ctx);
 int d2t_decode_attn_greedy_submit(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T, int32_t is_test,
                                   int64_t* tokens_dev, float* probs_dev, float* alpha_dev, d2t_stream stream,
                                   int64_t* ticket_out);
+/* d2t_decode_attn_greedy_submit for SEVERAL encoder batches of different row counts and memory lengths in ONE launch: the
+ * one-launch step loop has one block per row, so a bucket of 8 crops keeps 8 compute units busy for the whole loop; the rows
+ * of all collected batches fill the chip with the same blocks.  Rows never interact, so every row's tokens and probs are
+ * those of its own batch's d2t_decode_attn_greedy_submit call bit for bit.
+ *   memory_dev         [sum_i batch_rows[i] * batch_T[i]][256], batch after batch, each batch [rows][T][256];
+ *   batch_rows/batch_T HOST arrays [n_batches], read before the call returns;
+ *   tokens_dev         [B][S], probs_dev [B][S][V] with B = sum_i batch_rows[i], rows in batch order; no alignment maps.
+ * is_test != 0: the early exit is decided per BATCH inside the kernel (one exit word per batch): a batch's rows stop at that
+ * batch's stop step whatever the other batches of the launch do, the finalize kernel zeroes tokens / probs of batch k's rows
+ * behind ITS stop step, and d2t_decode_steps reports one entry per batch (one entry, batch_max_length + 1, without is_test).
+ * The next chain in turn, ordered behind `stream` by an event; one key projection over all packed rows, one loop launch, one
+ * finalize launch, one ticket.  The call does not wait for the decode; it may wait for an earlier table upload of the same
+ * chain (each chain has two small pinned staging slots that take turns, and a slot is rewritten only once its last upload
+ * has run: that upload stands in front of the chain's loop before last).  Refused before anything is enqueued (D2T_EINVAL unless stated): no batch or more
+ * than 64 batches, a batch without rows, more than 1024 rows in total, a memory length whose key count lies outside
+ * [1, 4096], a pointer of another device, a vocabulary over D2T_ATTN_MAX_CLASSES; a context without the Attn decoder
+ * (D2T_ESTATE).  d2t_decode_greedy_submit_ragged and d2t_decode_supports_ragged keep refusing / answering 0 for an Attn
+ * context: the two heads' groups are separate entries. */
+int d2t_decode_attn_greedy_submit_ragged(d2t_ctx* ctx, const float* memory_dev, int32_t n_batches, const int32_t* batch_rows,
+                                         const int32_t* batch_T, int32_t is_test, int64_t* tokens_dev, float* probs_dev,
+                                         d2t_stream stream, int64_t* ticket_out);
+/* 1 if d2t_decode_attn_greedy_submit_ragged serves this context (a finalized LSTM-attention head), 0 if it refuses. */
+int32_t d2t_decode_attn_supports_ragged_greedy(const d2t_ctx* ctx);
 /* Step counts of the batches of one asynchronous decode (blocks until it is complete). */
 int d2t_decode_steps(d2t_ctx* ctx, int64_t ticket, int32_t* steps_out, int32_t max_batches, int32_t* n_out);
 int64_t d2t_decode_last_ticket(const d2t_ctx* ctx);
@@ -734,6 +757,17 @@ int d2t_op_attn_decode(const d2t_op_attn_decode_args* a, d2t_stream stream);
  * outputs equal d2t_op_attn_decode's on its sample's memory alone bit for bit. */
 int d2t_op_attn_decode_ragged(const d2t_op_attn_decode_args* a, const int32_t* smp_row0, const int32_t* smp_T, int32_t st_ld,
                               d2t_stream stream);
+/* The group build of the loop (loop mode only: neither step mode nor teacher; AttnDecP::grp_*): the a->B <= 1024 rows are the
+ * rows of n_batches <= 64 batches in batch order, mem and kp ONE packed buffer each, and row b owns the len[b] rows from row
+ * row0[b] on.  row0 / len / row_batch: DEVICE arrays [B], batch_rows: DEVICE array [n_batches], read back and checked before
+ * the launch: 1 <= len[b] - key_off <= 4096, a->T the largest length, row0[b] >= 0, row0[b] + len[b] <= the sum of the rows'
+ * lengths, row_batch non-decreasing from 0 to n_batches - 1 in steps of one, batch_rows[k] the rows of batch k.  a->exit_state
+ * (optional) is ONE WORD PER BATCH [n_batches], zeroed by the entry; a->steps_dev must be NULL and no sv_* / mask / teacher
+ * field set.  The per-batch finalize kernel follows: steps_dev[k] (device [n_batches], required) = batch k's step count, and
+ * tokens / probs of its rows are zeroed behind it; without exit words every entry is S and nothing is zeroed.  A row's
+ * tokens, probs and end_step equal d2t_op_attn_decode's on its batch alone bit for bit. */
+int d2t_op_attn_decode_group(const d2t_op_attn_decode_args* a, const int32_t* row0, const int32_t* len, const int32_t* row_batch,
+                             const int32_t* batch_rows, int32_t n_batches, int32_t* steps_dev, d2t_stream stream);
 /* The finalize kernel alone on a caller-given exit word {rows ended : high 32 bits, largest end step : low 32 bits}:
  * *steps_dev = largest end step + 1 if all B rows ended and that is below S, else S; tokens [B][S], probs [B][S][V] and
  * alpha [B][S][Tk] (optional) zeroed for the steps [steps, S) of every row. */

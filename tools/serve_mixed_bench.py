@@ -14,9 +14,13 @@ set and consecutive forwards differ in row count and memory length.
                           (d2t_decode_beam_batch_ragged).
 
   --head attnv2   the stack every shipped configuration of the reference serves: C4's encoder and geometry under the Attnv2
-                  coverage-LSTM head with the parameters of config/test.yaml:38-51.  Needs --beam K (the greedy decode groups
-                  are the TFM head's); --mixed 0 then pays the host-side step loop's batch_max_length + 1 round trips once per
-                  size bucket, --mixed 1 once per page set (d2t_decode_attn_beam_batch_ragged).
+                  coverage-LSTM head with the parameters of config/test.yaml:38-51.
+                  --beam K: --mixed 0 pays the host-side step loop's batch_max_length + 1 round trips once per size bucket,
+                  --mixed 1 once per page set (d2t_decode_attn_beam_batch_ragged).
+                  --beam 0: greedy is_test forwards, pipelined on --chains chains.  --mixed 0: one launch of the one-block-
+                  per-row step loop per size bucket, as before Model.attn_decode_group existed; --mixed 1: the buckets'
+                  rows share a launch until the group holds --group batches or --group-rows rows (Model.attn_decode_group /
+                  attn_decode_group_rows, d2t_decode_attn_greedy_submit_ragged).
 
   --device-beam 1   (with --head attnv2 --beam K) Model.attn_beam_device: the search's bookkeeping stays on the device, one
                     captured graph per search instead of a host round trip per step;
@@ -65,10 +69,10 @@ def main():
     ap.add_argument("--end-bias", type=float, default=None, help="attnv2: bias of the generator's [s] logit")
     ap.add_argument("--max-length", type=int, default=None, help="attnv2: batch_max_length")
     args = ap.parse_args()
-    if args.head == "attnv2" and not args.beam:
-        ap.error("--head attnv2 times the beam search: give --beam K")
-    if (args.device_beam or args.submit or args.end_bias is not None or args.max_length) and args.head != "attnv2":
-        ap.error("--device-beam / --submit / --end-bias / --max-length belong to --head attnv2 --beam K")
+    if (args.device_beam or args.submit) and not (args.head == "attnv2" and args.beam):
+        ap.error("--device-beam / --submit belong to --head attnv2 --beam K")
+    if (args.end_bias is not None or args.max_length) and args.head != "attnv2":
+        ap.error("--end-bias / --max-length belong to --head attnv2")
     dev = torch.device("cuda", 0)
     cfg = synth.make_config("C4", device=str(dev), beam_size=1)  # (C4 asks for width 5; the searches here take --beam, forward() decodes greedily)
     if args.head == "attnv2":
@@ -85,6 +89,8 @@ def main():
     if args.mixed:
         model.decode_group_mixed, model.decode_group_rows = True, args.group_rows
     model.attn_beam_device = bool(args.device_beam)
+    if args.head == "attnv2" and not args.beam and args.mixed:
+        model.attn_decode_group, model.attn_decode_group_rows = args.group, args.group_rows
     opt = {"imgH": None, "imgW": None, "max_dimension": cfg["max_dimension"], "min_dimension": [32, 32], "mean": 0.5,
            "std": 0.5, "rgb": False, "pad": False, "device": str(dev)}
     pre = Preprocessor(opt, "demo")
@@ -187,7 +193,7 @@ def main():
             return
         for x in buckets.values():
             with torch.no_grad():
-                tokens, _, extra = model(x, go[:x.shape[0]], is_train=False, is_test=False)
+                tokens, _, extra = model(x, go[:x.shape[0]], is_train=False, is_test=attn)  # (the Attn heads serve with the exit)
             waiting.append((tokens, extra["decode"]))
         copy_out(False)
         consume(False)
@@ -210,7 +216,7 @@ def main():
     assert state["done"] == 3 * n * args.steps, (state["done"], 3 * n * args.steps)
     print(json.dumps({"metric": "formulas/s end to end on mixed-size pages (uint8 pages -> LaTeX strings)",
                       "value": round(state["done"] / el, 1), "unit": "formulas/s", "mixed": args.mixed, "steps": args.steps,
-                      "per_size": n, "group": args.group, "beam": args.beam, "head": args.head, "ms_per_page_set": round(el / args.steps * 1e3, 2),
+                      "per_size": n, "group": args.group, "group_rows": args.group_rows, "chains": args.chains, "beam": args.beam, "head": args.head, "ms_per_page_set": round(el / args.steps * 1e3, 2),
                       "postprocess_ms_per_page_set": round(state["t_post"] / args.steps * 1e3, 2),
                       "sizes": sorted(BUCKETS), "sample_latex_chars": len(state["sample"]),
                       "device_beam": args.device_beam, "submit": args.submit, "end_bias": args.end_bias, "max_length": L - 1,
