@@ -14,7 +14,7 @@ if os.environ.get("D2T_PROBE_LIB"):  # development tools only: a probe build of 
 
 D2T_OK = 0
 D2T_EINVAL, D2T_ENOMEM, D2T_EHIP, D2T_ESTATE = 1, 2, 3, 4  # include/d2t.h
-ENC_RESNET, ENC_HYBRID_VIT, ENC_VGG_BILSTM, ENC_RESNET_BILSTM = 0, 1, 2, 3
+ENC_RESNET, ENC_HYBRID_VIT, ENC_VGG_BILSTM, ENC_RESNET_BILSTM, ENC_VGG = 0, 1, 2, 3, 4
 DEC_TFM, DEC_ATTN = 0, 1
 ATTN_KEYS_ALL_INIT_MEAN, ATTN_KEYS_NOCLS_INIT_CLS, ATTN_KEYS_ALL_INIT_FIRST = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -28,7 +28,8 @@ class D2TConfig(C.Structure):
         "encoder", "in_channels", "backbone_out", "vit_depth", "vit_heads", "vit_dim", "patch_h", "patch_w",
         "max_h", "max_w", "dec_dim", "dec_heads", "dec_layers", "dec_ff", "vocab", "max_seq_len",
         "decoder", "attn_hidden", "attn_kernel_size", "attn_kernel_dim", "attn_keys", "attn_enc_init",
-        "attn_coverage", "bilstm_hidden", "batch_max_length", "gcb", "attn_cell", "attn_onehot", "vit_pos")]
+        "attn_coverage", "bilstm_hidden", "batch_max_length", "gcb", "attn_cell", "attn_onehot", "vit_pos",
+        "proj_height")]
 
 
 class D2TPrepConfig(C.Structure):  # include/d2t_prep.h d2t_prep_config

@@ -32,8 +32,8 @@ def decoder_attn_outputs(stages, decoder_attn, output_shape, feat_pad):
 
 
 class FeatExtractorBuilder(nn.Module):
-    """recognizers/build_feat.py:8-63 (parameter tree; ResNet or VGG; the height-mean for Seq=BiLSTM
-    runs inside the engine)."""
+    """recognizers/build_feat.py:8-63 (parameter tree; ResNet or VGG; for Seq=BiLSTM the height-mean -- or, with
+    mean_height False, proj_feat over the flattened height -- runs inside the engine)."""
 
     def __init__(self, flow, config):
         super().__init__()
@@ -41,7 +41,7 @@ class FeatExtractorBuilder(nn.Module):
         self.flow = flow
         self.feat_name = flow["Feat"]
         if self.feat_name != "None":
-            config["FeatureExtraction"]["params"].pop("mean_height", True)  # build_feat.py:16
+            self.mean_height = bool(config["FeatureExtraction"]["params"].pop("mean_height", True))  # build_feat.py:16
             if self.feat_name == "VGG":
                 self.FeatureExtraction = P.VGGFeatureExtractorParams(**config["FeatureExtraction"]["params"])
             elif self.feat_name == "ResNet":
@@ -49,6 +49,10 @@ class FeatExtractorBuilder(nn.Module):
             else:
                 raise NotImplementedError(f"FeatureExtraction '{self.feat_name}' is not on the accelerated path")
             self.FeatureExtraction_output = config["FeatureExtraction"]["params"]["output_channel"]
+            if not self.mean_height:
+                # build_feat.py:37-40: created whatever Seq is; only Seq=BiLSTM reads it (:56-61), over a feature map of
+                # height 3.  The engine runs it as a (3, 1) convolution over the NHWC map
+                self.proj_feat = nn.Linear(self.FeatureExtraction_output * 3, self.FeatureExtraction_output)
         else:
             if flow["Seq"] != "ViT":
                 raise Exception("No FeatureExtraction module specified")
@@ -498,6 +502,14 @@ class Model(nn.Module):
             self._engine.decode_wait(host_sync=host_sync)
 
     # -- engine plumbing -----------------------------------------------------
+    def engine_opt(self):
+        """The config the engine is built from: self.opt, except that a `mean_height: False` FeatExtractorBuilder popped from it
+        (build_feat.py:16) is put back -- into a copy of the two dicts above the key, never into the caller's."""
+        if getattr(self.featextractor, "mean_height", True):
+            return self.opt
+        fe = self.opt["FeatureExtraction"]
+        return {**self.opt, "FeatureExtraction": {**fe, "params": {**fe["params"], "mean_height": False}}}
+
     def engine(self, finalize=True):
         """The libd2t context of this model, with the current weights uploaded (and packed for inference)."""
         # the context lives where the parameters live (model.to("cuda:1") moves the engine with them); before the first
@@ -508,7 +520,7 @@ class Model(nn.Module):
             self.synchronize()
             self._engine, self._group = None, None  # parameters were moved to another GPU: a fresh context there
         if self._engine is None:
-            self._engine = Engine(self.opt, device=dev)
+            self._engine = Engine(self.engine_opt(), device=dev)
         self._engine.sync_weights(self, finalize=finalize)
         # what the context should run with; engine.SETTINGS holds the order and the conditions of the set_* calls
         apply_settings(self._engine, {
@@ -696,12 +708,8 @@ class Model(nn.Module):
             # fills every .grad
             from .train import train_forward
             self._refuse_train_attn_hooks()
-            if self.stages["Pred"] == "TFM":
-                if self.stages["Seq"] not in ("ViT", "None"):
-                    raise NotImplementedError("the training step is implemented for the HybridViT + TFM and ResNet + TFM stacks")
-            else:  # Attn / Attnv2
-                if self.stages["Seq"] not in ("ViT", "BiLSTM"):
-                    raise NotImplementedError("training the LSTM-attention head is implemented on the HybridViT and BiLSTM encoders")
+            if self.stages["Pred"] != "TFM" and self.stages["Seq"] not in ("ViT", "BiLSTM"):  # Attn / Attnv2
+                raise NotImplementedError("training the LSTM-attention head is implemented on the HybridViT and BiLSTM encoders")
             logits = train_forward(self, input, text)
             return logits.argmax(dim=2), logits, {}
         contextual_feature, output_shape, feat_pad = self.forward_encoder(input)

@@ -128,6 +128,7 @@ struct d2t_ctx {
   std::string bb;  // backbone key prefix ("...ConvNet.")
   ConvW stem, conv0_2, conv1, conv2, conv3, conv4_1, conv4_2, patch;
   ConvW vgg[7];      // VGG convs 0,3,6,8,11(+bn12),14(+bn15),18 (feature_extractor/vgg.py:16-41)
+  ConvW proj_feat;   // mean_height False: featextractor.proj_feat as a (3, 1) convolution (engine_weights.hip pack_proj_feat)
   BiLstmW lstm[2];   // seq_modeling/bilstm.py
   AttnW attn;        // prediction_head/seq2seq.py
   std::vector<Block> layers[4];

@@ -10,6 +10,22 @@
 
 namespace {
 
+// spatial size after the VGG (vgg.py:16-41) for an H x W crop: pools (2,2), (2,2), (2,1), (2,1), then the 2x2 convolution
+void vgg_hw(int H, int W, int* oh, int* ow) {
+  *oh = H / 2 / 2 / 2 / 2 - 1;
+  *ow = W / 2 / 2 - 1;
+}
+bool vgg_encoder(const d2t_config& g) { return g.encoder == D2T_ENC_VGG_BILSTM || g.encoder == D2T_ENC_VGG; }
+bool lstm_encoder(const d2t_config& g) { return g.encoder == D2T_ENC_VGG_BILSTM || g.encoder == D2T_ENC_RESNET_BILSTM; }
+
+// mean_height False: proj_feat = Linear(3 * C -> C) reads the whole height of the feature map, which must be 3 (build_feat.py:
+// 38-40,56-61; the reference fails in the matrix product otherwise)
+int proj_height_check(d2t_ctx* c, int fh) {
+  if (fh == 3) return D2T_OK;
+  return fail(c, D2T_EINVAL, "mean_height False: proj_feat reads a feature map of height 3 (64-pixel crops), this crop gives "
+              "height %d", fh);
+}
+
 // spatial size after the backbone (resnet.py:205-245) for an H x W crop
 void backbone_hw(int H, int W, int* oh, int* ow) {
   int h = H / 2, w = W / 2;          // maxpool1
@@ -295,8 +311,7 @@ int ensure_activations(d2t_ctx* c, int B, int H, int W, int T, int dim) {
     size_t v = (size_t)B * T * (hid > 3 * (size_t)dim ? hid : 3 * (size_t)dim);
     if (v > need_floats) need_floats = v;
   }
-  const bool lstm_enc = g.encoder == D2T_ENC_VGG_BILSTM || g.encoder == D2T_ENC_RESNET_BILSTM;
-  if (lstm_enc && (size_t)B * T * 8 * g.bilstm_hidden > need_floats) need_floats = (size_t)B * T * 8 * g.bilstm_hidden;
+  if (lstm_encoder(g) && (size_t)B * T * 8 * g.bilstm_hidden > need_floats) need_floats = (size_t)B * T * 8 * g.bilstm_hidden;
   if (c->act_cap >= need_floats * 4) return D2T_OK;
   hipDeviceSynchronize();
   for (int i = 0; i < 4; ++i) {
@@ -311,8 +326,10 @@ int ensure_activations(d2t_ctx* c, int B, int H, int W, int T, int dim) {
   return D2T_OK;
 }
 
-// VGG_FeatureExtractor.forward (feature_extractor/vgg.py:16-44)
-int encode_vgg(d2t_ctx* c, hipStream_t s, const float* image, int B, int H, int W, Act* out) {
+// VGG_FeatureExtractor.forward (feature_extractor/vgg.py:16-44).  final_out / final_extra: the last convolution (2x2, bias,
+// ReLU, no BatchNorm) writes there, with a row table added behind its ReLU (encode_vgg_flat)
+int encode_vgg(d2t_ctx* c, hipStream_t s, const float* image, int B, int H, int W, Act* out, float* final_out = nullptr,
+               const ConvP* final_extra = nullptr) {
   Net n{c, s};
   Act x{n.pick({}), B, H, W, c->vgg[0].Cout};
   HIPCHK(c, launch_stem(image, c->vgg[0].w, c->vgg[0].bias, x.p, B, c->vgg[0].Cin, H, W, x.C, ACT_RELU, s));
@@ -325,20 +342,30 @@ int encode_vgg(d2t_ctx* c, hipStream_t s, const float* image, int B, int H, int 
   x = n.conv(x, c->vgg[4]);
   x = n.conv(x, c->vgg[5]);
   x = n.pool_k(x, 2, 1);
-  x = n.conv(x, c->vgg[6], {.ph = 0, .pw = 0});
+  x = n.conv(x, c->vgg[6], {.ph = 0, .pw = 0, .extra = final_extra, .out = final_out});
   if (n.err != hipSuccess) return fail(c, D2T_EHIP, "VGG launch: %s", hipGetErrorString(n.err));
   *out = x;
   return D2T_OK;
 }
 
-// Behind either feature extractor's map f: AdaptiveAvgPool2d((None,1)) over the height (build_feat.py:50-55), then 2x
-// BidirectionalLSTM (seq_modeling/bilstm.py:6-24); the second one's Linear writes the memory [B][T][hidden]
+// Behind either feature extractor's map f: AdaptiveAvgPool2d((None,1)) over the height (build_feat.py:50-55) -- or, with
+// mean_height False, proj_feat over the [b, w, c * h] flattening of a map of height 3 (:56-61), which is a convolution with
+// window (3, 1) over the NHWC map (pack_proj_feat) -- then 2x BidirectionalLSTM (seq_modeling/bilstm.py:6-24); the second
+// one's Linear writes the memory [B][T][hidden]
 int encode_bilstm_tail(d2t_ctx* c, hipStream_t s, const Act& f, int T, float* memory) {
   if (f.W != T || f.C != 512) return fail(c, D2T_EINVAL, "unexpected feature map %dx%dx%d", f.H, f.W, f.C);
-  const Net n{c, s};
+  Net n{c, s};
   const int B = f.B, Hh = c->cfg.bilstm_hidden;
-  float* seq = n.pick({f.p});
-  HIPCHK(c, launch_mean_h(f.p, seq, B, f.H, f.W, f.C, s));
+  float* seq;
+  if (c->cfg.proj_height) {
+    if (int rc = proj_height_check(c, f.H)) return rc;
+    const Act y = n.conv(f, c->proj_feat, {.ph = 0, .pw = 0, .act = ACT_NONE, .out_split = 0});
+    if (n.err != hipSuccess) return fail(c, D2T_EHIP, "proj_feat launch: %s", hipGetErrorString(n.err));
+    seq = y.p;
+  } else {
+    seq = n.pick({f.p});
+    HIPCHK(c, launch_mean_h(f.p, seq, B, f.H, f.W, f.C, s));
+  }
   for (int i = 0; i < 2; ++i) {
     const BiLstmW& L = c->lstm[i];
     float* gates = n.pick({seq});
@@ -364,6 +391,18 @@ int encode_resnet_flat(d2t_ctx* c, hipStream_t s, const float* image, int B, int
   ex.row_add = pe; ex.rows_per_img = fh * fw; ex.img_stride = fh * fw; ex.row_off = 0; ex.row_add_off = 0;
   Act f{};
   return run_backbone(c, s, image, B, H, W, &f, memory, &ex, false);
+}
+
+// Feat=VGG, Seq=None: as encode_resnet_flat, in the epilogue of the VGG's last convolution (bias, ReLU, then the table's row)
+int encode_vgg_flat(d2t_ctx* c, hipStream_t s, const float* image, int B, int H, int W, float* memory) {
+  int fh, fw;
+  vgg_hw(H, W, &fh, &fw);
+  const float* pe;
+  if (int rc = get_pe2d(c, fh, fw, c->cfg.backbone_out, s, &pe)) return rc;
+  ConvP ex{};
+  ex.row_add = pe; ex.rows_per_img = fh * fw; ex.img_stride = fh * fw; ex.row_off = 0; ex.row_add_off = 0;
+  Act f{};
+  return encode_vgg(c, s, image, B, H, W, &f, memory, &ex);
 }
 
 // HybridEmbed.forward (patchembed.py:115-141) over the backbone's map f: zero-pad right/bottom + Conv2d(k=s=patch) as one
@@ -468,10 +507,12 @@ int d2t_create(const d2t_config* cfg, d2t_ctx** out) {
     if (cfg->vit_dim != 256 && cfg->vit_dim != 512) return fail(c, D2T_EINVAL, "ViT hidden_size must be 256 or 512");
     if (cfg->vit_dim / cfg->vit_heads != 32) return fail(c, D2T_EINVAL, "ViT head_dim must be 32");
     if (cfg->patch_h < 1 || cfg->patch_w < 1) return fail(c, D2T_EINVAL, "bad patch size");
-  } else if (cfg->encoder != D2T_ENC_RESNET && cfg->encoder != D2T_ENC_VGG_BILSTM &&
-             cfg->encoder != D2T_ENC_RESNET_BILSTM) {
+  } else if (cfg->encoder != D2T_ENC_RESNET && cfg->encoder != D2T_ENC_VGG && !lstm_encoder(*cfg)) {
     return fail(c, D2T_EINVAL, "unknown encoder %d", cfg->encoder);
   }
+  if (lstm_encoder(*cfg) && cfg->bilstm_hidden != 256) return fail(c, D2T_EINVAL, "BiLSTM hidden_size must be 256");
+  if (cfg->proj_height && !lstm_encoder(*cfg))
+    return fail(c, D2T_EINVAL, "proj_height (mean_height False) is read by the BiLSTM encoders only");
   if (cfg->decoder == D2T_DEC_TFM) {
     const int hd = cfg->dec_heads > 0 ? cfg->dec_dim / cfg->dec_heads : 0;
     if (cfg->dec_dim != 256 && cfg->dec_dim != 512) return fail(c, D2T_EINVAL, "decoder d_model must be 256 or 512");
@@ -479,18 +520,17 @@ int d2t_create(const d2t_config* cfg, d2t_ctx** out) {
     if (cfg->dec_heads != 8) return fail(c, D2T_EINVAL, "decoder nhead must be 8");
     if (cfg->dec_ff % 64) return fail(c, D2T_EINVAL, "dim_feedforward must be a multiple of 64");
     if (cfg->max_seq_len + 2 > 512) return fail(c, D2T_EINVAL, "max_seq_len must be <= 510");
-    if (cfg->encoder == D2T_ENC_VGG_BILSTM || cfg->encoder == D2T_ENC_RESNET_BILSTM)
-      return fail(c, D2T_EINVAL, "BiLSTM encoders are paired with the Attn decoder only");
+    if (lstm_encoder(*cfg) && cfg->dec_dim != cfg->bilstm_hidden)
+      return fail(c, D2T_EINVAL, "a TFM decoder behind the BiLSTM needs d_model = the BiLSTM hidden_size (256), got %d", cfg->dec_dim);
   } else if (cfg->decoder == D2T_DEC_ATTN) {
     if (cfg->attn_hidden != 256) return fail(c, D2T_EINVAL, "Attn hidden_size / input_size must be 256");
     if (cfg->attn_kernel_size < 0 || cfg->attn_kernel_size > 5) return fail(c, D2T_EINVAL, "Attn kernel_size must be <= 5");
     if (cfg->vocab > D2T_ATTN_MAX_CLASSES)
       return fail(c, D2T_EINVAL, "Attn decoder supports num_class <= %d, got %d", D2T_ATTN_MAX_CLASSES, cfg->vocab);
     if (cfg->batch_max_length < 1) return fail(c, D2T_EINVAL, "batch_max_length must be >= 1");
-    if (cfg->encoder == D2T_ENC_RESNET) return fail(c, D2T_EINVAL, "Feat=ResNet+Seq=None is paired with the TFM decoder only");
+    if (cfg->encoder == D2T_ENC_RESNET || cfg->encoder == D2T_ENC_VGG)
+      return fail(c, D2T_EINVAL, "Feat=ResNet|VGG + Seq=None is paired with the TFM decoder only");
     if (cfg->encoder == D2T_ENC_HYBRID_VIT && cfg->vit_dim != 256) return fail(c, D2T_EINVAL, "Attn over ViT needs hidden_size 256");
-    if ((cfg->encoder == D2T_ENC_VGG_BILSTM || cfg->encoder == D2T_ENC_RESNET_BILSTM) && cfg->bilstm_hidden != 256)
-      return fail(c, D2T_EINVAL, "BiLSTM hidden_size must be 256");
   } else {
     return fail(c, D2T_EINVAL, "unknown decoder %d", cfg->decoder);
   }
@@ -576,16 +616,12 @@ int d2t_encoder_shape(const d2t_ctx* c, int32_t H, int32_t W, int32_t* T, int32_
   if (!c) return D2T_EINVAL;
   if (H < 4 || W < 4) return D2T_EINVAL;
   int fh, fw;
-  if (c->cfg.encoder == D2T_ENC_VGG_BILSTM) {  // vgg.py:16-41: pools (2,2),(2,2),(2,1),(2,1), final 2x2 conv
-    fh = H / 2 / 2 / 2 / 2 - 1;
-    fw = W / 2 / 2 - 1;
-  } else {
-    backbone_hw(H, W, &fh, &fw);
-  }
+  if (vgg_encoder(c->cfg)) vgg_hw(H, W, &fh, &fw);
+  else backbone_hw(H, W, &fh, &fw);
   if (fh < 1 || fw < 1) return D2T_EINVAL;
   int gh = fh, gw = fw, pw = 0, ph = 0, t, dim = c->cfg.backbone_out;
-  if (c->cfg.encoder == D2T_ENC_VGG_BILSTM || c->cfg.encoder == D2T_ENC_RESNET_BILSTM) {
-    t = fw;  // the height is averaged away (build_feat.py:50-55)
+  if (lstm_encoder(c->cfg)) {
+    t = fw;  // the height is averaged (build_feat.py:50-55) or projected (:56-61) away
     dim = c->cfg.bilstm_hidden;
   } else if (c->cfg.encoder == D2T_ENC_HYBRID_VIT) {
     ph = (c->cfg.patch_h - fh % c->cfg.patch_h) % c->cfg.patch_h;
@@ -633,6 +669,12 @@ int d2t_encode_attn(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_
   if (g.encoder == D2T_ENC_HYBRID_VIT && g.vit_pos != D2T_VIT_POS_LEARNED_INTERP && T > c->pos_rows)  // the prefix slice would run off the table
     return fail(c, D2T_EINVAL, "crop %dx%d exceeds max_dimension (pos_embed rows %d)", H, W, c->pos_rows);
   if (T > memory_cap(c)) return fail(c, D2T_EINVAL, "memory length %d > %d unsupported", T, memory_cap(c));
+  if (g.proj_height) {  // refused before anything is launched: the caller's memory stays as it is
+    int fh, fw;
+    if (vgg_encoder(g)) vgg_hw(H, W, &fh, &fw);
+    else backbone_hw(H, W, &fh, &fw);
+    if (int rc = proj_height_check(c, fh)) return rc;
+  }
   if (int rc = ensure_activations(c, B, H, W, T, dim)) return rc;
   Act f{};
   switch (g.encoder) {
@@ -644,6 +686,8 @@ int d2t_encode_attn(d2t_ctx* c, const float* image, int32_t B, int32_t H, int32_
       return encode_bilstm_tail(c, s, f, T, memory);
     case D2T_ENC_HYBRID_VIT:
       return encode_vit(c, s, image, B, H, W, gh, gw, dim, memory, maps_dev, n_maps);
+    case D2T_ENC_VGG:
+      return encode_vgg_flat(c, s, image, B, H, W, memory);
     default:  // D2T_ENC_RESNET (d2t_create admits no other)
       return encode_resnet_flat(c, s, image, B, H, W, memory);
   }

@@ -5,18 +5,26 @@
 
 namespace {
 
-int pack_conv(d2t_ctx* c, const std::string& conv, const std::string& bn, ConvW* out, hipStream_t s) {
+// kh > 0: the weight is a Linear's [Cout][Cin * kh * kw] read as the OIHW filter [Cout][Cin][kh][kw] (pack_proj_feat)
+int pack_conv(d2t_ctx* c, const std::string& conv, const std::string& bn, ConvW* out, hipStream_t s, int kh = 0, int kw = 0) {
   const RawW *w, *g = nullptr, *b = nullptr, *mu = nullptr, *var = nullptr;
   int rc = need(c, conv + ".weight", &w);
   if (rc) return rc;
-  if (w->shape.size() != 4) return fail(c, D2T_EINVAL, "conv weight '%s' is not 4-D", conv.c_str());
+  if (kh > 0) {
+    if (w->shape.size() != 2 || w->shape[1] % (kh * kw))
+      return fail(c, D2T_EINVAL, "linear weight '%s' is not [out][in * %d]", conv.c_str(), kh * kw);
+  } else if (w->shape.size() != 4) {
+    return fail(c, D2T_EINVAL, "conv weight '%s' is not 4-D", conv.c_str());
+  }
   const RawW* cb = find(c, conv + ".bias");
   if (!bn.empty()) {
     if ((rc = need(c, bn + ".weight", &g)) || (rc = need(c, bn + ".bias", &b)) ||
         (rc = need(c, bn + ".running_mean", &mu)) || (rc = need(c, bn + ".running_var", &var)))
       return rc;
   }
-  out->Cout = (int)w->shape[0]; out->Cin = (int)w->shape[1]; out->KH = (int)w->shape[2]; out->KW = (int)w->shape[3];
+  out->Cout = (int)w->shape[0];
+  if (kh > 0) { out->Cin = (int)w->shape[1] / (kh * kw); out->KH = kh; out->KW = kw; }
+  else { out->Cin = (int)w->shape[1]; out->KH = (int)w->shape[2]; out->KW = (int)w->shape[3]; }
   if ((rc = owned_alloc(c, &out->w, w->numel)) || (rc = owned_alloc(c, &out->bias, (size_t)out->Cout))) return rc;
   HIPCHK(c, launch_pack_conv(w->p, cb ? cb->p : nullptr, g ? g->p : nullptr, b ? b->p : nullptr, mu ? mu->p : nullptr,
                              var ? var->p : nullptr, 1e-5f, out->w, out->bias, out->Cout, out->Cin, out->KH, out->KW,
@@ -67,6 +75,17 @@ int pack_vgg(d2t_ctx* c, hipStream_t s) {
     if (int rc = pack_conv(c, c->bb + convs[i], bns[i][0] ? c->bb + bns[i] : std::string(), &c->vgg[i], s)) return rc;
   if (c->vgg[0].Cin != c->cfg.in_channels || c->vgg[0].KH != 3 || c->vgg[0].KW != 3 || c->vgg[6].KH != 2 || c->vgg[6].Cout != 512)
     return fail(c, D2T_EINVAL, "unexpected VGG_FeatureExtractor shapes");
+  return D2T_OK;
+}
+
+// proj_feat (recognizers/build_feat.py:38-40,56-61): Linear(3 * C -> C) over visual_feature.permute(0, 3, 1, 2).flatten(-2),
+// whose column c * 3 + h is channel c at height h.  weight.view(C, C, 3, 1) therefore is the OIHW filter of a convolution with
+// window (3, 1), stride 1 and no padding over the [B][3][W][C] map, and its output [B][1][W][C] is the BiLSTM's input
+int pack_proj_feat(d2t_ctx* c, hipStream_t s) {
+  const int C = c->cfg.backbone_out;
+  if (int rc = pack_conv(c, "featextractor.proj_feat", "", &c->proj_feat, s, 3, 1)) return rc;
+  if (c->proj_feat.Cout != C || c->proj_feat.Cin != C || !c->proj_feat.bias || !find(c, "featextractor.proj_feat.bias"))
+    return fail(c, D2T_EINVAL, "featextractor.proj_feat must be Linear(%d -> %d) with a bias", 3 * C, C);
   return D2T_OK;
 }
 
@@ -458,15 +477,18 @@ int d2t_finalize_weights(d2t_ctx* c, d2t_stream stream) {
   c->graphs.clear();
   eng::free_packed(c);
   const d2t_config& g = c->cfg;
-  const bool vit = g.encoder == D2T_ENC_HYBRID_VIT, is_vgg = g.encoder == D2T_ENC_VGG_BILSTM;
-  const bool has_lstm = is_vgg || g.encoder == D2T_ENC_RESNET_BILSTM;
+  const bool vit = g.encoder == D2T_ENC_HYBRID_VIT, is_vgg = g.encoder == D2T_ENC_VGG_BILSTM || g.encoder == D2T_ENC_VGG;
+  const bool has_lstm = g.encoder == D2T_ENC_VGG_BILSTM || g.encoder == D2T_ENC_RESNET_BILSTM;
   const std::string sm = "seqmodeler.SequenceModeling.", pp = "predicter.Prediction.";
   c->bb = vit ? sm + "patch_embed.backbone.ConvNet." : "featextractor.FeatureExtraction.ConvNet.";
   int rc;
   if ((rc = is_vgg ? pack_vgg(c, s) : pack_resnet(c, s))) return rc;
+  if (has_lstm && g.proj_height && (rc = pack_proj_feat(c, s))) return rc;
   if (has_lstm && (rc = pack_bilstm(c, sm, s))) return rc;
   if (vit && (rc = pack_vit(c, sm, s))) return rc;
-  if (!vit && g.decoder == D2T_DEC_TFM && g.dec_dim != c->conv4_2.Cout)
+  if (has_lstm && g.decoder == D2T_DEC_TFM && g.dec_dim != g.bilstm_hidden)
+    return fail(c, D2T_EINVAL, "decoder d_model must equal the BiLSTM hidden_size");
+  if (!vit && !has_lstm && g.decoder == D2T_DEC_TFM && g.dec_dim != (is_vgg ? c->vgg[6].Cout : c->conv4_2.Cout))
     return fail(c, D2T_EINVAL, "decoder d_model must equal the backbone output_channel");
   if ((rc = g.decoder == D2T_DEC_ATTN ? pack_attn_head(c, pp, s) : pack_tfm_head(c, pp, s))) return rc;
   HIPCHK(c, hipStreamSynchronize(s));

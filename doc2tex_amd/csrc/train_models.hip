@@ -175,10 +175,16 @@ int d2t_train_forward(d2t_ctx* c, const float* image, int32_t B, int32_t H, int3
   const d2t_config& g = c->cfg;
   const bool lstm = g.decoder == D2T_DEC_ATTN;
   const bool lstm_enc = g.encoder == D2T_ENC_VGG_BILSTM || g.encoder == D2T_ENC_RESNET_BILSTM;
-  if (lstm && g.encoder == D2T_ENC_RESNET) return fail(c, D2T_ESTATE, "the Attn training step needs the HybridViT or a BiLSTM encoder");
-  if (!lstm && lstm_enc) return fail(c, D2T_ESTATE, "the BiLSTM encoders train with the Attn / Attnv2 heads");
+  const bool flat_enc = g.encoder == D2T_ENC_RESNET || g.encoder == D2T_ENC_VGG;
+  if (lstm && flat_enc) return fail(c, D2T_ESTATE, "the Attn training step needs the HybridViT or a BiLSTM encoder");
   if (lstm && L != g.batch_max_length + 1) return fail(c, D2T_EINVAL, "the Attn head trains on batch_max_length + 1 = %d steps", g.batch_max_length + 1);
   if (!lstm && L > g.max_seq_len + 1) return fail(c, D2T_EINVAL, "teacher sequence longer than max_seq_len + 1");
+  if (lstm_enc && g.proj_height) {  // refused before anything is launched, as d2t_encode does
+    int32_t fh = 0;
+    if (d2t_encoder_shape(c, H, W, nullptr, nullptr, &fh, nullptr, nullptr, nullptr) || fh != 3)
+      return fail(c, D2T_EINVAL, "mean_height False: proj_feat reads a feature map of height 3 (64-pixel crops), this crop gives "
+                  "height %d", fh);
+  }
   if (!c->train) c->train = new d2t_train_state();
   d2t_train_state* st = c->train;
   st->tape.reset();
@@ -195,17 +201,25 @@ int d2t_train_forward(d2t_ctx* c, const float* image, int32_t B, int32_t H, int3
     const std::string sp = "seqmodeler.SequenceModeling.";
     RC(tr.backbone(image, B, H, W, sp + "patch_embed.backbone.ConvNet.", &feat));
     RC(tr.vit(feat, sp, &mem, nullptr));
-  } else if (lstm_enc) {  // VGG | ResNet -> mean over the height -> 2 x BidirectionalLSTM (build_feat.py:50-55, build_seq.py)
+  } else if (lstm_enc) {  // VGG | ResNet -> mean over the height | proj_feat -> 2 x BidirectionalLSTM (build_feat.py:50-61, build_seq.py)
     const std::string fp = "featextractor.FeatureExtraction.ConvNet.";
     if (g.encoder == D2T_ENC_VGG_BILSTM) RC(tr.vgg(image, B, H, W, fp, &feat));
     else RC(tr.backbone(image, B, H, W, fp, &feat));
     int seq;
-    RC(tr.mean_h(feat, &seq));
+    if (g.proj_height) {
+      // mean_height False: Linear(3 * C -> C) over the [b, w, c * h] flattening = a (3, 1) convolution over the NHWC map whose
+      // OIHW filter is the weight as it lies in memory (engine_weights.hip pack_proj_feat); so is its gradient
+      RC(tr.conv_bn(feat, "featextractor.proj_feat", "", g.backbone_out, 3, 1, 1, 1, 0, 0, false, -1, &seq));
+    } else {
+      RC(tr.mean_h(feat, &seq));
+    }
     const int T = st->t[feat].W;
     RC(tr.bilstm_layer(seq, 0, "seqmodeler.SequenceModeling.0.", B, T, &seq));
     RC(tr.bilstm_layer(seq, 1, "seqmodeler.SequenceModeling.1.", B, T, &mem));
-  } else {  // Feat=ResNet, Seq=None: + PositionalEncoding2D, [B,C,H,W] -> [B,HW,C] (already the NHWC row layout)
-    RC(tr.backbone(image, B, H, W, "featextractor.FeatureExtraction.ConvNet.", &feat));
+  } else {  // Feat=ResNet | VGG, Seq=None: + PositionalEncoding2D, [B,C,H,W] -> [B,HW,C] (already the NHWC row layout)
+    const std::string fp = "featextractor.FeatureExtraction.ConvNet.";
+    if (g.encoder == D2T_ENC_VGG) RC(tr.vgg(image, B, H, W, fp, &feat));
+    else RC(tr.backbone(image, B, H, W, fp, &feat));
     const tape::TT f = st->t[feat];
     const float* pe;
     RC(d2t_internal_pe2d(c, f.H, f.W, f.cols, (hipStream_t)stream, &pe));

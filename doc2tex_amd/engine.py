@@ -8,7 +8,9 @@ from . import _lib
 
 
 def config_from_opt(opt):
-    """Flat reference config dict (config/train.yaml schema) -> D2TConfig."""
+    """Flat reference config dict (config/train.yaml schema) -> D2TConfig.  FeatureExtraction.params.mean_height is read
+    where it is present: FeatExtractorBuilder pops it from the caller's dict (build_feat.py:16), so a Model hands its engine
+    Model.engine_opt(), which carries the popped value."""
     feat = opt["FeatureExtraction"]["name"]
     seq = opt["SequenceModeling"]["name"]
     pred = opt["Prediction"]
@@ -56,10 +58,20 @@ def config_from_opt(opt):
             cfg.bilstm_hidden = int(opt["SequenceModeling"]["params"]["hidden_size"])
             if opt["SequenceModeling"]["params"].get("pos_enc", False):
                 raise NotImplementedError("BiLSTM pos_enc crashes in the reference (self.gated undefined, build_seq.py:55)")
-        elif feat == "ResNet":
-            cfg.encoder = _lib.ENC_RESNET
-        else:
-            raise NotImplementedError("Feat=VGG with Seq=None crashes in the reference (build_seq.py:78)")
+            if cfg.bilstm_hidden != 256:
+                raise NotImplementedError(f"BiLSTM hidden_size must be 256 (the recurrent kernels are built for it), got "
+                                          f"{cfg.bilstm_hidden}")
+            if pred["name"] == "TFM" and int(pp["d_model"]) != cfg.bilstm_hidden:
+                raise NotImplementedError(f"a TFM head behind the BiLSTM needs d_model = the BiLSTM hidden_size = 256, got d_model "
+                                          f"{int(pp['d_model'])} (the reference fails in cross-attention when the two differ)")
+            # mean_height False (build_feat.py:33-40,56-61): proj_feat over the flattened height instead of its mean
+            cfg.proj_height = int(not fp.get("mean_height", True))
+        elif pred["name"] != "TFM":
+            raise NotImplementedError(f"Feat={feat} with Seq=None and Pred={pred['name']} crashes in the reference: "
+                                      "SeqModelingBuilder.forward reads self.AdaptiveAvgPool, which only FeatExtractorBuilder "
+                                      "has (build_seq.py:78; Attnv2 matches neither branch and leaves the result unbound)")
+        else:  # + PositionalEncoding2D, [B,C,H,W] -> [B,HW,C] (build_seq.py:69-76); proj_feat, if built, is never used
+            cfg.encoder = _lib.ENC_RESNET if feat == "ResNet" else _lib.ENC_VGG
     else:
         raise NotImplementedError(f"Feat={feat} Seq={seq} is not on the accelerated path")
     cfg.vocab = int(opt["num_class"])

@@ -159,6 +159,30 @@ _CONFIGS["TA0"] = copy.deepcopy(_CONFIGS["TS0"])  # tiny HybridViT + Attn (v1): 
 _CONFIGS["TA0"]["Prediction"]["name"] = "Attn"     # initial state from token 0 (seq2seq.py:229-238)
 _CONFIGS["TL0"] = copy.deepcopy(_CONFIGS["TS0"])  # Luong cell: constructs, every forward raises (attention_cell.reset_mem)
 _CONFIGS["TL0"]["Prediction"]["params"].update({"attn_type": "luong", "method": "general"})
+# The remaining Feat x Seq x Pred pairings (tools/make_golden_stacks.py): BiLSTM encoders under the TFM head (d_model = the
+# BiLSTM's hidden_size, 256), VGG + PositionalEncoding2D + TFM (d_model 512), and `mean_height: False` -- proj_feat =
+# Linear(3 * C -> C) over the flattened height (recognizers/build_feat.py:33-40,56-61; feature height 3 = 64-pixel crops)
+def _conv_stack(feat, seq, pred, crop, mean_height=True):
+    fp = {"input_channel": 1, "output_channel": 512}
+    if not mean_height:
+        fp["mean_height"] = False
+    return {"FeatureExtraction": {"name": feat, "params": fp},
+            "SequenceModeling": {"name": seq, "params": {"hidden_size": 256} if seq == "BiLSTM" else {}},
+            "Prediction": pred, "max_dimension": list(crop), "_crop": crop, "_batch": 2}
+
+
+_CONFIGS["VBT"] = _conv_stack("VGG", "BiLSTM", _tfm(256, 2), (32, 96))
+_CONFIGS["RBT"] = _conv_stack("ResNet", "BiLSTM", _tfm(256, 2), (32, 96))
+_CONFIGS["VT"] = _conv_stack("VGG", "None", _tfm(512, 2), (32, 96))
+_CONFIGS["VBTP"] = _conv_stack("VGG", "BiLSTM", _tfm(256, 2), (64, 96), mean_height=False)
+_CONFIGS["RBTP"] = _conv_stack("ResNet", "BiLSTM", _tfm(256, 2), (64, 96), mean_height=False)
+_CONFIGS["VBAP"] = _conv_stack("VGG", "BiLSTM", _attn("Attn", "BiLSTM"), (64, 96), mean_height=False)
+_CONFIGS["RBAP"] = _conv_stack("ResNet", "BiLSTM", _attn("Attnv2", "BiLSTM"), (64, 96), mean_height=False)
+_CONFIGS["VTP"] = _conv_stack("VGG", "None", _tfm(512, 2), (64, 96), mean_height=False)  # proj_feat built, never read
+_CONFIGS["VBTD"] = copy.deepcopy(_CONFIGS["VBTP"])  # training with dropout in the decoder layers
+_CONFIGS["VBTD"]["Prediction"]["params"]["dropout"] = 0.1
+_CONFIGS["VBAD"] = copy.deepcopy(_CONFIGS["VBAP"])  # the LSTM head's droprate + scheduled sampling
+_CONFIGS["VBAD"]["Prediction"]["params"].update({"droprate": 0.25, "teacher_forcing": 0.7})
 _CONFIGS["C3"] = copy.deepcopy(_CONFIGS["C2"])
 _CONFIGS["C3"]["_batch"] = 32  # per GPU; 256 global over 8 GPUs
 

@@ -14,8 +14,8 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, image, text, names, *params):
         # the LSTM-attention head reads the engine's derived (transposed / folded) decoder weights, so it needs the
-        # finalize pass; the TFM head reads the raw copies only
-        eng = model.engine(finalize=model.stages["Pred"] != "TFM")
+        # finalize pass, and so does a BiLSTM encoder (its packed input projections); the TFM head reads the raw copies only
+        eng = model.engine(finalize=model.stages["Pred"] != "TFM" or model.stages["Seq"] == "BiLSTM")
         # dropout (nn.TransformerDecoderLayer(dropout=p) / the LSTM head's droprate on its generator output): masks from
         # the engine's Philox stream, seeded like torch's generator
         pp = model.opt["Prediction"]["params"]
@@ -66,5 +66,9 @@ class _TrainStep(torch.autograd.Function):
 def train_forward(model, image, text):
     """logits [B, L, V] with autograd history reaching every trainable parameter of `model`."""
     named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    if model.stages["Seq"] != "BiLSTM":
+        # mean_height False without a BiLSTM: the reference builds proj_feat and never reads it (build_feat.py:37-40,50-61), so
+        # it is no input of the step and its .grad stays None
+        named = [(n, p) for n, p in named if not n.startswith("featextractor.proj_feat.")]
     names = tuple(n for n, _ in named)
     return _TrainStep.apply(model, image, text, names, *[p for _, p in named])

@@ -69,8 +69,9 @@ enum {
 enum {
   D2T_ENC_RESNET = 0,        /* Feat=ResNet, Seq=None (+PositionalEncoding2D)          -> TFM decoder   */
   D2T_ENC_HYBRID_VIT = 1,    /* Seq=ViT over the ResNet backbone (HybridEmbed)                          */
-  D2T_ENC_VGG_BILSTM = 2,    /* Feat=VGG,    height-mean, 2x BidirectionalLSTM          -> Attn decoder  */
-  D2T_ENC_RESNET_BILSTM = 3  /* Feat=ResNet, height-mean, 2x BidirectionalLSTM                          */
+  D2T_ENC_VGG_BILSTM = 2,    /* Feat=VGG,    height-mean | proj_feat, 2x BidirectionalLSTM -> Attn | TFM (d_model 256) */
+  D2T_ENC_RESNET_BILSTM = 3, /* Feat=ResNet, height-mean | proj_feat, 2x BidirectionalLSTM                          */
+  D2T_ENC_VGG = 4            /* Feat=VGG, Seq=None (+PositionalEncoding2D)              -> TFM decoder   */
 };
 enum { D2T_DEC_TFM = 0, D2T_DEC_ATTN = 1 };
 /* d2t_config.attn_keys: which memory tokens the LSTM-attention decoder attends to / starts from */
@@ -122,6 +123,9 @@ typedef struct d2t_config {
                                (seq2seq.py:72-78), rnn.weight_ih is [4H][H + num_class] and there is no embedding table */
   /* appended in v4: the ViT encoder variants beside ViTEncoderV3 */
   int32_t vit_pos;          /* D2T_VIT_POS_* */
+  /* appended in v5: mean_height False (recognizers/build_feat.py:16,33-40,56-61) */
+  int32_t proj_height;      /* 1: a BiLSTM encoder reads proj_feat = Linear(3 * C -> C) over the [b, w, c * h] flattening of the
+                               feature map (its height must be 3: 64-pixel crops) instead of the mean over the height */
 } d2t_config;
 
 /* Largest num_class (d2t_config.vocab) of the LSTM-attention decoders: d2t_create refuses more.  probs [B][S][vocab] fp32
