@@ -179,6 +179,7 @@ SIGNATURES = {
     "d2t_op_decode_attention": (_I, [_P] * 4 + [_I] * 5 + [_P]),
     # the decode step's kernels one at a time (test infrastructure)
     "d2t_op_skinny": (_I, [_P] * 6 + [C.c_float, _P, _P] + [_I] * 6 + [_P, _L, _P]),
+    "d2t_op_skinny_form": (_I, [_P] * 6 + [C.c_float, _P, _P] + [_I] * 6 + [_P, _L, _I, _P]),
     "d2t_op_decoder_row": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 7 + [_P, _P, _I, _P, _I, _P]),
     "d2t_op_decoder_row_ragged": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 4 + [C.POINTER(_I), C.POINTER(_I), _P]),
     "d2t_op_decoder_row_ragged_beam": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 5 +

@@ -183,6 +183,188 @@ __global__ __launch_bounds__(NW * 64) void skinny_splitk_kernel(const SkinnyP p)
   }
 }
 
+// ---------------------------------------------------------------------------
+// Wide form of the same GEMM for decode groups (M >= SKINNY_WIDE_MIN_M rows, where the kernel above is bound by the
+// L2 traffic of its many small blocks): NWV waves own a block tile of (16*TM) rows x (16*TN) columns, so that every
+// operand row is fetched by fewer blocks and the LayerNorm prologue runs once per 16*TN columns instead of once per 16.
+// BITWISE the split-K kernel: a wave owns (16 x 16 sub-tile, K slice) units -- slice w = wave % NW, the row sub-tiles
+// split over the NWV/NW waves of a slice -- each with its own accumulator (the same 16x16x4 chain over c and x, y, z, w)
+// and its own LDS partial; the slices are summed in ascending w from zero, then bias, residual, activation.  The
+// LayerNorm statistics keep the per-(row, slice) lane sums and the ascending-slice sums of the kernel above, and ln_out
+// is the A operand itself, written from the registers.
+// Every global operand is requested before the first wait, the small ones first (the vector-memory counter retires in
+// order): step, bias, residual tile, ln_g / ln_b, then the rows, then the weight rows.
+// ---------------------------------------------------------------------------
+template <int NW, int NCH, int TM, int TN, int NWV>  // K == NW * NCH * 16; NWV waves
+__global__ __launch_bounds__(NWV * 64) void skinny_wide_kernel(const SkinnyP p) {
+  if (p.stop_at && *p.stop_at && *p.cur_step >= *p.stop_at) return;  // block-uniform
+  decode_wave_priority();
+  TraceScope trace_(p.trace);
+  constexpr int KS = NCH * 16, ROWS = 16 * TM, COLS = 16 * TN;
+  constexpr int G = NWV / NW;       // waves per K slice
+  constexpr int TMW = TM / G;       // row sub-tiles of one wave
+  constexpr int WG = NWV / 4;       // the epilogue: thread = sub-tile (wave >> 2) + WG e, accumulator register wave & 3, lane
+  constexpr int NE = TM * TN / WG;  // output elements per thread
+  static_assert(NW * G == NWV && TMW * G == TM && NE * WG == TM * TN && WG * 4 == NWV, "the waves share the units evenly");
+  __shared__ float part[NW][TM * TN][4][64];  // [slice][sub-tile][accumulator register][lane]
+  __shared__ float stat[NW][ROWS];
+  __shared__ float s_mean[ROWS], s_rstd[ROWS];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r = lane & 15, q = lane >> 4;
+  const int w = wave % NW, i0 = (wave / NW) * TMW;
+  const int mbase = blockIdx.y * ROWS, nbase = blockIdx.x * COLS;
+  const int k0 = w * KS + q * 4;
+
+  // ---- the epilogue's operands ----
+  const long long yoff = p.step_ptr ? (long long)(*p.step_ptr) * p.out_step_stride : 0;
+  float bias_v[NE], res_v[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const int st = (wave >> 2) + WG * e;
+    const int m = mbase + (st / TN) * 16 + q * 4 + (wave & 3), nn = nbase + (st % TN) * 16 + r;
+    const bool ok = m < p.M && nn < p.N;
+    bias_v[e] = p.bias && ok ? p.bias[nn] : 0.f;
+    res_v[e] = p.res && ok ? p.res[(size_t)m * p.ldres + nn] : 0.f;
+  }
+  float4 g4[NCH], b4[NCH];
+  if (p.ln_g) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      g4[c] = *reinterpret_cast<const float4*>(p.ln_g + k0 + c * 16);
+      b4[c] = *reinterpret_cast<const float4*>(p.ln_b + k0 + c * 16);
+    }
+  }
+  // ---- this wave's rows and weight rows, K slice w ----
+  float4 a[TMW][NCH], b[TN][NCH];
+#pragma unroll
+  for (int i = 0; i < TMW; ++i) {
+    const int m = mbase + (i0 + i) * 16 + r;
+    const bool mok = m < p.M;
+    const float* src = p.x + (size_t)(mok ? m : 0) * p.ldx + k0;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      a[i][c] = *reinterpret_cast<const float4*>(src + c * 16);
+      if (!mok) a[i][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = nbase + j * 16 + r;
+      const bool nok = n < p.N;
+      b[j][c] = *reinterpret_cast<const float4*>(p.w + (size_t)(nok ? n : 0) * (p.wld ? p.wld : p.K) + k0 + c * 16);
+      if (!nok) b[j][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+
+  if (p.ln_g) {
+    const float invK = 1.f / (float)p.K;
+#pragma unroll
+    for (int i = 0; i < TMW; ++i) {
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) s += (a[i][c].x + a[i][c].y) + (a[i][c].z + a[i][c].w);
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      if (q == 0) stat[w][(i0 + i) * 16 + r] = s;
+    }
+    __syncthreads();
+    if (tid < ROWS) {
+      float t = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) t += stat[ww][tid];
+      s_mean[tid] = t * invK;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < TMW; ++i) {
+      const float mu = s_mean[(i0 + i) * 16 + r];
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        a[i][c].x -= mu; a[i][c].y -= mu; a[i][c].z -= mu; a[i][c].w -= mu;
+        s += (a[i][c].x * a[i][c].x + a[i][c].y * a[i][c].y) + (a[i][c].z * a[i][c].z + a[i][c].w * a[i][c].w);
+      }
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      if (q == 0) stat[w][(i0 + i) * 16 + r] = s;
+    }
+    __syncthreads();
+    if (tid < ROWS) {
+      float t = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) t += stat[ww][tid];
+      s_rstd[tid] = 1.f / sqrtf(t * invK + p.ln_eps);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < TMW; ++i) {
+      const float rs = s_rstd[(i0 + i) * 16 + r];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        a[i][c].x = a[i][c].x * rs * g4[c].x + b4[c].x;
+        a[i][c].y = a[i][c].y * rs * g4[c].y + b4[c].y;
+        a[i][c].z = a[i][c].z * rs * g4[c].z + b4[c].z;
+        a[i][c].w = a[i][c].w * rs * g4[c].w + b4[c].w;
+      }
+    }
+    // ln_out: the normalised rows are the A operand itself, (x - mean) * rstd * g + b; a (row, column) has one writer,
+    // the block whose column tile holds that column (N >= K: launch_skinny)
+    if (p.ln_out) {
+#pragma unroll
+      for (int i = 0; i < TMW; ++i) {
+        const int m = mbase + (i0 + i) * 16 + r;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int k = k0 + c * 16;
+          if (m < p.M && k / COLS == (int)blockIdx.x) *reinterpret_cast<float4*>(p.ln_out + (size_t)m * p.K + k) = a[i][c];
+        }
+      }
+    }
+  }
+
+  f32x4 acc[TMW][TN];
+#pragma unroll
+  for (int i = 0; i < TMW; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // per accumulator the chain runs over c and x, y, z, w in that order; the TMW * TN independent chains are interleaved
+#define D2T_WIDE_MFMA(f)                                                                                     \
+  _Pragma("unroll") for (int i = 0; i < TMW; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j)             \
+    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][c].f, b[j][c].f, acc[i][j], 0, 0, 0)
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    D2T_WIDE_MFMA(x);
+    D2T_WIDE_MFMA(y);
+    D2T_WIDE_MFMA(z);
+    D2T_WIDE_MFMA(w);
+  }
+#undef D2T_WIDE_MFMA
+#pragma unroll
+  for (int i = 0; i < TMW; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) part[w][(i0 + i) * TN + j][reg][lane] = acc[i][j][reg];
+  __syncthreads();
+
+  // C/D map: col = lane&15 -> n, row = (lane>>4)*4 + reg -> m
+  float* y = p.y + yoff;
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const int st = (wave >> 2) + WG * e;
+    const int m = mbase + (st / TN) * 16 + q * 4 + (wave & 3), nn = nbase + (st % TN) * 16 + r;
+    if (m >= p.M || nn >= p.N) continue;
+    float v = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < NW; ++ww) v += part[ww][st][wave & 3][lane];
+    v += bias_v[e];
+    if (p.res) v += res_v[e];
+    y[(size_t)m * p.ldy + nn] = act_fn(v, p.act);
+  }
+}
+
 // generic fallback (any K % 16 == 0, no LayerNorm prologue): one wave per 16 rows
 __global__ __launch_bounds__(256) void skinny_generic_kernel(const SkinnyP p) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -226,11 +408,32 @@ static int decode_small() {
   return v;
 }
 
-hipError_t launch_skinny(const SkinnyP& p, hipStream_t s) {
+template <int NW, int NCH, int TM, int TN, int NWV>
+static void launch_skinny_wide(const SkinnyP& p, hipStream_t s) {
+  const dim3 grid((p.N + 16 * TN - 1) / (16 * TN), (p.M + 16 * TM - 1) / (16 * TM));
+  hipLaunchKernelGGL((skinny_wide_kernel<NW, NCH, TM, TN, NWV>), grid, dim3(NWV * 64), 0, s, p);
+}
+
+hipError_t launch_skinny(const SkinnyP& p, hipStream_t s) { return launch_skinny_form(p, SKINNY_FORM_AUTO, s); }
+
+hipError_t launch_skinny_form(const SkinnyP& p, int form, hipStream_t s) {
   if (p.M <= 0 || p.N <= 0) return hipSuccess;
   if (p.K % 16 != 0 || p.ldx % 4 != 0) return hipErrorInvalidValue;
   // ln_out[m][nn] is written by the block that owns output column nn: all K columns exist only when N >= K
   if (p.ln_out && (!p.ln_g || p.N < p.K)) return hipErrorInvalidValue;
+  const bool wide_k = p.K == 256 || p.K == 512 || p.K == 1024;
+  // measured alone on the chip: from 384 rows on the wide form is the faster one at K = 256 and 1024
+  if (form == SKINNY_FORM_AUTO)
+    form = (p.K == 256 || p.K == 1024) && p.M >= SKINNY_WIDE_MIN_M && !decode_small() ? SKINNY_FORM_WIDE : SKINNY_FORM_SPLITK;
+  if (form == SKINNY_FORM_WIDE) {
+    if (!wide_k) return hipErrorInvalidValue;
+    if (p.K == 256 && p.N > 512) launch_skinny_wide<4, 4, 2, 4, 4>(p, s);  // 32 x 64, four waves
+    else if (p.K == 256) launch_skinny_wide<4, 4, 2, 2, 4>(p, s);          // narrow outputs: 32 x 32
+    else if (p.K == 512) launch_skinny_wide<8, 4, 2, 2, 8>(p, s);          // 32 x 32, eight waves
+    else launch_skinny_wide<8, 8, 2, 1, 8>(p, s);                          // 32 x 16
+    return hipGetLastError();
+  }
+  if (form != SKINNY_FORM_SPLITK) return hipErrorInvalidValue;
   // narrow outputs (N <= 512) take 16-row tiles so that the few column tiles still fill >= 64 CUs
   const int mt = p.N <= 512 ? 1 : 2;
   const dim3 grid((p.N + 15) / 16, (p.M + 16 * mt - 1) / (16 * mt));

@@ -354,9 +354,10 @@ bool fetch_ints(hipStream_t s, const int* dev, size_t n, std::vector<int>* out) 
 }
 }  // namespace
 
-int d2t_op_skinny(const float* x, const float* w, const float* bias, const float* res, const float* ln_g, const float* ln_b,
-                  float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx, int32_t ldy, int32_t act,
-                  const int32_t* step, int64_t out_step_stride, d2t_stream stream) {
+namespace {
+int op_skinny(const float* x, const float* w, const float* bias, const float* res, const float* ln_g, const float* ln_b,
+              float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx, int32_t ldy, int32_t act,
+              const int32_t* step, int64_t out_step_stride, int form, d2t_stream stream) {
   if (!x || !w || !y || M < 1 || M > 65535 * 16 || N < 1 || K < 16 || K % 16 || ldx < K || ldx % 4 || ldy < N) return D2T_EINVAL;
   if (act != ACT_NONE && act != ACT_RELU && act != ACT_GELU) return D2T_EINVAL;
   if ((ln_g == nullptr) != (ln_b == nullptr) || (ln_out && !ln_g)) return D2T_EINVAL;
@@ -370,8 +371,24 @@ int d2t_op_skinny(const float* x, const float* w, const float* bias, const float
   p.M = M; p.K = K; p.N = N; p.ldx = ldx; p.ldy = ldy; p.ldres = N; p.act = act;
   p.step_ptr = step; p.out_step_stride = out_step_stride;
   p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_out = ln_out;
-  const hipError_t e = launch_skinny(p, s);
+  const hipError_t e = launch_skinny_form(p, form, s);
   return op_status(e);
+}
+}  // namespace
+
+int d2t_op_skinny(const float* x, const float* w, const float* bias, const float* res, const float* ln_g, const float* ln_b,
+                  float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx, int32_t ldy, int32_t act,
+                  const int32_t* step, int64_t out_step_stride, d2t_stream stream) {
+  return op_skinny(x, w, bias, res, ln_g, ln_b, ln_eps, y, ln_out, M, K, N, ldx, ldy, act, step, out_step_stride, SKINNY_FORM_AUTO,
+                   stream);
+}
+
+int d2t_op_skinny_form(const float* x, const float* w, const float* bias, const float* res, const float* ln_g,
+                       const float* ln_b, float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx,
+                       int32_t ldy, int32_t act, const int32_t* step, int64_t out_step_stride, int32_t form,
+                       d2t_stream stream) {
+  if (form != SKINNY_FORM_SPLITK && form != SKINNY_FORM_WIDE) return D2T_EINVAL;
+  return op_skinny(x, w, bias, res, ln_g, ln_b, ln_eps, y, ln_out, M, K, N, ldx, ldy, act, step, out_step_stride, form, stream);
 }
 
 namespace {

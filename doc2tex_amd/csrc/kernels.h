@@ -126,6 +126,13 @@ struct SkinnyP {
   const float* ln_g; const float* ln_b; float ln_eps; float* ln_out;
 };
 hipError_t launch_skinny(const SkinnyP& p, hipStream_t s);
+// The split-K builds (K = 256, 512, 1024) exist in two block shapes with bitwise equal results: the split-K form (block
+// tile 16 or 32 rows x 16 columns) and the wide form (32 x 64 at K = 256, 32 x 32 for N <= 512 and at K = 512, 32 x 16 at
+// K = 1024).  launch_skinny takes the wide one from SKINNY_WIDE_MIN_M rows on at K = 256 and 1024 (the smallest measured
+// multiple of 64 from which it is not the slower one alone on the chip); launch_skinny_form lets the operator tests name one.
+enum { SKINNY_FORM_AUTO = -1, SKINNY_FORM_SPLITK = 0, SKINNY_FORM_WIDE = 1 };
+constexpr int SKINNY_WIDE_MIN_M = 384;
+hipError_t launch_skinny_form(const SkinnyP& p, int form, hipStream_t s);
 
 // conv0_1: Cin = 1 or 3, 3x3, stride 1, pad 1, Cout % 4 == 0, fused bias + ReLU.  img NCHW planar [B][Cin][H][W],
 // w [Cout][9][Cin] (pack_conv's layout).

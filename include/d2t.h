@@ -589,6 +589,12 @@ int d2t_op_decode_attention(const float* q, const float* k, const float* v, floa
 int d2t_op_skinny(const float* x, const float* w, const float* bias, const float* res, const float* ln_g, const float* ln_b,
                   float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx, int32_t ldy, int32_t act,
                   const int32_t* step, int64_t out_step_stride, d2t_stream stream);
+/* The same with the kernel form named instead of chosen from M: form 0 the split-K kernel (block tile 16 / 32 rows x 16
+ * columns), form 1 the wide kernel of the decode groups (K = 256, 512, 1024 only).  The two give bitwise equal results. */
+int d2t_op_skinny_form(const float* x, const float* w, const float* bias, const float* res, const float* ln_g,
+                       const float* ln_b, float ln_eps, float* y, float* ln_out, int32_t M, int32_t K, int32_t N, int32_t ldx,
+                       int32_t ldy, int32_t act, const int32_t* step, int64_t out_step_stride, int32_t form,
+                       d2t_stream stream);
 /* The fused row step of one post-norm decoder layer for M rows at position t = *step (8 heads):
  *   a = SelfAttn(q, cache[0 .. t-1] + this step's k, v);  x1 = LN1(a @ sa_out_w^T + sa_out_b + xres)
  *   y2 = CrossAttn(x1, mem of the row's sample) @ ca_out_w^T + ca_out_b + x1          (pre-LN2)
