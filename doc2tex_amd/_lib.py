@@ -69,6 +69,12 @@ class D2TOpAttnLstmBwdArgs(C.Structure):  # include/d2t.h d2t_op_attn_lstm_bwd_a
         "dbscore")] + [(n, C.c_int32) for n in ("B", "T", "S", "V", "taps", "key_off", "coverage")]
 
 
+class D2TOpTrainAttentionArgs(C.Structure):  # include/d2t.h d2t_op_train_attention_args
+    _fields_ = [(n, C.c_void_p) for n in (
+        "q", "kv", "qkv", "dy", "keytok", "dropmask", "y", "dq", "dkv", "dqkv", "probs", "ds", "plan")] + \
+        [("dropscale", C.c_float)] + [(n, C.c_int32) for n in ("layout", "nb", "Lq", "Lk", "heads", "hd", "causal")]
+
+
 class D2TOpAttnBeamRec(C.Structure):  # include/d2t.h d2t_op_attn_beam_rec
     _fields_ = [(n, C.c_void_p) for n in (
         "ctrl", "tok", "scores", "map", "idx_h", "idx_m", "seg", "comp_n", "fin", "last_completed", "comp_t", "comp_par",
@@ -215,6 +221,7 @@ SIGNATURES = {
     "d2t_op_train_linear": (_I, [_P] * 10 + [_I] * 5 + [_P]),
     "d2t_op_train_layernorm": (_I, [_P] * 8 + [_I, _I, C.c_float, _P]),
     "d2t_op_train_attention": (_I, [_P] * 7 + [_I] * 6 + [_P]),
+    "d2t_op_train_attention_ex": (_I, [C.POINTER(D2TOpTrainAttentionArgs), _P]),
     "d2t_op_train_maxpool": (_I, [_P] * 4 + [_I] * 8 + [_P]),
     # the recurrent kernels one at a time (test infrastructure)
     "d2t_op_bilstm": (_I, [_P] * 5 + [_I] * 3 + [_P]),

@@ -544,6 +544,15 @@ struct AttnTrainP {
 };
 hipError_t launch_attn_train_fwd(const AttnTrainP& p, hipStream_t s);
 hipError_t launch_attn_train_bwd(const AttnTrainP& p, hipStream_t s);
+// Which kernel the two launchers take for (hd, Lq, Lk), with how many waves and how much LDS: the launchers' own selection
+// (they call it), also reported by the test entry d2t_op_train_attention_ex.  waves == 0: the launcher refuses the shape.
+enum { ATTN_FWD_LDS = 0, ATTN_FWD_GKV = 1 };
+enum { ATTN_BWD_FAST = 0, ATTN_BWD_PLAIN = 1, ATTN_BWD_GKV = 2 };
+struct AttnTrainPlan {
+  int fwd_form, fwd_waves, bwd_form, bwd_waves;
+  size_t fwd_lds, bwd_lds;
+};
+AttnTrainPlan attn_train_plan(int hd, int Lq, int Lk);
 hipError_t launch_embed_train(const float* E, const float* pe, const int64_t* tok, float* x, int rows, int L, int D,
                               float scale, hipStream_t s);
 hipError_t launch_embed_bwd(const float* dx, const int64_t* tok, float* dE, int rows, int V, int D, float scale, int pad_id,

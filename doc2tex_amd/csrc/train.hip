@@ -20,7 +20,9 @@ namespace tape {
 // ---------------- core ----------------
 int Tr::alloc(float** p, size_t floats) {
   *p = st->tape.alloc(floats);
-  return *p ? D2T_OK : fail(c, D2T_ENOMEM, "training tape: hipMalloc failed");
+  if (!*p) return fail(c, D2T_ENOMEM, "training tape: hipMalloc failed");
+  if (st->poison) TCHK(hipMemsetAsync(*p, 0xFF, floats * 4, s));
+  return D2T_OK;
 }
 int Tr::zeros(float** p, size_t floats) {
   RC(alloc(p, floats));
@@ -534,7 +536,7 @@ int Tr::bwd_ln(const Node& n) {
 }
 
 int Tr::attention(int qt, int qoff, int kvt, int koff, int voff, int nb, int Lq, int Lk, int heads, int hd, int causal,
-                  const int64_t* keytok, int* out, bool attn_dropout) {
+                  const int64_t* keytok, int* out, bool attn_dropout, const uint8_t* given_mask, float given_scale) {
   Node n = node(N_ATTN, qt, kvt);
   Node::Attn& a = n.attn;
   a.qoff = qoff; a.koff = koff; a.voff = voff; a.nb = nb; a.Lq = Lq; a.Lk = Lk; a.heads = heads; a.hd = hd;
@@ -542,6 +544,10 @@ int Tr::attention(int qt, int qoff, int kvt, int koff, int voff, int nb, int Lq,
   if (attn_dropout) {  // nn.MultiheadAttention(dropout=p): on the softmax probabilities
     RC(new_mask((size_t)nb * heads * Lq * Lk, &a.drop.mask));
     a.drop.scale = 1.f / (1.f - st->drop_p);
+  }
+  if (given_mask) {  // a caller's keep mask instead of a drawn one (d2t_op_train_attention_ex)
+    a.drop.mask = given_mask;
+    a.drop.scale = given_scale;
   }
   RC(new_tensor((long long)nb * Lq, heads * hd, out));
   AttnTrainP p{};

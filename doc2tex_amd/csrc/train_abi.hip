@@ -383,33 +383,74 @@ int d2t_op_train_layernorm(const float* x, const float* gamma, const float* beta
   return o.finish(run());
 }
 
+// One attention node, forward + backward, for both attention entries (include/d2t.h).  poison: the tape's blocks start as NaN
+// and the operands' gradient buffers are left to Tr::bwd_attn (own_grad); otherwise the gradients start as zeros.
+static int run_op_attention(const d2t_op_train_attention_args& a, bool poison, hipStream_t s) {
+  OpCtx o(0, s);
+  Tr& tr = o.tr;
+  o.st.poison = poison;
+  auto run = [&]() -> int {
+    const int D = a.heads * a.hd;
+    const size_t nprobs = (size_t)a.nb * a.heads * a.Lq * a.Lk;
+    int qt, kt, out;
+    if (a.layout == 1) {  // one packed tensor as both operands: the call of Tr::vit and of the decoder's self-attention
+      RC(tr.new_tensor((long long)a.nb * a.Lq, 3 * D, &qt, 0, 0, 0, const_cast<float*>(a.qkv)));
+      kt = qt;
+      RC(tr.attention(qt, 0, qt, D, 2 * D, a.nb, a.Lq, a.Lk, a.heads, a.hd, a.causal, a.keytok, &out, false, a.dropmask, a.dropscale));
+    } else {
+      RC(tr.new_tensor((long long)a.nb * a.Lq, D, &qt, 0, 0, 0, const_cast<float*>(a.q)));
+      RC(tr.new_tensor((long long)a.nb * a.Lk, 2 * D, &kt, 0, 0, 0, const_cast<float*>(a.kv)));
+      RC(tr.attention(qt, 0, kt, 0, D, a.nb, a.Lq, a.Lk, a.heads, a.hd, a.causal, a.keytok, &out, false, a.dropmask, a.dropscale));
+    }
+    float* saved = o.st.nodes.back().attn.probs;
+    RC(o.out(a.y, o.st.t[out].p, (size_t)a.nb * a.Lq * D));
+    RC(o.out(a.probs, saved, nprobs));
+    float* g;  // the tape hands a node's output gradient on as a mutable buffer: give it a private copy
+    RC(tr.alloc(&g, (size_t)a.nb * a.Lq * D));
+    RC(o.out(g, a.dy, (size_t)a.nb * a.Lq * D));
+    o.st.t[out].grad = g;
+    if (!poison) {
+      RC(tr.zeros(&o.st.t[qt].grad, (size_t)a.nb * a.Lq * D));
+      RC(tr.zeros(&o.st.t[kt].grad, (size_t)a.nb * a.Lk * 2 * D));
+    }
+    RC(tr.backward());
+    RC(o.out(a.ds, saved, nprobs));
+    if (a.layout == 1) {
+      RC(o.out(a.dqkv, o.st.t[qt].grad, (size_t)a.nb * a.Lq * 3 * D));
+    } else {
+      RC(o.out(a.dq, o.st.t[qt].grad, (size_t)a.nb * a.Lq * D));
+      RC(o.out(a.dkv, o.st.t[kt].grad, (size_t)a.nb * a.Lk * 2 * D));
+    }
+    return D2T_OK;
+  };
+  return o.finish(run());
+}
+
 // q [nb*Lq][heads*hd], kv [nb*Lk][2*heads*hd] (keys in the first half of a row, values in the second); keytok: optional
 // [nb][Lk] token ids whose PAD (0) entries are masked out (tgt_key_padding_mask, tfm.py:107-110); causal: additive -inf mask
 int d2t_op_train_attention(const float* q, const float* kv, const int64_t* keytok, const float* dy, float* y, float* dq,
                            float* dkv, int32_t nb, int32_t Lq, int32_t Lk, int32_t heads, int32_t hd, int32_t causal,
                            d2t_stream stream) {
   if (!q || !kv || !dy) return D2T_EINVAL;
-  OpCtx o(0, (hipStream_t)stream);
-  Tr& tr = o.tr;
-  auto run = [&]() -> int {
-    const int D = heads * hd;
-    int qt, kt, out;
-    RC(tr.new_tensor((long long)nb * Lq, D, &qt, 0, 0, 0, const_cast<float*>(q)));
-    RC(tr.new_tensor((long long)nb * Lk, 2 * D, &kt, 0, 0, 0, const_cast<float*>(kv)));
-    RC(tr.attention(qt, 0, kt, 0, D, nb, Lq, Lk, heads, hd, causal, keytok, &out));
-    RC(o.out(y, o.st.t[out].p, (size_t)nb * Lq * D));
-    float* g;  // the backward overwrites the incoming gradient's buffer in places: give it a private copy
-    RC(tr.alloc(&g, (size_t)nb * Lq * D));
-    RC(o.out(g, dy, (size_t)nb * Lq * D));
-    o.st.t[out].grad = g;
-    RC(tr.zeros(&o.st.t[qt].grad, (size_t)nb * Lq * D));
-    RC(tr.zeros(&o.st.t[kt].grad, (size_t)nb * Lk * 2 * D));
-    RC(tr.backward());
-    RC(o.out(dq, o.st.t[qt].grad, (size_t)nb * Lq * D));
-    RC(o.out(dkv, o.st.t[kt].grad, (size_t)nb * Lk * 2 * D));
-    return D2T_OK;
-  };
-  return o.finish(run());
+  d2t_op_train_attention_args a{};
+  a.q = q; a.kv = kv; a.keytok = keytok; a.dy = dy; a.y = y; a.dq = dq; a.dkv = dkv;
+  a.nb = nb; a.Lq = Lq; a.Lk = Lk; a.heads = heads; a.hd = hd; a.causal = causal;
+  return run_op_attention(a, false, (hipStream_t)stream);
+}
+
+int d2t_op_train_attention_ex(const d2t_op_train_attention_args* a, d2t_stream stream) {
+  if (!a || !a->dy || (a->layout != 0 && a->layout != 1)) return D2T_EINVAL;
+  if (a->layout == 0 ? (!a->q || !a->kv) : (!a->qkv || a->Lq != a->Lk)) return D2T_EINVAL;
+  if ((a->hd != 32 && a->hd != 64) || a->nb < 1 || a->Lq < 1 || a->Lk < 1 || a->heads < 1) return D2T_EINVAL;
+  if ((long long)a->nb * a->heads > 0x7fffffffll) return D2T_EINVAL;                            // one block per (batch, head)
+  if ((long long)a->nb * std::max(a->Lq, a->Lk) * 3 * a->heads * a->hd > (1ll << 31)) return D2T_EINVAL;
+  if ((long long)a->nb * a->heads * a->Lq * a->Lk > (1ll << 31)) return D2T_EINVAL;
+  if (a->dropmask && !(std::isfinite(a->dropscale) && a->dropscale > 0.f)) return D2T_EINVAL;
+  if (a->plan) {
+    const AttnTrainPlan pl = attn_train_plan(a->hd, a->Lq, a->Lk);
+    a->plan[0] = pl.fwd_form; a->plan[1] = pl.fwd_waves; a->plan[2] = pl.bwd_form; a->plan[3] = pl.bwd_waves;
+  }
+  return run_op_attention(*a, true, (hipStream_t)stream);
 }
 
 int d2t_op_train_maxpool(const float* x, const float* dy, float* y, float* dx, int32_t B, int32_t H, int32_t W, int32_t C,

@@ -294,36 +294,54 @@ static int attn_waves_gkv(int Lk) {
   int nw = (int)(ATTN_LDS / ((size_t)Lk * 4)) & ~3;
   return nw > 16 ? 16 : nw;
 }
+AttnTrainPlan attn_train_plan(int hd, int Lq, int Lk) {
+  AttnTrainPlan pl{};
+  if ((hd != 32 && hd != 64) || Lq < 1 || Lk < 1) return pl;
+  const int nwg = attn_waves_gkv(Lk);
+  const size_t lds_gkv = (size_t)nwg * Lk * 4;
+  const size_t base = ((size_t)Lk * (hd + 1) + (size_t)Lk * hd) * 4;
+  if (base + (size_t)4 * Lk * 4 > ATTN_LDS) {  // K and V of a head do not fit in LDS beside four score rows
+    pl.fwd_form = ATTN_FWD_GKV;
+    if (nwg >= 4) { pl.fwd_waves = nwg; pl.fwd_lds = lds_gkv; }
+  } else {
+    pl.fwd_form = ATTN_FWD_LDS;
+    pl.fwd_waves = attn_waves(base, Lk);
+    pl.fwd_lds = base + (size_t)pl.fwd_waves * Lk * 4;
+  }
+  const size_t lds = ((size_t)2 * Lk * (hd + 1) + 4 * (size_t)Lk) * 4;
+  const size_t base_fast = ((size_t)2 * Lk * (hd + 1) + (size_t)2 * Lq * hd) * 4;
+  const int nw = attn_waves(base_fast, Lk);
+  const size_t lds_fast = base_fast + (size_t)nw * Lk * 4;
+  if (lds_fast <= ATTN_LDS) {
+    pl.bwd_form = ATTN_BWD_FAST; pl.bwd_waves = nw; pl.bwd_lds = lds_fast;
+  } else if (lds > ATTN_LDS) {  // K and V of a head do not fit in LDS: rows from global memory
+    pl.bwd_form = ATTN_BWD_GKV;
+    if (nwg >= 4) { pl.bwd_waves = nwg; pl.bwd_lds = lds_gkv; }
+  } else {
+    pl.bwd_form = ATTN_BWD_PLAIN; pl.bwd_waves = 4; pl.bwd_lds = lds;
+  }
+  return pl;
+}
 hipError_t launch_attn_train_fwd(const AttnTrainP& p, hipStream_t s) {
-  const size_t base = ((size_t)p.Lk * (p.hd + 1) + (size_t)p.Lk * p.hd) * 4;
+  const AttnTrainPlan pl = attn_train_plan(p.hd, p.Lq, p.Lk);
+  if (!pl.fwd_waves) return hipErrorInvalidValue;
   return attn_for_hd(p.hd, [&](auto hd) {
     constexpr int HD = decltype(hd)::value;
-    if (base + (size_t)4 * p.Lk * 4 > ATTN_LDS) {  // K and V of a head do not fit in LDS beside four score rows
-      const int nwg = attn_waves_gkv(p.Lk);
-      if (nwg < 4) return hipErrorInvalidValue;
-      return launch_attn(attn_train_fwd_kernel<HD, true>, nwg, (size_t)nwg * p.Lk * 4, p, s);
-    }
-    const int nw = attn_waves(base, p.Lk);
-    return launch_attn(attn_train_fwd_kernel<HD, false>, nw, base + (size_t)nw * p.Lk * 4, p, s);
+    if (pl.fwd_form == ATTN_FWD_GKV) return launch_attn(attn_train_fwd_kernel<HD, true>, pl.fwd_waves, pl.fwd_lds, p, s);
+    return launch_attn(attn_train_fwd_kernel<HD, false>, pl.fwd_waves, pl.fwd_lds, p, s);
   });
 }
 hipError_t launch_attn_train_bwd(const AttnTrainP& p_in, hipStream_t s) {
   AttnTrainP p = p_in;
   static const int probe = D2T_PROBE_ENV("D2T_ATTN_BWD_PROBE");  // timing probe: skip phases (bit mask)
   p.probe = probe;
-  const size_t lds = ((size_t)2 * p.Lk * (p.hd + 1) + 4 * (size_t)p.Lk) * 4;
-  const size_t base_fast = ((size_t)2 * p.Lk * (p.hd + 1) + (size_t)2 * p.Lq * p.hd) * 4;
-  const int nw = attn_waves(base_fast, p.Lk);
-  const size_t lds_fast = base_fast + (size_t)nw * p.Lk * 4;
+  const AttnTrainPlan pl = attn_train_plan(p.hd, p.Lq, p.Lk);
+  if (!pl.bwd_waves) return hipErrorInvalidValue;
   return attn_for_hd(p.hd, [&](auto hd) {
     constexpr int HD = decltype(hd)::value;
-    if (lds_fast <= ATTN_LDS) return launch_attn(attn_train_bwd_fast_kernel<HD>, nw, lds_fast, p, s);
-    if (lds > ATTN_LDS) {  // K and V of a head do not fit in LDS: rows from global memory
-      const int nwg = attn_waves_gkv(p.Lk);
-      if (nwg < 4) return hipErrorInvalidValue;
-      return launch_attn(attn_train_bwd_kernel<HD, true>, nwg, (size_t)nwg * p.Lk * 4, p, s);
-    }
-    return launch_attn(attn_train_bwd_kernel<HD, false>, 4, lds, p, s);
+    if (pl.bwd_form == ATTN_BWD_FAST) return launch_attn(attn_train_bwd_fast_kernel<HD>, pl.bwd_waves, pl.bwd_lds, p, s);
+    if (pl.bwd_form == ATTN_BWD_GKV) return launch_attn(attn_train_bwd_kernel<HD, true>, pl.bwd_waves, pl.bwd_lds, p, s);
+    return launch_attn(attn_train_bwd_kernel<HD, false>, pl.bwd_waves, pl.bwd_lds, p, s);
   });
 }
 

@@ -161,7 +161,8 @@ struct Tr {  // builder / runner bound to one context and stream
   int layernorm(int in, const std::string& key, float eps, int* out, float* into = nullptr);
   int bwd_ln(const Node& n);
   int attention(int qt, int qoff, int kvt, int koff, int voff, int nb, int Lq, int Lk, int heads, int hd, int causal,
-                const int64_t* keytok, int* out, bool attn_dropout = false);
+                const int64_t* keytok, int* out, bool attn_dropout = false, const uint8_t* given_mask = nullptr,
+                float given_scale = 1.f);
   int bwd_attn(const Node& n);
   int dropout(int in, int* out, float p = -1.f);
   int bwd_dropout(const Node& n);
@@ -224,6 +225,7 @@ struct d2t_train_state {
   int B = 0, H = 0, W = 0, L = 0;
   int logits_id = -1;
   bool have_forward = false;
+  bool poison = false;  // test entries: every Tr::alloc block starts as 0xFF bytes (NaN), filled on the stream
   ~d2t_train_state() {
     tape.release();
     for (auto& kv : grads) hipFree(kv.second);

@@ -949,6 +949,30 @@ int d2t_op_train_layernorm(const float* x, const float* gamma, const float* beta
 int d2t_op_train_attention(const float* q, const float* kv, const int64_t* keytok, const float* dy, float* y, float* dq,
                            float* dkv, int32_t nb, int32_t Lq, int32_t Lk, int32_t heads, int32_t hd, int32_t causal,
                            d2t_stream stream);
+/* The same node with everything the training step passes it (Tr::attention + Tr::bwd_attn themselves; tests/test_train_attn_ops_gpu.py).
+ * layout 0, separate: q [nb*Lq][D], kv [nb*Lk][2D] as above (D = heads*hd); gradients dq, dkv.
+ * layout 1, packed: qkv [nb*L][3D], one tape tensor passed as both operands with column offsets 0 / D / 2D, the call of the ViT
+ *   blocks and of the decoder's self-attention; needs Lq == Lk; gradient dqkv [nb*L][3D].
+ * dropmask (optional): keep mask [nb][heads][Lq][Lk], bytes, of nn.MultiheadAttention's dropout on the probabilities, used
+ *   with dropscale (finite, > 0) instead of a drawn mask.
+ * Outputs, each optional: y [nb*Lq][D]; dq / dkv or dqkv; probs [nb][heads][Lq][Lk], the saved softmax, copied on the stream
+ *   between forward and backward; ds, the same shape, what the backward left in its place.
+ * plan (optional, host): {forward form, forward waves, backward form, backward waves} as the launchers select them; forward
+ *   0 = K / V in LDS, 1 = K / V from global memory; backward 0 = coalesced "fast", 1 = plain LDS, 2 = global K / V; waves 0 =
+ *   the launcher refuses the shape.
+ * Every tape buffer of the entry (y, probs, the gradients of q / kv / qkv) starts as 0xFF bytes, so an element no kernel
+ * writes comes back NaN.  Every size is checked before anything is launched: D2T_EINVAL with nothing written (plan included).
+ * A shape the launchers refuse (Lk > 10240) is a non-zero status with plan filled and no other buffer touched. */
+typedef struct d2t_op_train_attention_args {
+  const float *q, *kv, *qkv, *dy;
+  const int64_t* keytok;
+  const uint8_t* dropmask;
+  float *y, *dq, *dkv, *dqkv, *probs, *ds;
+  int32_t* plan;
+  float dropscale;
+  int32_t layout, nb, Lq, Lk, heads, hd, causal;
+} d2t_op_train_attention_args;
+int d2t_op_train_attention_ex(const d2t_op_train_attention_args* a, d2t_stream stream);
 int d2t_op_train_maxpool(const float* x, const float* dy, float* y, float* dx, int32_t B, int32_t H, int32_t W, int32_t C,
                          int32_t SH, int32_t SW, int32_t PH, int32_t PW, d2t_stream stream);
 /* The backward kernels of the recurrent paths one at a time (csrc/train_recurrent.hip; test infrastructure with the rules of
