@@ -61,7 +61,7 @@ struct DecLayer {
   LinW sa_in, sa_out, ca_q, ca_out, l1, l2;
   LNW n1, n2, n3;
   float *sa_out_t = nullptr, *ca_q_t = nullptr, *ca_out_t = nullptr;  // [k][n] copies for the row kernel
-  // absorbed cross-attention (decode.hip decoder_row_absorbed_kernel): the key projection as stored ([o][c], in ckv_w), the
+  // absorbed cross-attention (decode_row.hip decoder_row_absorbed_kernel): the key projection as stored ([o][c], in ckv_w), the
   // value projection transposed ([c][o]) and its bias
   const float* ca_wk = nullptr;
   float* ca_v_t = nullptr;
@@ -181,7 +181,7 @@ struct d2t_ctx {
   int beam_shared_tile = 0;
   int no_shortcut_fusion = 0;  // debug / A-B: 1 = the 1x1 shortcuts as their own kernels (d2t_set_conv_fusion)
   int no_pool_fusion = 0;  // debug / A-B: 1 = the two 2x2 max-pools as their own kernels (d2t_set_conv_fusion)
-  float* beam_qp = nullptr; size_t beam_qp_cap = 0;  // beam, absorbed cross-attention: q' / context rows + LN1 rows (decode.hip)
+  float* beam_qp = nullptr; size_t beam_qp_cap = 0;  // beam, absorbed cross-attention: q' / context rows + LN1 rows (decode_row.hip, decode_beam.hip)
   int* h_pinned = nullptr;
   void* zero_page = nullptr;  // 256 zero bytes: out-of-image taps of the split-bf16 convolution
   // Decode chains: each owns its stream, self-attention cache, workspace, state block and output staging, so that with two

@@ -1,6 +1,6 @@
 // libd2t engine, TFM head: the decode step, captured step loops, greedy decodes (plain, grouped, ragged) and the ticket /
 // wait / query entries of the C-ABI.  The beam searches are engine_tfm_beam.hip's; what the two share is engine_tfm.h's.
-// Host code only: the kernels are decode.hip's.
+// Host code only: the kernels are decode.hip's, decode_gemm.hip's and decode_row.hip's.
 #include "engine_tfm.h"
 
 // (LinOpts is filled with designated initializers: C++20, which hipcc's clang takes in C++17 too)
@@ -68,7 +68,7 @@ hipError_t stage_memory(float* ckv, size_t plane, const float* memory, size_t n,
   hipError_t e = hipMemcpyAsync(ckv, memory, n * sizeof(float), hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) return e;
   const Planes pl = slot_planes(ckv, plane);
-  return launch_split_bf16(memory, pl.hi, pl.lo, n, s);  // the planes of the split-bf16 cross-attention (decode.hip)
+  return launch_split_bf16(memory, pl.hi, pl.lo, n, s);  // the planes of the split-bf16 cross-attention (decode_row.hip)
 }
 
 hipError_t cross_kv(d2t_ctx* c, hipStream_t s, const float* memory, int B, int T, float* ckv) {

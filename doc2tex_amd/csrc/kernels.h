@@ -317,7 +317,7 @@ struct DecRowP {
   const int* rows_ptr;                // optional (device-side beam search): blocks of rows >= *rows_ptr return at once
 };
 hipError_t launch_decoder_row(const DecRowP& p, hipStream_t s);
-// the same step with the cross-attention taken over the encoder memory itself (absorbed K / V projections, decode.hip):
+// the same step with the cross-attention taken over the encoder memory itself (absorbed K / V projections, decode_row.hip):
 // mem [samples][T][256] (row b attends over sample c_row_map[b] or b), wk [256][256] as stored, wv_t [c][o], bv [256]
 // mem_hi / mem_lo (optional, greedy two-row kernel only): the same rows as bf16 hi / lo planes (launch_split_bf16) -> the
 // cross-attention runs on split-bf16 MFMAs

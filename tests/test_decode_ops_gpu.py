@@ -1,5 +1,5 @@
-"""GPU: the decode step's kernels (csrc/decode.hip) ONE AT A TIME through the d2t_op_* test entries, against references
-written here in float64 from each operation's definition -- the skinny split-K GEMM and its LayerNorm prologue, the
+"""GPU: the decode step's kernels (csrc/decode.hip, decode_gemm.hip, decode_row.hip, decode_beam.hip) ONE AT A TIME
+through the d2t_op_* test entries, against references written here in float64 from each operation's definition -- the skinny split-K GEMM and its LayerNorm prologue, the
 fused decoder-row kernels (kinds 0-5 of d2t_op_decoder_row), argmax + embed with its end-of-sequence bookkeeping, the
 beam top-k, the device-side Beam.advance, the ancestry table and the cache gather.
 

@@ -106,7 +106,7 @@ def test_batch_shard_invariance(cases):
 
 
 def test_two_row_decode_blocks_do_not_couple_their_rows(cases):
-    """The d_model-512 decoder (ResNet + TFM stacks: T1 / C1) steps two rows per block (decode.hip decoder_row2_kernel): a row's
+    """The d_model-512 decoder (ResNet + TFM stacks: T1 / C1) steps two rows per block (decode_row.hip decoder_row2_kernel): a row's
     logits must not depend on which row shares its block, nor on the batch being odd (the last block repeats its row)."""
     c = dict(_case(cases, "greedy", "t1_greedy"))
     cfg, m = engine_model(c["config"], c["max_seq_len"], c["wseed"], c["end_bias"])

@@ -1,4 +1,4 @@
-"""GPU: the wide form of the decode step's skinny GEMM (csrc/decode.hip skinny_wide_kernel, block tile 32 x 64 at K = 256,
+"""GPU: the wide form of the decode step's skinny GEMM (csrc/decode_gemm.hip skinny_wide_kernel, block tile 32 x 64 at K = 256,
 32 x 32 for N <= 512 and at K = 512, 32 x 16 at K = 1024) against the split-K form, through d2t_op_skinny_form (form 0
 split-K, 1 wide).
 
