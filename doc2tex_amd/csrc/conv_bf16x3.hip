@@ -514,8 +514,6 @@ hipError_t launch_conv_bf16x3(const ConvP& p, hipStream_t s) {
 }
 
 // grid of the element-wise kernels below: 256 threads per block, grid-stride loops, at most `cap` blocks
-static dim3 grid_1d(size_t n, size_t cap) { return dim3((unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap)); }
-
 __global__ void split_bf16_kernel(const float* __restrict__ w, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
                                   size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {

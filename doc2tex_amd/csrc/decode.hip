@@ -228,9 +228,7 @@ __global__ void transpose_kernel(const float* __restrict__ src, float* __restric
   }
 }
 hipError_t launch_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s) {
-  const long long total = (long long)rows * cols;
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048)), dim3(256),
-                     0, s, src, dst, rows, cols);
+  hipLaunchKernelGGL(transpose_kernel, grid_1d((size_t)rows * cols, 2048), dim3(256), 0, s, src, dst, rows, cols);
   return hipGetLastError();
 }
 

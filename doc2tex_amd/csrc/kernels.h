@@ -25,6 +25,9 @@
 
 namespace d2t {
 
+// grid of a grid-stride kernel over n elements: 256-thread blocks, at most cap of them
+inline dim3 grid_1d(size_t n, size_t cap) { return dim3((unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap)); }
+
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
 enum { STORE_ROWS = 0, STORE_KV = 1 };
 

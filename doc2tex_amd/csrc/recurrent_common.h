@@ -1,6 +1,6 @@
 // Device helpers shared by the recurrent kernels: the BiLSTM and LSTM-attention decoder of inference (recurrent.hip) and
-// their backward kernels (train_recurrent.hip).  Each states the order of its floating-point operations: the kernels'
-// results are compared bit for bit across builds.
+// their backward kernels (train_recurrent.hip); ops.hip takes the block reductions from here.  Each states the order of its
+// floating-point operations: the kernels' results are compared bit for bit across builds.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,23 +67,25 @@ static __device__ __forceinline__ float sum_parts(const float* part, int stride,
 static __device__ __forceinline__ float sum_parts4_paired(const float* part, int stride, int i) {
   return (part[i] + part[stride + i]) + (part[2 * stride + i] + part[3 * stride + i]);
 }
-// Sum of v over the block's 16 waves, in every thread: wave butterfly, then the 16 wave sums left to right.  red: 16 floats
-// nobody else touches until the block's next barrier.
+// Sum of v over the block's WAVES waves, in every thread: wave butterfly, then the wave sums left to right from 0.  red:
+// WAVES floats nobody else touches until the block's next barrier.
+template <int WAVES = 16>
 static __device__ __forceinline__ float block_sum(float v, float* red, int wave, int lane) {
   v = wsum(v);
   if (lane == 0) red[wave] = v;
   __syncthreads();
-  return sum_parts<16>(red, 1, 0);
+  return sum_parts<WAVES>(red, 1, 0);
 }
 
-// Maximum of v over the block's 16 waves, in every thread; red as above.
+// Maximum of v over the block's WAVES waves, in every thread; red as above.
+template <int WAVES = 16>
 static __device__ __forceinline__ float block_max(float v, float* red, int wave, int lane) {
   v = wmax(v);
   if (lane == 0) red[wave] = v;
   __syncthreads();
   v = red[0];
 #pragma unroll
-  for (int w = 1; w < 16; ++w) v = fmaxf(v, red[w]);
+  for (int w = 1; w < WAVES; ++w) v = fmaxf(v, red[w]);
   return v;
 }
 

@@ -1,5 +1,5 @@
-// Wave-wide reductions shared by the training kernels (train_kernels.hip, train_attn.hip, train_recurrent.hip) and the
-// recurrent kernels (recurrent_common.h).
+// Wave-wide reductions shared by the training kernels (train_kernels.hip, train_attn.hip, train_recurrent.hip), the
+// recurrent kernels (recurrent_common.h) and, through that header, the encoder's small kernels (ops.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

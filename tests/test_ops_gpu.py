@@ -136,7 +136,7 @@ def test_maxpool_vs_torch(H, W, C, s, p):
     assert torch.equal(y.cpu().permute(0, 3, 1, 2), ref)  # bit-exact
 
 
-@pytest.mark.parametrize("D,eps", [(256, 1e-6), (512, 1e-5)])
+@pytest.mark.parametrize("D,eps", [(256, 1e-6), (512, 1e-5), (1024, 1e-5)])
 def test_layernorm_vs_torch(D, eps):
     lib = _lib.require_device()
     x = _rand(77, D, seed=16, scale=3.0) + 0.5
@@ -149,7 +149,9 @@ def test_layernorm_vs_torch(D, eps):
     assert float((y.cpu() - ref).abs().max()) <= 2e-6
 
 
-@pytest.mark.parametrize("B,N,heads", [(2, 10, 8), (2, 261, 8), (1, 406, 8), (3, 65, 16)])
+# (33: the first partial second key tile; 513: the first chunked launch; 1695: the largest shipped crop)
+@pytest.mark.parametrize("B,N,heads", [(2, 10, 8), (2, 261, 8), (1, 406, 8), (3, 65, 16), (1, 33, 8), (1, 513, 8),
+                                       (1, 1695, 8)])
 def test_vit_attention_vs_torch(B, N, heads):
     lib = _lib.require_device()
     C_ = heads * 32
@@ -161,6 +163,22 @@ def test_vit_attention_vs_torch(B, N, heads):
     a = ((q @ k.transpose(-2, -1)) * 32 ** -0.5).softmax(-1)
     ref = (a @ v).transpose(1, 2).reshape(B, N, C_).float()
     assert float((y.cpu() - ref).abs().max()) <= 2e-6
+
+
+@pytest.mark.parametrize("N", [33, 513])
+def test_vit_attention_probs_same_y(N):
+    """d2t_op_vit_attention_probs (the kernel's build that also writes the maps) returns d2t_op_vit_attention's y bit for
+    bit: one chunk with a partial tile, and a chunked launch."""
+    lib = _lib.require_device()
+    B, heads = 2, 8
+    qd = _rand(B, N, 3, heads, 32, seed=20).to(DEV)
+    y = torch.full((B, N, heads * 32), float("nan"), device=DEV)
+    yp = torch.full_like(y, float("nan"))
+    maps = torch.empty((B, heads, N, N), device=DEV)
+    assert lib.d2t_op_vit_attention(_lib.ptr(qd), _lib.ptr(y), B, N, heads, _lib.stream_of(qd)) == 0
+    assert lib.d2t_op_vit_attention_probs(_lib.ptr(qd), _lib.ptr(yp), _lib.ptr(maps), B, N, heads, _lib.stream_of(qd)) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(y.cpu(), yp.cpu())
 
 
 @pytest.mark.parametrize("B,heads,hd,L,Lmax", [(3, 8, 32, 1, 152), (3, 8, 32, 152, 152), (2, 8, 32, 261, 261),
