@@ -59,7 +59,7 @@ class D2TOpConvRecordsArgs(C.Structure):  # include/d2t.h d2t_op_conv_records_ar
         [(n, C.c_int32) for n in (
             "in_fmt", "res_fmt", "out_fmt", "B", "H", "W", "Cin", "Cin2", "Cout", "KH", "KW", "SH", "SW", "PH", "PW", "OH", "OW",
             "act", "pool2", "rows_per_img", "img_stride", "row_off", "row_add_off", "row_add_rows", "out_rows", "kind",
-            "split_tail")]
+            "split_tail", "max_blocks", "reserved_cus")]
 
 
 class D2TOpAttnLstmBwdArgs(C.Structure):  # include/d2t.h d2t_op_attn_lstm_bwd_args

@@ -33,21 +33,13 @@
 // 256 x 256 tile on eight waves, a loader-less 8-wave form, Winograd F(2x2,3x3) -- all bit-identical or equally accurate, none
 // faster in serving (docs/experiments_r03.md).  They left the tree in round 4 (git history: round 3).
 
-#include "conv_common.h"
+#include <type_traits>
+
+#include "conv_dma.h"
 
 namespace d2t {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 namespace {
-constexpr int PBK = 32;   // K-step
-constexpr int PROW = 64;  // bytes per LDS row of one plane (32 bf16)
-// swz_chunk (conv_common.h) for the 16x16x32 fragment pattern (lane -> row lane & 15, 16-byte k-chunk lane >> 4): the 16-lane service groups
-// of a ds_read_b128 then pair rows 0-3 / 12-15 at chunk c with rows 4-11 at chunk c ^ 1, and XOR-ing bit 1 of the chunk
-// with bit 3 of the row spreads every group over all 64 banks (tools/probe/lds_swizzle_check.py)
-__device__ __forceinline__ int pswz16(int row, int c) { return c ^ ((row >> 2) & 2); }
-
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field on gfx9");
@@ -69,100 +61,6 @@ __device__ unsigned long long d2t_conv_phase[16];
 #endif
 }  // namespace
 
-// The vector-memory side of a tile for ONE issuing wave: which 16-row pieces of the A / B planes it copies, their per-lane
-// source addresses (XOR-swizzled k-chunk applied on the SOURCE: the LDS destination of a wave's LDS-DMA is linear) and the
-// per-row validity mask over the filter taps (out-of-image taps and rows beyond M / Cout read a zero page).
-// A operand: one LDS row per tile row holding the whole 128-byte record [hi 64 | lo 64]; a 1 KiB piece = 8 rows x 128 B, i.e.
-// a wave's LDS-DMA touches 8 full cache lines instead of 16 half lines (the vector-memory path's cost is per line touched:
-// 32-byte segments measured half the rate of 64-byte ones).  The eight 16-byte chunks of a row are XOR-ed with (row >> 1) & 7
-// -- on the source side of the DMA and on the ds_read side -- so that the 16-lane groups of a ds_read_b128 hit every bank once.
-__device__ __forceinline__ int aswz(int row, int c) { return c ^ ((row >> 1) & 7); }
-
-// F16 (ConvP::f16): only the hi half of a record (the fp16 activation) is staged -- a piece is 16 rows x 64 B, the A plane
-// BM x 64 B with the B planes' swizzle (pswz16)
-template <int BM, int BN, int LW, int ABL, bool S16 = false, bool F16 = false>
-struct DmaIssuer {
-  static constexpr int AJ = BM / ((F16 ? 16 : 8) * LW), BJ = BN / (16 * LW);
-  static constexpr int PLANE_A = BM * PROW, PLANE_B = BN * PROW, STAGE = (F16 ? 1 : 2) * PLANE_A + 2 * PLANE_B;
-  static constexpr int A_BYTES = (F16 ? 1 : 2) * PLANE_A;
-  static constexpr int PER_STEP = AJ + 2 * BJ;  // LDS-DMA instructions per K-step
-  static_assert(AJ >= 1 && BJ >= 1, "tile too small for the issuing waves");
-  static_assert(PER_STEP <= 31, "two K-steps of pieces must fit the 6-bit vmcnt");
-  int a_off[AJ];
-  int a_off2[AJ];  // second input (ConvP::in2_hi): element offset of this lane's chunk of the row's first record, -1 = no row
-  unsigned a_mask[AJ];
-  const uint16_t* b_hi[BJ];
-  const uint16_t* b_lo[BJ];
-  int kh, kw, c0, lw;
-
-  __device__ __forceinline__ void setup(const ConvP& p, int m0, int n0, int lw_, int lane) {
-    lw = lw_;
-    kh = kw = c0 = 0;
-    const int lr = lane >> 2, pos = lane & 3;
-    const int ohow = p.OH * p.OW;
-#pragma unroll
-    for (int j = 0; j < AJ; ++j) {
-      const int row = F16 ? (lw * AJ + j) * 16 + (lane >> 2) : (lw * AJ + j) * 8 + (lane >> 3);
-      const int c = F16 ? pswz16(row, lane & 3) : aswz(row, lane & 7);  // the chunk of the record that belongs at this lane's LDS position
-      const int m = m0 + row;
-      a_off[j] = 0;
-      a_off2[j] = -1;
-      a_mask[j] = 0;
-      if (m < p.M) {
-        if (p.Cin2) a_off2[j] = m * p.Cin2 * 2 + c * 8;
-        int b, oh, ow;
-        conv_row_coords(p, m, b, oh, ow);
-        const int ih0 = oh * p.SH - p.PH, iw0 = ow * p.SW - p.PW;
-        a_off[j] = ((b * p.H + ih0) * p.W + iw0) * p.Cin * 2 + c * 8;
-        for (int y = 0; y < p.KH; ++y)
-          for (int x = 0; x < p.KW; ++x)
-            if ((unsigned)(ih0 + y) < (unsigned)p.H && (unsigned)(iw0 + x) < (unsigned)p.W) a_mask[j] |= 1u << (y * p.KW + x);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < BJ; ++j) {
-      const int row = (lw * BJ + j) * 16 + lr;
-      const int c = S16 ? pswz16(row, pos) : swz_chunk(row, pos);
-      const int n = n0 + row;
-      const bool ok = n < p.Cout;
-      b_hi[j] = ok ? p.w_hi + (size_t)n * p.K + c * 8 : nullptr;
-      b_lo[j] = ok ? p.w_lo + (size_t)n * p.K + c * 8 : nullptr;
-    }
-  }
-  // K-steps must be issued in order (the tap / channel-chunk cursor advances)
-  __device__ __forceinline__ void issue(const ConvP& p, unsigned char* smem, int kt, int buf) {
-    unsigned char* ah = smem + buf * STAGE;
-    unsigned char* bh = ah + A_BYTES;
-    unsigned char* bl = bh + PLANE_B;
-    const uint16_t* zero = reinterpret_cast<const uint16_t*>(p.zero16);
-    const bool second = c0 >= p.Cin;  // the K-steps behind the filter taps: the 1x1 second input (wave-uniform)
-    const int tap = kh * p.KW + kw;
-    const int tapoff = second ? (c0 - p.Cin) * 2 : ((kh * p.W + kw) * p.Cin + c0) * 2;
-#pragma unroll
-    for (int j = 0; j < AJ; ++j) {
-      const uint16_t* src;
-      if (second) src = a_off2[j] >= 0 ? p.in2_hi + (a_off2[j] + tapoff) : zero;
-      else src = ((a_mask[j] >> tap) & 1u) ? p.in_hi + (a_off[j] + tapoff) : zero;
-      const int piece = (lw * AJ + j) * 1024;
-      if (ABL == 1) continue;
-      __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(ah + piece), 16, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < BJ; ++j) {
-      const int piece = (lw * BJ + j) * 1024;
-      if (ABL == 1) continue;
-      __builtin_amdgcn_global_load_lds(b_hi[j] ? b_hi[j] + (size_t)kt * PBK : zero, (lds_ptr_t)(bh + piece), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(b_lo[j] ? b_lo[j] + (size_t)kt * PBK : zero, (lds_ptr_t)(bl + piece), 16, 0, 0);
-    }
-    if (second) {
-      c0 += 32;
-    } else if (++kw == p.KW) {
-      kw = 0;
-      if (++kh == p.KH) { kh = 0; c0 += 32; }
-    }
-  }
-};
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The kernel body on v_mfma_f32_16x16x32_bf16 (round 3; rounds 1-2 used 32x32x16): one MFMA consumes the WHOLE K-step of
 // 32 for a 16 x 16 output block (16 cycles on a SIMD) instead of half of it for a 32 x 32 block (32 cycles).  Per K-step a
@@ -175,223 +73,189 @@ struct DmaIssuer {
 // rounding; every kernel that may compute rows of the same layer must use the same shape -- see launch_conv_bf16x3p).
 // The stagger splits a K-step by ROW BLOCKS (first two of A, then the other two) since it can no longer be split by k:
 // waves 4-7 carry the B fragments and the second pair of A fragments across the barrier.
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-
+//
 // F16 (ConvP::f16, fp16x2 mode): A = the fp16 hi halves of the records only (12 instead of 16 fragment reads, 8 instead of
 // 12 LDS-DMA pieces per loader and K-step), B = fp16 hi / lo planes, 32 MFMAs (x * w_lo, x * w_hi) instead of 48
 template <int BM, int BN, int WM, int WN, int NL, bool STG, int ABL = 0, bool F16 = false>  // ABL (probe builds): 1 no LDS-DMA, 2 no MFMA, 4 LDS-DMA never awaited
-__device__ __forceinline__ void conv_bf16x3p16_body(const ConvP& p, unsigned char* smem) {
-  constexpr int NW = WM * WN, NT = (NW + NL) * 64;
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int MI = WTM / 16, NJ = WTN / 16, MH = MI / 2;
-  constexpr int NSTG = 3;  // LDS stages in the ring
-  constexpr bool UPFRONT = ABL != 8;  // (8: the reads as the compiler schedules them, for A/B timing in probe builds)
+struct conv_bf16x3p16_body {
+  static constexpr int NW = WM * WN, NT = (NW + NL) * 64;
+  static constexpr int WTM = BM / WM, WTN = BN / WN;
+  static constexpr int MI = WTM / 16, NJ = WTN / 16, MH = MI / 2;
+  static constexpr int NSTG = 3;  // LDS stages in the ring
+  static constexpr bool UPFRONT = ABL != 8;  // (8: the reads as the compiler schedules them, for A/B timing in probe builds)
   static_assert(MI >= 2 && (MI & 1) == 0 && NJ >= 1 && NL > 0, "wave tile / loader configuration");
-  using Issuer = DmaIssuer<BM, BN, NL, ABL == 1 ? 1 : 0, true, F16>;
-  constexpr int PLANE_B = Issuer::PLANE_B, STAGE = Issuer::STAGE, PER_STEP = Issuer::PER_STEP, A_BYTES = Issuer::A_BYTES;
-  static_assert(F16 || BM * BN * 4 <= 3 * STAGE, "the fp32 epilogue tile must fit in the staging area");  // (F16: the kernel allocates the tile's 128 KB)
+  using Issuer = DmaIssuer<std::conditional_t<F16, AHalfF16, ARecords>, BM, BN, NL, true, ABL == 1>;
+  static constexpr int PLANE_B = Issuer::PLANE_B, STAGE = Issuer::STAGE, PER_STEP = Issuer::PER_STEP, A_BYTES = Issuer::A_BYTES;
+  // the ring, or the epilogue's fp32 tile where that is larger (the fp16x2 256 x 128 build: 32 KB stages, a 128 KB tile)
+  static constexpr int SMEM = NSTG * STAGE > BM * BN * 4 ? NSTG * STAGE : BM * BN * 4;
 
-  const int nt = (p.Cout + BN - 1) / BN;
-  const int ntiles = nt * ((p.M - p.m_base + BM - 1) / BM);  // rows [m_base, M): the rows a 256 x 256 launch left over
-  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const bool loader = wave >= NW;  // wave-uniform
-  const int KT = p.K / PBK;
-  const int G = gridDim.x, xq = G >> 3, xr = G & 7, xcd = blockIdx.x & 7;
-  const int slot = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
+  static __device__ __forceinline__ void run(const ConvP& p, unsigned char* smem) {
+    const int nt = (p.Cout + BN - 1) / BN;
+    const int ntiles = nt * ((p.M - p.m_base + BM - 1) / BM);  // rows [m_base, M): the rows a 256 x 256 launch left over
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const bool loader = wave >= NW;  // wave-uniform
+    const int KT = p.K / XBK;
+    const int G = gridDim.x, slot = xcd_logical_tile();
 
-  CONV_PHASE_INIT();
-  for (int tile = slot; tile < ntiles; tile += G) {
-    const int m0 = p.m_base + (tile / nt) * BM;
-    const int n0 = (tile % nt) * BN;
-    CONV_PHASE(0);  // previous tile's last barrier .. here (loop overhead; the first tile: kernel entry)
-    CONV_PHASE_TILE();
-    if (loader) {  // (the compute waves below run the same barrier sequence)
-      Issuer dma;
-      dma.setup(p, m0, n0, wave - NW, lane);
-      dma.issue(p, smem, 0, 0);
-      if (KT > 1) dma.issue(p, smem, 1, 1);
-      int nxt2 = 2;
-      for (int kt = 0; kt < KT; ++kt) {
-        if (ABL != 4) { if (kt + 1 < KT) wait_vm<PER_STEP>(); else wait_vm<0>(); }
+    CONV_PHASE_INIT();
+    for (int tile = slot; tile < ntiles; tile += G) {
+      const int m0 = p.m_base + (tile / nt) * BM;
+      const int n0 = (tile % nt) * BN;
+      CONV_PHASE(0);  // previous tile's last barrier .. here (loop overhead; the first tile: kernel entry)
+      CONV_PHASE_TILE();
+      if (loader) {  // (the compute waves below run the same barrier sequence)
+        Issuer dma(p, m0, n0, wave - NW, lane);
+        dma.issue(p, smem, 0, 0);
+        if (KT > 1) dma.issue(p, smem, 1, 1);
+        int nxt2 = 2;
+        for (int kt = 0; kt < KT; ++kt) {
+          if (ABL != 4) { if (kt + 1 < KT) wait_vm<PER_STEP>(); else wait_vm<0>(); }
+          __builtin_amdgcn_s_barrier();
+          if (kt + 2 < KT) dma.issue(p, smem, kt + 2, nxt2);
+          nxt2 = nxt2 == 2 ? 0 : nxt2 + 1;
+        }
+        if (ABL == 4) wait_vm<0>();
         __builtin_amdgcn_s_barrier();
-        if (kt + 2 < KT) dma.issue(p, smem, kt + 2, nxt2);
-        nxt2 = nxt2 == 2 ? 0 : nxt2 + 1;
+        __builtin_amdgcn_s_barrier();
+        if (wide_epilogue_ok(p)) { if (p.pool2) tile_rows_epilogue<Epi::pool, 8, BM, BN, NT>(p, smem, m0, n0, tid); else tile_rows_epilogue<Epi::lean, 8, BM, BN, NT>(p, smem, m0, n0, tid); }
+        __builtin_amdgcn_s_barrier();
+        continue;
       }
-      if (ABL == 4) wait_vm<0>();
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_s_barrier();
-      if (wide_epilogue_ok(p)) { if (p.pool2) tile_rows_epilogue<Epi::pool, 8, BM, BN, NT>(p, smem, m0, n0, tid); else tile_rows_epilogue<Epi::lean, 8, BM, BN, NT>(p, smem, m0, n0, tid); }
-      __builtin_amdgcn_s_barrier();
-      continue;
-    }
-    const int wm = wave / WN, wn = wave % WN;
-    const int r = lane & 15, q = lane >> 4;
-    f32x4v acc[MI][NJ];
+      const int wm = wave / WN, wn = wave % WN;
+      const int r = lane & 15, q = lane >> 4;
+      f32x4v acc[MI][NJ];
+      zero_acc(acc);
+      int offa[MI], offal[MI], offb[NJ];
 #pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    int offa[MI], offal[MI], offb[NJ];
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const int row = wm * WTM + i * 16 + r;
-      offa[i] = F16 ? row * PROW + pswz16(row, q) * 16 : row * 128 + aswz(row, q) * 16;
-      offal[i] = row * 128 + aswz(row, 4 + q) * 16;  // (unused with F16)
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int row = wn * WTN + j * 16 + r;
-      offb[j] = row * PROW + pswz16(row, q) * 16;
-    }
-    auto read_b = [&](const unsigned char* ah, bf16x8 (&fbh)[NJ], bf16x8 (&fbl)[NJ]) {
-      const unsigned char* bh = ah + A_BYTES;
-      const unsigned char* bl = bh + PLANE_B;
+      for (int i = 0; i < MI; ++i) {
+        const int row = wm * WTM + i * 16 + r;
+        offa[i] = F16 ? row * XROW + pswz16(row, q) * 16 : row * 128 + aswz(row, q) * 16;
+        offal[i] = row * 128 + aswz(row, 4 + q) * 16;  // (unused with F16)
+      }
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        fbh[j] = *reinterpret_cast<const bf16x8*>(bh + offb[j]);
-        fbl[j] = *reinterpret_cast<const bf16x8*>(bl + offb[j]);
+        const int row = wn * WTN + j * 16 + r;
+        offb[j] = row * XROW + pswz16(row, q) * 16;
       }
-    };
-    auto read_a = [&](const unsigned char* ah, auto half_c, bf16x8 (&fah)[MH], bf16x8 (&fal)[MH]) {
-      constexpr int half = decltype(half_c)::value;
-#pragma unroll
-      for (int i = 0; i < MH; ++i) {
-        fah[i] = *reinterpret_cast<const bf16x8*>(ah + offa[half * MH + i]);
-        if (!F16) fal[i] = *reinterpret_cast<const bf16x8*>(ah + offal[half * MH + i]);
-      }
-    };
-    auto mma = [&](auto half_c, const bf16x8 (&fah)[MH], const bf16x8 (&fal)[MH], const bf16x8 (&fbh)[NJ], const bf16x8 (&fbl)[NJ]) {
-      constexpr int half = decltype(half_c)::value;
-#pragma unroll
-      for (int i = 0; i < MH; ++i)
+      auto read_b = [&](const unsigned char* ah, bf16x8 (&fbh)[NJ], bf16x8 (&fbl)[NJ]) {
+        const unsigned char* bh = ah + A_BYTES;
+        const unsigned char* bl = bh + PLANE_B;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-          if (ABL == 2) {  // keep the reads alive, drop the matrix work
-            asm volatile("" ::"v"(fal[i]), "v"(fah[i]), "v"(fbh[j]), "v"(fbl[j]));
-            continue;
-          }
-          f32x4v c = acc[half * MH + i][j];
-          if (F16) {
-            const f16x8v xa = __builtin_bit_cast(f16x8v, fah[i]);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xa, __builtin_bit_cast(f16x8v, fbl[j]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xa, __builtin_bit_cast(f16x8v, fbh[j]), c, 0, 0, 0);
-            acc[half * MH + i][j] = c;
-            continue;
-          }
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fal[i], fbh[j], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fah[i], fbl[j], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fah[i], fbh[j], c, 0, 0, 0);
-          acc[half * MH + i][j] = c;
+          fbh[j] = *reinterpret_cast<const bf16x8*>(bh + offb[j]);
+          fbl[j] = *reinterpret_cast<const bf16x8*>(bl + offb[j]);
         }
-    };
-    using H0 = std::integral_constant<int, 0>;
-    using H1 = std::integral_constant<int, 1>;
-    int cur = 0;
-    const bool late = STG && wave >= NW / 2;
-    if (!late) {
-      for (int kt = 0; kt < KT; ++kt) {
-        __builtin_amdgcn_s_barrier();  // stage kt (and kt + 1) complete for everyone; nobody reads the stages before
-        if (kt == 0) CONV_PHASE(1);  // setup + the first two stages' LDS-DMA landed (pipeline fill)
-        const unsigned char* ah = smem + cur * STAGE;
-        // all sixteen fragment reads of the K-step go out before the first MFMA (the SIMD partner's carried MFMAs cover
-        // their latency); left to itself the compiler interleaves them in three groups, each with its own wait
-        bf16x8 fbh[NJ], fbl[NJ], fah[MH], fal[MH], fch[MH], fcl[MH];
-        read_b(ah, fbh, fbl);
-        read_a(ah, H0{}, fah, fal);
-        read_a(ah, H1{}, fch, fcl);
-        if (UPFRONT) __builtin_amdgcn_sched_barrier(0);
-        mma(H0{}, fah, fal, fbh, fbl);
-        mma(H1{}, fch, fcl, fbh, fbl);
-        cur = cur == NSTG - 1 ? 0 : cur + 1;
-      }
-    } else {
-      bf16x8 gah[MH], gal[MH], gbh[NJ], gbl[NJ];  // second-half A fragments and the step's B fragments, carried across the barrier
-      auto step = [&](auto carried_c, int kt) {
-        __builtin_amdgcn_s_barrier();
-        const unsigned char* ah = smem + cur * STAGE;
-        if (decltype(carried_c)::value) mma(H1{}, gah, gal, gbh, gbl);  // second half of the previous K-step
-        __builtin_amdgcn_sched_barrier(0);  // (no reads of this step hoisted above: the carried fragments die first)
-        read_b(ah, gbh, gbl);
-        {
-          bf16x8 fah[MH], fal[MH];
-          read_a(ah, H0{}, fah, fal);
-          if (UPFRONT) {  // the carried half's fragments are requested before the first half's MFMAs, not after them
-            read_a(ah, H1{}, gah, gal);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          mma(H0{}, fah, fal, gbh, gbl);
-        }
-        if (!UPFRONT) read_a(ah, H1{}, gah, gal);
-        // the reads have returned before this wave arrives at the next barrier (after it the stage may be overwritten)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        cur = cur == NSTG - 1 ? 0 : cur + 1;
       };
-      step(H0{}, 0);  // peeled: nothing carried into K-step 0
-      for (int kt = 1; kt < KT; ++kt) step(H1{}, kt);
-      mma(H1{}, gah, gal, gbh, gbl);
-    }
-    CONV_PHASE(2);  // the K loop of this wave
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // every wave is done with the last stages: the staging area becomes the epilogue's fp32 tile
-    CONV_PHASE(3);  // waiting for the other waves (staggered partners finish half a K-step later)
-    if (wide_epilogue_ok(p)) {  // block-uniform
-      acc_to_tile<Map16, BN>(acc, reinterpret_cast<float*>(smem), wm * WTM, wn * WTN, r, q);
+      auto read_a = [&](const unsigned char* ah, auto half_c, bf16x8 (&fah)[MH], bf16x8 (&fal)[MH]) {
+        constexpr int half = decltype(half_c)::value;
+#pragma unroll
+        for (int i = 0; i < MH; ++i) {
+          fah[i] = *reinterpret_cast<const bf16x8*>(ah + offa[half * MH + i]);
+          if (!F16) fal[i] = *reinterpret_cast<const bf16x8*>(ah + offal[half * MH + i]);
+        }
+      };
+      auto mma = [&](auto half_c, const bf16x8 (&fah)[MH], const bf16x8 (&fal)[MH], const bf16x8 (&fbh)[NJ], const bf16x8 (&fbl)[NJ]) {
+        constexpr int half = decltype(half_c)::value;
+#pragma unroll
+        for (int i = 0; i < MH; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            if (ABL == 2) {  // keep the reads alive, drop the matrix work
+              asm volatile("" ::"v"(fal[i]), "v"(fah[i]), "v"(fbh[j]), "v"(fbl[j]));
+              continue;
+            }
+            acc[half * MH + i][j] = product<F16>(acc[half * MH + i][j], fah[i], fal[i], fbh[j], fbl[j]);
+          }
+      };
+      using H0 = std::integral_constant<int, 0>;
+      using H1 = std::integral_constant<int, 1>;
+      int cur = 0;
+      const bool late = STG && wave >= NW / 2;
+      if (!late) {
+        for (int kt = 0; kt < KT; ++kt) {
+          __builtin_amdgcn_s_barrier();  // stage kt (and kt + 1) complete for everyone; nobody reads the stages before
+          if (kt == 0) CONV_PHASE(1);  // setup + the first two stages' LDS-DMA landed (pipeline fill)
+          const unsigned char* ah = smem + cur * STAGE;
+          // all sixteen fragment reads of the K-step go out before the first MFMA (the SIMD partner's carried MFMAs cover
+          // their latency); left to itself the compiler interleaves them in three groups, each with its own wait
+          bf16x8 fbh[NJ], fbl[NJ], fah[MH], fal[MH], fch[MH], fcl[MH];
+          read_b(ah, fbh, fbl);
+          read_a(ah, H0{}, fah, fal);
+          read_a(ah, H1{}, fch, fcl);
+          if (UPFRONT) __builtin_amdgcn_sched_barrier(0);
+          mma(H0{}, fah, fal, fbh, fbl);
+          mma(H1{}, fch, fcl, fbh, fbl);
+          cur = cur == NSTG - 1 ? 0 : cur + 1;
+        }
+      } else {
+        bf16x8 gah[MH], gal[MH], gbh[NJ], gbl[NJ];  // second-half A fragments and the step's B fragments, carried across the barrier
+        auto step = [&](auto carried_c, int kt) {
+          __builtin_amdgcn_s_barrier();
+          const unsigned char* ah = smem + cur * STAGE;
+          if (decltype(carried_c)::value) mma(H1{}, gah, gal, gbh, gbl);  // second half of the previous K-step
+          __builtin_amdgcn_sched_barrier(0);  // (no reads of this step hoisted above: the carried fragments die first)
+          read_b(ah, gbh, gbl);
+          {
+            bf16x8 fah[MH], fal[MH];
+            read_a(ah, H0{}, fah, fal);
+            if (UPFRONT) {  // the carried half's fragments are requested before the first half's MFMAs, not after them
+              read_a(ah, H1{}, gah, gal);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            mma(H0{}, fah, fal, gbh, gbl);
+          }
+          if (!UPFRONT) read_a(ah, H1{}, gah, gal);
+          // the reads have returned before this wave arrives at the next barrier (after it the stage may be overwritten)
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          cur = cur == NSTG - 1 ? 0 : cur + 1;
+        };
+        step(H0{}, 0);  // peeled: nothing carried into K-step 0
+        for (int kt = 1; kt < KT; ++kt) step(H1{}, kt);
+        mma(H1{}, gah, gal, gbh, gbl);
+      }
+      CONV_PHASE(2);  // the K loop of this wave
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      CONV_PHASE(4);  // accumulators to the LDS tile + barrier
-      if (p.pool2) tile_rows_epilogue<Epi::pool, 8, BM, BN, NT>(p, smem, m0, n0, tid);
-      else tile_rows_epilogue<Epi::lean, 8, BM, BN, NT>(p, smem, m0, n0, tid);
-      CONV_PHASE(5);  // this thread's rows: LDS reads, bias / residual / activation / split, stores issued
-    } else {  // (row remap, positional add, Cout % 32 != 0)
-      __builtin_amdgcn_s_barrier();
-      conv_epilogue<Map16, ElemThreeWay>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, q);
+      __builtin_amdgcn_s_barrier();  // every wave is done with the last stages: the staging area becomes the epilogue's fp32 tile
+      CONV_PHASE(3);  // waiting for the other waves (staggered partners finish half a K-step later)
+      if (wide_epilogue_ok(p)) {  // block-uniform
+        acc_to_tile<Map16, BN>(acc, reinterpret_cast<float*>(smem), wm * WTM, wn * WTN, r, q);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        CONV_PHASE(4);  // accumulators to the LDS tile + barrier
+        if (p.pool2) tile_rows_epilogue<Epi::pool, 8, BM, BN, NT>(p, smem, m0, n0, tid);
+        else tile_rows_epilogue<Epi::lean, 8, BM, BN, NT>(p, smem, m0, n0, tid);
+        CONV_PHASE(5);  // this thread's rows: LDS reads, bias / residual / activation / split, stores issued
+      } else {  // (row remap, positional add, Cout % 32 != 0)
+        __builtin_amdgcn_s_barrier();
+        conv_epilogue<Map16, ElemThreeWay>(p, acc, m0 + wm * WTM, n0 + wn * WTN, r, q);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // the tile is staging memory again (next tile's LDS-DMA)
+      CONV_PHASE(6);  // waiting for the slowest thread's epilogue
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // the tile is staging memory again (next tile's LDS-DMA)
-    CONV_PHASE(6);  // waiting for the slowest thread's epilogue
   }
-}
+};
 
 
-// non-template entry points (the host-side stub of a __global__ template using the LDS-DMA builtin is not emitted)
-__global__ __launch_bounds__(768, 3) void conv_bf16x3p16_256x128_s(const ConvP p) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[3 * (2 * 256 * PROW + 2 * 128 * PROW)];
-  conv_bf16x3p16_body<256, 128, 4, 2, 4, true>(p, smem);
-}
-// the dominant GEMM shape (512 -> 512 channels, 3x3: K = 4608) under its own symbol, so that rocprofv3's per-kernel rows
-// separate it from the other layers
-__global__ __launch_bounds__(768, 3) void conv_bf16x3p16_256x128_s_k4608(const ConvP p) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[3 * (2 * 256 * PROW + 2 * 128 * PROW)];
-  conv_bf16x3p16_body<256, 128, 4, 2, 4, true>(p, smem);
-}
-
+// 256 x 128 tile, 8 compute waves as 4 x 2 + 4 loaders, staggered; the dominant GEMM shape (512 -> 512 channels, 3x3:
+// K = 4608) under its own symbol, so that rocprofv3's per-kernel rows separate it from the other layers
+D2T_CONV_ENTRY(conv_bf16x3p16_256x128_s, 3, conv_bf16x3p16_body<256, 128, 4, 2, 4, true>)
+D2T_CONV_ENTRY(conv_bf16x3p16_256x128_s_k4608, 3, conv_bf16x3p16_body<256, 128, 4, 2, 4, true>)
 // 64 x 128 tile on the same body (eight 64 x 16 wave tiles + four loaders, 24 KB stages): the rows of a last, sparsely
 // filled round of 256-row tiles (launch_conv_bf16x3p).  Same MFMA shape, K order and products: bit-identical to the 256 x 128
 // build, so which of the two computes a row never shows in the values.
-__global__ __launch_bounds__(768, 3) void conv_bf16x3p16_64x128_tail(const ConvP p) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[3 * (2 * 64 * PROW + 2 * 128 * PROW)];
-  conv_bf16x3p16_body<64, 128, 1, 8, 4, false>(p, smem);
-}
-__global__ __launch_bounds__(768, 3) void conv_f16x2p16_64x128_tail(const ConvP p) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[3 * (64 * PROW + 2 * 128 * PROW)];  // 20 KB stages (>= the 32 KB fp32 tile)
-  conv_bf16x3p16_body<64, 128, 1, 8, 4, false, 0, true>(p, smem);
-}
-
-// fp16x2 builds of the pipelined kernel (ConvP::f16): 32 KB stages; the 128 KB are the epilogue's fp32 tile
-__global__ __launch_bounds__(768, 3) void conv_f16x2p16_256x128_s(const ConvP p) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[256 * 128 * 4];
-  conv_bf16x3p16_body<256, 128, 4, 2, 4, true, 0, true>(p, smem);
-}
-__global__ __launch_bounds__(768, 3) void conv_f16x2p16_256x128_s_k4608(const ConvP p) {  // the dominant shape, own symbol
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[256 * 128 * 4];
-  conv_bf16x3p16_body<256, 128, 4, 2, 4, true, 0, true>(p, smem);
-}
+D2T_CONV_ENTRY(conv_bf16x3p16_64x128_tail, 3, conv_bf16x3p16_body<64, 128, 1, 8, 4, false>)
+// fp16x2 builds (ConvP::f16)
+D2T_CONV_ENTRY(conv_f16x2p16_64x128_tail, 3, conv_bf16x3p16_body<64, 128, 1, 8, 4, false, 0, true>)
+D2T_CONV_ENTRY(conv_f16x2p16_256x128_s, 3, conv_bf16x3p16_body<256, 128, 4, 2, 4, true, 0, true>)
+D2T_CONV_ENTRY(conv_f16x2p16_256x128_s_k4608, 3, conv_bf16x3p16_body<256, 128, 4, 2, 4, true, 0, true>)
 
 #ifdef D2T_PROBES  // ablation probes of the 16x16x32 kernel (D2T_CONV_ABL=1|2|4): results are garbage by construction
 template <int ABL>
 __global__ __launch_bounds__(768, 3) void conv_bf16x3p16_probe(const ConvP p) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[3 * (2 * 256 * PROW + 2 * 128 * PROW)];
-  conv_bf16x3p16_body<256, 128, 4, 2, 4, true, ABL>(p, smem);
+  using Body = conv_bf16x3p16_body<256, 128, 4, 2, 4, true, ABL>;
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[Body::SMEM];
+  Body::run(p, smem);
 }
 #endif
 
@@ -412,7 +276,6 @@ hipError_t launch_conv_bf16x3p(const ConvP& p, hipStream_t s) {
   }
   if (p.pipelined != 3 || p.store_mode != STORE_ROWS) return hipErrorInvalidValue;  // (no head-split store in this kernel's epilogues)
   ConvP q = p;
-  q.wave_prio = D2T_PROBE_ENV("D2T_CONV_PRIO");
   const int nt = (p.Cout + 127) / 128;
   int grid = cus - (p.reserved_cus > 0 ? p.reserved_cus : 0);
   if (grid < 8) grid = 8;
@@ -456,7 +319,6 @@ hipError_t launch_conv_bf16x3p(const ConvP& p, hipStream_t s) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || tail_from < 0) return e;
   ConvP t = p;
-  t.wave_prio = q.wave_prio;
   t.m_base = tail_from;
   const int tt = ((p.M - tail_from + 63) / 64) * nt;
   if (p.f16) hipLaunchKernelGGL(conv_f16x2p16_64x128_tail, dim3(tt), dim3(768), 0, s, t);

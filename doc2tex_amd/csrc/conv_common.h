@@ -128,6 +128,13 @@ __device__ __forceinline__ size_t plane_idx(size_t row, int c, int C) {
 __device__ __forceinline__ int swz_chunk(int row, int c) { return c ^ ((row >> 2) & 3); }
 
 // GEMM row m -> output pixel (b, oh, ow): row-major, or pooled order when a 2x2 max-pool is fused (ConvP::pool2)
+__device__ __forceinline__ void row_major_coords(const ConvP& p, int m, int& b, int& oh, int& ow) {
+  const int ohow = p.OH * p.OW;
+  b = m / ohow;
+  const int rem = m - b * ohow;
+  oh = rem / p.OW;
+  ow = rem - oh * p.OW;
+}
 __device__ __forceinline__ void conv_row_coords(const ConvP& p, int m, int& b, int& oh, int& ow) {
   if (p.pool2) {
     const int q = m >> 2, sb = m & 3, pw2 = p.OW >> 1, ph2 = p.OH >> 1;
@@ -136,11 +143,129 @@ __device__ __forceinline__ void conv_row_coords(const ConvP& p, int m, int& b, i
     b = t / ph2;
     oh = 2 * (t - b * ph2) + (sb >> 1);
   } else {
-    const int ohow = p.OH * p.OW;
-    b = m / ohow;
-    const int rem = m - b * ohow;
-    oh = rem / p.OW;
-    ow = rem - oh * p.OW;
+    row_major_coords(p, m, b, oh, ow);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The K loop's phases, each written once for the fp32 kernel (conv_mfma.hip), the split-bf16 kernels (conv_bf16x3.hip) and
+// the pipelined kernel (conv_bf16x3p.hip).  All of them are inlined, and the callers' register budgets
+// decided their form: check the resource table of every kernel of the three sources after touching one.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int XBK = 32;   // K-step
+constexpr int XROW = 64;  // bytes per LDS row of one 16-bit plane (32 elements)
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// THE K ORDER, and with it the bits, of every convolution: position of the next K-step to fetch.  Taps cycle fastest (kw,
+// then kh), then the 32-channel chunk -> the taps of a chunk re-read the same 128-byte channel slices of neighbouring pixels
+// back to back (L2 / L1 hits instead of HBM).  SECOND: behind the last chunk the K-steps of a 1x1 second input follow
+// (ConvP::in2_hi, c0 - Cin = its channel chunk; wave-uniform).
+template <bool SECOND = false>
+struct TapCursor {
+  int kh = 0, kw = 0, c0 = 0;
+  __device__ __forceinline__ bool second(const ConvP& p) const { return SECOND && c0 >= p.Cin; }
+  __device__ __forceinline__ int tap(const ConvP& p) const { return kh * p.KW + kw; }  // bit of a row's tap mask
+  // element offset of this K-step's 32 channels from the first channel of a row's top-left tap (NHWC) -- or, in the second
+  // input, from the first channel of the row
+  __device__ __forceinline__ int offset(const ConvP& p) const { return second(p) ? c0 - p.Cin : (kh * p.W + kw) * p.Cin + c0; }
+  __device__ __forceinline__ void advance(const ConvP& p) {
+    if (second(p)) {
+      c0 += 32;
+    } else if (++kw == p.KW) {
+      kw = 0;
+      if (++kh == p.KH) { kh = 0; c0 += 32; }
+    }
+  }
+};
+
+// A GEMM row of the kernels that read fp32 rows: top-left input coordinate of output pixel m and the sample's first pixel
+struct F32Row {
+  int ih0, iw0, pix;
+};
+__device__ __forceinline__ F32Row f32_row(const ConvP& p, int m) {
+  if (m >= p.M) return {-0x40000000, 0, 0};  // never in range
+  int b, oh, ow;
+  row_major_coords(p, m, b, oh, ow);
+  return {oh * p.SH - p.PH, ow * p.SW - p.PW, b * p.H * p.W};
+}
+
+// A GEMM row of the kernels that read records: `off` = element offset (uint16 units) of 16-byte chunk `chunk` of the record
+// at the row's top-left tap, first channel chunk (negative in the padding); `mask` = validity over the filter taps (bit
+// kh * KW + kw; KH * KW <= 16).  Rows beyond M: no valid tap.
+// Through references, not a returned pair: with the pair the pipelined 256 x 128 build, which sits at its register limit,
+// came out with 28 instead of 20 bytes of scratch per lane and 2 % more instructions.
+__device__ __forceinline__ void rec_row(const ConvP& p, int m, int chunk, int& off, unsigned& mask) {
+  off = 0;
+  mask = 0;
+  if (m < p.M) {
+    int b, oh, ow;
+    conv_row_coords(p, m, b, oh, ow);
+    const int ih0 = oh * p.SH - p.PH, iw0 = ow * p.SW - p.PW;
+    off = ((b * p.H + ih0) * p.W + iw0) * p.Cin * 2 + chunk * 8;
+    for (int kh = 0; kh < p.KH; ++kh)
+      for (int kw = 0; kw < p.KW; ++kw)
+        if ((unsigned)(ih0 + kh) < (unsigned)p.H && (unsigned)(iw0 + kw) < (unsigned)p.W) mask |= 1u << (kh * p.KW + kw);
+  }
+}
+// 16-byte chunk `chunk` of K-step 0 of weight row n in the hi / lo planes; nullptr for rows beyond Cout
+struct WeightRow {
+  const uint16_t* hi;
+  const uint16_t* lo;
+};
+__device__ __forceinline__ WeightRow weight_row(const ConvP& p, int n, int chunk) {
+  const bool ok = n < p.Cout;
+  return {ok ? p.w_hi + (size_t)n * p.K + chunk * 8 : nullptr, ok ? p.w_lo + (size_t)n * p.K + chunk * 8 : nullptr};
+}
+
+template <class A, int MI, int NJ>
+__device__ __forceinline__ void zero_acc(A (&acc)[MI][NJ]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = A{};
+}
+
+// THE ARITHMETIC CONTRACT: one product of split operands on top of acc -- lo*hi, hi*lo, hi*hi in this order (the dropped
+// lo*lo term is ~2^-18 relative), or with F16 (ConvP::f16: a_hi holds the fp16 activation, a_lo is not read, the weights are
+// fp16 hi / lo) x*w_lo, x*w_hi.  The only place that spells the order of the MFMAs of a product: "the 256 x 128 kernel and
+// its 64 x 128 tail are bit-identical" rests on it.  One overload per MFMA shape (32x32x16: half a K-step, 16x16x32: all of it).
+template <bool F16 = false>
+__device__ __forceinline__ f32x16 product(f32x16 acc, bf16x8 a_hi, bf16x8 a_lo, bf16x8 b_hi, bf16x8 b_lo) {
+  if constexpr (F16) {
+    const f16x8 x = __builtin_bit_cast(f16x8, a_hi);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, __builtin_bit_cast(f16x8, b_lo), acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(x, __builtin_bit_cast(f16x8, b_hi), acc, 0, 0, 0);
+  } else {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_hi, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_lo, acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_hi, acc, 0, 0, 0);
+  }
+}
+template <bool F16 = false>
+__device__ __forceinline__ f32x4v product(f32x4v acc, bf16x8 a_hi, bf16x8 a_lo, bf16x8 b_hi, bf16x8 b_lo) {
+  if constexpr (F16) {
+    const f16x8 x = __builtin_bit_cast(f16x8, a_hi);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(x, __builtin_bit_cast(f16x8, b_lo), acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, __builtin_bit_cast(f16x8, b_hi), acc, 0, 0, 0);
+  } else {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_lo, b_hi, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_hi, b_lo, acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_hi, b_hi, acc, 0, 0, 0);
+  }
+}
+
+// Fragments of the 32x32x16 MFMAs from the swizzled 64-byte-row planes (swz_chunk): N blocks of 32 rows from row0 on, lane
+// (r = lane & 31, h = lane >> 5) reads 16-byte chunk c = 2 * kk + h of row r of each block.  LO = false: no lo plane (F16 A operand).
+template <bool LO = true, int N>
+__device__ __forceinline__ void read_frags32(const unsigned char* hi, const unsigned char* lo, int row0, int c, bf16x8 (&fh)[N], bf16x8 (&fl)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int row = row0 + i * 32;
+    const int off = row * XROW + swz_chunk(row, c) * 16;
+    fh[i] = *reinterpret_cast<const bf16x8*>(hi + off);
+    if (LO) fl[i] = *reinterpret_cast<const bf16x8*>(lo + off);
   }
 }
 
@@ -148,7 +273,7 @@ __device__ __forceinline__ void conv_row_coords(const ConvP& p, int m, int& b, i
 // same XCD so they share its L2 (bijective remap, cdna guide T1).
 __device__ __forceinline__ int xcd_logical_tile() {
   const int nwg = gridDim.x, orig = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
 }
 
 // C/D register maps of the MFMAs: row of register `reg` of a lane in the result block whose first row is `base`.  A lane's

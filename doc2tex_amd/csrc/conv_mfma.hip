@@ -21,7 +21,6 @@
 
 namespace d2t {
 
-constexpr int BK = 32;
 constexpr int LDS_LD = 36;  // padded row length in floats (144 B = 9 x 16 B)
 
 template <int BM, int BN>
@@ -45,23 +44,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvP p) {
   const int lrow = tid >> 3;  // 0..31
 
   // per-thread A rows: output pixel -> top-left input coordinate
-  int a_ih0[AR], a_iw0[AR], a_pix[AR];
-  const int ohow = p.OH * p.OW;
+  F32Row a[AR];
 #pragma unroll
-  for (int i = 0; i < AR; ++i) {
-    const int m = m0 + lrow + 32 * i;
-    if (m < p.M) {
-      const int b = m / ohow, rem = m - b * ohow;
-      const int oh = rem / p.OW, ow = rem - oh * p.OW;
-      a_ih0[i] = oh * p.SH - p.PH;
-      a_iw0[i] = ow * p.SW - p.PW;
-      a_pix[i] = b * p.H * p.W;
-    } else {
-      a_ih0[i] = -0x40000000;  // never in range
-      a_iw0[i] = 0;
-      a_pix[i] = 0;
-    }
-  }
+  for (int i = 0; i < AR; ++i) a[i] = f32_row(p, m0 + lrow + 32 * i);
   const float* b_ptr[BR];
   bool b_ok[BR];
 #pragma unroll
@@ -72,15 +57,15 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvP p) {
   }
 
   float4 ra[AR], rb[BR];
-  int kh = 0, kw = 0, c0 = 0;  // position of the NEXT K-step to fetch
-  const int KT = p.K / BK;
+  TapCursor<> cur;  // the NEXT K-step to fetch
+  const int KT = p.K / XBK;
 
   auto fetch = [&](int kt) {
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
-      const int ih = a_ih0[i] + kh, iw = a_iw0[i] + kw;
+      const int ih = a[i].ih0 + cur.kh, iw = a[i].iw0 + cur.kw;
       if ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
-        const float* src = p.in + (size_t)(a_pix[i] + ih * p.W + iw) * p.Cin + c0 + kq * 4;
+        const float* src = p.in + (size_t)(a[i].pix + ih * p.W + iw) * p.Cin + cur.c0 + kq * 4;
         ra[i] = *reinterpret_cast<const float4*>(src);
       } else {
         ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -88,15 +73,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvP p) {
     }
 #pragma unroll
     for (int i = 0; i < BR; ++i) {
-      rb[i] = b_ok[i] ? *reinterpret_cast<const float4*>(b_ptr[i] + (size_t)kt * BK)
+      rb[i] = b_ok[i] ? *reinterpret_cast<const float4*>(b_ptr[i] + (size_t)kt * XBK)
                       : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    // next K-step: taps cycle fastest, then the 32-channel chunk -> the nine taps of a chunk re-read the
-    // same 128-byte channel slices of neighbouring pixels back to back (L2 / L1 hits instead of HBM)
-    if (++kw == p.KW) {
-      kw = 0;
-      if (++kh == p.KH) { kh = 0; c0 += 32; }
-    }
+    cur.advance(p);
   };
   auto stage = [&](int buf) {
     float* a = As + buf * BM * LDS_LD;
@@ -112,29 +92,24 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvP p) {
   const int r = lane & 31, h = lane >> 5;
 
   f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   fetch(0);
   stage(0);
   __syncthreads();
 
   for (int kt = 0; kt < KT; ++kt) {
-    const int cur = kt & 1;
+    const int buf = kt & 1;
     if (kt + 1 < KT) fetch(kt + 1);  // global loads in flight under the MFMAs
-    const float* a = As + cur * BM * LDS_LD + (wm * WTM + r) * LDS_LD + h * 4;
-    const float* b = Bs + cur * BN * LDS_LD + (wn * WTN + r) * LDS_LD + h * 4;
+    const float* fa0 = As + buf * BM * LDS_LD + (wm * WTM + r) * LDS_LD + h * 4;
+    const float* fb0 = Bs + buf * BN * LDS_LD + (wn * WTN + r) * LDS_LD + h * 4;
 #pragma unroll
-    for (int kc = 0; kc < BK / 8; ++kc) {
+    for (int kc = 0; kc < XBK / 8; ++kc) {
       float4 fa[MI], fb[NJ];
 #pragma unroll
-      for (int i = 0; i < MI; ++i) fa[i] = *reinterpret_cast<const float4*>(a + i * 32 * LDS_LD + kc * 8);
+      for (int i = 0; i < MI; ++i) fa[i] = *reinterpret_cast<const float4*>(fa0 + i * 32 * LDS_LD + kc * 8);
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) fb[j] = *reinterpret_cast<const float4*>(b + j * 32 * LDS_LD + kc * 8);
+      for (int j = 0; j < NJ; ++j) fb[j] = *reinterpret_cast<const float4*>(fb0 + j * 32 * LDS_LD + kc * 8);
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -145,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvP p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
         }
     }
-    if (kt + 1 < KT) stage(cur ^ 1);
+    if (kt + 1 < KT) stage(buf ^ 1);
     __syncthreads();
   }
 
@@ -169,7 +144,7 @@ hipError_t launch_conv(const ConvP& p, hipStream_t s) {
   // bf16 weight planes select the split-bf16 kernel whatever the problem size, so that a row's result never depends on
   // how many other rows (batch size, shard) share the launch
   if (p.w_hi && p.w_lo && p.Cout >= 64) return launch_conv_bf16x3(p, s);
-  if (p.Cin % BK != 0 || p.K != p.KH * p.KW * p.Cin) return hipErrorInvalidValue;
+  if (p.Cin % XBK != 0 || p.K != p.KH * p.KW * p.Cin) return hipErrorInvalidValue;
   const long long tiles128 = (long long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
   if (p.Cout <= 64) {
     if ((long long)((p.M + 127) / 128) >= 256) return launch_cfg<128, 64>(p, s);

@@ -155,6 +155,7 @@ int d2t_op_conv_records(const d2t_op_conv_records_args* a, d2t_stream stream) {
       a->KH * a->KW > 16 || a->SH < 1 || a->SW < 1 || a->PH < 0 || a->PW < 0 || a->PH >= a->KH || a->PW >= a->KW)
     return D2T_EINVAL;
   if (a->act < ACT_NONE || a->act > ACT_GELU || (a->kind != 0 && a->kind != 3) || a->out_rows < 1) return D2T_EINVAL;
+  if (a->max_blocks < 0 || a->reserved_cus < 0) return D2T_EINVAL;
   if (a->in_fmt == 3 && a->Cout < 64) return D2T_EINVAL;  // (launch_conv sends fp32 rows with fewer channels to the fp32 kernel)
   if (a->H + 2 * a->PH < a->KH || a->W + 2 * a->PW < a->KW) return D2T_EINVAL;
   const int OH = a->OH >= 0 ? a->OH : (a->H + 2 * a->PH - a->KH) / a->SH + 1;
@@ -211,6 +212,7 @@ int d2t_op_conv_records(const d2t_op_conv_records_args* a, d2t_stream stream) {
   if (a->in_fmt != 4) { p.w_hi = whi; p.w_lo = wlo; }
   if (rec_in) { p.in_hi = a->x_rec; p.zero16 = zero; p.f16 = f16; } else p.in = a->x_f32;
   p.pipelined = a->kind; p.split_tail = a->split_tail != 0;
+  p.max_blocks = a->max_blocks; p.reserved_cus = a->reserved_cus;
   p.res = a->res_f32;
   if (a->res_rec) { p.res_hi = a->res_rec; p.res_fmt = 1 + a->res_fmt; }
   if (a->out_rec) { p.out_hi = a->out_rec; p.out_fmt = 1 + a->out_fmt; } else p.out = a->out_f32;

@@ -50,7 +50,6 @@ struct ConvP {
   const void* zero16;
   int max_blocks;        // > 0: launch at most this many (persistent) blocks of the split-bf16 kernel
   int reserved_cus;      // pipelined split-bf16 kernel (one block per CU): CUs left free for other streams' kernels
-  int wave_prio;         // pipelined kernel: s_setprio of its waves (experiments; 0 = default)
   int pipelined;         // 3: take the pipelined 256x128 kernel (conv_bf16x3p.hip) when the layer qualifies (Cout >= 128); 0: the 128-row kernels
   int split_tail;        // pipelined kernel: hand the rows of a sparsely filled last round of tiles to its 64 x 128 build
   // != 0: a 2x2 / stride 2 max-pool (resnet.py:94,106) fused into the epilogue of the split-record LDS-DMA kernels
@@ -58,7 +57,7 @@ struct ConvP {
   // row m = 4 * pooled pixel + (oh & 1) * 2 + (ow & 1), M = 4 * B * (OH / 2) * (OW / 2) -- and the wide epilogue writes one
   // record row per four tile rows (their maximum) at the pooled pixel.  Needs the wide epilogue (no remap, no residual).
   int pool2;
-  // second input of the pipelined split-record kernels (conv_bf16x3p.hip DmaIssuer): a 1x1 / stride 1 convolution over
+  // second input of the pipelined split-record kernels (conv_dma.h DmaIssuer): a 1x1 / stride 1 convolution over
   // `in2_hi` (split records [M][Cin2], the same pixels as the output) appended along K -- K = KH*KW*Cin + Cin2, the
   // weights' K rows concatenated.  A BasicBlock's shortcut (resnet.py:181-192) computed inside its conv2's launch:
   // conv2(t) + downsample(x) in ONE accumulator, no shortcut kernel, no residual round trip.

@@ -8,7 +8,7 @@
 //   stem_wgrad_kernel     the stem convolution (one or three image channels)
 //
 // The three GEMM kernels share their block coordinates (WgradBlock), the pixel -> input-row geometry (wgrad_src_row), the
-// transposing fragment read (frag_tr16) and the accumulator zeroing / store (zero_acc, wgrad_store_tile).
+// transposing fragment read (frag_tr16) and the accumulator store (wgrad_store_tile; conv_common.h zero_acc).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,15 +44,6 @@ __device__ __forceinline__ long long wgrad_src_row(const WgradP& p, long long r,
   const int ih = oh * p.SH - p.PH + kh, iw = ow * p.SW - p.PW + kw;
   ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
   return ((long long)b * p.H + ih) * p.W + iw;
-}
-template <int MI, int NJ>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NJ]) {
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 }
 // a wave's MI x NJ accumulators of 32 x 32 (MFMA layout: lane = column r + 32 h, register -> row) to out[M][N] from
 // (mw, nw) on; GUARD: the tile may reach past M / N

@@ -684,7 +684,9 @@ int d2t_op_records_merge(const uint16_t* planes, float* x, int64_t rows, int32_t
  * Remap (rows_per_img > 0): GEMM row m goes to output row (m / rows_per_img) * img_stride + row_off + m % rows_per_img.
  * row_add [row_add_rows][Cout] (optional): row row_add_off + m % rows_per_img (row_add_off without a remap) is added
  * behind the activation.
- * kind: 0 / 3 as d2t_set_conv_kernel; split_tail: ConvP::split_tail. */
+ * kind: 0 / 3 as d2t_set_conv_kernel; split_tail: ConvP::split_tail.
+ * max_blocks > 0: at most that many (persistent) blocks of the 128-row record kernels; reserved_cus > 0: the pipelined kernel
+ * runs one block on each of (CUs - reserved_cus) CUs, at least 8 (ConvP::max_blocks / reserved_cus).  Negative: refused. */
 typedef struct d2t_op_conv_records_args {
   const uint16_t* x_rec; const float* x_f32; const uint16_t* x2_rec;
   const float* w; const float* w2; const float* bias; const float* bias2;
@@ -694,6 +696,7 @@ typedef struct d2t_op_conv_records_args {
   int32_t B, H, W, Cin, Cin2, Cout, KH, KW, SH, SW, PH, PW, OH, OW, act, pool2;
   int32_t rows_per_img, img_stride, row_off, row_add_off, row_add_rows, out_rows;
   int32_t kind, split_tail;
+  int32_t max_blocks, reserved_cus;
 } d2t_op_conv_records_args;
 int d2t_op_conv_records(const d2t_op_conv_records_args* a, d2t_stream stream);
 /* The head-split K / V store of cross_kv (STORE_KV): y [slabs][kv_B][heads][kv_T][hd] from x [M = kv_B * kv_T][K] @ w [N][K]^T

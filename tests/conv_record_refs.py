@@ -1,4 +1,4 @@
-"""Restatements of the encoder's record path (csrc/conv_common.h, conv_bf16x3.hip, ops.hip, engine_weights.hip) in plain
+"""Restatements of the encoder's record path (csrc/conv_common.h, conv_records.hip, ops.hip, engine_weights.hip) in plain
 numpy / torch on the CPU, written from what the headers DOCUMENT, not from what the device returns: the three record formats
 bit by bit, the plane layout, the row orders and remaps of the convolution epilogues, the kernels' K order and the BatchNorm
 fold in float64.  Shared by tests/test_conv_records_gpu.py and tests/test_conv_record_refs_cpu.py, which pins every function

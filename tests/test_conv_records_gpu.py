@@ -126,10 +126,12 @@ def held(x, fmt):
 
 
 def conv_records(geom, x, w, bias, in_fmt, out=None, res=None, res_fmt=None, x2=None, w2=None, bias2=None, row_add=None,
-                 remap=None, kind=3, split_tail=1, pool2=0, act=1, out_rows=None, guard=0, grid=None):
+                 remap=None, kind=3, split_tail=1, pool2=0, act=1, out_rows=None, guard=0, grid=None, max_blocks=0,
+                 reserved_cus=0):
     """One d2t_op_conv_records.  geom = (B, H, W, Cin, Cout, (KH, KW), (SH, SW), (PH, PW)); x: device planes (in_fmt 0-2) or
     fp32 rows (3, 4); w [Cout][KH][KW][Cin]; out: None = fp32 rows, 0-2 = records of that format; res: device planes (res_fmt
-    0-2) or fp32 rows (res_fmt None); remap = (rows_per_img, img_stride, row_off, row_add_off); grid = (OH, OW) override.
+    0-2) or fp32 rows (res_fmt None); remap = (rows_per_img, img_stride, row_off, row_add_off); grid = (OH, OW) override;
+    max_blocks / reserved_cus: ConvP's grid caps.
     The output holds out_rows + guard rows prefilled with NaN / SENT16.  -> (rc, output on the host: fp32 [rows][Cout] or raw
     planes)"""
     lib = _lib.require_device()
@@ -161,6 +163,7 @@ def conv_records(geom, x, w, bias, in_fmt, out=None, res=None, res_fmt=None, x2=
     a.Cin2 = 0 if w2 is None else w2.shape[1]
     a.OH, a.OW = grid if grid else (-1, -1)
     a.act, a.pool2, a.kind, a.split_tail, a.out_rows = act, pool2, kind, split_tail, out_rows
+    a.max_blocks, a.reserved_cus = max_blocks, reserved_cus
     if remap:
         a.rows_per_img, a.img_stride, a.row_off, a.row_add_off = remap
     a.row_add_rows = 0 if row_add is None else row_add.shape[0]
@@ -465,6 +468,117 @@ def test_identity_remap_with_a_position_table(in_fmt):
     err = np.abs(plain - ref)
     print("identity remap", in_fmt, "max err", float(err.max()))
     assert (err <= {0: 4e-4, 1: 2e-4, 3: 4e-4, 4: 2e-4}[in_fmt]).all(), float(err.max())
+
+
+# --- the persistent tile loops and the K loops' ends ---
+def arithmetic_reference(x, w, b, geom, in_fmt):
+    """float64 convolution + bias + ReLU by this file's rule: of the unrounded inputs for the split-bf16 arithmetic (records of
+    format 0, fp32 rows split on the fly) and the fp32 kernel, of the ROUNDED inputs (the fp16 hi half of the record, fp16 hi +
+    lo weights) for fp16 records.  -> (reference, absolute bound)"""
+    B, H, W, Cin, Cout, k, st, pd = geom
+    if in_fmt == 1:
+        xr = R.mma_operand(*R.split_act(x.numpy(), 1), 1)
+        wh, wl = R.split_weight_f16(w.numpy())
+        wr = torch.from_numpy(R.f16_bits_to_f32(wh).astype(np.float64) + R.f16_bits_to_f32(wl))
+    else:
+        xr, wr = x.double().numpy(), w.double()
+    y = R.conv_ref(xr, B, H, W, wr.permute(0, 3, 1, 2).numpy(), b.double().numpy(), st, pd)
+    return R.finish_ref(y, 1), {0: 4e-4, 1: 2e-4, 3: 4e-4, 4: 2e-4}[in_fmt]
+
+
+@functools.lru_cache(maxsize=8)
+def round_inputs(H, Cout):
+    """one image of H x 64 pixels, 32 channels, 3x3 / pad 1"""
+    M, Cin = H * 64, 32
+    x = _rand(M, Cin, seed=141)
+    w = _rand(Cout, 3, 3, Cin, seed=142, scale=(2.0 / (9 * Cin)) ** 0.5)
+    b = _rand(Cout, seed=143, scale=0.1)
+    dev = dict(w=w.to(DEV), b=b.to(DEV), x={f: to_records(x.to(DEV), f) for f in (0, 1)})
+    return (1, H, 64, Cin, Cout, (3, 3), (1, 1), (1, 1)), dict(x=x, w=w, b=b), dev
+
+
+@pytest.mark.parametrize("in_fmt", [0, 1])
+@pytest.mark.parametrize("Cout", [64, 96, 256])
+def test_capped_grid_of_the_128_row_kernels_runs_several_rounds_per_block(Cout, in_fmt):
+    """ConvP::max_blocks on conv_bf16x3g_body's persistent loop: M = 1536 = 12 row tiles, so 12 tiles on conv_bf16x3g_128x64
+    (Cout 64) and 24 on ..._128x128_w8 (Cout 256); with fp16 records (in_fmt 1) conv_f16x2g_128x64.  A grid of 5 blocks takes
+    the tiles in identity order, one of 8 in the XCD order (G % 8 == 0), and in both the last round is short, so blocks leave
+    through `logical >= ntiles`.  Either equals the uncapped launch (one tile per block) bit for bit; that one meets the float64
+    bound.  fp16 records with 128 channels or more belong to the pipelined kernel alone (launch_conv_bf16x3 refuses them on
+    kind 0), so Cout 256 with in_fmt 1 is a refusal with any cap, and Cout 96 (12 tiles) is the case that runs
+    conv_f16x2g_128x128_w8 through its rounds."""
+    geom, host, d = round_inputs(24, Cout)
+    if (Cout, in_fmt) == (256, 1):
+        for cap in (0, 5, 8):
+            rc, y = conv_records(geom, d["x"][1], d["w"], d["b"], 1, kind=0, max_blocks=cap)
+            assert rc == _lib.D2T_EINVAL and np.isnan(y).all(), cap
+        return
+    rc, base = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, kind=0)
+    assert rc == 0 and np.isfinite(base).all()
+    ref, bound = arithmetic_reference(host["x"], host["w"], host["b"], geom, in_fmt)
+    err = np.abs(base - ref)
+    print("rounds g", Cout, in_fmt, "max err", float(err.max()))
+    assert (err <= bound).all(), float(err.max())
+    for cap in (5, 8):
+        rc, y = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, kind=0, max_blocks=cap)
+        assert rc == 0 and np.array_equal(y, base), cap
+    rc, y = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, kind=0, max_blocks=-1)
+    assert rc == _lib.D2T_EINVAL and np.isnan(y).all()
+
+
+@pytest.mark.parametrize("in_fmt", [0, 1])
+@pytest.mark.parametrize("H", [40, 36])
+def test_clamped_grid_of_the_pipelined_kernel_runs_several_rounds_per_block(H, in_fmt):
+    """ConvP::reserved_cus on conv_bf16x3p16_body's persistent loop: Cout 256 and 40 x 64 pixels are 20 tiles of 256 x 128; a
+    reservation beyond the chip's CUs clamps the grid to the launcher's minimum of 8 blocks, so a block runs 2 or 3 tiles.  With
+    split_tail 0 and 1 the output equals the unreserved launch (one tile per block) bit for bit; that one meets the float64 bound.
+    At 40 rows the 4 tiles behind the two whole rounds are exactly half a round, which launch_conv_bf16x3p (rem < 0.5 * grid)
+    leaves to the 256 x 128 kernel; at 36 rows (18 tiles: two rounds + 2) it hands rows 2048 .. 2303 to the 64 x 128 tail
+    kernel, whose rows then follow two rounds of the clamped grid."""
+    geom, host, d = round_inputs(H, 256)
+    rc, base = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, kind=3)
+    assert rc == 0 and np.isfinite(base).all()
+    ref, bound = arithmetic_reference(host["x"], host["w"], host["b"], geom, in_fmt)
+    err = np.abs(base - ref)
+    print("rounds p", H, in_fmt, "max err", float(err.max()))
+    assert (err <= bound).all(), float(err.max())
+    for tail in (0, 1):
+        rc, y = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, kind=3, split_tail=tail, reserved_cus=1 << 20)
+        assert rc == 0 and np.array_equal(y, base), tail
+    rc, y = conv_records(geom, d["x"][in_fmt], d["w"], d["b"], in_fmt, kind=3, reserved_cus=-1)
+    assert rc == _lib.D2T_EINVAL and np.isnan(y).all()
+
+
+# 1x1 convolutions of 1 .. 5 K-steps.  kind matters for records only; fp16 records with 128 channels need the pipelined kernel
+SHORT_K = [(f, Co, kind) for f in (0, 1) for Co in (64, 128) for kind in (0, 3) if (f, Co, kind) != (1, 128, 0)] + \
+    [(f, Co, 3) for f in (3, 4) for Co in (64, 128)]
+
+
+@pytest.mark.parametrize("in_fmt,Cout,kind", SHORT_K)
+@pytest.mark.parametrize("Cin", [32, 64, 96, 128, 160])
+def test_short_k_loops(Cin, in_fmt, Cout, kind):
+    """K loops of 1 to 5 steps on 2 x 5 x 13 = 130 rows (one row tile and two rows): the prologue alone, `if (KT > 1)` of the
+    on-the-fly kernel's and the pipelined loader's second fetch, the on-the-fly kernel's steady state with three / two / one
+    step left in both DEEP forms (<128, 64, 2, 2, true> at Cout 64, <128, 128, 4, 2, false> at 128), the peeled first step of
+    the pipelined body's staggered waves, the ring of three stages wrapping once, the fp32 kernel's and conv_bf16x3g_body's
+    two-stage loops.  Against float64 by this file's rule; the second sample's rows equal a batch-of-one launch bit for bit."""
+    B, H, W = 2, 5, 13
+    M = B * H * W
+    x = _rand(M, Cin, seed=151 + Cin)
+    w = _rand(Cout, 1, 1, Cin, seed=152, scale=(2.0 / Cin) ** 0.5)
+    b = _rand(Cout, seed=153, scale=0.1)
+    geom = (B, H, W, Cin, Cout, (1, 1), (1, 1), (0, 0))
+    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
+    xin = to_records(xd, in_fmt) if in_fmt <= 2 else xd
+    rc, y = conv_records(geom, xin, wd, bd, in_fmt, kind=kind, guard=1)
+    assert rc == 0 and np.isfinite(y[:M]).all() and np.isnan(y[M:]).all()
+    ref, bound = arithmetic_reference(x, w, b, geom, in_fmt)
+    err = np.abs(y[:M] - ref)
+    print("short K", (Cin, in_fmt, Cout, kind), "max err", float(err.max()))
+    assert (err <= bound).all(), float(err.max())
+    n = H * W * Cin * (2 if in_fmt <= 2 else 1)  # elements of one sample (records: two uint16 per value)
+    rc, y1 = conv_records((1,) + geom[1:], xin.reshape(-1)[n:], wd, bd, in_fmt, kind=kind)
+    assert rc == 0 and np.array_equal(y1, y[H * W:M])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
