@@ -94,7 +94,8 @@ NORM_ALB, NORM_RAW = 0, 1
 PREP_OK, PREP_UNBOUND_LOCAL, PREP_FALLBACK = 0, 1, 2
 PREP_FLAG_PASTE_MISMATCH = 1
 POST_NONE, POST_API, POST_DEMO = 0, 1, 2
-ATTN_MAP_BUDGET = 256 << 20  # include/d2t.h D2T_ATTN_MAP_BUDGET: bytes of a beam search's alignment history
+ATTN_MAP_BUDGET = 256 << 20  # include/d2t.h D2T_ATTN_MAP_BUDGET: bytes of a beam search's alignment history, or of a call's cross-attention maps
+TOK_PAD, TOK_GO, TOK_END = 0, 1, 2  # csrc/ctx.h: the TFM head's special tokens (converter/tfm_converter.py:8)
 ATTN_MAX_CLASSES = 16384  # include/d2t.h D2T_ATTN_MAX_CLASSES: largest num_class of the Attn / Attnv2 heads
 METRIC_ED_MAX_LEN = 32768  # include/d2t.h D2T_METRIC_ED_MAX_LEN: longest string d2t_metric_edit_distance takes
 METRIC_ED_LDS_LEN = 4095  # include/d2t.h D2T_METRIC_ED_LDS_LEN: shorter string of a pair up to which the DP stays in LDS
@@ -137,6 +138,7 @@ SIGNATURES = {
                                           _P]),
     "d2t_decode_supports_ragged_beam": (_I, [_P]),
     "d2t_ragged_beam_tables": (_L, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "d2t_decode_cross_attention": (_I, [_P, _P, _I, _I, _P, _I, C.c_uint32, _I, _P, _P]),
     "d2t_decode_attn_beam_batch": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P]),
     "d2t_decode_attn_beam_batch_alpha": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_I), C.POINTER(C.c_float), _P,
                                                _P]),
@@ -190,6 +192,7 @@ SIGNATURES = {
     "d2t_op_decoder_row_ragged": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 4 + [C.POINTER(_I), C.POINTER(_I), _P]),
     "d2t_op_decoder_row_ragged_beam": (_I, [_I] + [_P] * 13 + [C.c_float, _P, _P] + [_I] * 5 +
                                        [C.POINTER(_I), C.POINTER(_I), _P, _P, _I, _P]),
+    "d2t_op_cross_attn_probs": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "d2t_op_argmax_embed": (_I, [_P, _I] + [_P] * 13 + [_I] * 6 + [_P]),
     "d2t_op_beam_topk": (_I, [_P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
     "d2t_op_beam_advance": (_I, [_I, _L] + [_P] * 15 + [_I] * 6 + [_P]),

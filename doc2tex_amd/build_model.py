@@ -20,12 +20,13 @@ from .engine import Engine, apply_settings, beam_results, pack_memories
 
 def decoder_attn_outputs(stages, decoder_attn, output_shape, feat_pad):
     """The alignment-map entries Model.forward adds to addition_outputs (reference build_model.py:66-77): none unless
-    the decoder returned a map (LSTM-attention beam search with viz_attn) AND the encoder reports a feature grid (ViT).
-    An Attn (v1) head on the ViT attends over the cls row too; that row is dropped before the map is laid on the grid.
+    the decoder returned a map (beam search with viz_attn) AND the encoder reports a feature grid (ViT).
+    An Attn (v1) head on the ViT attends over the cls row too, and so does the TFM head (whose map is the last decoder
+    layer's head-mean cross-attention, Model._tfm_maps); that row is dropped before the map is laid on the grid.
     The key names are the reference's: "feat_width" is output_shape[0], "feat_height" output_shape[1]."""
     if decoder_attn is None or output_shape is None:
         return {}
-    if stages["Pred"] == "Attn" and stages["Seq"] == "ViT":
+    if stages["Pred"] in ("Attn", "TFM") and stages["Seq"] == "ViT":
         decoder_attn = decoder_attn[:, 1:]
     decoder_attn = decoder_attn.reshape(-1, output_shape[0], output_shape[1])
     return {"decoder_attn": decoder_attn, "feat_width": output_shape[0], "feat_height": output_shape[1], "feat_pad": feat_pad}
@@ -382,15 +383,26 @@ class Model(nn.Module):
 
         return_attn (LSTM-attention heads): [(seq, score, decoder_attn)] per sample, decoder_attn [len, Tk] being what
         forward_decoder returns for that sample alone with viz_attn set (decoder_attn_outputs lays it on the feature grid).
-        A batch whose alignment history would exceed _lib.ATTN_MAP_BUDGET bytes is searched in several parts."""
+        A batch whose alignment history would exceed _lib.ATTN_MAP_BUDGET bytes is searched in several parts.
+        TFM head, with return_attn or Prediction.viz_attn set: the same triple, decoder_attn [len, T] being the last decoder
+        layer's head-mean cross-attention of the returned hypothesis (one row per generated token, the cls row of a ViT
+        memory included), from a teacher-forced replay per sample after the search (_tfm_maps)."""
         beam = int(beam_size or self.opt.get("beam_size", 1))
+        if self.stages["Pred"] == "TFM" and getattr(self.predicter.Prediction, "viz_attn", False):
+            return_attn = True
         if isinstance(input, (list, tuple)):
-            return self._beam_search_mixed(input, beam, return_attn)
+            return self._beam_search_mixed(input, beam, return_attn)  # (TFM head with maps: tensor by tensor)
         memory, _, _ = self.forward_encoder(input)
         if self.stages["Pred"] == "TFM":
-            if return_attn:
-                raise ValueError("the TFM head has no decoder alignment maps (build_pred.py:46-49)")
-            return self.engine().decode_beam_batch(memory.contiguous(), beam)
+            eng, memory = self.engine(), memory.contiguous()
+            results = eng.decode_beam_batch(memory, beam)
+            if not return_attn:
+                return results
+            # with return_attn, or viz_attn set on the head: every sample's hypothesis replayed on its own (their lengths
+            # differ) -> (seq, score, decoder_attn [len, T]), the last layer's head-mean cross-attention
+            exact = self._exact_memory(input, memory)
+            eng = self.engine()  # (the model's own precision again)
+            return [r + (self._tfm_maps(eng, exact[i:i + 1], None, r[0])[0][0],) for i, r in enumerate(results)]
         eng = self.engine()
         if not return_attn:
             return eng.decode_attn_beam_batch(memory.contiguous(), beam)
@@ -618,8 +630,12 @@ class Model(nn.Module):
             return memory, grid, pad  # build_seq.py:59-66
         return memory, None, None  # build_seq.py:69-76
 
-    def forward_decoder(self, contextual_feature, text, is_train=True, is_test=False, rtl_text=None):
-        """build_model.py:45-53 / build_pred.py:28-50 / tfm.py:188-195."""
+    def forward_decoder(self, contextual_feature, text, is_train=True, is_test=False, rtl_text=None, maps_memory=None):
+        """build_model.py:45-53 / build_pred.py:28-50 / tfm.py:188-195.
+
+        maps_memory (TFM head with viz_attn; an extension): the memory the cross-attention maps are replayed over, where it is
+        not the one decoded -- Model.forward passes the crop's memory encoded in exact fp32 (_exact_memory).  None: the maps
+        are taken over contextual_feature itself."""
         beam_size = self.opt.get("beam_size", 1)  # read on every call, build_pred.py:31
         self._luong_check()
         eng = self.engine()
@@ -675,11 +691,29 @@ class Model(nn.Module):
                 "memory): call model.eval() first.  The teacher-forced training pass (tfm.py:103-118) runs through "
                 "Model.forward() under model.train(), encoder and decoder on one autograd node, so that loss.backward() "
                 "reaches the backbone")
+        # viz_attn on the TFM head (an attribute read on every call, like the LSTM heads'; absent = off): the decode itself is
+        # what it always is, and a teacher-forced replay over its tokens writes the cross-attention maps afterwards (_tfm_maps)
+        viz = bool(getattr(self.predicter.Prediction, "viz_attn", False))
         if beam_size > 1:
-            prediction, logits = eng.decode_beam(contextual_feature.contiguous(), beam_size)
+            memory = contextual_feature.contiguous()
+            prediction, logits = eng.decode_beam(memory, beam_size)
+            if viz:  # one row per generated token; the last layer's head mean is the decoder_attn Model.forward lays on the grid
+                last, cross = self._tfm_maps(eng, memory if maps_memory is None else maps_memory, None, prediction)
+                return prediction, logits, last[0], {"cross_attn": cross}
         else:
             if text.dim() != 2 or text.shape[1] != 1:
                 raise ValueError("eval decoding expects text = [B,1] start tokens ([GO])")
+            if viz:
+                # a pipelined or grouped forward with the flag on sends what has been collected, waits for every decode in
+                # flight and runs alone, synchronously (no handle): the greedy maps go to Prediction.alpha_stores [B, steps, T, 1]
+                # as the LSTM heads' do (seq2seq.py:267-272), the full request to addition_outputs["cross_attn"]
+                if self.pipelined:
+                    self.synchronize()
+                memory = contextual_feature.contiguous()
+                prediction, logits = eng.decode_greedy(memory, text[:, 0], is_test)
+                last, cross = self._tfm_maps(eng, memory if maps_memory is None else maps_memory, text[:, 0], prediction)
+                self.predicter.Prediction.alpha_stores = last.unsqueeze(-1)
+                return prediction, logits, None, {"cross_attn": cross}
             # pipelined: the forward returns while the step loop runs on an engine stream.  With is_test the early exit is
             # taken on the device; prediction / logits are then FULL-SIZE tensors whose valid length is only known once the
             # decode is complete -- addition_outputs["decode"].result() waits and returns them cut as the reference does
@@ -692,6 +726,51 @@ class Model(nn.Module):
             else:
                 prediction, logits = eng.decode_greedy(contextual_feature.contiguous(), text[:, 0], is_test)
         return prediction, logits, None, {}
+
+    def _exact_memory(self, input, memory):
+        """The encoder memory of `input` in exact fp32 arithmetic, for the map replay of the TFM head: `memory` itself when that
+        is what the model runs in, else the crop encoded once more with conv_precision 'fp32' (no hooks fire; the model's own
+        precision is back with the next engine() call, so the decode is what it is without the flag).  Why: attention
+        probabilities amplify the memory's rounding -- on a ResNet memory read by a d_model-512 decoder the split-bf16
+        backbone moves them by up to 2.9e-4, the fp32 one by 2e-5.  Pipelined: waits for the decodes
+        in flight first, as the flagged forward does anyway."""
+        if self.effective_conv_precision() == "fp32":
+            return memory
+        if self.pipelined:
+            self.synchronize()
+        saved = self._conv_precision, self._precision_auto
+        self._conv_precision, self._precision_auto = "fp32", False
+        try:
+            return self.engine().encode(input)[0]
+        finally:
+            self._conv_precision, self._precision_auto = saved
+
+    def _tfm_maps(self, eng, memory, start, generated):
+        """Cross-attention maps of a finished TFM decode (Engine.decode_cross_attention): the step loop replayed over
+        [start | generated[:, :-1]], so that row t is the attention of the query that produced generated[:, t].
+        start [B] (None: [GO], as the beam search starts); generated [B, steps] on any device.
+        Returns (last [B, steps, T], cross): `last` the last decoder layer's mean over the heads; `cross` what the head asks
+        for -- Prediction.viz_attn_layers (default all; negative indices allowed) as [B, nl, steps, T], or with
+        Prediction.viz_attn_heads [B, nl, H, steps, T].  Rows beyond the maps budget per call are replayed in parts."""
+        pred = self.predicter.Prediction
+        per_head = bool(getattr(pred, "viz_attn_heads", False))
+        want = eng.cross_attention_layers(getattr(pred, "viz_attn_layers", None))
+        top = eng.cfg.dec_layers - 1
+        layers = want if top in want else want + [top]
+        B, T = memory.shape[0], memory.shape[1]
+        generated = generated.to(device=memory.device, dtype=torch.int64)
+        if start is None:
+            start = torch.full((B,), _lib.TOK_GO, dtype=torch.int64, device=memory.device)
+        tokens_in = torch.cat([start.to(device=memory.device, dtype=torch.int64).reshape(B, 1), generated[:, :-1]], dim=1)
+        per = _lib.ATTN_MAP_BUDGET // max(1, eng.cross_attention_bytes(1, tokens_in.shape[1], T, len(layers), per_head))
+        if per < 1:
+            raise ValueError(f"the cross-attention maps of ONE sample ({len(layers)} layers, {tokens_in.shape[1]} steps, {T} memory "
+                             f"tokens) exceed the {_lib.ATTN_MAP_BUDGET}-byte budget: ask for fewer layers (viz_attn_layers) or "
+                             "the head mean (viz_attn_heads off)")
+        maps = torch.cat([eng.decode_cross_attention(memory[a:a + per], tokens_in[a:a + per], layers, per_head)
+                          for a in range(0, B, per)], dim=0)
+        last = maps[:, -1].mean(dim=1) if per_head else maps[:, -1]
+        return last, (maps if top in want else maps[:, :len(want)])
 
     def _luong_check(self):
         """attn_type 'luong': Attention.forward_greedy / forward_beam call `self.attention_cell.reset_mem()` first thing
@@ -713,8 +792,11 @@ class Model(nn.Module):
             logits = train_forward(self, input, text)
             return logits.argmax(dim=2), logits, {}
         contextual_feature, output_shape, feat_pad = self.forward_encoder(input)
+        extra = {}
+        if self.stages["Pred"] == "TFM" and getattr(self.predicter.Prediction, "viz_attn", False):
+            extra["maps_memory"] = self._exact_memory(input, contextual_feature)
         prediction, logits, decoder_attn, addition_outputs = self.forward_decoder(
-            contextual_feature, text=text, is_train=is_train, is_test=is_test, rtl_text=rtl_text)
-        # decoder_attn is always None for the TFM head (build_pred.py:34,46-49) and for greedy decoding
+            contextual_feature, text=text, is_train=is_train, is_test=is_test, rtl_text=rtl_text, **extra)
+        # decoder_attn is None for greedy decoding, and for the TFM head (build_pred.py:34,46-49) unless its viz_attn is set
         addition_outputs.update(decoder_attn_outputs(self.stages, decoder_attn, output_shape, feat_pad))
         return prediction, logits, addition_outputs

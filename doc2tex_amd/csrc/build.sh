@@ -10,7 +10,7 @@ OPT="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-unused-v
 OBJ=obj; LIB=libd2t.so
 if [ -n "$D2T_PROBES" ]; then OPT="$OPT -DD2T_PROBES"; OBJ=obj_probe; LIB=libd2t_probe.so; fi
 mkdir -p $OBJ
-SRCS="conv_mfma conv_bf16x3 conv_bf16x3p conv_records ops vit_attn decode decode_gemm decode_row decode_beam recurrent attn_beam train_kernels train_wgrad train_attn train_recurrent train train_models train_abi optim metrics engine engine_weights engine_tfm engine_tfm_beam engine_attn engine_ops prep post posembed"
+SRCS="conv_mfma conv_bf16x3 conv_bf16x3p conv_records ops vit_attn decode decode_gemm decode_row decode_maps decode_beam recurrent attn_beam train_kernels train_wgrad train_attn train_recurrent train train_models train_abi optim metrics engine engine_weights engine_tfm engine_tfm_beam engine_attn engine_ops prep post posembed"
 objs=""; stale=""
 for f in $SRCS; do
   o=$OBJ/$f.o

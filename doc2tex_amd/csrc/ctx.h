@@ -182,6 +182,10 @@ struct d2t_ctx {
   int no_shortcut_fusion = 0;  // debug / A-B: 1 = the 1x1 shortcuts as their own kernels (d2t_set_conv_fusion)
   int no_pool_fusion = 0;  // debug / A-B: 1 = the two 2x2 max-pools as their own kernels (d2t_set_conv_fusion)
   float* beam_qp = nullptr; size_t beam_qp_cap = 0;  // beam, absorbed cross-attention: q' / context rows + LN1 rows (decode_row.hip, decode_beam.hip)
+  // d2t_decode_cross_attention: everything the teacher-forced replay works in -- step workspace, self-attention cache,
+  // projected cross K / V, the tokens by step, its step counter.  Its own buffer: a replay shares nothing with the chains, their
+  // memory slots or their captured loops, and it synchronises before it returns, so the buffer is idle between calls
+  float* maps_ws = nullptr; size_t maps_ws_cap = 0;
   int* h_pinned = nullptr;
   void* zero_page = nullptr;  // 256 zero bytes: out-of-image taps of the split-bf16 convolution
   // Decode chains: each owns its stream, self-attention cache, workspace, state block and output staging, so that with two

@@ -1229,4 +1229,54 @@ hipError_t launch_decoder_row(const DecRowP& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// decoder_row_kernel (one wave per head) that also hands out the row's cross-attention query: q2 goes to q2_out [M][D], where
+// cross_attn_probs_kernel (decode_maps.hip) reads it.  Launched only by the teacher-forced replay behind
+// d2t_decode_cross_attention.  The same phases in the same order; its own kernel and not a build of decoder_row_kernel so
+// that the decode's kernels stay what they are, instruction for instruction.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int D, int HD>
+__global__ __launch_bounds__(512, 2) void decoder_row_maps_kernel(const DecRowP p, float* __restrict__ q2_out) {
+  constexpr int NTH = 512, G = NTH / (D / 4);
+  ROW_KERNEL_ENTRY(p, false);
+  __shared__ __attribute__((aligned(16))) float a_s[D], y_s[D], x1_s[D], q2_s[D], part_s[G * D];
+  const int tid = threadIdx.x, head = tid >> 6, lane = tid & 63;
+  const int b = blockIdx.x;
+  const int t = *p.step_ptr;
+  row_self_attention<D, HD>(p, b, head, t, lane, a_s + head * HD);
+  __syncthreads();
+  row_gemv<D, NTH>(a_s, p.wo_t, part_s, tid);
+  __syncthreads();
+  if (tid < D) y_s[tid] = sum_parts<G, D>(part_s, tid, p.bo[tid] + p.xres[(size_t)b * D + tid]);
+  __syncthreads();
+  if (head == 0) row_ln1<D>(y_s, x1_s, lane, p);
+  __syncthreads();
+  row_gemv<D, NTH>(x1_s, p.wq_t, part_s, tid);
+  __syncthreads();
+  if (tid < D) {
+    const float q = sum_parts<G, D>(part_s, tid, p.bq[tid]);
+    q2_s[tid] = q;
+    q2_out[(size_t)b * D + tid] = q;
+  }
+  __syncthreads();
+  {
+    const int cb = p.c_row_map ? p.c_row_map[b] : b;
+    const float* Kc = p.ck + (size_t)cb * p.c_batch_stride + (size_t)head * p.T * HD;
+    const float* Vc = p.cv + (size_t)cb * p.c_batch_stride + (size_t)head * p.T * HD;
+    row_attention<HD, 8>(q2_s + head * HD, Kc, Vc, nullptr, nullptr, -1, p.T, a_s + head * HD, lane);
+  }
+  __syncthreads();
+  row_gemv<D, NTH>(a_s, p.wco_t, part_s, tid);
+  __syncthreads();
+  if (tid < D) p.y2[(size_t)b * D + tid] = sum_parts<G, D>(part_s, tid, p.bco[tid] + x1_s[tid]);
+}
+
+hipError_t launch_decoder_row_maps(const DecRowP& p, float* q2_out, hipStream_t s) {
+  if (p.heads != 8 || !q2_out || p.anc || p.rows_ptr) return hipErrorInvalidValue;
+  if (p.D == 256) hipLaunchKernelGGL((decoder_row_maps_kernel<256, 32>), dim3(p.M), dim3(512), 0, s, p, q2_out);
+  else if (p.D == 512) hipLaunchKernelGGL((decoder_row_maps_kernel<512, 64>), dim3(p.M), dim3(512), 0, s, p, q2_out);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 }  // namespace d2t

@@ -575,6 +575,7 @@ void d2t_destroy(d2t_ctx* c) {
   if (c->beam_hist) hipFree(c->beam_hist);
   if (c->h_beam) hipHostFree(c->h_beam);
   if (c->beam_qp) hipFree(c->beam_qp);
+  if (c->maps_ws) hipFree(c->maps_ws);
   if (c->h_pinned) hipHostFree(c->h_pinned);
   if (c->zero_page) hipFree(c->zero_page);
   if (c->gc_ws) hipFree(c->gc_ws);

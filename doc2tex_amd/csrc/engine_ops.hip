@@ -524,6 +524,18 @@ int d2t_op_decoder_row(int32_t kind, const float* qkv, const float* xres, float*
   return row_op_finish(s, buf, e);
 }
 
+// cross_attn_probs_kernel alone (decode_maps.hip): the probabilities of M query rows, row b over its own T projected keys
+int d2t_op_cross_attn_probs(const float* q, const float* keys, int32_t M, int32_t D, int32_t T, int32_t per_head, float* out,
+                            d2t_stream stream) {
+  if (!q || !keys || !out || M < 1 || M > 65535 || T < 1 || T > 4096 || (D != 256 && D != 512)) return D2T_EINVAL;
+  CrossProbsP p{};
+  p.q = q; p.q_stride = D; p.ck = keys; p.c_batch_stride = (long long)T * D; p.M = M; p.D = D; p.T = T;
+  p.out = out; p.out_head_stride = per_head ? T : 0; p.out_row_stride = (long long)(per_head ? 8 : 1) * T;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = launch_cross_attn_probs(p, s);
+  return row_op_finish(s, nullptr, e);
+}
+
 // The ragged builds of the greedy absorbed row kernels (kind as d2t_op_decoder_row: 1 / 2 = fp32 MFMA two-row / one-row,
 // 3 / 4 = split-bf16 two-row / one-row): mem is ONE packed [mem_rows][256] buffer, row b attends over the len[b] rows from
 // row0[b] on (host arrays, validated here, uploaded for the launch).

@@ -37,6 +37,11 @@ struct StepArgs {
   float* ckv = nullptr;          // the memory slot this decode reads
   float* skv = nullptr;          // the self-attention cache it reads / appends
   const int* step = nullptr;     // the chain's state block: the device step counter
+  // maps != nullptr (the replay of d2t_decode_cross_attention only; every decode leaves it null and enqueues what it always
+  // has): the row work runs the projected-K/V one-row build that keeps its cross-attention query, and for every layer in
+  // layer_mask cross_attn_probs writes this step's probabilities -- k-th chosen layer of row b at maps + b * maps_row_stride +
+  // k * maps_layer_stride (+ head * maps_head_stride; 0: the head mean) + step * T.  logits == nullptr then skips the vocabulary
+  struct Maps { float* maps = nullptr; long long row_stride = 0, layer_stride = 0, head_stride = 0; uint32_t layer_mask = 0; } maps;
 };
 
 // What every TFM decode entry refuses before anything is enqueued: missing arguments (have_args: the entry's own pointers and
@@ -54,6 +59,9 @@ hipError_t stage_memory(float* ckv, size_t plane, const float* memory, size_t n,
 // cross-attention K,V of every layer into the slot ckv, once per batch: [layers*2][B][heads][T][hd] (absorbed form: the
 // memory itself and its planes)
 hipError_t cross_kv(d2t_ctx* c, hipStream_t s, const float* memory, int B, int T, float* ckv);
+// the projected form of it, whatever the context decodes with; exact: the fp32 GEMM even where the context's convolution
+// arithmetic is split-bf16 (the replay of d2t_decode_cross_attention: scores of wide-ranged memories move by 1e-4 otherwise)
+hipError_t cross_kv_projected(d2t_ctx* c, hipStream_t s, const float* memory, int B, int T, float* ckv, bool exact = false);
 // one decode step for a.rows rows up to the vocabulary logits; bf.x holds the embedded input of this step
 hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, const StepArgs& a);
 unsigned long long* trace_slot(d2t_ctx* c);

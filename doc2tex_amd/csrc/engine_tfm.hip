@@ -77,9 +77,15 @@ hipError_t cross_kv(d2t_ctx* c, hipStream_t s, const float* memory, int B, int T
   // absorbed form: no projection at all -- the step loop reads the memory rows; the slot keeps a copy so that the captured
   // loop holds an engine address and the caller's tensor is free again as soon as this copy has run
   if (c->dec_absorbed) return stage_memory(ckv, (size_t)B * T * d, memory, (size_t)B * T * d, s);
+  return cross_kv_projected(c, s, memory, B, T, ckv);
+}
+
+hipError_t cross_kv_projected(d2t_ctx* c, hipStream_t s, const float* memory, int B, int T, float* ckv, bool exact) {
+  const d2t_config& g = c->cfg;
+  const int d = g.dec_dim;
   ConvP p{};
   p.in = memory; p.w = c->ckv_w; p.bias = c->ckv_b; p.out = ckv;
-  if (c->conv_bf16x3 && c->ckv_hi) { p.w_hi = c->ckv_hi; p.w_lo = c->ckv_lo; }
+  if (!exact && c->conv_bf16x3 && c->ckv_hi) { p.w_hi = c->ckv_hi; p.w_lo = c->ckv_lo; }
   linear_shape(p, B * T, d, g.dec_layers * 2 * d);
   p.store_mode = STORE_KV; p.kv_T = T; p.kv_heads = g.dec_heads; p.kv_hd = d / g.dec_heads; p.kv_B = B;
   return launch_conv(p, s);
@@ -153,7 +159,17 @@ hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, const StepA
     r.stop_at = stop;
     r.anc = a.anc; r.anc_stride = Lmax; r.one_row = beam > 0;
     r.rows_ptr = a.rows_ptr;
-    if (c->dec_absorbed && c->beam_shared_tile && beam > 0 && beam <= 6 && c->beam_qp && row_map)
+    if (a.maps.maps) {  // the replay: a.ckv holds projected K / V whatever the context decodes with
+      TRY(launch_decoder_row_maps(r, bf.q2, s));
+      if (a.maps.layer_mask >> l & 1u) {
+        const int k = __builtin_popcount(a.maps.layer_mask & ((1u << l) - 1u));
+        CrossProbsP cp{};
+        cp.q = bf.q2; cp.q_stride = d; cp.ck = r.ck; cp.c_batch_stride = r.c_batch_stride; cp.M = M; cp.D = d; cp.T = T;
+        cp.out = a.maps.maps + (size_t)k * a.maps.layer_stride; cp.out_row_stride = a.maps.row_stride;
+        cp.out_head_stride = a.maps.head_stride; cp.step_ptr = step;
+        TRY(launch_cross_attn_probs(cp, s));
+      }
+    } else if (c->dec_absorbed && c->beam_shared_tile && beam > 0 && beam <= 6 && c->beam_qp && row_map)
       TRY(launch_decoder_row_beam(r, a.ckv, (long long)T * d, L.ca_wk, L.ca_v_t, L.ca_bv, c->beam_qp,
                                   c->beam_qp + (size_t)kvB * 8 * d, a.seg, ckvB, s));
     else if (c->dec_absorbed && rg)
@@ -164,8 +180,9 @@ hipError_t decode_step(d2t_ctx* c, hipStream_t s, const DecBufs& bf, const StepA
     TRY(lin(sl, bf.y2, d, L.l1, bf.f, g.dec_ff, {.act = ACT_RELU, .ln = &L.n2, .ln_out = bf.x2}));
     TRY(lin(sl, bf.f, g.dec_ff, L.l2, bf.y3, d, {.res = bf.x2}));
   }
-  TRY(lin(sl, bf.y3, d, c->out_proj, a.logits, (int)a.logit_row_stride,
-          {.ln = &c->dec[g.dec_layers - 1].n3, .out_by_step = true, .out_step_stride = a.logit_step_stride}));
+  if (a.logits)
+    TRY(lin(sl, bf.y3, d, c->out_proj, a.logits, (int)a.logit_row_stride,
+            {.ln = &c->dec[g.dec_layers - 1].n3, .out_by_step = true, .out_step_stride = a.logit_step_stride}));
 #undef TRY
   return hipSuccess;
 }
@@ -512,6 +529,60 @@ int greedy_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* st
   if (call.steps_out) *call.steps_out = steps;
   return D2T_OK;
 }
+
+// The replay's workspace (d2t_ctx::maps_ws): the step workspace | self-attention cache | projected cross K / V of every layer |
+// the fed tokens by step [S][B] | its step counter; returns its bytes
+struct MapsWs { DecBufs bf; float *skv, *ckv; int64_t* tok; int* step; };
+size_t maps_ws_carve(void* base, const d2t_config& g, int B, int T, int S, MapsWs* w) {
+  const int d = g.dec_dim, Lmax = g.max_seq_len + 2;
+  Carver cv(base);
+  cv.at = dec_bufs_carve(Carver(base), B, d, g.dec_ff, &w->bf);
+  w->skv = cv.take<float>((size_t)g.dec_layers * 2 * B * Lmax * d, 256);
+  w->ckv = cv.take<float>((size_t)g.dec_layers * 2 * B * T * d, 256);
+  w->tok = cv.take<int64_t>((size_t)S * B, 256);
+  w->step = cv.take<int>(4, 256);
+  return cv.total();
+}
+
+// Teacher-forced replay of the step loop: step t is fed tokens_in[b][t] and writes the cross-attention probabilities of its
+// query as row t of the maps.  Everything runs on the caller's stream in the replay's own buffers, with plain launches: no
+// chain, memory slot or captured loop of the context is touched.  Always the projected-K/V row work (decode_step, a.maps).
+int cross_attention_impl(d2t_ctx* c, const float* memory, int B, int T, const int64_t* tokens_in, int S, uint32_t layer_mask,
+                         int per_head, float* maps, hipStream_t user) {
+  const d2t_config& g = c->cfg;
+  const int d = g.dec_dim, nl = __builtin_popcount(layer_mask), H = g.dec_heads;
+  const size_t n_tok = (size_t)B * S;
+  int rc;
+  // the fed tokens index the embedding table: read them back, refuse ids outside the vocabulary, lay them out by step
+  if ((rc = ensure_host_beam(c, 2 * n_tok * sizeof(int64_t)))) return rc;
+  int64_t *h_in = reinterpret_cast<int64_t*>(c->h_beam), *h_by_step = h_in + n_tok;
+  HIPCHK(c, hipMemcpyAsync(h_in, tokens_in, n_tok * sizeof(int64_t), hipMemcpyDeviceToHost, user));
+  HIPCHK(c, hipStreamSynchronize(user));
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < S; ++t) {
+      const int64_t tok = h_in[(size_t)b * S + t];
+      if (tok < 0 || tok >= g.vocab) return fail(c, D2T_EINVAL, "tokens_in[%d][%d] = %lld is outside the vocabulary of %d", b, t, (long long)tok, g.vocab);
+      h_by_step[(size_t)t * B + b] = tok;
+    }
+  MapsWs w;
+  if ((rc = ensure(c, &c->maps_ws, &c->maps_ws_cap, maps_ws_carve(nullptr, g, B, T, S, &w)))) return rc;
+  maps_ws_carve(c->maps_ws, g, B, T, S, &w);
+  HIPCHK(c, hipMemcpyAsync(w.tok, h_by_step, n_tok * sizeof(int64_t), hipMemcpyHostToDevice, user));
+  HIPCHK(c, cross_kv_projected(c, user, memory, B, T, w.ckv, true));  // fp32 whatever the context's convolution arithmetic
+  StepArgs sa;
+  sa.rows = B; sa.T = T; sa.kvB = B; sa.ckv = w.ckv; sa.skv = w.skv; sa.step = w.step;
+  sa.maps.maps = maps; sa.maps.layer_mask = layer_mask;
+  sa.maps.head_stride = per_head ? (long long)S * T : 0;
+  sa.maps.layer_stride = (long long)(per_head ? H : 1) * S * T;
+  sa.maps.row_stride = sa.maps.layer_stride * nl;
+  for (int t = 0; t < S; ++t) {
+    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.step), t, 1, user));
+    HIPCHK(c, launch_embed_tokens(c->word_embed, c->word_pe, w.tok + (size_t)t * B, w.step, w.bf.x, B, d, user));
+    HIPCHK(c, decode_step(c, user, w.bf, sa));
+  }
+  HIPCHK(c, hipStreamSynchronize(user));  // the pinned staging and the workspace are idle again; the maps are complete
+  return D2T_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -584,6 +655,26 @@ int d2t_decode_greedy_submit_ragged(d2t_ctx* c, const float* memory, int32_t n_b
   const int rc = greedy_impl(c, memory, (int)B, 0, start_tokens, (hipStream_t)stream, call);
   if (rc == D2T_OK && ticket_out) *ticket_out = c->last_ticket;
   return rc;
+}
+
+int d2t_decode_cross_attention(d2t_ctx* c, const float* memory, int32_t B, int32_t T, const int64_t* tokens_in, int32_t S,
+                               uint32_t layer_mask, int32_t per_head, float* maps, d2t_stream stream) {
+  DevGuard dg_(c);
+  if (int rc = tfm_check(c, memory && tokens_in && maps && B >= 1 && T >= 1, T, NOT_TFM)) return rc;
+  const d2t_config& g = c->cfg;
+  if (g.dec_heads != 8) return fail(c, D2T_ESTATE, "cross-attention maps need the 8-head decoder (this one has %d heads)", g.dec_heads);
+  if (S < 1 || S > g.max_seq_len + 1) return fail(c, D2T_EINVAL, "%d replay steps: 1 .. max_seq_len + 1 = %d", S, g.max_seq_len + 1);
+  if (B > 65535) return fail(c, D2T_EINVAL, "%d rows: at most 65535 per call", B);
+  if (!layer_mask || (g.dec_layers < 32 && (layer_mask >> g.dec_layers)))
+    return fail(c, D2T_EINVAL, "layer_mask 0x%x: at least one layer, none at or above dec_layers = %d", layer_mask, g.dec_layers);
+  const unsigned long long bytes = 4ull * B * __builtin_popcount(layer_mask) * (per_head ? g.dec_heads : 1) * S * T;
+  if (bytes > D2T_ATTN_MAP_BUDGET)
+    return fail(c, D2T_EINVAL, "cross-attention maps of %llu bytes exceed the %llu-byte budget: split the batch", bytes,
+                (unsigned long long)D2T_ATTN_MAP_BUDGET);
+  if (int rc = check_dev_ptr(c, memory, "memory")) return rc;
+  if (int rc = check_dev_ptr(c, tokens_in, "tokens_in")) return rc;
+  if (int rc = check_dev_ptr(c, maps, "maps")) return rc;
+  return cross_attention_impl(c, memory, B, T, tokens_in, S, layer_mask, per_head != 0, maps, (hipStream_t)stream);
 }
 
 // 1: this context decodes ragged groups (TFM decoder on the absorbed cross-attention); 0: d2t_decode_greedy_submit_ragged refuses

@@ -319,6 +319,22 @@ struct DecRowP {
   const int* rows_ptr;                // optional (device-side beam search): blocks of rows >= *rows_ptr return at once
 };
 hipError_t launch_decoder_row(const DecRowP& p, hipStream_t s);
+// the same step, one row per block, that also writes the rows' cross-attention queries q2 [M][D] (bias included, not yet
+// scaled) to q2_out: the replay of d2t_decode_cross_attention, which launch_cross_attn_probs follows
+hipError_t launch_decoder_row_maps(const DecRowP& p, float* q2_out, hipStream_t s);
+// Cross-attention probabilities of M query rows over T <= 4096 projected keys (8 heads, D = 256 or 512):
+//   P[b][h][j] = softmax_j(q[b][h] . ck[sample of b][h][j] / sqrt(D / 8))
+// out_head_stride != 0: P itself, head h of row b at out + b * out_row_stride + h * out_head_stride; 0: the mean over the heads,
+// summed in head order, at out + b * out_row_stride.  step_ptr (optional): out advances by *step_ptr * T floats.
+struct CrossProbsP {
+  const float* q; int q_stride;
+  const float* ck; long long c_batch_stride;  // [samples][8][T][D / 8]
+  const int* c_row_map;                       // optional: row b reads sample c_row_map[b]
+  int M, D, T;
+  float* out; long long out_row_stride, out_head_stride;
+  const int* step_ptr;
+};
+hipError_t launch_cross_attn_probs(const CrossProbsP& p, hipStream_t s);
 // the same step with the cross-attention taken over the encoder memory itself (absorbed K / V projections, decode_row.hip):
 // mem [samples][T][256] (row b attends over sample c_row_map[b] or b), wk [256][256] as stored, wv_t [c][o], bv [256]
 // mem_hi / mem_lo (optional, greedy two-row kernel only): the same rows as bf16 hi / lo planes (launch_split_bf16) -> the

@@ -539,6 +539,57 @@ class Engine:
         s = steps.value
         return tokens[:, :s], logits[:, :s]
 
+    def cross_attention_layers(self, layers=None):
+        """The decoder layers a map request names, ascending and without repeats: None = all, negative indices from the end."""
+        n = self.cfg.dec_layers
+        if layers is None:
+            return list(range(n))
+        out = set()
+        for l in layers:
+            l = int(l)
+            if not -n <= l < n:
+                raise ValueError(f"doc2tex_amd: decoder layer {l} of a cross-attention map request; the decoder has {n} layers")
+            out.add(l % n)
+        if not out:
+            raise ValueError("doc2tex_amd: a cross-attention map request names no layer")
+        return sorted(out)
+
+    def cross_attention_bytes(self, B, S, T, n_layers, per_head):
+        """Bytes of the maps decode_cross_attention returns for B rows of S steps over T memory tokens."""
+        return int(B) * int(n_layers) * (self.cfg.dec_heads if per_head else 1) * int(S) * int(T) * 4
+
+    def decode_cross_attention(self, memory, tokens_in, layers=None, per_head=False):
+        """Cross-attention maps of the TFM decoder over tokens that are already known (d2t_decode_cross_attention): a
+        teacher-forced replay of the step loop.  memory [B, T, d]; tokens_in [B, S] int64, column 0 the start token, column t
+        the token fed at step t.  Returns fp32 [B, nl, S, T] (the mean over the heads) or, per_head, [B, nl, H, S, T]: row t is
+        the attention of the query that produced token t + 1; nl counts `layers` (None: all; negative indices allowed), kept
+        in ascending order.  Maps beyond _lib.ATTN_MAP_BUDGET bytes raise ValueError before any device work."""
+        if self.cfg.decoder != _lib.DEC_TFM:
+            raise RuntimeError("doc2tex_amd: decode_cross_attention needs the TFM head (the LSTM-attention heads return their "
+                               "maps from the decode itself: return_alpha)")
+        chosen = self.cross_attention_layers(layers)
+        if memory.dim() != 3 or tokens_in.dim() != 2 or tokens_in.shape[0] != memory.shape[0]:
+            raise ValueError(f"doc2tex_amd: memory {tuple(memory.shape)} / tokens_in {tuple(tokens_in.shape)}: expected [B, T, d] and [B, S]")
+        B, T, _ = memory.shape
+        S = tokens_in.shape[1]
+        if not 1 <= S <= self.cfg.max_seq_len + 1:
+            raise ValueError(f"doc2tex_amd: {S} replay steps; the decoder runs 1 .. max_seq_len + 1 = {self.cfg.max_seq_len + 1}")
+        need = self.cross_attention_bytes(B, S, T, len(chosen), per_head)
+        if need > _lib.ATTN_MAP_BUDGET:
+            raise ValueError(f"doc2tex_amd: cross-attention maps of {need} bytes ({B} rows x {len(chosen)} layers x "
+                             f"{self.cfg.dec_heads if per_head else 1} x {S} steps x {T} tokens) exceed the "
+                             f"{_lib.ATTN_MAP_BUDGET}-byte budget: split the batch")
+        self._on_device(memory, "memory")
+        memory = memory.float().contiguous()
+        tokens_in = tokens_in.to(device=memory.device, dtype=torch.int64).contiguous()
+        shape = (B, len(chosen)) + ((self.cfg.dec_heads,) if per_head else ()) + (S, T)
+        maps = torch.empty(shape, dtype=torch.float32, device=memory.device)
+        mask = sum(1 << l for l in chosen)
+        self._check(self.lib.d2t_decode_cross_attention(self.ctx, _lib.ptr(memory), B, T, _lib.ptr(tokens_in), S, mask,
+                                                        int(bool(per_head)), _lib.ptr(maps), _lib.stream_of(memory)),
+                    "decode_cross_attention")
+        return maps
+
     def attn_keys(self, T):
         """Keys the LSTM-attention decoder attends over in a memory of T tokens (AttentionV2 + TFM drops the cls row)."""
         return T - (1 if self.cfg.attn_keys == _lib.ATTN_KEYS_NOCLS_INIT_CLS else 0)

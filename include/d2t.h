@@ -379,6 +379,25 @@ int32_t d2t_decode_supports_ragged_beam(const d2t_ctx* ctx);
  * len_out[i] = T[i] (either may be NULL); returns the packed row total. */
 int64_t d2t_ragged_beam_tables(int32_t N, const int32_t* T, int32_t* row0_out, int32_t* len_out);
 
+/* Cross-attention maps of the TFM decoder: which memory tokens every generated token looked at.  A teacher-forced replay
+ * of the step loop over tokens the caller already has (a greedy decode's, a beam hypothesis'): step t < S is fed
+ * tokens_in[b][t] (device, [B][S]; column 0 = the start token) instead of an argmax, and the softmax(q . K^T / sqrt(hd))
+ * of its cross-attention query over the T memory tokens is written as row t -- the attention of the query that produced
+ * token t + 1.  No early exit; every id must lie inside the vocabulary (read back and checked).
+ *   per_head == 0: maps [B][nl][S][T], the mean over the 8 heads summed in head order (torch's average_attn_weights)
+ *   per_head != 0: maps [B][nl][8][S][T]
+ * nl = popcount(layer_mask), the chosen layers (bit l = decoder layer l) in ascending order.  fp32; rows sum to 1.
+ * The replay always runs the projected-K/V form of the row work, in fp32 throughout (the K / V projection of the memory too,
+ * whatever d2t_set_conv_precision says), in buffers of its own and with plain launches on `stream`:
+ * it changes no setting, memory slot or captured loop of the context, so decodes before and after it are what they are
+ * without it; it does not wait for decodes in flight either (it shares nothing with them).  Synchronous: returns once the
+ * maps are complete.  Roughly the cost of one more decode of S steps, without its vocabulary GEMM.
+ * Refused before anything is enqueued: a context without the TFM decoder (D2T_ESTATE); S outside [1, max_seq_len + 1], T
+ * outside d2t_decode_greedy's range, B > 65535, an empty layer_mask or a bit at or above dec_layers, a pointer of another
+ * device, maps larger than D2T_ATTN_MAP_BUDGET bytes ("split the batch"), a token id outside the vocabulary (D2T_EINVAL). */
+int d2t_decode_cross_attention(d2t_ctx* ctx, const float* memory_dev, int32_t B, int32_t T, const int64_t* tokens_in_dev,
+                               int32_t S, uint32_t layer_mask, int32_t per_head, float* maps_dev, d2t_stream stream);
+
 /* LSTM-attention beam search for ONE sample (reference: Attention.forward_beam, prediction_head/seq2seq.py:83-222;
  * AttentionV2.forward_beam, seq2seq_v2.py:12-174 -- what config/test.yaml runs with beam_size 5 / 10).  Coverage
  * attention only.  memory [1][T][256]; seq_out (host, >= batch_max_length + 1 entries) receives the token ids without
@@ -631,6 +650,12 @@ int d2t_op_decoder_row_ragged_beam(int32_t kind, const float* qkv, const float* 
                                    float* y2, const int32_t* step, int32_t M, int32_t Lmax, int32_t rows, int32_t mem_rows,
                                    int32_t samples, const int32_t* row0, const int32_t* len, const int32_t* row_map,
                                    const int32_t* anc, int32_t anc_stride, d2t_stream stream);
+/* The map kernel of d2t_decode_cross_attention alone (8 heads, D = 256 or 512, 1 <= T <= 4096, M <= 65535):
+ * P[b][h][j] = softmax_j(q[b][h] . keys[b][h][j] / sqrt(D / 8)).  q [M][D] (the cross-attention queries, bias included, not
+ * scaled); keys [M][8][T][D / 8] (row b's projected keys).  per_head != 0: out [M][8][T] = P; 0: out [M][T], the mean over
+ * the heads summed in head order.  Writes exactly those floats. */
+int d2t_op_cross_attn_probs(const float* q, const float* keys, int32_t M, int32_t D, int32_t T, int32_t per_head, float* out,
+                            d2t_stream stream);
 /* One greedy step (launch_argmax_embed) at t = *step < S: tokens[b][t] = first maximum of logits[b][t][:V] (logits [B][S][V],
  * tokens [B][S]); end-of-sequence bookkeeping in ended [B], end_count, steps_done; *step becomes t + 1, done_count (zero
  * before the first launch) is back at zero afterwards; x [B][d] (optional) = emb[token] * sqrt(d) + pe[t + 1] (pe [S + 1][d]).
