@@ -75,6 +75,12 @@ class D2TOpTrainAttentionArgs(C.Structure):  # include/d2t.h d2t_op_train_attent
         [("dropscale", C.c_float)] + [(n, C.c_int32) for n in ("layout", "nb", "Lq", "Lk", "heads", "hd", "causal")]
 
 
+class D2TOpWgradArgs(C.Structure):  # include/d2t.h d2t_op_wgrad_args
+    _fields_ = [(n, C.c_void_p) for n in ("a", "b", "part", "tile")] + [("P", C.c_int64)] + \
+        [(n, C.c_int32) for n in ("M", "N", "lda", "ldb", "geom", "B", "H", "W", "OH", "OW", "KH", "KW", "SH", "SW", "PH", "PW",
+                                  "S", "chunk", "bf16x3", "records")]
+
+
 class D2TOpAttnBeamRec(C.Structure):  # include/d2t.h d2t_op_attn_beam_rec
     _fields_ = [(n, C.c_void_p) for n in (
         "ctrl", "tok", "scores", "map", "idx_h", "idx_m", "seg", "comp_n", "fin", "last_completed", "comp_t", "comp_par",
@@ -256,6 +262,23 @@ SIGNATURES = {
     "d2t_op_train_mean_h": (_I, [_P] * 4 + [_I] * 4 + [_P]),
     "d2t_op_train_maxpool_w": (_I, [_P] * 4 + [_I] * 9 + [_P]),
     "d2t_op_train_ew": (_I, [_P] * 4 + [_L, _I, _P]),
+    # the weight-gradient, BatchNorm, LayerNorm, stem and data-movement launchers one at a time (test infrastructure)
+    "d2t_op_wgrad": (_I, [C.POINTER(D2TOpWgradArgs), _P]),
+    "d2t_op_wgrad_plan": (_I, [_L, _I, _I, _I, _I, C.POINTER(_L)]),
+    "d2t_op_wgrad_reduce": (_I, [_P, _P] + [_I] * 6 + [_P]),
+    "d2t_op_colreduce": (_I, [_I] + [_P] * 6 + [_L, _I, C.POINTER(_I), _P]),
+    "d2t_op_colreduce_final": (_I, [_P, _I, _I, _P, _P, _I, _P]),
+    "d2t_op_bn_finalize": (_I, [_P, _I, _I, _L, C.c_float, C.c_float] + [_P] * 6),
+    "d2t_op_bn_apply": (_I, [_P] * 8 + [_L, _I, _I, _P]),
+    "d2t_op_bn_bwd_apply": (_I, [_P] * 11 + [_L, _I, _P]),
+    "d2t_op_ln_train": (_I, [_P] * 6 + [_I, _I, C.c_float, _P]),
+    "d2t_op_ln_bwd": (_I, [_P] * 7 + [_I, _I, _P]),
+    "d2t_op_stem_raw": (_I, [_P] * 3 + [_I] * 5 + [_P]),
+    "d2t_op_stem_wgrad": (_I, [_P] * 3 + [_I] * 7 + [_P]),
+    "d2t_op_dilate": (_I, [_P, _P] + [_I] * 10 + [_P]),
+    "d2t_op_flip_oihw": (_I, [_P, _P] + [_I] * 4 + [_P]),
+    "d2t_op_pad_cols": (_I, [_P, _P, _L, _I, _I, _P]),
+    "d2t_op_copy2d": (_I, [_P, _I, _P, _I, _L, _I, _P]),
 }
 # include/d2t_prep.h
 SIGNATURES_PREP = {

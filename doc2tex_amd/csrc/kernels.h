@@ -534,8 +534,10 @@ int colreduce_chunks(long long R, int C);
 hipError_t launch_colreduce(const ColRedP& p, hipStream_t s);
 hipError_t launch_colreduce_final(const float* part, int chunks, int C, float* out0, float* out1, int accumulate,
                                   hipStream_t s);
-hipError_t launch_bn_finalize(const float* part, int chunks, int C, long long R, float eps, float momentum, float* mean,
-                              float* rstd, float* run_mean, float* run_var, hipStream_t s);
+// CR_SUM_SQ sums about the channel's value in row 0: part = sum (a - a[0][c]) | sum (a - a[0][c])^2; launch_bn_finalize takes
+// the same matrix z (its row 0 is the shift): mean = z[0][c] + E[z - z[0][c]], var = E[(z - z[0][c])^2] - E[z - z[0][c]]^2
+hipError_t launch_bn_finalize(const float* part, int chunks, int C, long long R, float eps, float momentum, const float* z,
+                              float* mean, float* rstd, float* run_mean, float* run_var, hipStream_t s);
 hipError_t launch_bn_apply(const float* z, const float* mean, const float* rstd, const float* g, const float* b,
                            const float* res, float* y, long long R, int C, int relu, hipStream_t s, uint16_t* planes = nullptr);
 hipError_t launch_bn_bwd_apply(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,

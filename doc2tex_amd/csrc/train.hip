@@ -167,13 +167,9 @@ int Tr::colsum(const float* a, long long R, int C, float* dst) {
   p.a = a; p.R = R; p.C = C; p.mode = CR_SUM;
   return colreduce2(p, dst, nullptr);
 }
-// dW[M][N](taps) = a^T (x) b  with the split-K two-pass reduction
-int Tr::wgrad(const float* a, int lda, const float* b, int ldb, long long P, int M, int N, int taps, const Node::Conv* geom,
-              const TT* xin, const TT* yout, float* dst, int layout, const uint16_t* a_rec, const uint16_t* b_rec) {
-  // both operands exist as split-bf16 records (a convolution between BatchNorm layers): the LDS-DMA kernel
-  static const bool rec_off = D2T_PROBE_ENV_STR("D2T_WGRAD_REC") && D2T_PROBE_ENV("D2T_WGRAD_REC") == 0;
-  const WgradRecTile* rec =
-      !rec_off && a_rec && b_rec && geom && c->conv_bf16x3 && c->zero_page && lda == M && ldb == N ? wgrad_rec_tile(M, N) : nullptr;
+// The split of a weight gradient's P rows into S chunks of `chunk` rows (rec: the record kernel's tile, or nullptr for the
+// plain kernels).  chunk % 32 == 0, no chunk is empty, S <= 64 on the plain path.
+WgradPlan wgrad_plan(long long P, int M, int N, int taps, const WgradRecTile* rec) {
   const int tile = (M <= 64 || N <= 64) ? 64 : 128;
   const long long tiles = rec ? (long long)(M / rec->bm) * (N / rec->bn) * taps
                               : (long long)((M + tile - 1) / tile) * ((N + tile - 1) / tile) * taps;
@@ -196,6 +192,17 @@ int Tr::wgrad(const float* a, int lda, const float* b, int ldb, long long P, int
   if (rec) S = std::max<long long>(1, std::min<long long>(smax, rec_rounds * slots / tiles));
   long long chunk = ((P + S - 1) / S + 31) / 32 * 32;
   S = (P + chunk - 1) / chunk;
+  return WgradPlan{S, chunk};
+}
+// dW[M][N](taps) = a^T (x) b  with the split-K two-pass reduction
+int Tr::wgrad(const float* a, int lda, const float* b, int ldb, long long P, int M, int N, int taps, const Node::Conv* geom,
+              const TT* xin, const TT* yout, float* dst, int layout, const uint16_t* a_rec, const uint16_t* b_rec) {
+  // both operands exist as split-bf16 records (a convolution between BatchNorm layers): the LDS-DMA kernel
+  static const bool rec_off = D2T_PROBE_ENV_STR("D2T_WGRAD_REC") && D2T_PROBE_ENV("D2T_WGRAD_REC") == 0;
+  const WgradRecTile* rec =
+      !rec_off && a_rec && b_rec && geom && c->conv_bf16x3 && c->zero_page && lda == M && ldb == N ? wgrad_rec_tile(M, N) : nullptr;
+  const WgradPlan plan = wgrad_plan(P, M, N, taps, rec);
+  const long long S = plan.S, chunk = plan.chunk;
   RC(ensure_part((size_t)S * taps * M * N));
   WgradP p{};
   p.a = a; p.b = b; p.part = st->part; p.P = P; p.M = M; p.N = N; p.lda = lda; p.ldb = ldb; p.taps = taps;
@@ -337,7 +344,7 @@ int Tr::bn_forward(Node::Conv& n, long long P) {
   const RawW *rm, *rv;
   RC(need(c, n.bnkey + ".running_mean", &rm));
   RC(need(c, n.bnkey + ".running_var", &rv));
-  TCHK(launch_bn_finalize(st->part, chunks, C, P, 1e-5f, 0.1f, n.mean, n.rstd, rm->p, rv->p, s));
+  TCHK(launch_bn_finalize(st->part, chunks, C, P, 1e-5f, 0.1f, n.z, n.mean, n.rstd, rm->p, rv->p, s));
   return D2T_OK;
 }
 // The first layer, a 3x3 convolution of the image's one or three channels on kernels of its own (weight gradient

@@ -674,4 +674,181 @@ int d2t_op_sum_rows_strided(const float* x, float* out, int32_t B, int64_t strid
   return op_status(launch_sum_rows_strided(x, out, B, stride_rows, row, D, (hipStream_t)stream));
 }
 
+// The weight-gradient, BatchNorm, LayerNorm, stem and data-movement launchers one at a time (include/d2t.h): caller tensors
+// in the kernels' own layouts, asynchronous on the stream, every size checked first.
+static const long long OP_MAX_ELEMS = 1ll << 31;
+
+int d2t_op_wgrad_plan(int64_t P, int32_t M, int32_t N, int32_t taps, int32_t records, int64_t* out) {
+  if (!out || P < 1 || M < 1 || N < 1 || taps < 1) return D2T_EINVAL;
+  const WgradRecTile* rec = records ? wgrad_rec_tile(M, N) : nullptr;
+  if (records && !rec) return D2T_EINVAL;
+  const WgradPlan pl = wgrad_plan(P, M, N, taps, rec);
+  const int plain = (M <= 64 || N <= 64) ? 64 : 128;
+  out[0] = pl.S; out[1] = pl.chunk; out[2] = rec ? rec->bm : plain; out[3] = rec ? rec->bn : plain;
+  return D2T_OK;
+}
+
+int d2t_op_wgrad(const d2t_op_wgrad_args* a, d2t_stream stream) {
+  if (!a || !a->a || !a->b || !a->part) return D2T_EINVAL;
+  if (a->P < 1 || a->M < 1 || a->N < 1 || a->lda < a->M || a->ldb < a->N || a->S < 1 || a->chunk < 1) return D2T_EINVAL;
+  if (a->M % 4 || a->N % 4 || a->lda % 4 || a->ldb % 4) return D2T_EINVAL;  // 16-byte operand loads
+  if ((long long)a->S * a->chunk < a->P || (long long)(a->S - 1) * a->chunk >= a->P || a->S > 65535) return D2T_EINVAL;
+  int taps = 1;
+  long long brows = a->P;
+  if (a->geom) {
+    if (a->B < 1 || a->H < 1 || a->W < 1 || a->OH < 1 || a->OW < 1 || a->KH < 1 || a->KW < 1 || a->SH < 1 || a->SW < 1 ||
+        a->PH < 0 || a->PW < 0 || a->KH * a->KW > 65535)
+      return D2T_EINVAL;
+    if ((long long)a->B * a->OH * a->OW != a->P) return D2T_EINVAL;
+    taps = a->KH * a->KW;
+    brows = (long long)a->B * a->H * a->W;
+  }
+  if (a->P * a->lda > OP_MAX_ELEMS || brows * a->ldb > OP_MAX_ELEMS || (long long)a->S * taps * a->M * a->N > OP_MAX_ELEMS)
+    return D2T_EINVAL;
+  const WgradRecTile* rec = nullptr;
+  if (a->records) {
+    rec = wgrad_rec_tile(a->M, a->N);
+    if (!rec || !a->geom || !a->bf16x3 || a->lda != a->M || a->ldb != a->N || a->chunk % 16) return D2T_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  WgradP p{};
+  p.a = a->a; p.b = a->b; p.part = a->part; p.P = a->P; p.M = a->M; p.N = a->N; p.lda = a->lda; p.ldb = a->ldb; p.taps = taps;
+  p.KW = 1; p.S = a->S; p.chunk = a->chunk; p.bf16x3 = a->bf16x3 ? 1 : 0;
+  if (a->geom) {
+    p.geom = 1; p.H = a->H; p.W = a->W; p.OH = a->OH; p.OW = a->OW;
+    p.KW = a->KW; p.SH = a->SH; p.SW = a->SW; p.PH = a->PH; p.PW = a->PW;
+  }
+  if (a->tile) {
+    const int plain = (a->M <= 64 || a->N <= 64) ? 64 : 128;
+    a->tile[0] = rec ? rec->bm : plain; a->tile[1] = rec ? rec->bn : plain;
+  }
+  if (!rec) return op_status(launch_wgrad(p, s));
+  // record operands: [row][32 x hi | 32 x lo] per 32 columns = as many bytes as the fp32 rows; 256 zero bytes for the padding taps
+  void *ar = nullptr, *br = nullptr, *zero = nullptr;
+  hipError_t e = hipMalloc(&ar, (size_t)a->P * a->M * 4);
+  if (e == hipSuccess) e = hipMalloc(&br, (size_t)brows * a->N * 4);
+  if (e == hipSuccess) e = hipMalloc(&zero, 256);
+  if (e == hipSuccess) e = hipMemsetAsync(zero, 0, 256, s);
+  if (e == hipSuccess) e = launch_split_act(a->a, reinterpret_cast<uint16_t*>(ar), (size_t)a->P, a->M, s, 0);
+  if (e == hipSuccess) e = launch_split_act(a->b, reinterpret_cast<uint16_t*>(br), (size_t)brows, a->N, s, 0);
+  if (e == hipSuccess) {
+    p.a_rec = reinterpret_cast<const uint16_t*>(ar); p.b_rec = reinterpret_cast<const uint16_t*>(br); p.zero = zero;
+    e = launch_wgrad(p, s);
+  }
+  const hipError_t e2 = hipStreamSynchronize(s);  // the operand records are the entry's own
+  if (ar) hipFree(ar);
+  if (br) hipFree(br);
+  if (zero) hipFree(zero);
+  return e != hipSuccess ? op_status(e) : op_status(e2);
+}
+
+int d2t_op_wgrad_reduce(const float* part, float* dst, int32_t S, int32_t taps, int32_t M, int32_t N, int32_t layout,
+                        int32_t accumulate, d2t_stream stream) {
+  if (!part || !dst || S < 1 || taps < 1 || M < 1 || N < 1 || (layout != 0 && layout != 1) || (layout == 0 && taps != 1))
+    return D2T_EINVAL;
+  if ((long long)S * taps * M * N > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_wgrad_reduce(part, dst, S, taps, M, N, layout, accumulate != 0, (hipStream_t)stream));
+}
+
+int d2t_op_colreduce(int32_t mode, const float* a, const float* y, const float* z, const float* mean, const float* rstd,
+                     float* part, int64_t R, int32_t C, int32_t* chunks, d2t_stream stream) {
+  if (mode < CR_SUM || mode > CR_LN_BWD || R < 1 || C < 4 || C % 4 || R * C > OP_MAX_ELEMS) return D2T_EINVAL;
+  if (chunks) *chunks = colreduce_chunks(R, C);
+  if (!part) return chunks ? D2T_OK : D2T_EINVAL;
+  if (!a || (mode >= CR_BN_BWD && (!z || !mean || !rstd)) || (y && mode != CR_BN_BWD)) return D2T_EINVAL;
+  ColRedP p{};
+  p.a = a; p.y = y; p.z = z; p.mean = mean; p.rstd = rstd; p.part = part; p.R = R; p.C = C; p.mode = mode;
+  return op_status(launch_colreduce(p, (hipStream_t)stream));
+}
+
+int d2t_op_colreduce_final(const float* part, int32_t chunks, int32_t C, float* out0, float* out1, int32_t accumulate,
+                           d2t_stream stream) {
+  if (!part || !out0 || chunks < 1 || C < 1 || (long long)chunks * 2 * C > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_colreduce_final(part, chunks, C, out0, out1, accumulate != 0, (hipStream_t)stream));
+}
+
+int d2t_op_bn_finalize(const float* part, int32_t chunks, int32_t C, int64_t R, float eps, float momentum, const float* z,
+                       float* mean, float* rstd, float* run_mean, float* run_var, d2t_stream stream) {
+  if (!part || !z || !mean || !rstd || chunks < 1 || C < 1 || R < 1 || (long long)chunks * 2 * C > OP_MAX_ELEMS) return D2T_EINVAL;
+  if (!(eps >= 0.f) || !(momentum >= 0.f && momentum <= 1.f) || (run_mean == nullptr) != (run_var == nullptr)) return D2T_EINVAL;
+  return op_status(launch_bn_finalize(part, chunks, C, R, eps, momentum, z, mean, rstd, run_mean, run_var, (hipStream_t)stream));
+}
+
+int d2t_op_bn_apply(const float* z, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* res,
+                    float* y, uint16_t* planes, int64_t R, int32_t C, int32_t relu, d2t_stream stream) {
+  if (!z || !mean || !rstd || !gamma || !beta || !y || R < 1 || C < 4 || C % 4 || R * C > OP_MAX_ELEMS) return D2T_EINVAL;
+  if (planes && C % 32) return D2T_EINVAL;
+  return op_status(launch_bn_apply(z, mean, rstd, gamma, beta, res, y, R, C, relu != 0, (hipStream_t)stream, planes));
+}
+
+int d2t_op_bn_bwd_apply(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
+                        const float* gamma, const float* s0, const float* s1, float* dz, float* gout, uint16_t* planes, int64_t R,
+                        int32_t C, d2t_stream stream) {
+  if (!dy || !z || !mean || !rstd || !gamma || !s0 || !s1 || !dz || R < 1 || C < 4 || C % 4 || R * C > OP_MAX_ELEMS)
+    return D2T_EINVAL;
+  if (planes && C % 32) return D2T_EINVAL;
+  return op_status(launch_bn_bwd_apply(dy, y, z, mean, rstd, gamma, s0, s1, dz, gout, R, C, (hipStream_t)stream, planes));
+}
+
+static bool ln_width(int D) { return D == 128 || D == 256 || D == 512; }  // one wave per row, D / 64 elements per lane
+
+int d2t_op_ln_train(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int32_t rows,
+                    int32_t D, float eps, d2t_stream stream) {
+  if (!x || !gamma || !beta || !y || !mean || !rstd || rows < 1 || !ln_width(D) || !(eps >= 0.f)) return D2T_EINVAL;
+  if ((long long)rows * D > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_ln_train(x, gamma, beta, y, mean, rstd, rows, D, eps, (hipStream_t)stream));
+}
+
+int d2t_op_ln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* add,
+                  float* dx, int32_t rows, int32_t D, d2t_stream stream) {
+  if (!dy || !x || !mean || !rstd || !gamma || !dx || rows < 1 || !ln_width(D)) return D2T_EINVAL;
+  if ((long long)rows * D > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_ln_bwd(dy, x, mean, rstd, gamma, add, dx, rows, D, (hipStream_t)stream));
+}
+
+static bool stem_shape(int B, int Cin, int H, int W, int Cout) {
+  return B >= 1 && H >= 1 && W >= 1 && (Cin == 1 || Cin == 3) && (Cout == 32 || Cout == 64) &&
+         (long long)B * H * W * Cout <= OP_MAX_ELEMS;
+}
+
+int d2t_op_stem_raw(const float* img, const float* w, float* z, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                    d2t_stream stream) {
+  if (!img || !w || !z || !stem_shape(B, Cin, H, W, Cout)) return D2T_EINVAL;
+  return op_status(launch_stem_raw(img, w, z, B, Cin, H, W, Cout, (hipStream_t)stream));
+}
+
+int d2t_op_stem_wgrad(const float* img, const float* dz, float* part, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                      int32_t chunk, int32_t nchunks, d2t_stream stream) {
+  if (!img || !dz || !part || !stem_shape(B, Cin, H, W, Cout) || chunk < 1 || nchunks < 1) return D2T_EINVAL;
+  const long long P = (long long)B * H * W;
+  if ((long long)nchunks * chunk < P || (long long)(nchunks - 1) * chunk >= P) return D2T_EINVAL;
+  if ((long long)nchunks * 9 * Cin * Cout > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_stem_wgrad(img, dz, part, B, Cin, H, W, Cout, chunk, nchunks, (hipStream_t)stream));
+}
+
+int d2t_op_dilate(const float* src, float* dst, int32_t B, int32_t OH, int32_t OW, int32_t C, int32_t DH, int32_t DW, int32_t SH,
+                  int32_t SW, int32_t offh, int32_t offw, d2t_stream stream) {
+  if (!src || !dst || src == dst || B < 1 || OH < 1 || OW < 1 || C < 1 || DH < 1 || DW < 1 || SH < 1 || SW < 1 || offh < 0 || offw < 0)
+    return D2T_EINVAL;
+  if ((long long)B * OH * OW * C > OP_MAX_ELEMS || (long long)B * DH * DW * C > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_dilate(src, dst, B, OH, OW, C, DH, DW, SH, SW, offh, offw, (hipStream_t)stream));
+}
+
+int d2t_op_flip_oihw(const float* w, float* out, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, d2t_stream stream) {
+  if (!w || !out || w == out || Cout < 1 || Cin < 1 || KH < 1 || KW < 1 || (long long)Cout * Cin * KH * KW > OP_MAX_ELEMS)
+    return D2T_EINVAL;
+  return op_status(launch_flip_oihw(w, out, Cout, Cin, KH, KW, (hipStream_t)stream));
+}
+
+int d2t_op_pad_cols(const float* src, float* dst, int64_t rows, int32_t Cs, int32_t Cd, d2t_stream stream) {
+  if (!src || !dst || src == dst || rows < 1 || Cs < 1 || Cd < Cs || rows * Cd > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_pad_cols(src, dst, (size_t)rows, Cs, Cd, (hipStream_t)stream));
+}
+
+int d2t_op_copy2d(const float* src, int32_t lds, float* dst, int32_t ldd, int64_t rows, int32_t cols, d2t_stream stream) {
+  if (!src || !dst || src == dst || rows < 1 || cols < 1 || lds < cols || ldd < cols) return D2T_EINVAL;
+  if (rows * lds > OP_MAX_ELEMS || rows * ldd > OP_MAX_ELEMS) return D2T_EINVAL;
+  return op_status(launch_copy2d(src, lds, dst, ldd, (size_t)rows, cols, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -48,6 +48,11 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const ColRedP p, int row
     if (p.mode == CR_BN_BWD) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) { mu[k] = p.mean[c + k]; rs[k] = p.rstd[c + k]; }
+    } else if (p.mode == CR_SUM_SQ) {
+      // the sums are taken about the channel's value in row 0 (read once per thread): sum (a - k) and sum (a - k)^2 keep
+      // their bits where the mean lies many standard deviations from zero, E[a^2] - mean^2 from raw fp32 sums does not
+      const float4 k4 = *reinterpret_cast<const float4*>(p.a + c);
+      mu[0] = k4.x; mu[1] = k4.y; mu[2] = k4.z; mu[3] = k4.w;
     }
 #pragma unroll 8
     for (long long r = r0 + ty; r < r1; r += 16) {
@@ -59,7 +64,7 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const ColRedP p, int row
         for (int k = 0; k < 4; ++k) s0[k] += a[k];
       } else if (p.mode == CR_SUM_SQ) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { s0[k] += a[k]; s1[k] = fmaf(a[k], a[k], s1[k]); }
+        for (int k = 0; k < 4; ++k) { const float d = a[k] - mu[k]; s0[k] += d; s1[k] = fmaf(d, d, s1[k]); }
       } else if (p.mode == CR_BN_BWD) {  // a = dy, y = post-activation output (nullable), z = pre-BN conv output
         const float4 z4 = *reinterpret_cast<const float4*>(p.z + off);
         const float z[4] = {z4.x, z4.y, z4.z, z4.w};
@@ -137,19 +142,20 @@ hipError_t launch_colreduce_final(const float* part, int chunks, int C, float* o
   hipLaunchKernelGGL(colreduce_final_kernel, dim3((C + 31) / 32), dim3(256), 0, s, part, chunks, C, out0, out1, accumulate);
   return hipGetLastError();
 }
-// BatchNorm batch statistics from (sum, sum of squares) partials; running statistics updated in place
-// (momentum 0.1, unbiased variance: nn.BatchNorm2d defaults used by resnet.py).
+// BatchNorm batch statistics from the CR_SUM_SQ partials of z (sums of z - k and of (z - k)^2, k = z[0][c]: the shift);
+// running statistics updated in place (momentum 0.1, unbiased variance: nn.BatchNorm2d defaults used by resnet.py).
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int chunks, int C, long long R, float eps,
-                                                          float momentum, float* mean, float* rstd, float* run_mean,
-                                                          float* run_var) {
+                                                          float momentum, const float* __restrict__ shift, float* mean,
+                                                          float* rstd, float* run_mean, float* run_var) {
   __shared__ double red[2][8][32];
   const int c = blockIdx.x * 32 + (threadIdx.x & 31), lane8 = threadIdx.x >> 5;
   double a, b;
   chunk_sums(part, chunks, C, c, lane8, red, a, b);
   if (lane8 != 0 || c >= C) return;
-  const double m = a / (double)R;
-  double var = b / (double)R - m * m;
+  const double md = a / (double)R;  // E[z - k]
+  double var = b / (double)R - md * md;
   if (var < 0.0) var = 0.0;
+  const double m = (double)shift[c] + md;
   mean[c] = (float)m;
   rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
   if (run_mean) {
@@ -158,9 +164,9 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
   }
 }
-hipError_t launch_bn_finalize(const float* part, int chunks, int C, long long R, float eps, float momentum, float* mean,
-                              float* rstd, float* run_mean, float* run_var, hipStream_t s) {
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, part, chunks, C, R, eps, momentum, mean,
+hipError_t launch_bn_finalize(const float* part, int chunks, int C, long long R, float eps, float momentum, const float* z,
+                              float* mean, float* rstd, float* run_mean, float* run_var, hipStream_t s) {
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, part, chunks, C, R, eps, momentum, z, mean,
                      rstd, run_mean, run_var);
   return hipGetLastError();
 }

@@ -110,6 +110,11 @@ struct Node {
   }
 };
 
+// how Tr::wgrad splits the P rows of a weight gradient: S chunks of `chunk` rows each (train.hip; reported by the test entry
+// d2t_op_wgrad_plan)
+struct WgradPlan { long long S, chunk; };
+WgradPlan wgrad_plan(long long P, int M, int N, int taps, const WgradRecTile* rec);
+
 struct Tr {  // builder / runner bound to one context and stream
   d2t_ctx* c;
   d2t_train_state* st;

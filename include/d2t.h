@@ -1080,6 +1080,83 @@ int d2t_op_train_maxpool_w(const float* x, const float* dy, float* y, float* dx,
 /* Tr::gelu (op 0) or Tr::relu (op 1) over n elements, n % 4 == 0: y = f(x), dx = dy f'(x) */
 int d2t_op_train_ew(const float* x, const float* dy, float* y, float* dx, int64_t n, int32_t op, d2t_stream stream);
 
+/* ---- the weight-gradient, BatchNorm, LayerNorm, stem and data-movement kernels of the training step one LAUNCHER at a time
+ * (test infrastructure; tests/test_train_gemm_ops_gpu.py) ----
+ * Each entry calls one launcher of csrc/train_wgrad.hip / train_kernels.hip on caller tensors in the kernel's own layout
+ * (fp32, device, row-major, maps NHWC), asynchronously on the stream, so that a NaN pre-fill and a guard tail of the caller's
+ * buffers speak about the kernel itself.  Every size is checked before anything is launched; what a launcher does not serve is
+ * D2T_EINVAL with nothing written. */
+/* launch_wgrad: part[z][tap][m][n] = sum_{p in chunk z} a[p][m] * b[src(p, tap)][n], z < S, chunk z = rows [z chunk, (z+1) chunk).
+ * a [P][lda], part [S][taps][M][N].  geom == 0: b [P][ldb], src(p) = p, taps = 1.  geom != 0: b is the NHWC map [B][H][W][ldb],
+ * row p = output pixel (b, oh, ow) of [B][OH][OW], tap = kh * KW + kw reads (oh * SH - PH + kh, ow * SW - PW + kw), zero in the
+ * padding; taps = KH * KW and P = B * OH * OW.  S * chunk >= P > (S - 1) * chunk.  M, N, lda, ldb % 4 == 0.
+ * bf16x3: split-bf16 arithmetic where the launcher has it (M, N > 64).  records != 0: the entry builds both operand records
+ * (launch_split_act, format 0) in buffers of its own with a zero page of its own and passes them; that needs geom, bf16x3,
+ * lda == M, ldb == N, chunk % 16 == 0 and a tile for (M, N), and the entry then waits for the stream before it returns.
+ * tile (optional, host): [2] receives the block tile taken -- bm, bn of the record kernel, or 64, 64 / 128, 128. */
+typedef struct d2t_op_wgrad_args {
+  const float *a, *b;
+  float* part;
+  int32_t* tile;
+  int64_t P;
+  int32_t M, N, lda, ldb, geom, B, H, W, OH, OW, KH, KW, SH, SW, PH, PW, S, chunk, bf16x3, records;
+} d2t_op_wgrad_args;
+int d2t_op_wgrad(const d2t_op_wgrad_args* a, d2t_stream stream);
+/* Host only: the S / chunk Tr::wgrad chooses for P rows of an M x N gradient with `taps` filter taps; records != 0: for the
+ * record kernel (EINVAL where (M, N) has no tile).  out [4] = S, chunk, tile bm, tile bn. */
+int d2t_op_wgrad_plan(int64_t P, int32_t M, int32_t N, int32_t taps, int32_t records, int64_t* out);
+/* launch_wgrad_reduce: dst = (accumulate ? dst : 0) + sum_z part[z][tap][m][n]; layout 0: dst [M][N] (taps == 1), layout 1:
+ * OIHW dst [M][N][taps].  The kernel with one block per output is taken for (taps M N <= 4096 and S >= 256) or
+ * (taps M N <= 65536 and S >= 128). */
+int d2t_op_wgrad_reduce(const float* part, float* dst, int32_t S, int32_t taps, int32_t M, int32_t N, int32_t layout,
+                        int32_t accumulate, d2t_stream stream);
+/* launch_colreduce: per-chunk column sums of [R][C] matrices into part [chunks][2][C] (mode 0: sum a | 0;  1: the sums about
+ * the channel's value in row 0, sum (a - a[0][c]) | sum (a - a[0][c])^2;
+ * 2 (BatchNorm backward): g = dy (y > 0 where y is given) -> sum g | sum g (z - mean[c]) rstd[c];  3 (LayerNorm backward):
+ * sum a | sum a (z - mean[r]) rstd[r]).  *chunks (host) receives colreduce_chunks(R, C); with part == NULL nothing else happens.
+ * C % 4 == 0. */
+int d2t_op_colreduce(int32_t mode, const float* a, const float* y, const float* z, const float* mean, const float* rstd,
+                     float* part, int64_t R, int32_t C, int32_t* chunks, d2t_stream stream);
+/* launch_colreduce_final: out0[c] = (accumulate ? out0[c] : 0) + sum_k part[k][0][c], out1 (optional) from part[k][1][c] */
+int d2t_op_colreduce_final(const float* part, int32_t chunks, int32_t C, float* out0, float* out1, int32_t accumulate,
+                           d2t_stream stream);
+/* launch_bn_finalize: part [chunks][2][C] of mode 1 over z [R][C] (the same z: its row 0 is the shift of the sums) -> mean,
+ * rstd = 1 / sqrt(biased variance + eps); run_mean / run_var (both or neither) updated in place with `momentum` and the
+ * unbiased variance (the biased one where R == 1) */
+int d2t_op_bn_finalize(const float* part, int32_t chunks, int32_t C, int64_t R, float eps, float momentum, const float* z,
+                       float* mean, float* rstd, float* run_mean, float* run_var, d2t_stream stream);
+/* launch_bn_apply: y = act((z - mean) rstd gamma + beta (+ res)), [R][C], C % 4 == 0; planes (optional, C % 32 == 0): the
+ * split-bf16 records of y, R * C * 2 uint16 */
+int d2t_op_bn_apply(const float* z, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* res,
+                    float* y, uint16_t* planes, int64_t R, int32_t C, int32_t relu, d2t_stream stream);
+/* launch_bn_bwd_apply: g = dy (y > 0 where y is given); dz = gamma rstd (g - s0 / R - xhat s1 / R); gout (optional) = g;
+ * planes (optional, C % 32 == 0): the records of dz */
+int d2t_op_bn_bwd_apply(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
+                        const float* gamma, const float* s0, const float* s1, float* dz, float* gout, uint16_t* planes, int64_t R,
+                        int32_t C, d2t_stream stream);
+/* launch_ln_train / launch_ln_bwd: LayerNorm over rows of D = 128, 256 or 512 with saved mean / rstd [rows];
+ * dx = rstd (dy gamma - mean_c(dy gamma) - xhat mean_c(dy gamma xhat)) (+ add) */
+int d2t_op_ln_train(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int32_t rows,
+                    int32_t D, float eps, d2t_stream stream);
+int d2t_op_ln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* add,
+                  float* dx, int32_t rows, int32_t D, d2t_stream stream);
+/* launch_stem_raw: z [B][H][W][Cout] = conv3x3, pad 1 of the NCHW image [B][Cin][H][W] with raw OIHW weights, no bias.
+ * launch_stem_wgrad: part [nchunks][9 Cin][Cout], tap = (ci * 3 + kh) * 3 + kw, over pixel chunks of `chunk` rows of
+ * dz [B H W][Cout]; nchunks * chunk >= B H W > (nchunks - 1) * chunk.  Cin 1 or 3, Cout 32 or 64. */
+int d2t_op_stem_raw(const float* img, const float* w, float* z, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                    d2t_stream stream);
+int d2t_op_stem_wgrad(const float* img, const float* dz, float* part, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout,
+                      int32_t chunk, int32_t nchunks, d2t_stream stream);
+/* dst [B][DH][DW][C]: dst[b][oh SH + offh][ow SW + offw] = src[b][oh][ow] where that lies inside, zero elsewhere */
+int d2t_op_dilate(const float* src, float* dst, int32_t B, int32_t OH, int32_t OW, int32_t C, int32_t DH, int32_t DW, int32_t SH,
+                  int32_t SW, int32_t offh, int32_t offw, d2t_stream stream);
+/* out [Cin][Cout][KH][KW] = w [Cout][Cin][KH - 1 - kh][KW - 1 - kw] */
+int d2t_op_flip_oihw(const float* w, float* out, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW, d2t_stream stream);
+/* dst [rows][Cd] = src [rows][Cs] zero-padded on the right, Cd >= Cs */
+int d2t_op_pad_cols(const float* src, float* dst, int64_t rows, int32_t Cs, int32_t Cd, d2t_stream stream);
+/* dst[r][0 .. cols) = src[r][0 .. cols), row strides lds, ldd >= cols; the rest of dst is not written */
+int d2t_op_copy2d(const float* src, int32_t lds, float* dst, int32_t ldd, int64_t rows, int32_t cols, d2t_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ training tape, forward + backward, on caller tensors), against float64 torch aut
 where the op has them (fp32 MFMA / split-bf16 for the convolution, data-gradient and weight-gradient GEMMs).  The other
 kernels of the step have their operator tests in test_train_small_ops_gpu.py (GlobalContext, embedding, dropout masks, the
 position-table resize, mean over the height, the (2,1) pool, GELU / ReLU, the token-row movers) and
-test_recurrent_ops_gpu.py (BiLSTM, LSTM-attention decoder).
+test_recurrent_ops_gpu.py (BiLSTM, LSTM-attention decoder).  The weight-gradient, BatchNorm, LayerNorm, stem and data-movement
+LAUNCHERS are held one at a time, on caller tensors and with tolerances from the arithmetic, by test_train_gemm_ops_gpu.py.
 
 Tolerance = max |engine - fp64| relative to max |fp64| of that tensor: 1e-4 for fp32 arithmetic (fp32 accumulation
 over up to ~10^5 terms in the weight gradients), 1e-4 for split-bf16 (2^-16 per product, averaged over the same
