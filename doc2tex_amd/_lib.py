@@ -93,6 +93,29 @@ class D2TOptimTensor(C.Structure):  # include/d2t.h d2t_optim_tensor
                [(n, C.c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps", "bc1", "sqrt_bc2")]
 
 
+class D2TOptimLambTensor(C.Structure):  # include/d2t.h d2t_optim_lamb_tensor
+    _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "mirror")] + [("numel", C.c_int64)] + \
+               [(n, C.c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "beta3", "eps", "bc1", "sqrt_bc2")] + \
+               [("adapt", C.c_int32), ("trust_clip", C.c_int32)]
+
+
+class D2TOptimAdampTensor(C.Structure):  # include/d2t.h d2t_optim_adamp_tensor
+    _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "mirror", "mode")] + \
+               [("numel", C.c_int64), ("rows", C.c_int64)] + \
+               [(n, C.c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps", "bc1", "sqrt_bc2", "delta", "wd_ratio")] + \
+               [("nesterov", C.c_int32), ("pad_", C.c_int32)]
+
+
+class D2TOptimMadgradTensor(C.Structure):  # include/d2t.h d2t_optim_madgrad_tensor
+    _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "grad_sum_sq", "s", "x0", "mirror")] + [("numel", C.c_int64)] + \
+               [(n, C.c_double) for n in ("lr", "weight_decay", "momentum", "eps", "lamb")] + \
+               [("decoupled_decay", C.c_int32), ("pad_", C.c_int32)]
+
+
+class D2TOptimLookaheadTensor(C.Structure):  # include/d2t.h d2t_optim_lookahead_tensor
+    _fields_ = [(n, C.c_void_p) for n in ("fast", "slow", "mirror")] + [("numel", C.c_int64)]
+
+
 OPTIM_CHUNK = 32768  # include/d2t.h D2T_OPTIM_CHUNK: elements one block of the optimizer kernels handles
 
 PREP_DEMO, PREP_API = 0, 1
@@ -221,6 +244,10 @@ SIGNATURES = {
     "d2t_optim_last_error": (C.c_char_p, [_P]),
     "d2t_optim_chunk": (_I, []),
     "d2t_optim_step": (_I, [_P, C.POINTER(D2TOptimTensor), _I, _I, C.c_float, _P, _P]),
+    "d2t_optim_lamb_step": (_I, [_P, C.POINTER(D2TOptimLambTensor), _I, C.c_float, _P, _P]),
+    "d2t_optim_adamp_step": (_I, [_P, C.POINTER(D2TOptimAdampTensor), _I, C.c_float, _P, _P]),
+    "d2t_optim_madgrad_step": (_I, [_P, C.POINTER(D2TOptimMadgradTensor), _I, C.c_float, _P, _P]),
+    "d2t_optim_lookahead_sync": (_I, [_P, C.POINTER(D2TOptimLookaheadTensor), _I, C.c_float, _P]),
     "d2t_weight_ptr": (_I, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(_L)]),
     # validation metrics (csrc/metrics.hip)
     "d2t_metric_edit_distance_workspace": (_I, [_I, _L, C.POINTER(_L)]),

@@ -10,12 +10,12 @@ OPT="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -Wno-unused-v
 OBJ=obj; LIB=libd2t.so
 if [ -n "$D2T_PROBES" ]; then OPT="$OPT -DD2T_PROBES"; OBJ=obj_probe; LIB=libd2t_probe.so; fi
 mkdir -p $OBJ
-SRCS="conv_mfma conv_bf16x3 conv_bf16x3p conv_records ops vit_attn decode decode_gemm decode_row decode_maps decode_beam recurrent attn_beam train_kernels train_wgrad train_attn train_recurrent train train_models train_abi optim metrics engine engine_weights engine_tfm engine_tfm_beam engine_attn engine_ops prep post posembed"
+SRCS="conv_mfma conv_bf16x3 conv_bf16x3p conv_records ops vit_attn decode decode_gemm decode_row decode_maps decode_beam recurrent attn_beam train_kernels train_wgrad train_attn train_recurrent train train_models train_abi optim optim_family metrics engine engine_weights engine_tfm engine_tfm_beam engine_attn engine_ops prep post posembed"
 objs=""; stale=""
 for f in $SRCS; do
   o=$OBJ/$f.o
   objs="$objs $o"
-  if [ ! -f $o ] || [ $f.hip -nt $o ] || [ kernels.h -nt $o ] || [ conv_common.h -nt $o ] || [ conv_dma.h -nt $o ] || [ train_common.h -nt $o ] || [ train_tape.h -nt $o ] || [ recurrent_common.h -nt $o ] || [ decode_common.h -nt $o ] || [ decode_row_common.h -nt $o ] || [ ctx.h -nt $o ] || [ engine_impl.h -nt $o ] || [ engine_tfm.h -nt $o ] || [ beam_host.h -nt $o ] || [ attn_beam_host.h -nt $o ] || [ carve.h -nt $o ] || [ ../../include/d2t.h -nt $o ] || [ ../../include/d2t_prep.h -nt $o ] || [ unicode_tables.h -nt $o ] || [ build.sh -nt $o ]; then
+  if [ ! -f $o ] || [ $f.hip -nt $o ] || [ kernels.h -nt $o ] || [ conv_common.h -nt $o ] || [ conv_dma.h -nt $o ] || [ train_common.h -nt $o ] || [ train_tape.h -nt $o ] || [ recurrent_common.h -nt $o ] || [ decode_common.h -nt $o ] || [ decode_row_common.h -nt $o ] || [ ctx.h -nt $o ] || [ engine_impl.h -nt $o ] || [ engine_tfm.h -nt $o ] || [ beam_host.h -nt $o ] || [ attn_beam_host.h -nt $o ] || [ carve.h -nt $o ] || [ optim_common.h -nt $o ] || [ ../../include/d2t.h -nt $o ] || [ ../../include/d2t_prep.h -nt $o ] || [ unicode_tables.h -nt $o ] || [ build.sh -nt $o ]; then
     stale="$stale $f"
   fi
 done

@@ -2,16 +2,11 @@
 // kernels: the global gradient norm, then Adam / AdamW with the clip coefficient applied on the fly and the new parameter
 // written twice -- to the module's tensor and to the engine's raw copy of it -- so that the next forward uploads nothing.
 // include/d2t.h has the contract.  Three launches and one table copy per step, no host synchronisation.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
 
-#include "../../include/d2t.h"
+#include "optim_common.h"
 
 namespace d2t {
 
@@ -35,43 +30,16 @@ struct OptimChunk {
 };
 static_assert(sizeof(OptimChunk) == 80, "table entries are 16-byte multiples");
 
-constexpr int OPT_THREADS = 256;
-
 __device__ inline bool chunk_vec(const OptimChunk& c) {
   return ((reinterpret_cast<uintptr_t>(c.p) | reinterpret_cast<uintptr_t>(c.g) | reinterpret_cast<uintptr_t>(c.m) |
            reinterpret_cast<uintptr_t>(c.v) | reinterpret_cast<uintptr_t>(c.mirror)) & 15) == 0;
-}
-
-// sum of the 256 threads' values in a fixed order (lanes by halving strides, then waves 0..3); valid in thread 0
-__device__ inline double block_sum(double x) {
-  __shared__ double part[OPT_THREADS / 64];
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double r = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < OPT_THREADS / 64; ++w) r += part[w];
-  return r;
 }
 
 // partial[blockIdx.x] = sum of squares of the chunk's gradient: each thread a serial fp32 sum of its (at most
 // D2T_OPTIM_CHUNK / 256) elements, everything above that in double
 __global__ __launch_bounds__(OPT_THREADS) void optim_sumsq_kernel(const OptimChunk* __restrict__ table, double* __restrict__ partial) {
   const OptimChunk c = table[blockIdx.x];
-  float acc = 0.f;
-  int i = threadIdx.x;
-  if ((reinterpret_cast<uintptr_t>(c.g) & 15) == 0) {
-    const int n4 = c.n >> 2;
-    for (; i < n4; i += OPT_THREADS) {
-      const float4 g = reinterpret_cast<const float4*>(c.g)[i];
-      acc += g.x * g.x;
-      acc += g.y * g.y;
-      acc += g.z * g.z;
-      acc += g.w * g.w;
-    }
-    i = (n4 << 2) + threadIdx.x;
-  }
-  for (; i < c.n; i += OPT_THREADS) acc += c.g[i] * c.g[i];
+  const float acc = chunk_sumsq(c.g, c.n);
   const double s = block_sum((double)acc);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
@@ -136,60 +104,9 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_adam_kernel(const OptimChun
 
 using d2t::OptimChunk;
 
-struct d2t_optim {
-  int device = 0;
-  std::string err;
-  // the chunk table travels through a pinned block and its device mirror, four in rotation: the host never waits on the
-  // previous step's copy
-  struct Stage { void *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; } stage[4];
-  unsigned calls = 0;
-  double* partial = nullptr;
-  size_t partial_cap = 0;  // entries
-  float* coef = nullptr;
-};
-
-namespace {
-
-int ofail(d2t_optim* o, int code, const char* fmt, ...) {
-  if (o) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    o->err = buf;
-  }
-  return code;
-}
-#define OHIP(o, expr)                                                                           \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return ofail(o, D2T_EHIP, "%s: %s", #expr, hipGetErrorString(e_));  \
-  } while (0)
-
-struct OptDevGuard {
-  int prev = -1;
-  explicit OptDevGuard(const d2t_optim* o) {
-    int cur = -1;
-    if (o && hipGetDevice(&cur) == hipSuccess && cur != o->device && hipSetDevice(o->device) == hipSuccess) prev = cur;
-  }
-  ~OptDevGuard() { if (prev >= 0) hipSetDevice(prev); }
-};
-
-// the kernels dereference every pointer of a record: each must be device memory of the optimizer's device
-int optim_dev_ptr(d2t_optim* o, const void* p, int rec, const char* what) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return ofail(o, D2T_EINVAL, "tensor %d: %s is not device memory", rec, what);
-  }
-  if (a.type != hipMemoryTypeDevice) return ofail(o, D2T_EINVAL, "tensor %d: %s is not device memory", rec, what);
-  if (a.device != o->device)
-    return ofail(o, D2T_EINVAL, "tensor %d: %s is on HIP device %d but this optimizer lives on device %d", rec, what, a.device, o->device);
-  return D2T_OK;
-}
-
-}  // namespace
+using d2t::ofail;
+using d2t::optim_dev_ptr;
+using d2t::OptDevGuard;
 
 extern "C" {
 
@@ -219,6 +136,7 @@ void d2t_optim_destroy(d2t_optim* o) {
   }
   if (o->partial) hipFree(o->partial);
   if (o->coef) hipFree(o->coef);
+  if (o->family) hipFree(o->family);
   delete o;
 }
 
@@ -256,20 +174,9 @@ int d2t_optim_step(d2t_optim* o, const d2t_optim_tensor* recs, int32_t n, int32_
     return D2T_OK;
   }
   const size_t bytes = chunks * sizeof(OptimChunk);
-  d2t_optim::Stage& g = o->stage[o->calls++ & 3];
-  if (g.pending) {
-    OHIP(o, hipEventSynchronize(g.ev));
-    g.pending = false;
-  }
-  if (bytes > g.cap) {
-    if (g.h) { OHIP(o, hipHostFree(g.h)); OHIP(o, hipFree(g.d)); }
-    g.h = g.d = nullptr;
-    g.cap = 0;
-    OHIP(o, hipHostMalloc(&g.h, bytes * 2, hipHostMallocDefault));
-    OHIP(o, hipMalloc(&g.d, bytes * 2));
-    g.cap = bytes * 2;
-    if (!g.ev) OHIP(o, hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
-  }
+  d2t_optim::Stage* gp = nullptr;
+  if (int rc = d2t::optim_stage_take(o, bytes, &gp)) return rc;
+  d2t_optim::Stage& g = *gp;
   if (clip && chunks > o->partial_cap) {
     if (o->partial) { OHIP(o, hipDeviceSynchronize()); OHIP(o, hipFree(o->partial)); }
     o->partial = nullptr;
@@ -299,9 +206,7 @@ int d2t_optim_step(d2t_optim* o, const d2t_optim_tensor* recs, int32_t n, int32_
       *t++ = c;
     }
   }
-  OHIP(o, hipMemcpyAsync(g.d, g.h, bytes, hipMemcpyHostToDevice, s));
-  OHIP(o, hipEventRecord(g.ev, s));
-  g.pending = true;
+  if (int rc = d2t::optim_stage_send(o, g, bytes, s)) return rc;
   const OptimChunk* table = static_cast<const OptimChunk*>(g.d);
   if (clip) {
     hipLaunchKernelGGL(d2t::optim_sumsq_kernel, dim3((unsigned)chunks), dim3(d2t::OPT_THREADS), 0, s, table, o->partial);

@@ -915,6 +915,93 @@ const char* d2t_optim_last_error(d2t_optim* opt);
 int32_t d2t_optim_chunk(void); /* D2T_OPTIM_CHUNK, for bindings */
 int d2t_optim_step(d2t_optim* opt, const d2t_optim_tensor* tensors, int32_t n, int32_t decoupled, float max_grad_norm,
                    float* norm_dev, d2t_stream stream);
+/* ---- the optimizer family: LAMB, AdamP, MADGRAD, Lookahead (csrc/optim_family.hip) -----------------------------------
+ * The other optimizers of the reference's builder (modules/optim/builder.py:76-94) on the same pattern and the same
+ * d2t_optim object: a table of chunks through its staging rotation, 16-byte accesses where all of a chunk's pointers allow
+ * and scalar ones otherwise.  For every entry point below:
+ *   - it enqueues on `stream` and never waits for the device (the first call allocates scratch);
+ *   - every sum above one element (p^2, u^2, the per-row dot products) is a double, added in a fixed order without
+ *     atomics; the global gradient norm is d2t_optim_step's (one fp32 sum per thread, double above it).  Results are
+ *     bit-reproducible for the same pointers' alignment;
+ *   - every pointer of every record must be device memory of the optimizer's device, sizes non-negative and scalars
+ *     finite: D2T_EINVAL before anything is enqueued otherwise, with a message in d2t_optim_last_error;
+ *   - the new parameter is stored to `param` and, where given, to `mirror` (the engine's raw copy, d2t_weight_ptr); the
+ *     gradients are only read.  Records must not overlap one another.  Scalars are doubles, rounded to fp32 once.
+ *
+ * d2t_optim_lamb_step (reference optim/lamb.py:113-216), four launches: norm = sqrt(sum g^2) over all records [norm_dev,
+ * may be NULL]; divisor = norm / max_grad_norm where norm > max_grad_norm (> 0, required), else 1 -- LAMB's own rule,
+ * without clip_grad_norm_'s 1e-6; then per element g' = g / divisor, m = beta1 m + beta3 g', v = beta2 v + (1 - beta2) g'^2,
+ * u = (m / bc1) / (sqrt(v) / sqrt_bc2 + eps) [+ weight_decay p where weight_decay != 0].  With `adapt` (the caller sets it
+ * where weight_decay != 0 or always_adapt): trust = |p| / |u| over the tensor if both are > 0, else 1, min(trust, 1) under
+ * trust_clip; otherwise trust = 1.  p -= lr (u trust).  u is formed in both passes from the new m, v and the old p; the
+ * per-chunk sums of p^2 and u^2 are added per tensor in chunk order by every block of the apply pass.  bc1 = sqrt_bc2 = 1
+ * is bias_correction=False; beta3 = 1 is grad_averaging=False. */
+typedef struct d2t_optim_lamb_tensor {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* mirror; /* NULL: none */
+  int64_t numel;
+  double lr, weight_decay, beta1, beta2, beta3, eps, bc1, sqrt_bc2;
+  int32_t adapt, trust_clip;
+} d2t_optim_lamb_tensor;
+int d2t_optim_lamb_step(d2t_optim* opt, const d2t_optim_lamb_tensor* tensors, int32_t n, float max_grad_norm, float* norm_dev,
+                        d2t_stream stream);
+/* d2t_optim_adamp_step (reference optim/adamp.py:25-40, 66-129), three launches plus the two of the norm when
+ * max_grad_norm > 0 (d2t_optim_step's clip: g' = g coef, norm_dev required then):
+ *   1. m = beta1 m + (1 - beta1) g', v = beta2 v + (1 - beta2) g'^2; perturb = (beta1 m + (1 - beta1) g') / denom under
+ *      nesterov, else m / denom, denom = sqrt(v) / sqrt_bc2 + eps; for a record with rows > 0 (a tensor of more than one
+ *      dimension, rows = size(0), row length numel / rows) the sums g'.p, g'.g', p.p and p.perturb of every row;
+ *   2. one block per record: cos(x, y) = x.y / (max(|x|, eps) max(|y|, eps)) as F.cosine_similarity; mode 1 (channel) where
+ *      max over rows of |cos(g'_i, p_i)| < delta / sqrt(row length), else mode 2 (layer) where |cos(g', p)| over the whole
+ *      tensor < delta / sqrt(numel), else 0; written to *mode [device int32, may be NULL] -- no host read;
+ *   3. in a projecting mode perturb -= p_n (p.perturb) / (|p| + eps), p_n = p / (|p| + eps), over the row (mode 1) or the
+ *      tensor (mode 2); p *= 1 - lr weight_decay (wd_ratio if projected, else 1) where weight_decay > 0;
+ *      p -= (lr / bc1) perturb.
+ * A record with rows > 0 holds at most 2^31 - 1 elements. */
+typedef struct d2t_optim_adamp_tensor {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* mirror; /* NULL: none */
+  int32_t* mode; /* NULL: the decision is not reported */
+  int64_t numel, rows;
+  double lr, weight_decay, beta1, beta2, eps, bc1, sqrt_bc2, delta, wd_ratio;
+  int32_t nesterov, pad_;
+} d2t_optim_adamp_tensor;
+int d2t_optim_adamp_step(d2t_optim* opt, const d2t_optim_adamp_tensor* tensors, int32_t n, float max_grad_norm, float* norm_dev,
+                         d2t_stream stream);
+/* d2t_optim_madgrad_step (reference optim/madgrad.py:102-195, dense path), one launch plus the two of the norm when
+ * max_grad_norm > 0 (as above).  lamb = (lr + eps) sqrt(step), formed by the caller.  Per element: where weight_decay != 0,
+ * p *= 1 - lr weight_decay under decoupled_decay, else g' += weight_decay p; x = x0 where momentum != 0 (x0 is read only),
+ * else p + s / (cbrt(grad_sum_sq) + eps), rebuilt before the accumulators move (x0 is not touched, may be NULL);
+ * grad_sum_sq += lamb g'^2; s += lamb g'; z = x - s / (cbrt(grad_sum_sq) + eps); p = z where momentum == 0, else
+ * (1 - ck) p + ck z with ck = 1 - momentum. */
+typedef struct d2t_optim_madgrad_tensor {
+  float* param;
+  const float* grad;
+  float* grad_sum_sq;
+  float* s;
+  float* x0;     /* used where momentum != 0 */
+  float* mirror; /* NULL: none */
+  int64_t numel;
+  double lr, weight_decay, momentum, eps, lamb;
+  int32_t decoupled_decay, pad_;
+} d2t_optim_madgrad_tensor;
+int d2t_optim_madgrad_step(d2t_optim* opt, const d2t_optim_madgrad_tensor* tensors, int32_t n, float max_grad_norm,
+                           float* norm_dev, d2t_stream stream);
+/* d2t_optim_lookahead_sync (reference optim/lookahead.py:30-41), one launch: slow += alpha (fast - slow), then fast = slow
+ * and, where given, mirror = slow.  0 <= alpha <= 1. */
+typedef struct d2t_optim_lookahead_tensor {
+  float* fast;
+  float* slow;
+  float* mirror; /* NULL: none */
+  int64_t numel;
+} d2t_optim_lookahead_tensor;
+int d2t_optim_lookahead_sync(d2t_optim* opt, const d2t_optim_lookahead_tensor* tensors, int32_t n, float alpha,
+                             d2t_stream stream);
 /* Device pointer and element count of the engine's raw copy of a loaded tensor, by state_dict key: what d2t_read_weight
  * copies from and d2t_reload_weights writes to.  Valid until the tensor is loaded again with another size or the context
  * is destroyed.  D2T_ESTATE with a message for a name that is not loaded. */
